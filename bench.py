@@ -1,7 +1,13 @@
 #!/usr/bin/env python3
 """bench.py -- frames/s of the coarse (FDR) + fine (sync_and_demodulate) path.
 
-    python bench.py --gpus N --steps K --warmup W [--total-frames T] [--repeats R]
+    python bench.py --gpus N --steps K --warmup W [--total-frames T] [--repeats R] [--dump-outputs DIR] [--full]
+
+A plain run does what the headline figure needs and nothing else: it sets up (frames, the schedule-form / streams
+trial), warms up (W steps, then short regions until two agree), times ONE region of K steps, writes the last step's
+outputs when --dump-outputs is given, and prints the line (`value`, `ms_per_step`, the trial, the configuration).
+Everything else the line used to carry -- the legs listed under "Extra objects" below, the repeats, the parity spot
+check, the gather checks -- runs only with --full (the --no-* switches then turn single legs off).
 
 One step = one pass of the whole hot path (K1 spectrogram, K2 spectrum/peaks,
 K3 coarse search + selection over ALL candidates, then the S0..S5 refinement
@@ -31,9 +37,15 @@ torch.distributed's gather; the line carries devices, device_name, rccl_version,
 gather that was used and whether it equalled torch's gather byte for byte.
 
 The timed region (K steps between barrier + synchronize) is repeated R times
-(default 5); `value` is the MEDIAN repeat, all repeats are listed.
+(default 1; with --full 5); `value` is the MEDIAN repeat, all repeats are listed.
 
-Prints ONE JSON line (rank 0).  Extra objects:
+--dump-outputs DIR: after the timed regions, what the last timed step handed its caller -- the frame's candidates
+(slots past npk zeroed: they are never written), npk, the top candidate's refinement record and the packed slab row --
+as DIR/<name>.npy, one file per field, float32 (binary32 fields, bytes) or float64 (int32 / binary64 fields).  The
+frames are seeded, so the same arguments give the same inputs in every run.  Above 64 MB in all a fixed, seeded sample
+of the frames is written (their indices in DIR/sample_frame_index.npy).
+
+Prints ONE JSON line (rank 0).  Extra objects (--full only):
   roofline      the dominant kernel, the tone-correlation schedule (k6_sched, or the K4 family
                 of the staged form).  It is FP32-VALU bound (no FMA: the reference's
                 two-rounding sums), so `bound` = "valu_fp32_nofma": achieved = binary32
@@ -174,12 +186,44 @@ def parity_spot_check(snap, D, N, form):
                     "regions"}
 
 
+DUMP_BUDGET = 60 * 10 ** 6                # bytes --dump-outputs writes at most (64 MB less room for the .npy headers)
+
+
+def dump_outputs(dirname, ln, slab, B, N):
+    """--dump-outputs: what the last timed step handed its caller (lane `ln`'s candidate / npk / record buffers and that
+    step's slab row), one float32 / float64 .npy per field; above DUMP_BUDGET a fixed, seeded sample of the frames."""
+    npk = ln["npk"].cpu().numpy().astype(np.int64)
+    cands = np.frombuffer(ln["cands"].cpu().numpy().tobytes(), N.CAND_DTYPE).reshape(B, -1).copy()
+    cands[np.arange(cands.shape[1])[None, :] >= npk[:, None]] = np.zeros((), N.CAND_DTYPE)   # never written past npk
+    rec = np.frombuffer(ln["out"].cpu().numpy().tobytes(), N.DEMOD_DTYPE).reshape(B)
+    slab = slab.cpu().numpy().copy()
+    slab[:, 4:16] = 0                                                                          # the slab's pad bytes
+    arrays = {"npk": npk, "slab": slab}
+    arrays.update(("cand_" + f, cands[f]) for f in N.CAND_DTYPE.names)
+    arrays.update(("rec_" + f, rec[f]) for f in N.DEMOD_DTYPE.names if not f.startswith("_"))
+    # binary32 fields and bytes as float32, int32 / int64 / binary64 fields as float64: every value exact
+    arrays = {k: v.astype(np.float32 if v.dtype in (np.float32, np.uint8) else np.float64) for k, v in arrays.items()}
+    per_frame = sum(v.nbytes for v in arrays.values()) / max(B, 1)
+    if per_frame * B > DUMP_BUDGET:
+        rows = np.sort(np.random.default_rng(0).choice(B, int(DUMP_BUDGET // per_frame) - 1, replace=False))
+        arrays = {k: v[rows] for k, v in arrays.items()}
+        arrays["sample_frame_index"] = rows.astype(np.float64)
+    os.makedirs(dirname, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(dirname, k + ".npy"), np.ascontiguousarray(v))
+
+
 def parse_args():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=10)
-    ap.add_argument("--repeats", type=int, default=5, help="repeats of the timed K-step region")
+    ap.add_argument("--repeats", type=int, default=None, help="repeats of the timed K-step region (default 1; --full: 5)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beside the headline (CPU baseline, roofline and per-kernel times, fast_search, "
+                         "configs[2..4], lazy S5, host-pointer and end-to-end legs, parity spot check, gather checks)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32 / float64, <= 64 MB)")
     ap.add_argument("--frames", type=int, default=256, help="frames per GPU per step (weak scaling)")
     ap.add_argument("--total-frames", type=int, default=0,
                     help="strong scaling: frames per step over ALL ranks (configs[3]: 65536)")
@@ -206,7 +250,7 @@ def parse_args():
     ap.add_argument("--configs4-seeds", type=int, default=-1,
                     help="noisy copies per SNR of the configs[4] leg (recording + AWGN, end to end incl. host Fano), sharded "
                          "round-robin over the ranks; 0 skips it; default: 64 unless --no-host-legs / --total-frames "
-                         "(and, at one rank, --no-cpu) is given")
+                         "(and, at one rank, --no-cpu) is given; --full only")
     ap.add_argument("--streams", type=int, default=0,
                     help="HIP streams (each with its own context and scratch) the steps rotate over; 0 = per --sched trial")
     return ap.parse_args()
@@ -249,6 +293,8 @@ def main():
     args = parse_args()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         spawn_ranks(args)
+    full = args.full
+    repeats = args.repeats if args.repeats is not None else (5 if full else 1)
 
     import torch
     import torch.distributed as dist
@@ -316,7 +362,7 @@ def main():
 
     # the end-to-end pipes (their contexts, lane streams and copy streams) are created here as well, for
     # the same reason; they idle until their legs run
-    host_legs = rank == 0 and world == 1 and not args.no_host_legs and args.total_frames <= 0
+    host_legs = full and rank == 0 and world == 1 and not args.no_host_legs and args.total_frames <= 0
     pipes_e2e = {f: G.Pipe(batch_frames=B, max_per_frame=1, lanes=0, sched=f) for f in ("fused", "staged")} if host_legs else {}
     pipe_st = G.Pipe(hop=3375, batch_frames=B, max_per_frame=1, lanes=0) if host_legs else None
 
@@ -448,7 +494,7 @@ def main():
     # gives 3 streams 5.5 % more: the trial is now >= 100 steps, two regions per pair after a warm one, and a smaller
     # stream count is taken only when it wins by more than 2 %; the table and the choice are top-level scalars of the line)
     trials = {}
-    KT = max(K, args.trial_steps * 256 // max(B, 1))          # (>= 100 steps of the 256-frame batch; configs[3]'s 65 536-frame steps: K)
+    KT = args.trial_steps * 256 // max(B, 1) or K             # (100 steps of the 256-frame batch whatever --steps; configs[3]'s 65 536-frame steps: K)
     if args.sched == "auto" or args.streams <= 0:
         cands = []
         for fused in ((True, False) if args.sched == "auto" else ((args.sched == "fused"),)):
@@ -473,24 +519,28 @@ def main():
 
     for i in range(args.warmup):
         step(lanes, i)
-    # warm up until two consecutive K-step regions agree within 2 % (clocks, caches, the lanes' rotation over
-    # the distinct batches: round 2's first timed repeat was 11 % below the others), at most 8 regions
+    # warm up until two consecutive regions agree within 2 % (clocks, caches, the lanes' rotation over
+    # the distinct batches: round 2's first timed repeat was 11 % below the others), at most 8 regions of
+    # min(K, KT) steps: a warm-up whose length does not grow with --steps
     warm_regions = []
     for _ in range(8):
-        warm_regions.append(region(lanes, K, gather=False)[0])
+        warm_regions.append(region(lanes, min(K, KT), gather=False)[0])
         if len(warm_regions) >= 2 and abs(warm_regions[-1] - warm_regions[-2]) <= 0.02 * warm_regions[-2]:
             break
     # ---- the timed region, R times ----
     reps = []
-    for _ in range(max(1, args.repeats)):
+    for _ in range(max(1, repeats)):
         dt, t_enq, gathered = region(lanes, K)
         reps.append((dt, t_enq))
+    # ---- what the last timed step computed: lane (K - 1) mod streams, slab row K - 1 ----
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, lanes[(K - 1) % len(lanes)], slab_ring[K - 1, :B], B, N)
     # ---- parity spot check, part 1 (outside the timed regions): freeze what the TIMED lanes wrote in their last steps --
     # the candidate / record buffers of every lane, the slab row of that step and the frames it read -- on the host; the
     # oracle runs on them at the end of the run (part 2), so the line says whether the bytes `value` was measured on are
     # the reference's (round 5's k4_jig bug sat in exactly this path, unseen by the forms-against-forms tests)
     spot_snap = []
-    if rank == 0 and not args.no_spot_check:
+    if full and rank == 0 and not args.no_spot_check:
         SPOT = 8
         live_lanes = [l for l in range(len(lanes)) if l < K]
         for q in range(SPOT):
@@ -505,7 +555,7 @@ def main():
                               "out": np.frombuffer(ln["out"].view(B, -1)[b].cpu().numpy().tobytes(), N.DEMOD_DTYPE).copy(),
                               "slab": slab_ring[i_last % K, b].cpu().numpy().copy()})
     gathered_sha = None
-    if rank == 0 and global_frames and gathered is not None:
+    if full and rank == 0 and global_frames and gathered is not None:
         # [world, K * Bmax, SLAB] -> per step, global frame order (b = local * G + rank), padding rows dropped
         import hashlib
         gs = gathered.view(world, K, Bmax, D.SLAB_BYTES).cpu()
@@ -514,7 +564,7 @@ def main():
             hh.update(D.restore_order(gs[:, k], args.total_frames).contiguous().numpy().tobytes())
         gathered_sha = hh.hexdigest()
     gather_checked = None
-    if abi_ctx is not None:          # once, outside the timed regions: the two gathers give the same bytes
+    if full and abi_ctx is not None:     # once, outside the timed regions: the two gathers give the same bytes
         ref = D.gather_slabs(slab_ring.view(K * Bmax, D.SLAB_BYTES), dst=0)
         if rank == 0:
             gather_checked = bool(torch.equal(ref.to(dev), gathered))
@@ -527,7 +577,7 @@ def main():
     # ---- BASELINE configs[3] at N = 1 (65 536 frames through the same lanes: SCALE's strong-scaling reference point)
     fast_leg = None
     c3_leg = None
-    if world == 1 and not strong and not args.no_lazy:
+    if full and world == 1 and not strong and not args.no_lazy:
         nfl = min(3, max_lanes)                 # --streams 1 / 2 leaves fewer lane streams than the default three
         fl_lanes = make_lanes(nfl, False, {"fast_search": 1})
         region(fl_lanes, min(K, 10), gather=False)
@@ -564,63 +614,64 @@ def main():
                           "gather of all %d slabs at the end (what `--gpus N --total-frames 65536` shards round-robin)"
                           % (n3 * B, n3, B, n3 * B)}
 
-    # ---- per-kernel HIP-event times: single stream, same rotating batches (untimed for `value`) ----
-    ctx.prof_enable(True)
-    ctx.prof_read()
-    n1 = min(K, 20)
-    for i in range(n1):
-        step(lanes[:1], i)
-    barrier()
-    prof = ctx.prof_read()
-    ctx.prof_enable(False)
-    # the dominant kernel alone (events around it only: every recorded event is a marker packet)
-    ctx.prof_enable(("tonecorr",))
-    ctx.prof_read()
-    for i in range(n1):
-        step(lanes[:1], i)
-    barrier()
-    k4 = ctx.prof_read()["tonecorr"]
-    ctx.prof_enable(False)
+    if full:
+        # ---- per-kernel HIP-event times: single stream, same rotating batches (untimed for `value`) ----
+        ctx.prof_enable(True)
+        ctx.prof_read()
+        n1 = min(K, 20)
+        for i in range(n1):
+            step(lanes[:1], i)
+        barrier()
+        prof = ctx.prof_read()
+        ctx.prof_enable(False)
+        # the dominant kernel alone (events around it only: every recorded event is a marker packet)
+        ctx.prof_enable(("tonecorr",))
+        ctx.prof_read()
+        for i in range(n1):
+            step(lanes[:1], i)
+        barrier()
+        k4 = ctx.prof_read()["tonecorr"]
+        ctx.prof_enable(False)
 
-    # ---- what the batch contained (outside the timed region) ----------------
-    lanes[0]["ctx"].pipeline_batch_into(batches[0], lanes[0]["cands"], lanes[0]["npk"], lanes[0]["out"], max_per_frame=1)
-    torch.cuda.synchronize()
-    cands = np.frombuffer(lanes[0]["cands"].cpu().numpy().tobytes(), N.CAND_DTYPE).reshape(B, -1)
-    npk = lanes[0]["npk"].cpu().numpy()
-    out = np.frombuffer(lanes[0]["out"].cpu().numpy().tobytes(), N.DEMOD_DTYPE).reshape(B, 1)
-    top_lin = np.array([cands[b, 0]["m_type"] == 0 if npk[b] > 0 else False for b in range(B)])
-    live = npk > 0
-    worth = out[:, 0]["worth_a_try"] > 0
-    nlive, nlin, nworth = int(live.sum()), int((live & top_lin).sum()), int(worth.sum())
-    # hypotheses the reference resolves per candidate: S0 5, S1 5, S2 2 (linear), S3 5, S4 5, S5 17
-    fine_hyps = 10 * nlive + 2 * nlin + 27 * nworth
-    # correlations the kernels run: the stage winner repeated by S1/S3/S4 and by try 0 of S5 is carried
-    # (both forms since round 3), S0's last lag is its first one symbol later
-    reuse_on = ctx.get_option("reuse") != 0
-    fine_corr = fine_hyps - ((nlive + 3 * nworth) if reuse_on else 0) - nlive
-    # binary32 operations those correlations need: 8 per sample, tone and hypothesis; the per-symbol
-    # phasor recurrences (6) only where the algorithm cannot share them: the two drift tries of S2, and since round 4
-    # ONE recurrence per mirrored symbol pair of the two (k4_pair.hip: 163 pair-rows for 2 x 162 symbols; the candidates
-    # of this workload come from an FDR with maxdrift = 0, so every linear one is mirrored)
-    ops_step = float(fine_corr) * OPS_MAC + (163.0 / 162.0) * nlin * OPS_PHASOR
+        # ---- what the batch contained (outside the timed region) ----------------
+        lanes[0]["ctx"].pipeline_batch_into(batches[0], lanes[0]["cands"], lanes[0]["npk"], lanes[0]["out"], max_per_frame=1)
+        torch.cuda.synchronize()
+        cands = np.frombuffer(lanes[0]["cands"].cpu().numpy().tobytes(), N.CAND_DTYPE).reshape(B, -1)
+        npk = lanes[0]["npk"].cpu().numpy()
+        out = np.frombuffer(lanes[0]["out"].cpu().numpy().tobytes(), N.DEMOD_DTYPE).reshape(B, 1)
+        top_lin = np.array([cands[b, 0]["m_type"] == 0 if npk[b] > 0 else False for b in range(B)])
+        live = npk > 0
+        worth = out[:, 0]["worth_a_try"] > 0
+        nlive, nlin, nworth = int(live.sum()), int((live & top_lin).sum()), int(worth.sum())
+        # hypotheses the reference resolves per candidate: S0 5, S1 5, S2 2 (linear), S3 5, S4 5, S5 17
+        fine_hyps = 10 * nlive + 2 * nlin + 27 * nworth
+        # correlations the kernels run: the stage winner repeated by S1/S3/S4 and by try 0 of S5 is carried
+        # (both forms since round 3), S0's last lag is its first one symbol later
+        reuse_on = ctx.get_option("reuse") != 0
+        fine_corr = fine_hyps - ((nlive + 3 * nworth) if reuse_on else 0) - nlive
+        # binary32 operations those correlations need: 8 per sample, tone and hypothesis; the per-symbol
+        # phasor recurrences (6) only where the algorithm cannot share them: the two drift tries of S2, and since round 4
+        # ONE recurrence per mirrored symbol pair of the two (k4_pair.hip: 163 pair-rows for 2 x 162 symbols; the candidates
+        # of this workload come from an FDR with maxdrift = 0, so every linear one is mirrored)
+        ops_step = float(fine_corr) * OPS_MAC + (163.0 / 162.0) * nlin * OPS_PHASOR
 
-    # host tail alone: de-interleave + Fano on the persistent pool (all the cores this process may use),
-    # one call per 256-record batch as the pipeline makes them
-    nthr = G.host_threads()                  # affinity and cgroup CPU quota applied
-    G.decode_batch(out[:8, 0], nthreads=nthr)
-    _, _, okv = G.decode_batch(out[:, 0], nthreads=nthr)
-    ht = []
-    for _ in range(7):
-        t_h = time.perf_counter()
-        for _k in range(8):
-            G.decode_batch(out[:, 0], nthreads=nthr)
-        ht.append(8 * B / (time.perf_counter() - t_h))
-    host_tail = {"records": int(B), "decoded": int(okv.sum()), "threads": nthr, "calls_per_repeat": 8,
-                 "records_per_s": float(np.median(ht)), "min": min(ht), "max": max(ht)}
+        # host tail alone: de-interleave + Fano on the persistent pool (all the cores this process may use),
+        # one call per 256-record batch as the pipeline makes them
+        nthr = G.host_threads()                  # affinity and cgroup CPU quota applied
+        G.decode_batch(out[:8, 0], nthreads=nthr)
+        _, _, okv = G.decode_batch(out[:, 0], nthreads=nthr)
+        ht = []
+        for _ in range(7):
+            t_h = time.perf_counter()
+            for _k in range(8):
+                G.decode_batch(out[:, 0], nthreads=nthr)
+            ht.append(8 * B / (time.perf_counter() - t_h))
+        host_tail = {"records": int(B), "decoded": int(okv.sum()), "threads": nthr, "calls_per_repeat": 8,
+                     "records_per_s": float(np.median(ht)), "min": min(ht), "max": max(ht)}
 
     # ---- lazy jiggered shifts: only try 0 (fused form) ----
     lazy = None
-    if rank == 0 and not args.no_lazy:
+    if full and rank == 0 and not args.no_lazy:
         torch.cuda.synchronize()
         lazy_by_lanes = {}
         lz = None
@@ -665,7 +716,7 @@ def main():
         dist.barrier()
 
     # a host copy of one batch: for the host-pointer legs and for cpu_baseline (which --no-host-legs alone does not switch off)
-    frames_cpu = batches[0].cpu().numpy() if (rank == 0 and world == 1 and not (args.no_host_legs and args.no_cpu)) else None
+    frames_cpu = batches[0].cpu().numpy() if (full and rank == 0 and world == 1 and not (args.no_host_legs and args.no_cpu)) else None
     # the same batch handed over as HOST buffers (what a GNU Radio block does per PDU batch):
     # H2D of the frames + D2H of every result, PCIe inclusive; never `value`
     host_rate = None
@@ -824,7 +875,7 @@ def main():
     pmc = None
     tpath = os.path.join(ROOT, "profiles", "k4_traffic.json")
     traffic_stale = None
-    if os.path.exists(tpath):                 # PMC passes taken with rocprofv3 on this workload (tools/run_profiles.sh)
+    if full and os.path.exists(tpath):        # PMC passes taken with rocprofv3 on this workload (tools/run_profiles.sh)
         pmc = json.load(open(tpath))
         if pmc.get("library_sources_sha256") != N.source_digest():
             # counters of ANOTHER build say nothing about this one: loud, and no figure rather than a stale one
@@ -835,13 +886,6 @@ def main():
                 print("WARNING: " + traffic_stale, file=sys.stderr)
             pmc = None
     if rank == 0:
-        k4_ms_step = k4["ms"] / n1
-        k4_launch_ms = k4["ms"] / max(k4["launches"], 1)
-        achieved_tops = ops_step / (k4_ms_step * 1e-3) / 1e12 if k4_ms_step > 0 else 0.0
-        eff_gbs = fine_corr * HYP_BYTES / (k4_ms_step * 1e-3) / 1e9 if k4_ms_step > 0 else 0.0
-        kern = {k: {"ms_per_step": v["ms"] / n1, "launches_per_step": v["launches"] / n1} for k, v in prof.items()}
-        kern["tonecorr"] = {"ms_per_step": k4_ms_step, "launches_per_step": k4["launches"] / n1}
-        pm = (pmc or {}).get("fused" if fused else "staged", {}) if pmc else {}
         result = {
             "metric": "2-min WSPR frames decoded/sec (coarse+sync)",
             "value": frames_per_step * K / dt,
@@ -869,11 +913,7 @@ def main():
                                                      ("%d (sharded round-robin, %d per GPU)" % (args.total_frames, Bmax))
                                                      if strong else ("%d per GPU" % B), args.snr),
                        "frames_per_gpu": B, "distinct_batches": nb, "bytes_of_distinct_frames": nb * B * 360000,
-                       "candidates_per_frame_mean": float(npk.mean()),
-                       "fine_hypotheses_per_step": fine_hyps,
-                       "fine_correlations_run_per_step": fine_corr,
-                       "coarse_hypotheses_per_step": int(npk.sum()) * 130 * ctx.info.cell_hyps,
-                       "top_candidate_decodes": int(okv.sum()), "parallelism": "dp%d" % world,
+                       "parallelism": "dp%d" % world,
                        "sched": "fused (k6_sched)" if fused else "staged (k4_* + k5_fold_step)",
                        "streams_per_gpu": ns,
                        "trial_ms_per_step": {("%s x%d streams" % ("fused" if f else "staged", s)): 1e3 * v / KT
@@ -883,6 +923,22 @@ def main():
                        "rccl_version": rccl_version(torch),
                        "gather": gather_how, "gather_equals_torch_gather": gather_checked,
                        "gathered_slabs_sha256": gathered_sha},
+            "host_enqueue_ms_per_step": 1e3 * t_enq / K,
+        }
+    if full and rank == 0:
+        k4_ms_step = k4["ms"] / n1
+        k4_launch_ms = k4["ms"] / max(k4["launches"], 1)
+        achieved_tops = ops_step / (k4_ms_step * 1e-3) / 1e12 if k4_ms_step > 0 else 0.0
+        eff_gbs = fine_corr * HYP_BYTES / (k4_ms_step * 1e-3) / 1e9 if k4_ms_step > 0 else 0.0
+        kern = {k: {"ms_per_step": v["ms"] / n1, "launches_per_step": v["launches"] / n1} for k, v in prof.items()}
+        kern["tonecorr"] = {"ms_per_step": k4_ms_step, "launches_per_step": k4["launches"] / n1}
+        pm = (pmc or {}).get("fused" if fused else "staged", {}) if pmc else {}
+        result["config"].update({"candidates_per_frame_mean": float(npk.mean()),
+                                 "fine_hypotheses_per_step": fine_hyps,
+                                 "fine_correlations_run_per_step": fine_corr,
+                                 "coarse_hypotheses_per_step": int(npk.sum()) * 130 * ctx.info.cell_hyps,
+                                 "top_candidate_decodes": int(okv.sum())})
+        result.update({
             "roofline": {"kernel": "k6_sched" if fused else "k4_* (6 launches)", "bound": "valu_fp32_nofma",
                          "achieved": achieved_tops, "peak": FP32_NOFMA_PEAK_TOPS, "unit": "Top/s",
                          "frac": achieved_tops / FP32_NOFMA_PEAK_TOPS,
@@ -912,15 +968,14 @@ def main():
             "end_to_end_decoded": e2e,
             "host_stream_pcie_inclusive": stream_leg,
             "host_tail_fano": host_tail,
-            "host_enqueue_ms_per_step": 1e3 * t_enq / K,
-        }
+        })
 
     if rank == 0:
         for (f, s_), v in sorted(trials.items()):       # top-level scalars: the driver's record keeps them
             result["trial_%s_x%d_ms" % ("fused" if f else "staged", s_)] = 1e3 * v / KT
 
     # ---- configs[2]: the (freq, lag, drift) sweep, N=1 only -----------------
-    if rank == 0 and world == 1 and not args.no_sweep and not strong:
+    if full and rank == 0 and world == 1 and not args.no_sweep and not strong:
         from gr_uwspr_amd import sweep as SW
         Bs = args.sweep_frames
         del batches
@@ -977,7 +1032,7 @@ def main():
     # noisy copies of every SNR are sharded round-robin over the ranks (copy s on rank s mod N), every rank decodes its
     # shard on ITS share of the host's CPUs (uwspr_host_set_ranks), and the counts are added up: SUM of frames / decodes,
     # MAX of the ranks' times -- no data-path exchange, three small all-reduces at the end.
-    c4_seeds = args.configs4_seeds
+    c4_seeds = args.configs4_seeds if full else 0
     if c4_seeds < 0:
         c4_seeds = 64 if (not args.no_host_legs and not strong and (world > 1 or not args.no_cpu)) else 0
     if c4_seeds > 0:
@@ -1035,9 +1090,10 @@ def main():
                               "gpu_equals_lazy": bool(okf[1 + i] == 1.0),
                               "gpu_frames_per_s": cnt[i, 0] / max(tim[i, 0], 1e-9),
                               "gpu_lazy_frames_per_s": cnt[i, 0] / max(tim[i, 1], 1e-9)} for i in range(nsn)]}
-    if rank == 0:
+    if full and rank == 0:
         result["parity_spot_check"] = parity_spot_check(spot_snap, D, N, "fused" if fused else "staged") if spot_snap else None
         result["cpu_baseline"] = cpu_baseline(frames_cpu[:256]) if frames_cpu is not None else None
+    if rank == 0:
         print(json.dumps(result))
         sys.stdout.flush()
     if dist.is_initialized():

@@ -4,7 +4,8 @@
 // recv + p * bytes, the root's self copy, who sends and who receives, root != 0, error propagation -- can run with
 // world > 1 on a box with ONE GPU (RCCL itself refuses two ranks on one device).
 //
-// Transport: one UNIX stream socket per rank, <base>.<rank>, base = the path in the unique id.  The operations of a
+// Transport: one UNIX stream socket per rank in the abstract namespace (no file, so no limit from the length of a
+// directory name: sun_path holds 108 bytes), named <base>.<rank>, base = the name in the unique id.  The operations of a
 // group are queued and executed at ncclGroupEnd: hipStreamSynchronize(stream) (what was enqueued before the gather
 // has finished, as it would have on the stream), then sends = D2H copy + connect + write, receives = accept + read +
 // H2D copy, matched by the sender's rank.  Synchronous where RCCL is asynchronous; a peer that never shows up is a
@@ -99,7 +100,7 @@ sockaddr_un addr_of(const std::string &base, int rank) {
   sockaddr_un a;
   memset(&a, 0, sizeof(a));
   a.sun_family = AF_UNIX;
-  snprintf(a.sun_path, sizeof(a.sun_path), "%s.%d", base.c_str(), rank);
+  snprintf(a.sun_path + 1, sizeof(a.sun_path) - 1, "%s.%d", base.c_str(), rank);   // sun_path[0] = 0: abstract
   return a;
 }
 
@@ -187,11 +188,9 @@ extern "C" {
 int ncclGetUniqueId(uid_t128 *id) {
   if (!id) return kInvalidArgument;
   memset(id, 0, sizeof(*id));
-  const char *dir = getenv("FAKE_RCCL_DIR");
   struct timeval tv;
   gettimeofday(&tv, nullptr);
-  snprintf(id->internal, sizeof(id->internal), "%s/fake_rccl_%d_%ld%06ld", dir ? dir : "/tmp", (int)getpid(), (long)tv.tv_sec,
-           (long)tv.tv_usec);
+  snprintf(id->internal, sizeof(id->internal), "fake_rccl_%d_%ld%06ld", (int)getpid(), (long)tv.tv_sec, (long)tv.tv_usec);
   return kOk;
 }
 
@@ -200,7 +199,6 @@ int ncclCommInitRank(void **out, int nranks, uid_t128 id, int rank) {
   id.internal[127] = 0;
   comm *c = new comm{rank, nranks, std::string(id.internal), -1, {}};
   const sockaddr_un a = addr_of(c->base, rank);
-  unlink(a.sun_path);
   c->lfd = socket(AF_UNIX, SOCK_STREAM, 0);
   if (c->lfd < 0 || bind(c->lfd, (const sockaddr *)&a, sizeof(a)) != 0 || listen(c->lfd, 64) != 0) {
     if (c->lfd >= 0) close(c->lfd);
@@ -214,9 +212,7 @@ int ncclCommInitRank(void **out, int nranks, uid_t128 id, int rank) {
 int ncclCommDestroy(void *p) {
   comm *c = (comm *)p;
   if (!c) return kInvalidArgument;
-  close(c->lfd);
-  const sockaddr_un a = addr_of(c->base, c->rank);
-  unlink(a.sun_path);
+  close(c->lfd);                                     // (an abstract socket goes with its last descriptor)
   delete c;
   return kOk;
 }

@@ -127,7 +127,8 @@ def test_c_abi_gather_equals_the_torch_gather_on_one_rank(G, monkeypatch):
 
 
 def _bench_line(extra, timeout=420):
-    """One `bench.py` run as the driver starts it (a child process; rank 0's JSON line on stdout)."""
+    """One `bench.py --full` run as the driver starts it (a child process; rank 0's JSON line on stdout): the gathered
+    slabs' digest, the spot check and the configs[4] leg are --full legs."""
     import json
     import subprocess
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", MASTER_ADDR="127.0.0.1")
@@ -135,7 +136,7 @@ def _bench_line(extra, timeout=420):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--repeats", "1",
            "--total-frames", "50", "--sched", "staged", "--streams", "2", "--no-cpu", "--no-sweep", "--no-lazy",
-           "--no-host-legs"] + extra
+           "--no-host-legs", "--full"] + extra
     r = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=timeout, cwd=ROOT)
     assert r.returncode == 0, r.stderr.decode()[-2000:]
     lines = [ln for ln in r.stdout.decode().splitlines() if ln.startswith("{")]
@@ -226,7 +227,7 @@ def _run_world(exe, world, root, rows, mode, tmp_path, timeout_s=60):
     tag = "w%d_r%d_%s" % (world, root, mode)
     import gr_uwspr_amd as G
     env = dict(os.environ, LD_LIBRARY_PATH=os.pathsep.join([FAKE_DIR, G.native.LIBDIR, os.environ.get("LD_LIBRARY_PATH", "")]),
-               FAKE_RCCL_DIR=str(tmp_path), FAKE_RCCL_LOG=str(tmp_path / ("ops_" + tag)), FAKE_RCCL_TIMEOUT_S=str(timeout_s))
+               FAKE_RCCL_LOG=str(tmp_path / ("ops_" + tag)), FAKE_RCCL_TIMEOUT_S=str(timeout_s))
     env.pop("UWSPR_OPTIONS", None)
     uidfile = str(tmp_path / ("uid_" + tag))
     t0 = time.time()

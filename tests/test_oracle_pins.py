@@ -41,17 +41,22 @@ def test_slm_against_real_reference_table(oracle):
                 assert a.tobytes() == tab[i, ci, t].tobytes(), (i, cf, t)
 
 
-def test_slm_against_live_reference(oracle):
+@pytest.fixture(scope="module")
+def live_ref():
+    """What the real reference returned on the inputs of the live tests (tests/golden/make_live_ref.py): the answers
+    those tests use where oracle/_ref is not built."""
+    return np.load(os.path.join(GOLDEN, "live_ref.npz"))
+
+
+def test_slm_against_live_reference(oracle, live_ref):
     R = oracle.ref()
-    if R is None:
-        pytest.skip("oracle/_ref not built (no /root/reference here)")
     rng = np.random.default_rng(3)
-    for _ in range(2000):
+    for i in range(2000):
         V1, V2 = rng.uniform(-3, 3, 2)
         p1, p2 = int(rng.integers(-50, 50)), int(rng.integers(0, 900))
         t = float(rng.integers(0, 120))
         a = np.float32(oracle.slm_frequency_drift(V1, V2, p1, p2, 1500.0, t))
-        b = np.float32(R.ref_slm_frequency_drift(V1, V2, p1, p2, 1500.0, t))
+        b = np.float32(R.ref_slm_frequency_drift(V1, V2, p1, p2, 1500.0, t)) if R is not None else live_ref["slm_out"][i]
         assert a.tobytes() == b.tobytes()
 
 
@@ -103,23 +108,28 @@ def test_ve3emb_fdr_known_answer(oracle, ve3emb, known):
     assert lin_drift == k2["drift"]
 
 
-def test_ve3emb_decodes_through_real_reference_fano(oracle, ve3emb, known):
-    """oracle FDR -> oracle schedule -> soft symbols -> REAL lib/Fano.cc -> REAL unpk_."""
-    if oracle.ref() is None:
-        pytest.skip("oracle/_ref not built")
+def test_ve3emb_decodes_through_real_reference_fano(oracle, ve3emb, known, live_ref):
+    """oracle FDR -> oracle schedule -> soft symbols -> REAL lib/Fano.cc -> REAL unpk_ (where oracle/_ref is not
+    built: the symbols must be those the real Fano was run on, and its answers are the stored ones)."""
+    live = oracle.ref() is not None
     c = oracle.FDR().transform(ve3emb)[0]
     d = oracle.demod_candidate(c, 1500, ve3emb)
     assert d["worth_a_try"] == 1
     blob = None
     for idt in range(17):
         if d["jig_sync"][idt] > 0.12 and d["jig_rms"][idt] > 40.625:
-            rc, data, _, _ = oracle.ref_fano_decode(oracle.deinterleave(d["symbols"][idt]))
+            x = oracle.deinterleave(d["symbols"][idt])
+            if live:
+                rc, data, _, _ = oracle.ref_fano_decode(x)
+            else:
+                assert np.asarray(x, np.uint8).tobytes() == live_ref["ve3emb_symbols"][idt].tobytes(), idt
+                rc, data = int(live_ref["ve3emb_rc"][idt]), live_ref["ve3emb_data"][idt]
             if rc == 0:
                 blob = data[:7]
                 break
     assert blob is not None and bytes(blob).hex() == known["blob_hex"]
     msg = [int(x) - 256 if x > 127 else int(x) for x in blob]
-    assert oracle.ref_unpk(msg) == known["message"]
+    assert (oracle.ref_unpk(msg) if live else str(live_ref["ve3emb_message"])) == known["message"]
 
 
 def test_nonlinear_t0_equivalence(oracle, ve3emb):

@@ -9,7 +9,7 @@ for rep in 1 2; do
     i=$((i+1))
     if [ "$fl" = "-" ]; then export UWSPR_EXTRA_HIPFLAGS=""; else export UWSPR_EXTRA_HIPFLAGS="$fl"; fi
     python3 -c "import gr_uwspr_amd as G; G.build()" 2>/dev/null
-    timeout -k 10 200 python3 bench.py --steps 240 --warmup 24 --no-cpu --no-sweep --no-lazy --no-host-legs > $O/${i}_$rep.log 2>&1
+    timeout -k 10 200 python3 bench.py --steps 240 --warmup 24 --no-cpu --no-sweep --no-lazy --no-host-legs --full > $O/${i}_$rep.log 2>&1
     python3 - "$O/${i}_$rep.log" "$fl" >> $O/summary.txt <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

@@ -15,7 +15,7 @@ for rep in 1 2; do
   for ns in 1 2 3; do
     for form in lib exp; do
       if [ $form = exp ]; then export UWSPR_EXTRA_HIPFLAGS="$EXP"; export UWSPR_OPTIONS=sched_grid=512; else unset UWSPR_EXTRA_HIPFLAGS; unset UWSPR_OPTIONS; fi
-      timeout -k 10 200 python3 bench.py --steps 200 --warmup 20 --no-cpu --no-sweep --no-lazy --no-host-legs --sched fused --streams $ns \
+      timeout -k 10 200 python3 bench.py --steps 200 --warmup 20 --no-cpu --no-sweep --no-lazy --no-host-legs --full --sched fused --streams $ns \
           > $O/${form}_x${ns}_r$rep.json 2> $O/${form}_x${ns}_r$rep.err
       python3 - $form $ns $O/${form}_x${ns}_r$rep.json <<'PY' | tee -a $O/summary.txt
 import json, sys

@@ -9,7 +9,7 @@ for rep in 1 2; do
   i=0
   for setting in "$@"; do
     i=$((i+1))
-    env $setting timeout -k 10 200 python3 bench.py --steps 200 --warmup 20 --no-cpu --no-sweep --no-lazy --no-host-legs \
+    env $setting timeout -k 10 200 python3 bench.py --steps 200 --warmup 20 --no-cpu --no-sweep --no-lazy --no-host-legs --full \
         --sched ${SCHED:-staged} --streams ${STREAMS:-3} > $O/s${i}_r$rep.json 2> $O/s${i}_r$rep.err
     python3 - "$setting" $O/s${i}_r$rep.json <<'PY'
 import json, sys

@@ -18,7 +18,7 @@ python3 tools/prof_summary.py $P/pmc_write_$form | sed -n '/counters/,$p'
 python3 tools/prof_summary.py $P/pmc_sq_$form | sed -n '/counters/,$p'
 done
 echo
-echo "# ===== default bench.py (form and streams by its own trial) ====="
+echo "# ===== bench.py --full (form and streams by its own trial) ====="
 python3 tools/prof_summary.py $P/trace_default
 echo
 echo "# FETCH_SIZE calibration (tools/fetch_calib.hip)"

@@ -16,7 +16,7 @@ for form in fused staged; do
   timeout -k 10 300 rocprofv3 --pmc GRBM_GUI_ACTIVE SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_WAIT_INST_ANY SQ_WAIT_ANY SQ_ACTIVE_INST_ANY --kernel-trace --output-format csv -d $OUT/pmc_sq_$form -- $B --steps 3 --warmup 1 > $OUT/pmc_sq_$form.log 2>&1
   echo "$form done"
 done
-timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_default -- python3 bench.py --steps 20 --warmup 3 --no-cpu > $OUT/trace_default.log 2>&1
+timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_default -- python3 bench.py --steps 20 --warmup 3 --no-cpu --full > $OUT/trace_default.log 2>&1
 timeout -k 10 120 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $OUT/calib_fetch -- /tmp/fetch_calib > $OUT/calib.log 2>&1
-timeout -k 10 400 python3 bench.py > $OUT/bench_plain.log 2>&1
+timeout -k 10 400 python3 bench.py --full > $OUT/bench_plain.log 2>&1
 echo done
