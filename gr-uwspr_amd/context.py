@@ -15,6 +15,14 @@ def _is_torch(x):
     return hasattr(x, "data_ptr") and hasattr(x, "is_cuda")
 
 
+def _audio_array(x):
+    """a 1-D contiguous float32 or int16 numpy array, as it is (no conversion: the library reads both)"""
+    a = np.asarray(x)
+    if a.ndim != 1 or a.dtype not in (np.float32, np.int16):
+        raise TypeError("audio: a 1-D float32 or int16 array, not %s %s" % (a.dtype, a.shape))
+    return np.ascontiguousarray(a)
+
+
 class FrameView:
     """B frames that are not a contiguous [B, fl, 2] array: either a raw device pointer (what
     stream_take_view returns: frames in place in the stream buffer) or a host array holding a stretch
@@ -287,6 +295,36 @@ class Context:
             a = np.ascontiguousarray(iq, np.float32)
             self._chk(self.L.uwspr_stream_push(self.h, C.c_void_p(a.ctypes.data), a.size // 2, N.HOST, C.byref(n)))
         return n.value
+
+    def stream_push_audio(self, x, where="host"):
+        """Append 12 kS/s real audio (uwspr_stream_push_audio): a 1-D numpy float32 or int16 array, or a torch CUDA
+        float32 / int16 tensor; -> frames ready.  Stream sample m is the front-end's output at audio index 32 m.
+        A page-locked array (host_alloc) goes as one DMA; where="async" only enqueues it (keep it unchanged until
+        stream_wait_uploads())."""
+        n = C.c_int(0)
+        if _is_torch(x):
+            import torch
+            fmt = {torch.float32: N.AUDIO_F32, torch.int16: N.AUDIO_S16}.get(x.dtype)
+            if fmt is None or x.dim() != 1 or not x.is_cuda:
+                raise TypeError("stream_push_audio: a 1-D float32 or int16 CUDA tensor, not %s %s" % (x.dtype, tuple(x.shape)))
+            copied = not x.is_contiguous()
+            x = x.contiguous()
+            if self._stream_ptr is None:
+                torch.cuda.current_stream(x.device).synchronize()
+            self._chk(self.L.uwspr_stream_push_audio(self.h, C.c_void_p(x.data_ptr()), x.numel(), fmt, N.DEVICE, C.byref(n)))
+            if copied:   # the copy stream reads the temporary after this call returns: keep it until it has
+                self.stream_wait_uploads()
+            return n.value
+        a = _audio_array(x)
+        self._chk(self.L.uwspr_stream_push_audio(self.h, C.c_void_p(a.ctypes.data), a.size,
+                                                 N.AUDIO_S16 if a.dtype == np.int16 else N.AUDIO_F32,
+                                                 {"host": N.HOST, "async": N.HOST_ASYNC}[where], C.byref(n)))
+        return n.value
+
+    def stream_reset(self, pos=0):
+        """uwspr_stream_reset: drop what is buffered; the next sample pushed has stream index pos (audio: audio
+        index 32 pos, after a zero history)"""
+        self._chk(self.L.uwspr_stream_reset(self.h, int(pos)))
 
     def stream_take(self, nframes, into):
         """The next nframes frames into a torch CUDA float32 tensor [nframes, fl, 2]; -> stream
@@ -605,6 +643,12 @@ class Pipe:
         a = np.ascontiguousarray(iq, np.float32)
         self._chk(self.L.uwspr_pipe_push(self.h, C.c_void_p(a.ctypes.data), a.size // 2))
 
+    def push_audio(self, x):
+        """12 kS/s real audio (uwspr_pipe_push_audio): a 1-D numpy float32 or int16 array of any length"""
+        a = _audio_array(x)
+        self._chk(self.L.uwspr_pipe_push_audio(self.h, C.c_void_p(a.ctypes.data), a.size,
+                                               N.AUDIO_S16 if a.dtype == np.int16 else N.AUDIO_F32))
+
     def acquire(self, nsamples):
         """-> numpy view [nsamples, 2] of the page-locked staging buffer to fill; then commit(nsamples)."""
         ptr = C.c_void_p()
@@ -644,3 +688,50 @@ class Pipe:
         st = N.PipeStats()
         self._chk(self.L.uwspr_pipe_get_stats(self.h, C.byref(st)))
         return {k: getattr(st, k) for k, _ in N.PipeStats._fields_}
+
+
+# ---- recordings ---------------------------------------------------------------------------------------------------
+AUDIO_RATE = 12000
+
+
+def read_wav(path):
+    """A 16-bit PCM WAV (stdlib wave) -> (channel 0 as int16, rate).  Anything else -- another sample width, a float
+    WAV, a rate other than the front-end's 12000 S/s -- raises ValueError."""
+    import wave
+    try:
+        w = wave.open(str(path), "rb")
+    except wave.Error as e:   # e.g. "unknown format: 3" = IEEE float
+        raise ValueError("%s: not a 16-bit PCM WAV (%s)" % (path, e)) from None
+    with w:
+        width, nch, rate, n = w.getsampwidth(), w.getnchannels(), w.getframerate(), w.getnframes()
+        if width != 2:
+            raise ValueError("%s: %d-bit samples; 16-bit PCM only" % (path, 8 * width))
+        if rate != AUDIO_RATE:
+            raise ValueError("%s: %d S/s; the front-end takes %d S/s" % (path, rate, AUDIO_RATE))
+        raw = w.readframes(n)
+    x = np.frombuffer(raw, dtype="<i2").reshape(-1, nch)[:, 0]
+    return np.ascontiguousarray(x, dtype=np.int16), rate
+
+
+def decode_wav(path, **pipe_opts):
+    """Decode a 12 kS/s recording as the receiver flowgraph does (examples/AudioSourceDecode.grc): the file through a
+    Pipe's push_audio -> one dict per decoded record, in frame order: frame, t (stream_pos / 375 s), the coarse freq
+    and snr, and the unpacked text."""
+    x, _ = read_wav(path)
+    pipe = Pipe(**pipe_opts)
+    try:
+        piece = 12000 * 60
+        for k in range(0, x.size, piece):
+            pipe.push_audio(x[k:k + piece])
+        pipe.flush()
+        recs = pipe.collect(cap=1 << 20)
+    finally:
+        pipe.close()
+    out = []
+    for r in recs:
+        if not r["decoded"]:
+            continue
+        out.append({"frame": int(r["frame"]), "t": int(r["stream_pos"]) / 375.0,
+                    "freq": float(r["coarse"]["freq"]), "snr": float(r["coarse"]["snr"]),
+                    "text": unpack_message(r["message"])[1]})
+    return out

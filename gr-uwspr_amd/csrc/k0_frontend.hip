@@ -40,6 +40,7 @@ constexpr int K0_DEC = 32;
 constexpr int K0_WG = 1024;             // 16 wavefronts x 2 tap phases
 constexpr int K0_R = 8;                 // outputs per lane
 constexpr int K0_OUT = 64 * K0_R;       // outputs per workgroup
+constexpr int K0_COMPACT_D = 512;       // read-ahead of the compact mode (the grc mode's is 0)
 
 __host__ __device__ constexpr int k0_L(int J) { return 64 + J / 8; }          // column groups per row segment
 __host__ __device__ constexpr int k0_row(int J) { return 8 * k0_L(J) + 1; }   // floats per polyphase row (+1: the loader's lanes hit 32 banks)
@@ -60,28 +61,37 @@ __device__ __forceinline__ void k0_block(float (&ar)[K0_R], float (&ai)[K0_R], c
   }
 }
 
-// taps: [32][J] float2, taps[p][jj] = g[32 (J - 1 - jj) + p] (zero beyond the filter); dcols = D / 32
-__global__ __launch_bounds__(K0_WG) void k0_frontend(const float *__restrict__ audio, int nin,
+// a sample as the filter sees it: float as it is, int16 scaled by 2^-15 (exact; GNU Radio's wavfile_source)
+__device__ __forceinline__ float k0_sample(float v) { return v; }
+__device__ __forceinline__ float k0_sample(int16_t v) { return (float)v * (1.0f / 32768); }
+
+// taps: [32][J] float2, taps[p][jj] = g[32 (J - 1 - jj) + p] (zero beyond the filter); dcols = D / 32.
+// Origins: audio[b][0] is sample in0 of its record and out[b][0] is output m_first, i.e. out[b][i] = y[m_first + i]
+// reads audio[b][n - in0]; samples outside [in0, in0 + nin) count as zero.  The batch call passes 0 and 0, the
+// stream form the absolute audio index of its buffer and the decimated index of the ring slot it writes.  An output's
+// arithmetic is the same wherever it falls in a workgroup or a launch (the tap order is fixed per output).
+template <typename T>
+__global__ __launch_bounds__(K0_WG) void k0_frontend(const T *__restrict__ audio, int nin, long long in0,
                                                      const float2 *__restrict__ taps, float2 *__restrict__ out,
-                                                     int nout, int J, int dcols) {
+                                                     int nout, long long m_first, int J, int dcols) {
   extern __shared__ __align__(16) float k0_lds[];
   const int L = k0_L(J), ROW = k0_row(J);
   float *xs = k0_lds;
   float2 *tp = reinterpret_cast<float2 *>(k0_lds + K0_DEC * ROW);   // (32 ROW floats: a multiple of 8 bytes)
   const int b = blockIdx.y, tid = threadIdx.x;
-  const int m0 = blockIdx.x * K0_OUT;
-  const float *x = audio + (size_t)b * nin;
+  const long long m0 = m_first + (long long)blockIdx.x * K0_OUT;
+  const T *x = audio + (size_t)b * nin;
   // Output m, tap k = 32 j + p reads n = 32 (m - j + dcols) - p: row (32 - p) mod 32, column m - j + dcols - (p > 0).
   // With cb = m0 - J + dcols the workgroup's rows start at column cb; row 0 is stored one column late, so that for
   // every phase the sample of (output m0 + o, tap jj = J - 1 - j) sits at position o + jj of its row.
-  const int cb = m0 - J + dcols;
+  const long long cb = m0 - J + dcols;
   const int span = K0_DEC * (K0_OUT + J);
   for (int e = tid; e < span; e += K0_WG) {
     const int r = e & (K0_DEC - 1);
     const int pos = (e >> 5) - (r == 0 ? 1 : 0);
     if (pos < 0) continue;
-    const long n = (long)K0_DEC * cb + e;
-    const float v = (n >= 0 && n < nin) ? x[n] : 0.0f;
+    const long long n = (long long)K0_DEC * cb + e - in0;   // index into this buffer
+    const float v = (n >= 0 && n < nin) ? k0_sample(x[n]) : 0.0f;
     xs[r * ROW + (pos & 7) * L + (pos >> 3)] = v;
   }
   for (int i = tid; i < K0_DEC * J; i += K0_WG) tp[i] = taps[i];
@@ -127,7 +137,7 @@ __global__ __launch_bounds__(K0_WG) void k0_frontend(const float *__restrict__ a
       const float2 q = part[(ww * K0_R + i) * 64 + l];
       re += q.x; im += q.y;
     }
-    const int m = m0 + K0_R * l + i;
+    const int m = blockIdx.x * K0_OUT + K0_R * l + i;
     if (m < nout) out[(size_t)b * nout + m] = make_float2(re, im);
   }
 }
@@ -219,7 +229,7 @@ int frontend_design(int mode, int stage, std::vector<double> &outv, int *delay) 
   if (mode == UWSPR_FRONTEND_COMPACT) {
     if (stage != 0) return UWSPR_ERR_ARG;
     // h[k] e^{-j pi (D - k) / 4}: Hamming-windowed sinc, cutoff 100 Hz, 1025 taps, unit DC gain, D = 512
-    const int NT = 1025, D = 512;
+    const int NT = 1025, D = K0_COMPACT_D;
     std::vector<double> h(NT);
     const double fc = 100.0 / 12000.0;
     double sum = 0.0;
@@ -279,17 +289,48 @@ int frontend_tap_image(int mode, std::vector<float> &img, int *J_out, int *dcols
   return (D % K0_DEC) ? UWSPR_ERR_ARG : UWSPR_OK;
 }
 
+int frontend_read_ahead(int mode) {
+  return mode == UWSPR_FRONTEND_COMPACT ? K0_COMPACT_D : mode == UWSPR_FRONTEND_GRC ? 0 : -1;
+}
+
 int frontend_prepare() {
-  // up to 160 KB of dynamic LDS (149 KB in the grc mode)
-  return hipFuncSetAttribute(reinterpret_cast<const void *>(k0_frontend), hipFuncAttributeMaxDynamicSharedMemorySize,
+  // up to 160 KB of dynamic LDS (149 KB in the grc mode); int16 samples are widened before they reach LDS
+  return hipFuncSetAttribute(reinterpret_cast<const void *>(k0_frontend<float>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                             160 * 1024) == hipSuccess &&
+         hipFuncSetAttribute(reinterpret_cast<const void *>(k0_frontend<int16_t>), hipFuncAttributeMaxDynamicSharedMemorySize,
                              160 * 1024) == hipSuccess ? 0 : -1;
 }
 
 void launch_frontend(uwspr_ctx *c, const float *audio, int B, int nin, float2 *out, int nout) {
   prof_scope ps(c, UWSPR_K_SPECTROGRAM, B);
   dim3 grid((nout + K0_OUT - 1) / K0_OUT, B);
-  hipLaunchKernelGGL(k0_frontend, grid, dim3(K0_WG), k0_lds_bytes(c->fe_J), c->stream, audio, nin,
-                     (const float2 *)c->d_fe_taps, out, nout, c->fe_J, c->fe_dcols);
+  hipLaunchKernelGGL(k0_frontend<float>, grid, dim3(K0_WG), k0_lds_bytes(c->fe_J), c->stream, audio, nin, 0LL,
+                     (const float2 *)c->d_fe_taps, out, nout, 0LL, c->fe_J, c->fe_dcols);
+}
+
+// the stream form (stream_ring::push_audio): one record, outputs m_first .. m_first + nout - 1 from the buffer that
+// holds audio [in0, in0 + nin)
+void launch_frontend_stream(hipStream_t s, const void *audio, bool s16, int nin, long long in0, const float *taps,
+                            int J, int dcols, float *out, int nout, long long m_first) {
+  dim3 grid((nout + K0_OUT - 1) / K0_OUT, 1);
+  if (s16)
+    hipLaunchKernelGGL(k0_frontend<int16_t>, grid, dim3(K0_WG), k0_lds_bytes(J), s, (const int16_t *)audio, nin, in0,
+                       (const float2 *)taps, (float2 *)out, nout, m_first, J, dcols);
+  else
+    hipLaunchKernelGGL(k0_frontend<float>, grid, dim3(K0_WG), k0_lds_bytes(J), s, (const float *)audio, nin, in0,
+                       (const float2 *)taps, (float2 *)out, nout, m_first, J, dcols);
+}
+
+// int16 samples into a float stream buffer: the value K0's int16 loader computes (k0_sample)
+__global__ void k_widen_s16(const int16_t *__restrict__ in, float *__restrict__ out, size_t n) {
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
+    out[i] = k0_sample(in[i]);
+}
+
+void launch_widen_s16(hipStream_t s, const int16_t *in, float *out, size_t n) {
+  if (n == 0) return;
+  const size_t blocks = (n + 255) / 256;
+  hipLaunchKernelGGL(k_widen_s16, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), 0, s, in, out, n);
 }
 
 }  // namespace uwspr

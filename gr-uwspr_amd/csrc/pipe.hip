@@ -504,7 +504,9 @@ extern "C" int uwspr_pipe_commit(uwspr_pipe *q, int nsamples) {
   (void)hipSetDevice(q->device);
   const int s = q->stage_cur;
   q->stage_cur = -1;
+  if (nsamples > 0 && q->ring.kind == RING_AUDIO) return parg(q, "uwspr_pipe_commit: the pipe's stream is audio");
   if (nsamples > 0) {
+    q->ring.kind = RING_IQ;
     // room behind the unconsumed samples: launch what is complete first if the ring is full
     while (q->ring.have + (size_t)nsamples > q->ring.cap && q->ring.ready() > 0) {
       const int rc = launch_from_ring(q, q->ring.ready() < q->o.batch_frames ? q->ring.ready() : q->o.batch_frames);
@@ -533,6 +535,48 @@ extern "C" int uwspr_pipe_push(uwspr_pipe *q, const float *iq, int nsamples) {
     if (rc) return rc;
     memcpy(dst, iq + 2 * off, n * 2 * sizeof(float));
     if ((rc = uwspr_pipe_commit(q, (int)n))) return rc;
+    off += n;
+  }
+  return UWSPR_OK;
+}
+
+// Audio through the same page-locked staging (its bytes: batch_frames * hop (I,Q) pairs per buffer), then K0 on the
+// copy stream into the ring (stream_ring::push_audio); batches are launched from the ring as uwspr_pipe_commit does.
+extern "C" int uwspr_pipe_push_audio(uwspr_pipe *q, const void *audio, int nsamples, int format) {
+  if (!q || (nsamples > 0 && !audio) || nsamples < 0) return UWSPR_ERR_ARG;
+  if (const int f = q->failed.load()) return f;
+  if (format != UWSPR_AUDIO_F32 && format != UWSPR_AUDIO_S16) return parg(q, "uwspr_pipe_push_audio: format %d", format);
+  if (q->p.fs != 375) return parg(q, "uwspr_pipe_push_audio: the front-end is 12000 -> 375 S/s (fs=%d)", q->p.fs);
+  if (nsamples == 0) return UWSPR_OK;
+  const bool s16 = format == UWSPR_AUDIO_S16;
+  const int mode = q->lanes[0].ctx->opt[UWSPR_OPT_FRONTEND];
+  stream_ring &r = q->ring;
+  if (r.kind == RING_IQ) return parg(q, "uwspr_pipe_push_audio: the pipe's stream is (I,Q)");
+  if (r.kind == RING_AUDIO && mode != r.au.mode)
+    return parg(q, "uwspr_pipe_push_audio: option frontend changed to %d while the audio stream runs in mode %d", mode, r.au.mode);
+  (void)hipSetDevice(q->device);
+  if (const int rc = open_ingest(q)) return rc;
+  if (r.kind != RING_AUDIO && !r.audio_latch(mode, s16))
+    return pfail(q, UWSPR_ERR_HIP, "audio stream set-up: %s", hipGetErrorString(r.err));
+  const size_t es = s16 ? 2 : 4, piece = q->stage_samples * 2 * sizeof(float) / es;
+  for (size_t off = 0; off < (size_t)nsamples;) {
+    const size_t n = (size_t)nsamples - off < piece ? (size_t)nsamples - off : piece;
+    const int s = q->stage_next;
+    if (q->stage_busy[s]) { PHIP(q, hipEventSynchronize(q->stage_ev[s])); q->stage_busy[s] = false; }
+    memcpy(q->h_stage[s], (const char *)audio + off * es, n * es);
+    const size_t nout = (size_t)r.audio_outputs(n, mode);
+    while (r.have + nout > r.cap && r.ready() > 0) {
+      const int rc = launch_from_ring(q, r.ready() < q->o.batch_frames ? r.ready() : q->o.batch_frames);
+      if (rc) return rc;
+    }
+    if (!r.push_audio(q->h_stage[s], n, s16, false)) return pfail(q, UWSPR_ERR_HIP, "audio stream: %s", hipGetErrorString(r.err));
+    PHIP(q, hipEventRecord(q->stage_ev[s], r.copy));
+    q->stage_busy[s] = true;
+    q->stage_next = (s + 1) % uwspr_pipe::NSTAGE;
+    while (r.ready() >= q->o.batch_frames) {
+      const int rc = launch_from_ring(q, q->o.batch_frames);
+      if (rc) return rc;
+    }
     off += n;
   }
   return UWSPR_OK;

@@ -22,6 +22,16 @@
 
 namespace uwspr {
 
+// K0's stream form (k0_frontend.hip)
+int frontend_tap_image(int mode, std::vector<float> &img, int *J, int *dcols);
+int frontend_prepare();
+int frontend_read_ahead(int mode);
+void launch_frontend_stream(hipStream_t s, const void *audio, bool s16, int nin, long long in0, const float *taps,
+                            int J, int dcols, float *out, int nout, long long m_first);
+void launch_widen_s16(hipStream_t s, const int16_t *in, float *out, size_t n);
+
+enum { RING_EMPTY = 0, RING_IQ = 1, RING_AUDIO = 2 };   // what the stream is, decided by its first push
+
 struct stream_ring {
   int fl = 0, hop = 0, maxf = 0;
   float *buf[2] = {nullptr, nullptr};
@@ -41,6 +51,24 @@ struct stream_ring {
   int pin_next = 0;
   bool last_direct = false;            // the last append DMAs straight from the caller's (page-locked) buffer
   hipError_t err = hipSuccess;
+  int kind = RING_EMPTY;
+  // Audio streams (push_audio): 12 kS/s real samples go through K0 into the ring.  Output m of the stream is
+  // y[m] = sum_k g[k] x[32 m + D - k] (audio index 32 m = stream index m) and is produced as soon as x[32 m + D]
+  // has been pushed.  The device buffer holds [history | new samples]: the history is the audio from index
+  // 32 (m_next + dcols - J) on, at most 32 J samples, zero before the stream's first sample.
+  struct audio_state {
+    int mode = -1;                     // latched by the first push after open / reset
+    int s16 = 0;                       // the buffer holds int16 samples (every push so far was int16), else float
+    int J = 0, dcols = 0, taps_mode = -1;
+    float *d_taps = nullptr;           // [32][J] float2, the stream's own copy (a batch call may swap the context's)
+    char *d_buf[2] = {nullptr, nullptr};
+    size_t buf_bytes = 0;
+    int cur = 0;
+    long long a0 = 0;                  // audio index of d_buf[cur][0]
+    size_t hist = 0;                   // samples held in d_buf[cur]: audio [a0, a0 + hist)
+    long long m_next = 0;              // stream index of the next output
+  } au;
+  static constexpr size_t AUDIO_PIECE = 4u << 20;   // most new samples per K0 launch (131072 outputs: 256 workgroups)
 
   bool is_open() const { return buf[0] != nullptr; }
 
@@ -50,6 +78,9 @@ struct stream_ring {
     if (pin) { (void)hipHostFree(pin); pin = nullptr; }
     for (int k = 0; k < 2; k++) if (pin_ev[k]) { (void)hipEventDestroy(pin_ev[k]); pin_ev[k] = nullptr; }
     if (ev_up) { (void)hipEventDestroy(ev_up); ev_up = nullptr; }
+    for (int k = 0; k < 2; k++) if (au.d_buf[k]) { (void)hipFree(au.d_buf[k]); au.d_buf[k] = nullptr; }
+    if (au.d_taps) { (void)hipFree(au.d_taps); au.d_taps = nullptr; }
+    au = audio_state();
     if (copy) { (void)hipStreamDestroy(copy); copy = nullptr; }
     cap = 0; have = 0; base = 0; up_pending = false;
   }
@@ -64,6 +95,7 @@ struct stream_ring {
     if ((err = hipStreamCreateWithFlags(&copy, hipStreamNonBlocking)) != hipSuccess) { close(); return false; }
     if ((err = hipEventCreateWithFlags(&ev_up, hipEventDisableTiming)) != hipSuccess) { close(); return false; }
     cur = 0; base = 0; have = 0; pos = 0; up_pending = false; pin_next = 0;
+    kind = RING_EMPTY;
     pin_busy[0] = pin_busy[1] = false;
     return true;
   }
@@ -77,7 +109,8 @@ struct stream_ring {
 
   // drop what is buffered.  Kernels may still be reading views of the current buffer, so the next append
   // goes through make_room() (base = cap: nothing fits) to the OTHER buffer, behind its readers.
-  void reset(long long p) { have = 0; base = cap; pos = p; }
+  // An audio stream starts again at audio index 32 p with a zero history.
+  void reset(long long p) { have = 0; base = cap; pos = p; kind = RING_EMPTY; au.mode = -1; au.m_next = p; }
 
   // make space for n more samples behind the unconsumed ones
   bool make_room(size_t n) {
@@ -93,48 +126,153 @@ struct stream_ring {
     return true;
   }
 
-  // src: host (page-locked or pageable) when !on_device, else device memory that `src_ready` (may be
-  // null: already complete) orders.  Returns with the transfer enqueued on the copy stream; a
-  // page-locked source must stay unmodified until wait_uploads().
-  bool append(const float *src, size_t n, bool on_device, hipEvent_t src_ready = nullptr) {
-    if (n == 0) return true;
-    last_direct = false;
-    if (!make_room(n)) { if (err == hipSuccess) err = hipErrorOutOfMemory; return false; }
-    float *dst = buf[cur] + 2 * (base + have);
-    const size_t bytes = n * 2 * sizeof(float);
-    if (on_device) {
-      if (src_ready && (err = hipStreamWaitEvent(copy, src_ready, 0)) != hipSuccess) return false;
-      if ((err = hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, copy)) != hipSuccess) return false;
-    } else {
-      hipPointerAttribute_t at;
-      const bool locked = hipPointerGetAttributes(&at, src) == hipSuccess && at.type == hipMemoryTypeHost;
-      if (!locked) (void)hipGetLastError();   // an ordinary pointer is "invalid value" to the query: not an error here
-      if (locked) {
-        last_direct = true;
-        if ((err = hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, copy)) != hipSuccess) return false;
-      } else {
-        if (!pin) {
-          if ((err = hipHostMalloc((void **)&pin, 2 * PIECE, hipHostMallocDefault)) != hipSuccess) { pin = nullptr; return false; }
-          for (int k = 0; k < 2; k++)
-            if ((err = hipEventCreateWithFlags(&pin_ev[k], hipEventDisableTiming)) != hipSuccess) return false;
-        }
-        size_t off = 0;
-        while (off < bytes) {
-          const size_t m = bytes - off < PIECE ? bytes - off : PIECE;
-          const int h = pin_next;
-          pin_next ^= 1;
-          if (pin_busy[h] && (err = hipEventSynchronize(pin_ev[h])) != hipSuccess) return false;
-          memcpy(pin + (size_t)h * PIECE, (const char *)src + off, m);
-          if ((err = hipMemcpyAsync((char *)dst + off, pin + (size_t)h * PIECE, m, hipMemcpyHostToDevice, copy)) != hipSuccess) return false;
-          if ((err = hipEventRecord(pin_ev[h], copy)) != hipSuccess) return false;
-          pin_busy[h] = true;
-          off += m;
-        }
-      }
-    }
+  // n samples of space behind the unconsumed ones for a producer on the copy stream (a kernel), then commit(n)
+  float *reserve(size_t n) {
+    if (!make_room(n)) { if (err == hipSuccess) err = hipErrorOutOfMemory; return nullptr; }
+    return buf[cur] + 2 * (base + have);
+  }
+  bool commit(size_t n) {
     have += n;
     if ((err = hipEventRecord(ev_up, copy)) != hipSuccess) return false;
     up_pending = true;
+    return true;
+  }
+
+  // bytes from src to device memory dst on the copy stream.  src: host (page-locked or pageable) when !on_device,
+  // else device memory that `src_ready` (may be null: already complete) orders.  A page-locked source is read by
+  // the DMA itself (last_direct) and must stay unmodified until wait_uploads().
+  bool upload(void *dst, const void *src, size_t bytes, bool on_device, hipEvent_t src_ready) {
+    if (on_device) {
+      if (src_ready && (err = hipStreamWaitEvent(copy, src_ready, 0)) != hipSuccess) return false;
+      return (err = hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, copy)) == hipSuccess;
+    }
+    hipPointerAttribute_t at;
+    const bool locked = hipPointerGetAttributes(&at, src) == hipSuccess && at.type == hipMemoryTypeHost;
+    if (!locked) (void)hipGetLastError();   // an ordinary pointer is "invalid value" to the query: not an error here
+    if (locked) {
+      last_direct = true;
+      return (err = hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, copy)) == hipSuccess;
+    }
+    if (!pin) {
+      if ((err = hipHostMalloc((void **)&pin, 2 * PIECE, hipHostMallocDefault)) != hipSuccess) { pin = nullptr; return false; }
+      for (int k = 0; k < 2; k++)
+        if ((err = hipEventCreateWithFlags(&pin_ev[k], hipEventDisableTiming)) != hipSuccess) return false;
+    }
+    size_t off = 0;
+    while (off < bytes) {
+      const size_t m = bytes - off < PIECE ? bytes - off : PIECE;
+      const int h = pin_next;
+      pin_next ^= 1;
+      if (pin_busy[h] && (err = hipEventSynchronize(pin_ev[h])) != hipSuccess) return false;
+      memcpy(pin + (size_t)h * PIECE, (const char *)src + off, m);
+      if ((err = hipMemcpyAsync((char *)dst + off, pin + (size_t)h * PIECE, m, hipMemcpyHostToDevice, copy)) != hipSuccess) return false;
+      if ((err = hipEventRecord(pin_ev[h], copy)) != hipSuccess) return false;
+      pin_busy[h] = true;
+      off += m;
+    }
+    return true;
+  }
+
+  // n (I,Q) pairs (see upload).  Returns with the transfer enqueued on the copy stream.
+  bool append(const float *src, size_t n, bool on_device, hipEvent_t src_ready = nullptr) {
+    if (n == 0) return true;
+    last_direct = false;
+    float *dst = reserve(n);
+    if (!dst) return false;
+    if (!upload(dst, src, n * 2 * sizeof(float), on_device, src_ready)) return false;
+    return commit(n);
+  }
+
+  // ---- audio streams
+  // stream index one past the last output that audio [.., a_end) completes (floor division: a_end may be < D)
+  static long long audio_complete(long long a_end, int dcols) {
+    const long long t = a_end - 1 - 32LL * dcols;
+    return (t >= 0 ? t / 32 : -((-t + 31) / 32)) + 1;
+  }
+  // outputs a push of n samples would add, for a stream in front-end mode `mode`
+  long long audio_outputs(size_t n, int mode) const {
+    const int dcols = frontend_read_ahead(mode) / 32;
+    const long long a_end = au.mode >= 0 ? au.a0 + (long long)au.hist : 32LL * au.m_next;
+    const long long m = audio_complete(a_end + (long long)n, dcols);
+    return m > au.m_next ? m - au.m_next : 0;
+  }
+
+  // The first audio push after open / reset: taps of `mode`, buffers, a zero history.
+  bool audio_latch(int mode, bool s16) {
+    if (au.taps_mode != mode) {
+      std::vector<float> img;
+      int J = 0, dcols = 0;
+      if (frontend_tap_image(mode, img, &J, &dcols) || frontend_prepare()) { err = hipErrorInvalidValue; return false; }
+      if ((err = hipStreamSynchronize(copy)) != hipSuccess) return false;   // (launches with the old taps)
+      if (au.d_taps) { (void)hipFree(au.d_taps); au.d_taps = nullptr; }
+      if ((err = hipMalloc((void **)&au.d_taps, img.size() * sizeof(float))) != hipSuccess) { au.d_taps = nullptr; return false; }
+      if ((err = hipMemcpy(au.d_taps, img.data(), img.size() * sizeof(float), hipMemcpyHostToDevice)) != hipSuccess) return false;
+      au.taps_mode = mode; au.J = J; au.dcols = dcols;
+    }
+    const size_t need = (32 * (size_t)au.J + 32 + AUDIO_PIECE) * sizeof(float);
+    if (au.buf_bytes < need) {
+      if ((err = hipStreamSynchronize(copy)) != hipSuccess) return false;
+      for (int k = 0; k < 2; k++) {
+        if (au.d_buf[k]) { (void)hipFree(au.d_buf[k]); au.d_buf[k] = nullptr; }
+        if ((err = hipMalloc((void **)&au.d_buf[k], need)) != hipSuccess) { au.d_buf[k] = nullptr; au.buf_bytes = 0; return false; }
+      }
+      au.buf_bytes = need;
+    }
+    au.mode = mode; au.s16 = s16;
+    au.a0 = 32 * (au.m_next + au.dcols - au.J);
+    au.hist = (size_t)(32LL * au.m_next - au.a0);
+    if ((err = hipMemsetAsync(au.d_buf[au.cur], 0, au.hist * (s16 ? 2 : 4), copy)) != hipSuccess) return false;
+    kind = RING_AUDIO;
+    return true;
+  }
+
+  // n audio samples (int16 when s16, else float) from src (see upload): upload behind the history, K0 for the outputs
+  // that became complete straight into the ring, keep the new tail as history.  The caller has latched the stream
+  // and checked room() against audio_outputs(n).  An int16 stream stays int16 while every push is; a float push
+  // widens its history once (s / 32768, exact) and from then on int16 pushes are widened on arrival, so formats may
+  // mix and every output sees the same sample values.
+  bool push_audio(const void *src, size_t n, bool s16_in, bool on_device, hipEvent_t src_ready = nullptr) {
+    last_direct = false;
+    if (n && au.s16 && !s16_in) {
+      launch_widen_s16(copy, (const int16_t *)au.d_buf[au.cur], (float *)au.d_buf[au.cur ^ 1], au.hist);
+      if ((err = hipGetLastError()) != hipSuccess) return false;
+      au.cur ^= 1; au.s16 = 0;
+    }
+    const bool widen = s16_in && !au.s16;   // int16 samples into a float buffer
+    const size_t es = au.s16 ? 2 : 4, es_in = s16_in ? 2 : 4;
+    for (size_t off = 0; off < n;) {
+      const size_t k = n - off < AUDIO_PIECE ? n - off : AUDIO_PIECE;
+      char *b = au.d_buf[au.cur];
+      if (widen) {   // (the other buffer is free until the tail copy below, which comes after on the same stream)
+        char *tmp = au.d_buf[au.cur ^ 1];
+        if (!upload(tmp, (const char *)src + off * es_in, k * es_in, on_device, src_ready)) return false;
+        launch_widen_s16(copy, (const int16_t *)tmp, (float *)(b + au.hist * es), k);
+        if ((err = hipGetLastError()) != hipSuccess) return false;
+      } else if (!upload(b + au.hist * es, (const char *)src + off * es_in, k * es_in, on_device, src_ready)) {
+        return false;
+      }
+      const long long a_end = au.a0 + (long long)(au.hist + k);
+      const long long m_end = audio_complete(a_end, au.dcols);
+      if (m_end > au.m_next) {
+        const int nout = (int)(m_end - au.m_next);
+        float *dst = reserve((size_t)nout);
+        if (!dst) return false;
+        launch_frontend_stream(copy, b, au.s16, (int)(au.hist + k), au.a0, au.d_taps, au.J, au.dcols, dst, nout, au.m_next);
+        if ((err = hipGetLastError()) != hipSuccess) return false;
+        if (!commit((size_t)nout)) return false;
+        au.m_next = m_end;
+      }
+      const long long a0n = 32 * (au.m_next + au.dcols - au.J);
+      au.hist = (size_t)(a_end - a0n);
+      if (a0n != au.a0) {   // the tail to the front of the other buffer
+        if ((err = hipMemcpyAsync(au.d_buf[au.cur ^ 1], b + (size_t)(a0n - au.a0) * es, au.hist * es,
+                                  hipMemcpyDeviceToDevice, copy)) != hipSuccess) return false;
+        au.cur ^= 1; au.a0 = a0n;
+      }
+      off += k;
+    }
+    if (n && (err = hipEventRecord(ev_up, copy)) != hipSuccess) return false;
+    if (n) up_pending = true;
     return true;
   }
 

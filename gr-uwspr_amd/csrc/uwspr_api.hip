@@ -999,9 +999,11 @@ extern "C" int uwspr_stream_push(uwspr_ctx *c, const float *iq, int nsamples, in
   if (!r.is_open()) return fail(c, UWSPR_ERR_ARG, "uwspr_stream_push before uwspr_stream_open");
   if (nsamples < 0 || (nsamples > 0 && !iq)) return fail(c, UWSPR_ERR_ARG, "iq/nsamples");
   if (where != UWSPR_HOST && where != UWSPR_DEVICE && where != UWSPR_HOST_ASYNC) return fail(c, UWSPR_ERR_ARG, "where=%d", where);
+  if (r.kind == RING_AUDIO && nsamples > 0) return fail(c, UWSPR_ERR_ARG, "uwspr_stream_push on an audio stream (reset it first)");
   if (r.have + (size_t)nsamples > r.cap)
     return fail(c, UWSPR_ERR_ARG, "stream buffer full (%zu + %d > %zu samples): take frames first", r.have, nsamples, r.cap);
   if (nsamples > 0) {
+    r.kind = RING_IQ;
     bool ok;
     if (where == UWSPR_DEVICE) {   // produced by work on the context's stream
       HIPCHK(c, hipEventRecord(c->ring_ev, c->stream));
@@ -1015,6 +1017,40 @@ extern "C" int uwspr_stream_push(uwspr_ctx *c, const float *iq, int nsamples, in
       if (ok && where == UWSPR_HOST && r.last_direct) ok = r.wait_uploads();
     }
     if (!ok) return fail(c, UWSPR_ERR_HIP, "stream upload: %s", hipGetErrorString(r.err));
+  }
+  if (nready) *nready = r.ready();
+  return UWSPR_OK;
+}
+
+// 12 kS/s audio -> K0 on the ring's copy stream -> the ring (stream_ring::push_audio)
+extern "C" int uwspr_stream_push_audio(uwspr_ctx *c, const void *audio, int nsamples, int format, int where, int *nready) {
+  int rc = ready(c);
+  if (rc) return rc;
+  stream_ring &r = c->ring;
+  if (!r.is_open()) return fail(c, UWSPR_ERR_ARG, "uwspr_stream_push_audio before uwspr_stream_open");
+  if (nsamples < 0 || (nsamples > 0 && !audio)) return fail(c, UWSPR_ERR_ARG, "audio/nsamples");
+  if (format != UWSPR_AUDIO_F32 && format != UWSPR_AUDIO_S16) return fail(c, UWSPR_ERR_ARG, "audio format %d", format);
+  if (where != UWSPR_HOST && where != UWSPR_DEVICE && where != UWSPR_HOST_ASYNC) return fail(c, UWSPR_ERR_ARG, "where=%d", where);
+  if (c->p.fs != 375) return fail(c, UWSPR_ERR_UNSUPPORTED, "front-end is 12000 -> 375 S/s (fs=%d)", c->p.fs);
+  const int mode = c->opt[UWSPR_OPT_FRONTEND];
+  if (nsamples > 0 && r.kind == RING_IQ) return fail(c, UWSPR_ERR_ARG, "uwspr_stream_push_audio on an (I,Q) stream (reset it first)");
+  if (nsamples > 0 && r.kind == RING_AUDIO && mode != r.au.mode)
+    return fail(c, UWSPR_ERR_ARG, "option frontend changed to %d while the audio stream runs in mode %d (reset it first)", mode, r.au.mode);
+  const long long nout = r.audio_outputs((size_t)nsamples, mode);
+  if (r.have + (size_t)nout > r.cap)
+    return fail(c, UWSPR_ERR_ARG, "stream buffer full (%zu + %lld > %zu samples): take frames first", r.have, nout, r.cap);
+  if (nsamples > 0) {
+    if (r.kind != RING_AUDIO && !r.audio_latch(mode, format == UWSPR_AUDIO_S16))
+      return fail(c, UWSPR_ERR_HIP, "audio stream set-up: %s", hipGetErrorString(r.err));
+    bool ok;
+    if (where == UWSPR_DEVICE) {   // produced by work on the context's stream
+      HIPCHK(c, hipEventRecord(c->ring_ev, c->stream));
+      ok = r.push_audio(audio, (size_t)nsamples, format == UWSPR_AUDIO_S16, true, c->ring_ev);
+    } else {
+      ok = r.push_audio(audio, (size_t)nsamples, format == UWSPR_AUDIO_S16, false);
+      if (ok && where == UWSPR_HOST && r.last_direct) ok = r.wait_uploads();   // as uwspr_stream_push
+    }
+    if (!ok) return fail(c, UWSPR_ERR_HIP, "audio stream: %s", hipGetErrorString(r.err));
   }
   if (nready) *nready = r.ready();
   return UWSPR_OK;

@@ -32,6 +32,7 @@ HIPFLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off",
 
 NSYM, NSLM, NK0, NIFR, NJIG = 162, 125, 26, 5, 17
 HOST, DEVICE, DEVICE_FRAMES, HOST_ASYNC = 0, 1, 2, 3
+AUDIO_F32, AUDIO_S16 = 0, 1
 LINEAR, NONLINEAR = 0, 1
 
 
@@ -229,7 +230,7 @@ class Prof(C.Structure):
 ABI_SYMBOLS = [
     "uwspr_ctx_create", "uwspr_ctx_destroy", "uwspr_last_error", "uwspr_status_string",
     "uwspr_get_info", "uwspr_set_stream", "uwspr_synchronize", "uwspr_frontend_batch",
-    "uwspr_frontend_design", "uwspr_set_frame_stride", "uwspr_stream_open", "uwspr_stream_push", "uwspr_stream_wait_uploads",
+    "uwspr_frontend_design", "uwspr_set_frame_stride", "uwspr_stream_open", "uwspr_stream_push", "uwspr_stream_push_audio", "uwspr_stream_wait_uploads",
     "uwspr_stream_take_view", "uwspr_stream_take", "uwspr_stream_reset",
     "uwspr_device_alloc", "uwspr_device_free", "uwspr_host_alloc", "uwspr_host_free", "uwspr_fdr_batch",
     "uwspr_fdr_read_spectrum", "uwspr_fdr_keep_syncgrid", "uwspr_fdr_read_syncgrid",
@@ -239,7 +240,7 @@ ABI_SYMBOLS = [
     "uwspr_c2_read",
     "uwspr_dist_unique_id", "uwspr_dist_init", "uwspr_dist_gather", "uwspr_dist_finalize",
     "uwspr_pipe_open", "uwspr_pipe_close", "uwspr_pipe_last_error", "uwspr_pipe_acquire", "uwspr_pipe_commit",
-    "uwspr_pipe_push", "uwspr_pipe_submit_device", "uwspr_pipe_flush", "uwspr_pipe_collect", "uwspr_pipe_get_stats",
+    "uwspr_pipe_push", "uwspr_pipe_push_audio", "uwspr_pipe_submit_device", "uwspr_pipe_flush", "uwspr_pipe_collect", "uwspr_pipe_get_stats",
     "uwspr_pipe_inject_failure", "uwspr_pipe_set_option",
 ]
 
@@ -283,6 +284,7 @@ def lib():
     L.uwspr_frontend_design.argtypes = [ip, ip, vp, ip, vp]
     L.uwspr_stream_open.argtypes = [vp, ip, ip]
     L.uwspr_stream_push.argtypes = [vp, vp, ip, ip, C.POINTER(C.c_int)]
+    L.uwspr_stream_push_audio.argtypes = [vp, vp, ip, ip, ip, C.POINTER(C.c_int)]
     L.uwspr_stream_take.argtypes = [vp, ip, vp, C.POINTER(vp), C.POINTER(C.c_longlong)]
     L.uwspr_stream_reset.argtypes = [vp, C.c_longlong]
     L.uwspr_set_frame_stride.argtypes = [vp, ip]
@@ -336,6 +338,7 @@ def lib():
     L.uwspr_pipe_acquire.argtypes = [vp, ip, C.POINTER(vp)]
     L.uwspr_pipe_commit.argtypes = [vp, ip]
     L.uwspr_pipe_push.argtypes = [vp, vp, ip]
+    L.uwspr_pipe_push_audio.argtypes = [vp, vp, ip, ip]
     L.uwspr_pipe_submit_device.argtypes = [vp, vp, ip, ip]
     L.uwspr_pipe_flush.argtypes = [vp]
     L.uwspr_pipe_collect.argtypes = [vp, vp, ip, ip]

@@ -28,12 +28,13 @@
 extern "C" {
 #endif
 
-#define UWSPR_ABI_VERSION 5   /* 2: frame stride, in-place stream views, uwspr_pipe_*, uwspr_dist_*, uwspr_host_threads;
+#define UWSPR_ABI_VERSION 6   /* 2: frame stride, in-place stream views, uwspr_pipe_*, uwspr_dist_*, uwspr_host_threads;
                                  3: uwspr_set_option / uwspr_get_option, uwspr_pipe_set_option, uwspr_pipe_inject_failure,
                                     uwspr_pipe_opts.spare_after_us (was reserved);
                                  4: option "frontend" (the flowgraph's GNU Radio chain is the default front-end),
                                     uwspr_frontend_design replaces uwspr_frontend_taps;
-                                 5: uwspr_host_set_ranks (the host's CPU share divided between the ranks of a node) */
+                                 5: uwspr_host_set_ranks (the host's CPU share divided between the ranks of a node);
+                                 6: audio streams: uwspr_stream_push_audio, uwspr_pipe_push_audio */
 
 typedef enum {
   UWSPR_OK = 0,
@@ -49,7 +50,7 @@ typedef enum {
 /* UWSPR_DEVICE_FRAMES (uwspr_fdr_batch, uwspr_demod_batch, uwspr_pipeline_batch, uwspr_demod_resume): the frames are device
  * memory (e.g. what uwspr_stream_take returned), every other pointer of the call is host memory. */
 enum { UWSPR_HOST = 0, UWSPR_DEVICE = 1, UWSPR_DEVICE_FRAMES = 2,
-       UWSPR_HOST_ASYNC = 3 /* uwspr_stream_push only: see there */ };
+       UWSPR_HOST_ASYNC = 3 /* uwspr_stream_push, uwspr_stream_push_audio only: see there */ };
 enum { UWSPR_LINEAR = 0, UWSPR_NONLINEAR = 1 };   /* enum Modes, lib/candidate_t.h:36 */
 
 #define UWSPR_NSYM 162      /* symbols per frame */
@@ -207,6 +208,21 @@ int uwspr_stream_wait_uploads(uwspr_ctx *ctx);
 int uwspr_stream_take_view(uwspr_ctx *ctx, int nframes, const float **frames, int *stride, long long *first_pos);
 int uwspr_stream_take(uwspr_ctx *ctx, int nframes, float *dev_dst, const float **frames, long long *first_pos);
 int uwspr_stream_reset(uwspr_ctx *ctx, long long pos);
+/* Audio streams: the receiver flowgraph's whole front half (examples/AudioSourceDecode.grc: audio_source at 12 kS/s
+ * (:376) -> float_to_complex -> band-pass -> low-pass -> rational_resampler /32 (:1804) ->
+ * sliding_window_stream_to_pdu (:1973)) on a pushed stream of real 12 kS/s samples.  Each push uploads the new samples
+ * behind the front-end's history on the stream's copy stream and runs the front-end (option "frontend", as
+ * uwspr_frontend_batch) there for the outputs that just became complete, straight into the stream buffer:
+ *     stream sample m = y[m] = sum_k g[k] x[32 m + D - k]     (audio index 32 m <-> stream index m; D = 0 or 512)
+ * x being the pushed audio (x[0] = the first sample after uwspr_stream_open; zero before it).  y[m] is produced as soon
+ * as x[32 m + D] has been pushed: no flush, no padding at the live end.  Frames, takes and first_pos keep their
+ * meaning: frame k's audio time is first_pos / 375 s.  uwspr_stream_reset(ctx, pos) zeroes the history and makes the
+ * next pushed sample x[32 pos].  The first push after open / reset makes the stream an audio or an (I,Q) stream; a
+ * push of the other kind or a change of option "frontend" while it runs fail that call with UWSPR_ERR_ARG (the
+ * stream is unharmed).  where: as for uwspr_stream_push.  int16 samples count as s / 32768 (GNU Radio's
+ * wavfile_source), exactly, so pushes of either format may follow each other: the outputs are the same bytes. */
+enum { UWSPR_AUDIO_F32 = 0, UWSPR_AUDIO_S16 = 1 };
+int uwspr_stream_push_audio(uwspr_ctx *ctx, const void *audio, int nsamples, int format, int where, int *nready);
 /* device memory for callers without a HIP runtime of their own (the block mirror's frame hand-over) */
 int uwspr_device_alloc(size_t bytes, void **ptr);
 void uwspr_device_free(void *ptr);
@@ -422,6 +438,12 @@ int uwspr_pipe_acquire(uwspr_pipe *pipe, int nsamples, float **iq);
 int uwspr_pipe_commit(uwspr_pipe *pipe, int nsamples);
 /* acquire + memcpy + commit for samples that live elsewhere */
 int uwspr_pipe_push(uwspr_pipe *pipe, const float *iq, int nsamples);
+/* The same for 12 kS/s real audio (format UWSPR_AUDIO_F32 / UWSPR_AUDIO_S16; examples/AudioSourceDecode.grc's chain
+ * from audio_source (:376) on): pieces of any length are copied into the page-locked staging and go through the
+ * front-end on the copy stream into the pipe's stream, as uwspr_stream_push_audio does (stream sample m = the
+ * front-end's output at audio index 32 m; records' stream_pos / 375 = audio time in s).  A pipe's stream is audio or
+ * (I,Q), decided by its first push; the front-end mode is the lanes' option "frontend" at that push. */
+int uwspr_pipe_push_audio(uwspr_pipe *pipe, const void *audio, int nsamples, int format);
 /* B frames already in device memory (frame b at frames + 2*stride*b floats, stride 0 = fl): searched as one
  * batch.  The memory must stay valid until the batch's results have been collected. */
 int uwspr_pipe_submit_device(uwspr_pipe *pipe, const float *dev_frames, int B, int stride);
