@@ -644,8 +644,17 @@ class Pipe:
         self._chk(self.L.uwspr_pipe_push(self.h, C.c_void_p(a.ctypes.data), a.size // 2))
 
     def push_audio(self, x):
-        """12 kS/s real audio (uwspr_pipe_push_audio): a 1-D numpy float32 or int16 array of any length"""
-        a = _audio_array(x)
+        """12 kS/s real audio: a 1-D numpy float32 or int16 array of any length (uwspr_pipe_push_audio), or a 2-D
+        [n, C] one of C interleaved channels (uwspr_pipe_push_audio_channels; the first push fixes C)"""
+        a = np.asarray(x)
+        if a.ndim == 2:
+            if a.dtype not in (np.float32, np.int16):
+                raise TypeError("audio: a [n, C] float32 or int16 array, not %s %s" % (a.dtype, a.shape))
+            a = np.ascontiguousarray(a)
+            self._chk(self.L.uwspr_pipe_push_audio_channels(self.h, C.c_void_p(a.ctypes.data), a.shape[0], a.shape[1],
+                                                            N.AUDIO_S16 if a.dtype == np.int16 else N.AUDIO_F32))
+            return
+        a = _audio_array(a)
         self._chk(self.L.uwspr_pipe_push_audio(self.h, C.c_void_p(a.ctypes.data), a.size,
                                                N.AUDIO_S16 if a.dtype == np.int16 else N.AUDIO_F32))
 
@@ -694,9 +703,12 @@ class Pipe:
 AUDIO_RATE = 12000
 
 
-def read_wav(path):
-    """A 16-bit PCM WAV (stdlib wave) -> (channel 0 as int16, rate).  Anything else -- another sample width, a float
-    WAV, a rate other than the front-end's 12000 S/s -- raises ValueError."""
+def read_wav(path, channels=None):
+    """A 16-bit PCM WAV (stdlib wave) -> (channel 0 as int16, rate); channels="all": ([n, C] int16, rate), every
+    channel.  Anything else -- another sample width, a float WAV, a rate other than the front-end's 12000 S/s --
+    raises ValueError."""
+    if channels not in (None, "all"):
+        raise ValueError("read_wav: channels=None (channel 0) or \"all\", not %r" % (channels,))
     import wave
     try:
         w = wave.open(str(path), "rb")
@@ -709,19 +721,22 @@ def read_wav(path):
         if rate != AUDIO_RATE:
             raise ValueError("%s: %d S/s; the front-end takes %d S/s" % (path, rate, AUDIO_RATE))
         raw = w.readframes(n)
-    x = np.frombuffer(raw, dtype="<i2").reshape(-1, nch)[:, 0]
+    x = np.frombuffer(raw, dtype="<i2").reshape(-1, nch)
+    if channels is None:
+        x = x[:, 0]
     return np.ascontiguousarray(x, dtype=np.int16), rate
 
 
-def decode_wav(path, **pipe_opts):
+def decode_wav(path, channels=None, **pipe_opts):
     """Decode a 12 kS/s recording as the receiver flowgraph does (examples/AudioSourceDecode.grc): the file through a
     Pipe's push_audio -> one dict per decoded record, in frame order: frame, t (stream_pos / 375 s), the coarse freq
-    and snr, and the unpacked text."""
-    x, _ = read_wav(path)
+    and snr, and the unpacked text.  channels="all": every channel of the file through one pipe, records in (take,
+    channel, frame) order, each dict with its "channel"."""
+    x, _ = read_wav(path, channels)
     pipe = Pipe(**pipe_opts)
     try:
         piece = 12000 * 60
-        for k in range(0, x.size, piece):
+        for k in range(0, x.shape[0], piece):
             pipe.push_audio(x[k:k + piece])
         pipe.flush()
         recs = pipe.collect(cap=1 << 20)
@@ -731,7 +746,10 @@ def decode_wav(path, **pipe_opts):
     for r in recs:
         if not r["decoded"]:
             continue
-        out.append({"frame": int(r["frame"]), "t": int(r["stream_pos"]) / 375.0,
-                    "freq": float(r["coarse"]["freq"]), "snr": float(r["coarse"]["snr"]),
-                    "text": unpack_message(r["message"])[1]})
+        d = {"frame": int(r["frame"]), "t": int(r["stream_pos"]) / 375.0,
+             "freq": float(r["coarse"]["freq"]), "snr": float(r["coarse"]["snr"]),
+             "text": unpack_message(r["message"])[1]}
+        if channels == "all":
+            d["channel"] = int(r["channel"])
+        out.append(d)
     return out

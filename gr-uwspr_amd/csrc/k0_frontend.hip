@@ -70,17 +70,31 @@ __device__ __forceinline__ float k0_sample(int16_t v) { return (float)v * (1.0f 
 // reads audio[b][n - in0]; samples outside [in0, in0 + nin) count as zero.  The batch call passes 0 and 0, the
 // stream form the absolute audio index of its buffer and the decimated index of the ring slot it writes.  An output's
 // arithmetic is the same wherever it falls in a workgroup or a launch (the tap order is fixed per output).
-template <typename T>
+// MC (the multichannel stream form): audio is [nin][nch] interleaved and b is a channel, not a record.  Workgroup
+// (output block, channel) reads x[n nch + b] and writes plane b of the ring (out + b * plane); the channels of one
+// output block read the same input lines, so they are consecutive after xcd_swizzle and share an XCD's L2.  Only the
+// loader's address and the output's plane differ: channel b's outputs are bit for bit those of its one-channel stream.
+// (nch and plane are not read by the other forms, whose code is that of the one-record kernel.)
+template <typename T, bool MC>
 __global__ __launch_bounds__(K0_WG) void k0_frontend(const T *__restrict__ audio, int nin, long long in0,
                                                      const float2 *__restrict__ taps, float2 *__restrict__ out,
-                                                     int nout, long long m_first, int J, int dcols) {
+                                                     int nout, long long m_first, int J, int dcols, int nch,
+                                                     long long plane) {
   extern __shared__ __align__(16) float k0_lds[];
   const int L = k0_L(J), ROW = k0_row(J);
   float *xs = k0_lds;
   float2 *tp = reinterpret_cast<float2 *>(k0_lds + K0_DEC * ROW);   // (32 ROW floats: a multiple of 8 bytes)
-  const int b = blockIdx.y, tid = threadIdx.x;
-  const long long m0 = m_first + (long long)blockIdx.x * K0_OUT;
-  const T *x = audio + (size_t)b * nin;
+  const int tid = threadIdx.x;
+  int b;
+  unsigned blk;   // (unsigned, as blockIdx.x)
+  if constexpr (MC) {
+    const unsigned lb = xcd_swizzle(blockIdx.x, gridDim.x);
+    blk = lb / (unsigned)nch; b = (int)(lb - blk * (unsigned)nch);
+  } else {
+    blk = blockIdx.x; b = blockIdx.y;
+  }
+  const long long m0 = m_first + (long long)blk * K0_OUT;
+  const T *x = MC ? audio + b : audio + (size_t)b * nin;
   // Output m, tap k = 32 j + p reads n = 32 (m - j + dcols) - p: row (32 - p) mod 32, column m - j + dcols - (p > 0).
   // With cb = m0 - J + dcols the workgroup's rows start at column cb; row 0 is stored one column late, so that for
   // every phase the sample of (output m0 + o, tap jj = J - 1 - j) sits at position o + jj of its row.
@@ -91,7 +105,7 @@ __global__ __launch_bounds__(K0_WG) void k0_frontend(const T *__restrict__ audio
     const int pos = (e >> 5) - (r == 0 ? 1 : 0);
     if (pos < 0) continue;
     const long long n = (long long)K0_DEC * cb + e - in0;   // index into this buffer
-    const float v = (n >= 0 && n < nin) ? k0_sample(x[n]) : 0.0f;
+    const float v = (n >= 0 && n < nin) ? k0_sample(x[MC ? n * nch : n]) : 0.0f;
     xs[r * ROW + (pos & 7) * L + (pos >> 3)] = v;
   }
   for (int i = tid; i < K0_DEC * J; i += K0_WG) tp[i] = taps[i];
@@ -137,8 +151,8 @@ __global__ __launch_bounds__(K0_WG) void k0_frontend(const T *__restrict__ audio
       const float2 q = part[(ww * K0_R + i) * 64 + l];
       re += q.x; im += q.y;
     }
-    const int m = blockIdx.x * K0_OUT + K0_R * l + i;
-    if (m < nout) out[(size_t)b * nout + m] = make_float2(re, im);
+    const int m = blk * K0_OUT + K0_R * l + i;
+    if (m < nout) out[MC ? (size_t)b * plane + m : (size_t)b * nout + m] = make_float2(re, im);
   }
 }
 
@@ -295,30 +309,43 @@ int frontend_read_ahead(int mode) {
 
 int frontend_prepare() {
   // up to 160 KB of dynamic LDS (149 KB in the grc mode); int16 samples are widened before they reach LDS
-  return hipFuncSetAttribute(reinterpret_cast<const void *>(k0_frontend<float>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                             160 * 1024) == hipSuccess &&
-         hipFuncSetAttribute(reinterpret_cast<const void *>(k0_frontend<int16_t>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                             160 * 1024) == hipSuccess ? 0 : -1;
+  const void *k[] = {reinterpret_cast<const void *>(k0_frontend<float, false>), reinterpret_cast<const void *>(k0_frontend<int16_t, false>),
+                     reinterpret_cast<const void *>(k0_frontend<float, true>), reinterpret_cast<const void *>(k0_frontend<int16_t, true>)};
+  for (const void *f : k)
+    if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return -1;
+  return 0;
 }
 
 void launch_frontend(uwspr_ctx *c, const float *audio, int B, int nin, float2 *out, int nout) {
   prof_scope ps(c, UWSPR_K_SPECTROGRAM, B);
   dim3 grid((nout + K0_OUT - 1) / K0_OUT, B);
-  hipLaunchKernelGGL(k0_frontend<float>, grid, dim3(K0_WG), k0_lds_bytes(c->fe_J), c->stream, audio, nin, 0LL,
-                     (const float2 *)c->d_fe_taps, out, nout, 0LL, c->fe_J, c->fe_dcols);
+  hipLaunchKernelGGL((k0_frontend<float, false>), grid, dim3(K0_WG), k0_lds_bytes(c->fe_J), c->stream, audio, nin, 0LL,
+                     (const float2 *)c->d_fe_taps, out, nout, 0LL, c->fe_J, c->fe_dcols, 1, 0LL);
 }
 
-// the stream form (stream_ring::push_audio): one record, outputs m_first .. m_first + nout - 1 from the buffer that
-// holds audio [in0, in0 + nin)
+// the stream form (stream_ring::push_audio): outputs m_first .. m_first + nout - 1 from the buffer that holds audio
+// [in0, in0 + nin) -- one record, or with nch > 1 frames of nch interleaved channels, channel c's outputs at
+// out + 2 * c * plane floats
 void launch_frontend_stream(hipStream_t s, const void *audio, bool s16, int nin, long long in0, const float *taps,
-                            int J, int dcols, float *out, int nout, long long m_first) {
-  dim3 grid((nout + K0_OUT - 1) / K0_OUT, 1);
+                            int J, int dcols, float *out, int nout, long long m_first, int nch, long long plane) {
+  const int nblk = (nout + K0_OUT - 1) / K0_OUT;
+  if (nch > 1) {
+    const dim3 grid(nblk * nch, 1);
+    if (s16)
+      hipLaunchKernelGGL((k0_frontend<int16_t, true>), grid, dim3(K0_WG), k0_lds_bytes(J), s, (const int16_t *)audio, nin, in0,
+                         (const float2 *)taps, (float2 *)out, nout, m_first, J, dcols, nch, plane);
+    else
+      hipLaunchKernelGGL((k0_frontend<float, true>), grid, dim3(K0_WG), k0_lds_bytes(J), s, (const float *)audio, nin, in0,
+                         (const float2 *)taps, (float2 *)out, nout, m_first, J, dcols, nch, plane);
+    return;
+  }
+  dim3 grid(nblk, 1);
   if (s16)
-    hipLaunchKernelGGL(k0_frontend<int16_t>, grid, dim3(K0_WG), k0_lds_bytes(J), s, (const int16_t *)audio, nin, in0,
-                       (const float2 *)taps, (float2 *)out, nout, m_first, J, dcols);
+    hipLaunchKernelGGL((k0_frontend<int16_t, false>), grid, dim3(K0_WG), k0_lds_bytes(J), s, (const int16_t *)audio, nin, in0,
+                       (const float2 *)taps, (float2 *)out, nout, m_first, J, dcols, 1, 0LL);
   else
-    hipLaunchKernelGGL(k0_frontend<float>, grid, dim3(K0_WG), k0_lds_bytes(J), s, (const float *)audio, nin, in0,
-                       (const float2 *)taps, (float2 *)out, nout, m_first, J, dcols);
+    hipLaunchKernelGGL((k0_frontend<float, false>), grid, dim3(K0_WG), k0_lds_bytes(J), s, (const float *)audio, nin, in0,
+                       (const float2 *)taps, (float2 *)out, nout, m_first, J, dcols, 1, 0LL);
 }
 
 // int16 samples into a float stream buffer: the value K0's int16 loader computes (k0_sample)

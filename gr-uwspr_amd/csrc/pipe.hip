@@ -50,7 +50,7 @@ struct pipe_lane {
   double host_since = 0.0; // > 0: its first GPU pass is complete and it has been in its host tail since then (now_s())
   int64_t seq = 0;         // batch number (emission order)
   std::vector<uwspr_decode> recs;   // the batch's records, built by the coordinator, emitted in batch order
-  int B = 0, stride = 0;
+  int B = 0, stride = 0, channel = 0;
   const float *frames = nullptr;
   int64_t frame0 = 0, pos0 = -1;
   std::vector<uint8_t> dec;          // [B*per] decoded flags
@@ -83,7 +83,7 @@ struct uwspr_pipe {
   std::vector<pipe_lane> lanes;
   double spare_after = 2.5e-3;   // seconds of host tail after which a spare lane may open (take_lane)
   int next_lane = 0;
-  int64_t next_frame = 0;
+  int64_t next_frame[UWSPR_PIPE_MAX_CHANNELS] = {};   // per channel (submitted frames and (I,Q) streams: channel 0)
 
   stream_ring ring;
   static constexpr int NSTAGE = 4;
@@ -232,6 +232,7 @@ static int finish_batch(uwspr_pipe *q, pipe_lane &L) {
         uwspr_decode d;
         memset(&d, 0, sizeof(d));
         d.frame = L.frame0 + b;
+        d.channel = (int16_t)L.channel;
         d.stream_pos = L.pos0 >= 0 ? L.pos0 + (int64_t)b * L.stride : -1;
         d.cand = j; d.npk = L.h_npk[b];
         d.coarse = L.h_cands[(size_t)b * per + j];
@@ -323,10 +324,11 @@ static pipe_lane *take_lane(uwspr_pipe *q) {
   return pick;
 }
 
-static int launch(uwspr_pipe *q, pipe_lane &L, const float *frames, int B, int stride, int64_t pos0, int ringbuf) {
+static int launch(uwspr_pipe *q, pipe_lane &L, const float *frames, int B, int stride, int64_t pos0, int ringbuf,
+                  int channel = 0) {
   const int per = q->per;
-  L.B = B; L.stride = stride; L.frames = frames; L.pos0 = pos0; L.frame0 = q->next_frame;
-  q->next_frame += B;
+  L.B = B; L.stride = stride; L.frames = frames; L.pos0 = pos0; L.channel = channel; L.frame0 = q->next_frame[channel];
+  q->next_frame[channel] += B;
   if (q->inject_where.load() == 0 && q->next_seq == q->inject_seq.load())
     return pfail(q, UWSPR_ERR_HIP, "injected failure at the launch of batch %lld", (long long)q->next_seq);
   int rc = uwspr_set_frame_stride(L.ctx, stride);
@@ -357,18 +359,28 @@ static void release_lane(uwspr_pipe *q, pipe_lane &L) {   // a launch that faile
   q->cv_lane.notify_all();
 }
 
+// k frames of every channel: one batch per channel, channels 0..nch-1, each in place in its plane.  The view consumes
+// the frames of all planes; the lanes of channels 1.. wait for the same uploads (nothing is appended in between: the
+// producer thread is the only writer) and each lane's event joins the buffer's readers.
 static int launch_from_ring(uwspr_pipe *q, int k) {
-  pipe_lane *L = take_lane(q);
+  stream_ring &r = q->ring;
   const float *frames = nullptr;
   long long pos = 0;
   int buf = 0;
-  if (!q->ring.view(k, L->stream, &frames, &pos, &buf)) {
-    release_lane(q, *L);
-    return pfail(q, UWSPR_ERR_HIP, "stream view: %s", hipGetErrorString(q->ring.err));
+  for (int c = 0; c < r.nch; c++) {
+    pipe_lane *L = take_lane(q);
+    if (c == 0 && !r.view(k, L->stream, &frames, &pos, &buf)) {
+      release_lane(q, *L);
+      return pfail(q, UWSPR_ERR_HIP, "stream view: %s", hipGetErrorString(r.err));
+    }
+    if (c > 0 && (r.err = hipStreamWaitEvent(L->stream, r.ev_up, 0)) != hipSuccess) {
+      release_lane(q, *L);
+      return pfail(q, UWSPR_ERR_HIP, "stream view: %s", hipGetErrorString(r.err));
+    }
+    const int rc = launch(q, *L, frames + 2 * (size_t)c * r.plane, k, r.hop, pos, buf, c);
+    if (rc) { release_lane(q, *L); return rc; }
   }
-  const int rc = launch(q, *L, frames, k, q->ring.hop, pos, buf);
-  if (rc) release_lane(q, *L);
-  return rc;
+  return UWSPR_OK;
 }
 
 extern "C" const char *uwspr_pipe_last_error(const uwspr_pipe *q) { return q ? q->err : "null pipe"; }
@@ -464,11 +476,18 @@ extern "C" int uwspr_pipe_open(const uwspr_params *p, int device, const uwspr_pi
   return UWSPR_OK;
 }
 
-// the device ring (a few batches of slack beyond what can be in flight) and the page-locked staging buffers
-static int open_ingest(uwspr_pipe *q) {
-  if (q->ring.is_open()) return UWSPR_OK;
-  if (!q->ring.open(q->fl, q->o.hop, q->o.batch_frames, q->o.lanes + 3))
-    return pfail(q, UWSPR_ERR_NOMEM, "stream ring: %s", hipGetErrorString(q->ring.err));
+// the device ring and the page-locked staging buffers.  Per channel plane: ceil(lanes / nch) + 3 takes of slack (at
+// most `lanes` batches are in flight, nch per take) + fl.  A ring nothing was pushed into yet takes the channel count
+// of the first push (a pipe's stream kind and channel count are latched by its first push).
+static int open_ingest(uwspr_pipe *q, int nch) {
+  stream_ring &r = q->ring;
+  if (r.is_open() && (r.nch == nch || r.kind != RING_EMPTY)) return UWSPR_OK;
+  const bool staged = r.is_open();
+  const int takes = (q->o.lanes + nch - 1) / nch + 3;
+  if (!r.open(q->fl, q->o.hop, q->o.batch_frames, takes, nch))
+    return pfail(q, UWSPR_ERR_NOMEM, "stream ring (%d channel planes of %lld pairs, 2 buffers): %s", nch,
+                 (long long)takes * q->o.batch_frames * q->o.hop + q->fl, hipGetErrorString(r.err));
+  if (staged) return UWSPR_OK;
   for (int k = 0; k < uwspr_pipe::NSTAGE; k++) {
     PHIP(q, hipHostMalloc((void **)&q->h_stage[k], q->stage_samples * 2 * sizeof(float), hipHostMallocDefault));
     PHIP(q, hipEventCreateWithFlags(&q->stage_ev[k], hipEventDisableTiming));
@@ -488,7 +507,7 @@ extern "C" int uwspr_pipe_acquire(uwspr_pipe *q, int nsamples, float **iq) {
   if (nsamples <= 0 || (size_t)nsamples > q->stage_samples)
     return parg(q, "uwspr_pipe_acquire(%d): at most %zu samples per piece", nsamples, q->stage_samples);
   (void)hipSetDevice(q->device);
-  if (const int rc = open_ingest(q)) return rc;
+  if (const int rc = open_ingest(q, 1)) return rc;
   const int s = q->stage_next;
   if (q->stage_busy[s]) { PHIP(q, hipEventSynchronize(q->stage_ev[s])); q->stage_busy[s] = false; }
   q->stage_cur = s;
@@ -541,26 +560,36 @@ extern "C" int uwspr_pipe_push(uwspr_pipe *q, const float *iq, int nsamples) {
 }
 
 // Audio through the same page-locked staging (its bytes: batch_frames * hop (I,Q) pairs per buffer), then K0 on the
-// copy stream into the ring (stream_ring::push_audio); batches are launched from the ring as uwspr_pipe_commit does.
-extern "C" int uwspr_pipe_push_audio(uwspr_pipe *q, const void *audio, int nsamples, int format) {
-  if (!q || (nsamples > 0 && !audio) || nsamples < 0) return UWSPR_ERR_ARG;
+// copy stream into the ring (stream_ring::push_audio); batches are launched from the ring as uwspr_pipe_commit does,
+// one per channel.  One channel is the same call with nchannels = 1.
+extern "C" int uwspr_pipe_push_audio_channels(uwspr_pipe *q, const void *audio, int nframes, int nchannels, int format) {
+  if (!q || (nframes > 0 && !audio) || nframes < 0) return UWSPR_ERR_ARG;
   if (const int f = q->failed.load()) return f;
+  if (nchannels < 1 || nchannels > UWSPR_PIPE_MAX_CHANNELS)
+    return parg(q, "uwspr_pipe_push_audio_channels: nchannels %d (1..%d)", nchannels, UWSPR_PIPE_MAX_CHANNELS);
   if (format != UWSPR_AUDIO_F32 && format != UWSPR_AUDIO_S16) return parg(q, "uwspr_pipe_push_audio: format %d", format);
   if (q->p.fs != 375) return parg(q, "uwspr_pipe_push_audio: the front-end is 12000 -> 375 S/s (fs=%d)", q->p.fs);
-  if (nsamples == 0) return UWSPR_OK;
-  const bool s16 = format == UWSPR_AUDIO_S16;
-  const int mode = q->lanes[0].ctx->opt[UWSPR_OPT_FRONTEND];
+  if (nframes == 0) return UWSPR_OK;
   stream_ring &r = q->ring;
   if (r.kind == RING_IQ) return parg(q, "uwspr_pipe_push_audio: the pipe's stream is (I,Q)");
+  if (r.kind == RING_AUDIO && nchannels != r.nch)
+    return parg(q, "uwspr_pipe_push_audio_channels: %d channels into a stream of %d", nchannels, r.nch);
+  const bool s16 = format == UWSPR_AUDIO_S16;
+  const int mode = q->lanes[0].ctx->opt[UWSPR_OPT_FRONTEND];
   if (r.kind == RING_AUDIO && mode != r.au.mode)
     return parg(q, "uwspr_pipe_push_audio: option frontend changed to %d while the audio stream runs in mode %d", mode, r.au.mode);
   (void)hipSetDevice(q->device);
-  if (const int rc = open_ingest(q)) return rc;
+  if (const int rc = open_ingest(q, nchannels)) return rc;
   if (r.kind != RING_AUDIO && !r.audio_latch(mode, s16))
-    return pfail(q, UWSPR_ERR_HIP, "audio stream set-up: %s", hipGetErrorString(r.err));
-  const size_t es = s16 ? 2 : 4, piece = q->stage_samples * 2 * sizeof(float) / es;
-  for (size_t off = 0; off < (size_t)nsamples;) {
-    const size_t n = (size_t)nsamples - off < piece ? (size_t)nsamples - off : piece;
+    return pfail(q, r.err == hipErrorOutOfMemory ? UWSPR_ERR_NOMEM : UWSPR_ERR_HIP, "audio stream set-up (%d channels): %s",
+                 nchannels, hipGetErrorString(r.err));
+  const size_t es = (s16 ? 2 : 4) * (size_t)nchannels;   // bytes per frame
+  size_t piece = q->stage_samples * 2 * sizeof(float) / es;
+  // several channels: whole K0 workgroups per piece (32 * 512 frames), so a launch has no ragged last output block
+  constexpr size_t kBlockFrames = 32 * 512;
+  if (nchannels > 1 && piece >= kBlockFrames) piece = piece / kBlockFrames * kBlockFrames;
+  for (size_t off = 0; off < (size_t)nframes;) {
+    const size_t n = (size_t)nframes - off < piece ? (size_t)nframes - off : piece;
     const int s = q->stage_next;
     if (q->stage_busy[s]) { PHIP(q, hipEventSynchronize(q->stage_ev[s])); q->stage_busy[s] = false; }
     memcpy(q->h_stage[s], (const char *)audio + off * es, n * es);
@@ -580,6 +609,10 @@ extern "C" int uwspr_pipe_push_audio(uwspr_pipe *q, const void *audio, int nsamp
     off += n;
   }
   return UWSPR_OK;
+}
+
+extern "C" int uwspr_pipe_push_audio(uwspr_pipe *q, const void *audio, int nsamples, int format) {
+  return uwspr_pipe_push_audio_channels(q, audio, nsamples, 1, format);
 }
 
 extern "C" int uwspr_pipe_submit_device(uwspr_pipe *q, const float *dev_frames, int B, int stride) {

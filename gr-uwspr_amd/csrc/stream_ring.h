@@ -13,6 +13,11 @@
 // Memory: two linear buffers of `cap` samples.  Appends go behind the unconsumed samples; when the
 // current buffer is full the unconsumed tail (< fl + a take) moves to the front of the other buffer
 // (rare: cap is several takes) after every reader of THAT buffer has finished.
+//
+// Channel planes (uwspr_pipe_push_audio_channels): a buffer holds nch planes of `plane` pairs each, one stream per
+// channel.  The channels advance in lockstep, so the bookkeeping (base, have, pos, cur, the events) is shared:
+// reserve / view return plane 0 and channel c is at + 2 * c * plane floats; the tail move is one 2-D copy of all
+// planes.  The audio history is one interleaved [time][nch] buffer.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -27,7 +32,7 @@ int frontend_tap_image(int mode, std::vector<float> &img, int *J, int *dcols);
 int frontend_prepare();
 int frontend_read_ahead(int mode);
 void launch_frontend_stream(hipStream_t s, const void *audio, bool s16, int nin, long long in0, const float *taps,
-                            int J, int dcols, float *out, int nout, long long m_first);
+                            int J, int dcols, float *out, int nout, long long m_first, int nch, long long plane);
 void launch_widen_s16(hipStream_t s, const int16_t *in, float *out, size_t n);
 
 enum { RING_EMPTY = 0, RING_IQ = 1, RING_AUDIO = 2 };   // what the stream is, decided by its first push
@@ -35,7 +40,9 @@ enum { RING_EMPTY = 0, RING_IQ = 1, RING_AUDIO = 2 };   // what the stream is, d
 struct stream_ring {
   int fl = 0, hop = 0, maxf = 0;
   float *buf[2] = {nullptr, nullptr};
-  size_t cap = 0;                      // samples per buffer
+  size_t cap = 0;                      // samples per buffer (per plane)
+  int nch = 1;                         // channel planes per buffer
+  size_t plane = 0;                    // pairs from one plane to the next (>= cap)
   int cur = 0;
   size_t base = 0, have = 0;           // unconsumed samples: buf[cur][base, base + have)
   long long pos = 0;                   // stream index of buf[cur][base]
@@ -52,10 +59,10 @@ struct stream_ring {
   bool last_direct = false;            // the last append DMAs straight from the caller's (page-locked) buffer
   hipError_t err = hipSuccess;
   int kind = RING_EMPTY;
-  // Audio streams (push_audio): 12 kS/s real samples go through K0 into the ring.  Output m of the stream is
-  // y[m] = sum_k g[k] x[32 m + D - k] (audio index 32 m = stream index m) and is produced as soon as x[32 m + D]
-  // has been pushed.  The device buffer holds [history | new samples]: the history is the audio from index
-  // 32 (m_next + dcols - J) on, at most 32 J samples, zero before the stream's first sample.
+  // Audio streams (push_audio): 12 kS/s real samples (frames of nch interleaved samples) go through K0 into the
+  // ring.  Output m of the stream is y[m] = sum_k g[k] x[32 m + D - k] (audio index 32 m = stream index m) and is
+  // produced as soon as x[32 m + D] has been pushed.  The device buffer holds [history | new frames]: the history is
+  // the audio from index 32 (m_next + dcols - J) on, at most 32 J frames, zero before the stream's first sample.
   struct audio_state {
     int mode = -1;                     // latched by the first push after open / reset
     int s16 = 0;                       // the buffer holds int16 samples (every push so far was int16), else float
@@ -65,10 +72,13 @@ struct stream_ring {
     size_t buf_bytes = 0;
     int cur = 0;
     long long a0 = 0;                  // audio index of d_buf[cur][0]
-    size_t hist = 0;                   // samples held in d_buf[cur]: audio [a0, a0 + hist)
+    size_t hist = 0;                   // frames held in d_buf[cur]: audio [a0, a0 + hist)
     long long m_next = 0;              // stream index of the next output
   } au;
-  static constexpr size_t AUDIO_PIECE = 4u << 20;   // most new samples per K0 launch (131072 outputs: 256 workgroups)
+  // most new samples per K0 launch: AUDIO_PIECE / nch frames (one channel: 131072 outputs, 256 workgroups), so the
+  // history buffers hold at most (32 J + 32) nch + AUDIO_PIECE samples whatever the channel count
+  static constexpr size_t AUDIO_PIECE = 4u << 20;
+  size_t audio_piece_frames() const { return AUDIO_PIECE / (size_t)nch; }
 
   bool is_open() const { return buf[0] != nullptr; }
 
@@ -82,16 +92,18 @@ struct stream_ring {
     if (au.d_taps) { (void)hipFree(au.d_taps); au.d_taps = nullptr; }
     au = audio_state();
     if (copy) { (void)hipStreamDestroy(copy); copy = nullptr; }
-    cap = 0; have = 0; base = 0; up_pending = false;
+    cap = 0; plane = 0; nch = 1; have = 0; base = 0; up_pending = false;
   }
 
-  // takes_of_slack: how many full takes fit behind one another before the tail has to move
-  bool open(int fl_, int hop_, int max_frames, int takes_of_slack = 6) {
+  // takes_of_slack: how many full takes fit behind one another before the tail has to move; nplanes: channels
+  bool open(int fl_, int hop_, int max_frames, int takes_of_slack = 6, int nplanes = 1) {
     close();
     fl = fl_; hop = hop_; maxf = max_frames;
     cap = (size_t)takes_of_slack * max_frames * hop + fl;
+    nch = nplanes;
+    plane = nch == 1 ? cap : (cap + 63) / 64 * 64;   // (planes start 512-byte aligned)
     for (int k = 0; k < 2; k++)
-      if ((err = hipMalloc((void **)&buf[k], cap * 2 * sizeof(float))) != hipSuccess) { close(); return false; }
+      if ((err = hipMalloc((void **)&buf[k], plane * nch * 2 * sizeof(float))) != hipSuccess) { close(); return false; }
     if ((err = hipStreamCreateWithFlags(&copy, hipStreamNonBlocking)) != hipSuccess) { close(); return false; }
     if ((err = hipEventCreateWithFlags(&ev_up, hipEventDisableTiming)) != hipSuccess) { close(); return false; }
     cur = 0; base = 0; have = 0; pos = 0; up_pending = false; pin_next = 0;
@@ -120,13 +132,17 @@ struct stream_ring {
     for (hipEvent_t e : readers[other])
       if ((err = hipStreamWaitEvent(copy, e, 0)) != hipSuccess) return false;
     readers[other].clear();
-    if (have && (err = hipMemcpyAsync(buf[other], buf[cur] + 2 * base, have * 2 * sizeof(float),
-                                      hipMemcpyDeviceToDevice, copy)) != hipSuccess) return false;
+    if (have && nch == 1 && (err = hipMemcpyAsync(buf[other], buf[cur] + 2 * base, have * 2 * sizeof(float),
+                                                  hipMemcpyDeviceToDevice, copy)) != hipSuccess) return false;
+    if (have && nch > 1 && (err = hipMemcpy2DAsync(buf[other], plane * 2 * sizeof(float), buf[cur] + 2 * base,
+                                                   plane * 2 * sizeof(float), have * 2 * sizeof(float), (size_t)nch,
+                                                   hipMemcpyDeviceToDevice, copy)) != hipSuccess) return false;
     cur = other; base = 0;
     return true;
   }
 
-  // n samples of space behind the unconsumed ones for a producer on the copy stream (a kernel), then commit(n)
+  // n samples of space behind the unconsumed ones (in every plane) for a producer on the copy stream (a kernel), then
+  // commit(n).  Returns plane 0.
   float *reserve(size_t n) {
     if (!make_room(n)) { if (err == hipSuccess) err = hipErrorOutOfMemory; return nullptr; }
     return buf[cur] + 2 * (base + have);
@@ -173,7 +189,7 @@ struct stream_ring {
     return true;
   }
 
-  // n (I,Q) pairs (see upload).  Returns with the transfer enqueued on the copy stream.
+  // n (I,Q) pairs (see upload) of a one-plane ring.  Returns with the transfer enqueued on the copy stream.
   bool append(const float *src, size_t n, bool on_device, hipEvent_t src_ready = nullptr) {
     if (n == 0) return true;
     last_direct = false;
@@ -209,7 +225,7 @@ struct stream_ring {
       if ((err = hipMemcpy(au.d_taps, img.data(), img.size() * sizeof(float), hipMemcpyHostToDevice)) != hipSuccess) return false;
       au.taps_mode = mode; au.J = J; au.dcols = dcols;
     }
-    const size_t need = (32 * (size_t)au.J + 32 + AUDIO_PIECE) * sizeof(float);
+    const size_t need = ((32 * (size_t)au.J + 32) * nch + audio_piece_frames() * nch) * sizeof(float);
     if (au.buf_bytes < need) {
       if ((err = hipStreamSynchronize(copy)) != hipSuccess) return false;
       for (int k = 0; k < 2; k++) {
@@ -221,32 +237,34 @@ struct stream_ring {
     au.mode = mode; au.s16 = s16;
     au.a0 = 32 * (au.m_next + au.dcols - au.J);
     au.hist = (size_t)(32LL * au.m_next - au.a0);
-    if ((err = hipMemsetAsync(au.d_buf[au.cur], 0, au.hist * (s16 ? 2 : 4), copy)) != hipSuccess) return false;
+    if ((err = hipMemsetAsync(au.d_buf[au.cur], 0, au.hist * nch * (s16 ? 2 : 4), copy)) != hipSuccess) return false;
     kind = RING_AUDIO;
     return true;
   }
 
-  // n audio samples (int16 when s16, else float) from src (see upload): upload behind the history, K0 for the outputs
-  // that became complete straight into the ring, keep the new tail as history.  The caller has latched the stream
-  // and checked room() against audio_outputs(n).  An int16 stream stays int16 while every push is; a float push
+  // n audio frames of nch samples (int16 when s16, else float) from src (see upload): upload behind the history, K0
+  // for the outputs that became complete straight into the ring (one plane per channel), keep the new tail as
+  // history.  The caller has latched the stream and checked room() against audio_outputs(n).  An int16 stream stays int16 while every push is; a float push
   // widens its history once (s / 32768, exact) and from then on int16 pushes are widened on arrival, so formats may
   // mix and every output sees the same sample values.
   bool push_audio(const void *src, size_t n, bool s16_in, bool on_device, hipEvent_t src_ready = nullptr) {
     last_direct = false;
+    const size_t C = (size_t)nch;
     if (n && au.s16 && !s16_in) {
-      launch_widen_s16(copy, (const int16_t *)au.d_buf[au.cur], (float *)au.d_buf[au.cur ^ 1], au.hist);
+      launch_widen_s16(copy, (const int16_t *)au.d_buf[au.cur], (float *)au.d_buf[au.cur ^ 1], au.hist * C);
       if ((err = hipGetLastError()) != hipSuccess) return false;
       au.cur ^= 1; au.s16 = 0;
     }
     const bool widen = s16_in && !au.s16;   // int16 samples into a float buffer
-    const size_t es = au.s16 ? 2 : 4, es_in = s16_in ? 2 : 4;
+    const size_t es = (au.s16 ? 2 : 4) * C, es_in = (s16_in ? 2 : 4) * C;   // bytes per frame
+    const size_t piece = audio_piece_frames();
     for (size_t off = 0; off < n;) {
-      const size_t k = n - off < AUDIO_PIECE ? n - off : AUDIO_PIECE;
+      const size_t k = n - off < piece ? n - off : piece;
       char *b = au.d_buf[au.cur];
       if (widen) {   // (the other buffer is free until the tail copy below, which comes after on the same stream)
         char *tmp = au.d_buf[au.cur ^ 1];
         if (!upload(tmp, (const char *)src + off * es_in, k * es_in, on_device, src_ready)) return false;
-        launch_widen_s16(copy, (const int16_t *)tmp, (float *)(b + au.hist * es), k);
+        launch_widen_s16(copy, (const int16_t *)tmp, (float *)(b + au.hist * es), k * C);
         if ((err = hipGetLastError()) != hipSuccess) return false;
       } else if (!upload(b + au.hist * es, (const char *)src + off * es_in, k * es_in, on_device, src_ready)) {
         return false;
@@ -257,7 +275,8 @@ struct stream_ring {
         const int nout = (int)(m_end - au.m_next);
         float *dst = reserve((size_t)nout);
         if (!dst) return false;
-        launch_frontend_stream(copy, b, au.s16, (int)(au.hist + k), au.a0, au.d_taps, au.J, au.dcols, dst, nout, au.m_next);
+        launch_frontend_stream(copy, b, au.s16, (int)(au.hist + k), au.a0, au.d_taps, au.J, au.dcols, dst, nout, au.m_next,
+                               nch, (long long)plane);
         if ((err = hipGetLastError()) != hipSuccess) return false;
         if (!commit((size_t)nout)) return false;
         au.m_next = m_end;
@@ -282,7 +301,8 @@ struct stream_ring {
     return true;
   }
 
-  // The next k frames in place; `consumer` is the stream whose kernels will read them.
+  // The next k frames in place (plane 0; channel c at + 2 * c * plane floats); `consumer` is the stream whose kernels
+  // will read them.
   // *bufidx = which buffer they live in (for reader_done).
   bool view(int k, hipStream_t consumer, const float **frames, long long *first_pos, int *bufidx) {
     if (k <= 0 || k > ready()) { err = hipErrorInvalidValue; return false; }

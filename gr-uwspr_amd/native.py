@@ -204,8 +204,9 @@ class Info(C.Structure):
 DECODE_DTYPE = np.dtype([("frame", "<i8"), ("stream_pos", "<i8"), ("cand", "<i4"), ("npk", "<i4"),
                          ("coarse", CAND_DTYPE), ("f1", "<f4"), ("drift1", "<f4"), ("sync1", "<f4"),
                          ("shift1", "<i4"), ("worth_a_try", "<i4"), ("decoded", "<i4"), ("idt", "<i4"),
-                         ("message", "i1", (7,)), ("_pad", "u1", (5,))])
-assert DECODE_DTYPE.itemsize == 112
+                         ("message", "i1", (7,)), ("_pad0", "u1"), ("channel", "<i2"), ("_pad", "u1", (2,))])
+assert DECODE_DTYPE.itemsize == 112 and DECODE_DTYPE.fields["channel"][1] == 108
+PIPE_MAX_CHANNELS = 64
 
 
 class PipeOpts(C.Structure):
@@ -240,7 +241,7 @@ ABI_SYMBOLS = [
     "uwspr_c2_read",
     "uwspr_dist_unique_id", "uwspr_dist_init", "uwspr_dist_gather", "uwspr_dist_finalize",
     "uwspr_pipe_open", "uwspr_pipe_close", "uwspr_pipe_last_error", "uwspr_pipe_acquire", "uwspr_pipe_commit",
-    "uwspr_pipe_push", "uwspr_pipe_push_audio", "uwspr_pipe_submit_device", "uwspr_pipe_flush", "uwspr_pipe_collect", "uwspr_pipe_get_stats",
+    "uwspr_pipe_push", "uwspr_pipe_push_audio", "uwspr_pipe_push_audio_channels", "uwspr_pipe_submit_device", "uwspr_pipe_flush", "uwspr_pipe_collect", "uwspr_pipe_get_stats",
     "uwspr_pipe_inject_failure", "uwspr_pipe_set_option",
 ]
 
@@ -339,6 +340,7 @@ def lib():
     L.uwspr_pipe_commit.argtypes = [vp, ip]
     L.uwspr_pipe_push.argtypes = [vp, vp, ip]
     L.uwspr_pipe_push_audio.argtypes = [vp, vp, ip, ip]
+    L.uwspr_pipe_push_audio_channels.argtypes = [vp, vp, ip, ip, ip]
     L.uwspr_pipe_submit_device.argtypes = [vp, vp, ip, ip]
     L.uwspr_pipe_flush.argtypes = [vp]
     L.uwspr_pipe_collect.argtypes = [vp, vp, ip, ip]

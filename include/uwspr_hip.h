@@ -34,7 +34,9 @@ extern "C" {
                                  4: option "frontend" (the flowgraph's GNU Radio chain is the default front-end),
                                     uwspr_frontend_design replaces uwspr_frontend_taps;
                                  5: uwspr_host_set_ranks (the host's CPU share divided between the ranks of a node);
-                                 6: audio streams: uwspr_stream_push_audio, uwspr_pipe_push_audio */
+                                 6: audio streams: uwspr_stream_push_audio, uwspr_pipe_push_audio; multichannel
+                                    audio into one pipe: uwspr_pipe_push_audio_channels, uwspr_decode.channel (carved
+                                    out of the padding: the record stays 112 bytes) */
 
 typedef enum {
   UWSPR_OK = 0,
@@ -422,7 +424,9 @@ typedef struct uwspr_decode {
   int32_t decoded;        /* 1: message holds the 7 bytes sync_and_demodulate publishes (cc:528-530) */
   int32_t idt;            /* the jiggered try that decoded (-1: none) */
   int8_t message[7];
-  uint8_t _pad[5];
+  uint8_t _pad0;
+  int16_t channel;        /* the audio channel of a multichannel pipe (uwspr_pipe_push_audio_channels); 0 otherwise */
+  uint8_t _pad[2];
 } uwspr_decode;
 typedef struct uwspr_pipe_stats {
   int64_t frames, batches, candidates, decoded, resumed;   /* resumed: records whose other tries were produced */
@@ -444,6 +448,22 @@ int uwspr_pipe_push(uwspr_pipe *pipe, const float *iq, int nsamples);
  * front-end's output at audio index 32 m; records' stream_pos / 375 = audio time in s).  A pipe's stream is audio or
  * (I,Q), decided by its first push; the front-end mode is the lanes' option "frontend" at that push. */
 int uwspr_pipe_push_audio(uwspr_pipe *pipe, const void *audio, int nsamples, int format);
+/* Several channels through one pipe: audio is [nframes][nchannels] interleaved (the WAV / ALSA layout), in either
+ * format, pieces of any length, formats mixing between pushes as for one channel.  The first audio push latches the
+ * channel count (1..UWSPR_PIPE_MAX_CHANNELS); a push with another count, an audio push into an (I,Q) pipe or the
+ * reverse, and a bad format fail that call with UWSPR_ERR_ARG and the pipe goes on.  uwspr_pipe_push_audio(p, x, n, f)
+ * is uwspr_pipe_push_audio_channels(p, x, n, 1, f).  Every channel is its own stream: a record's channel says which,
+ * and per channel frame and stream_pos count as a one-channel pipe fed that channel alone counts them, so (channel,
+ * frame) identifies a record.  A batch holds frames of one channel; the batches of a take (batch_frames frames of
+ * every channel) are launched channel 0..nchannels-1, so records come in (take, channel, frame) order.  flush launches
+ * the short last batch of every channel; the stats count frames over all channels.
+ * Device memory of the stream, made by the first push (UWSPR_ERR_NOMEM, with a message, if it does not fit): two
+ * buffers of nchannels planes of (ceil(lanes / nchannels) + 3) * batch_frames * hop + fl (I,Q) pairs (8 bytes; each
+ * plane rounded up to 64 pairs when nchannels > 1), plus two audio buffers of ((32 J + 32) * nchannels + 4 Mi)
+ * samples (4 bytes; J = 216 taps per phase in the default "grc" front-end, 32 in "compact").  Defaults (hop 3375,
+ * batch_frames 256, 9 lanes): 2 x 83 MB for one channel, 2 x 28 MB per channel from 9 channels on. */
+#define UWSPR_PIPE_MAX_CHANNELS 64
+int uwspr_pipe_push_audio_channels(uwspr_pipe *pipe, const void *audio, int nframes, int nchannels, int format);
 /* B frames already in device memory (frame b at frames + 2*stride*b floats, stride 0 = fl): searched as one
  * batch.  The memory must stay valid until the batch's results have been collected. */
 int uwspr_pipe_submit_device(uwspr_pipe *pipe, const float *dev_frames, int B, int stride);
