@@ -435,6 +435,88 @@ class Context:
                                           C.c_void_p(sync_t.data_ptr()),
                                           C.c_void_p(sym_t.data_ptr()) if sym_t is not None else None))
 
+    # -- transmit side (K7: uwspr_tx_*) ------------------------------------
+    def tx_baseband(self, signals, n=45000, t0=0, channel=0, out=None):
+        """375 S/s baseband samples [t0, t0 + n) of one channel's signals (tx_signals), as c2_read returns a .c2 file:
+        numpy [n, 2] float32, or written into `out` (a torch CUDA float32 tensor of n pairs)."""
+        sig = tx_signals(signals)
+        sp = C.c_void_p(C.addressof(sig)) if len(sig) else None
+        if out is not None and _is_torch(out):
+            import torch
+            if not (out.is_cuda and out.is_contiguous() and out.dtype == torch.float32 and out.numel() >= 2 * n):
+                raise TypeError("tx_baseband: out must be a contiguous float32 CUDA tensor of >= %d elements, not %s %s"
+                                % (2 * n, out.dtype, tuple(out.shape)))
+            if self._stream_ptr is None:
+                torch.cuda.current_stream(out.device).synchronize()
+            self._chk(self.L.uwspr_tx_baseband(self.h, sp, len(sig), int(channel), int(t0), int(n),
+                                               C.c_void_p(out.data_ptr()), N.DEVICE))
+            if self._stream_ptr is None:
+                self.synchronize()
+            return out
+        iq = np.empty((n, 2), np.float32)
+        self._chk(self.L.uwspr_tx_baseband(self.h, sp, len(sig), int(channel), int(t0), int(n),
+                                           C.c_void_p(iq.ctypes.data), N.HOST))
+        return iq
+
+    def tx_render(self, signals, nframes, t0=0, channels=1, sigma=0.0, seed=0, background=None, background_gain=1.0,
+                  format="f32", out=None):
+        """12 kS/s audio frames [t0, t0 + nframes) of a `channels`-channel recording (uwspr_tx_render) -> numpy
+        [nframes, channels] float32 / int16 (format "f32" / "s16"), or written into `out`, a torch CUDA tensor of that
+        shape and dtype (what stream_push_audio / a pipe takes, with no PCIe crossing).  sigma, seed, background
+        (a 1-D float32 / int16 numpy array or torch tensor, or None) and background_gain are one value for every channel
+        or a list of one per channel.  A background is moved to where the output is made: to out's device for device
+        output (once per call: keep it there for repeated renders), to host memory for host output."""
+        sig = tx_signals(signals)
+        dev_out = out is not None and _is_torch(out)
+        if dev_out and not out.is_cuda:
+            raise TypeError("tx_render: out must be a CUDA tensor (or None for a numpy result)")
+        Cn = int(channels)
+        per = lambda v: list(v) if isinstance(v, (list, tuple)) else [v] * Cn   # noqa: E731
+        sg, sd, bg, bgg = per(sigma), per(seed), per(background), per(background_gain)
+        ch = (N.TxChannel * max(Cn, 1))()
+        keep, moved = [], False
+        for k in range(min(Cn, len(ch))):
+            ch[k].sigma, ch[k].seed, ch[k].background_gain = float(sg[k]), int(sd[k]) & (2 ** 64 - 1), float(bgg[k])
+            b = bg[k]
+            if b is None:
+                continue
+            if dev_out:
+                import torch
+                b = b if _is_torch(b) else torch.from_numpy(_audio_array(b))
+                if b.dtype not in (torch.float32, torch.int16) or b.dim() != 1:
+                    raise TypeError("background: a 1-D float32 or int16 array, not %s %s" % (b.dtype, tuple(b.shape)))
+                moved = moved or not b.is_cuda or b.device != out.device or not b.is_contiguous()
+                b = b.to(out.device).contiguous()
+                fmt = N.AUDIO_S16 if b.dtype == torch.int16 else N.AUDIO_F32
+                ch[k].background, ch[k].background_len = b.data_ptr(), b.numel()
+            else:
+                if _is_torch(b):
+                    b = b.detach().cpu().numpy()
+                b = _audio_array(b)
+                fmt = N.AUDIO_S16 if b.dtype == np.int16 else N.AUDIO_F32
+                ch[k].background, ch[k].background_len = b.ctypes.data, b.size
+            ch[k].background_format = fmt
+            keep.append(b)
+        fmt = {"f32": N.AUDIO_F32, "s16": N.AUDIO_S16}[format]
+        sp = C.c_void_p(C.addressof(sig)) if len(sig) else None
+        if dev_out:
+            import torch
+            if not (out.is_contiguous() and out.numel() >= int(nframes) * Cn and
+                    out.dtype == (torch.int16 if fmt == N.AUDIO_S16 else torch.float32)):
+                raise TypeError("tx_render: out must be a contiguous %s CUDA tensor of >= %d elements, not %s %s"
+                                % ("int16" if fmt == N.AUDIO_S16 else "float32", int(nframes) * Cn, out.dtype, tuple(out.shape)))
+            if self._stream_ptr is None or moved:   # (a moved background was copied on torch's stream)
+                torch.cuda.current_stream(out.device).synchronize()
+            self._chk(self.L.uwspr_tx_render(self.h, sp, len(sig), C.byref(ch), Cn, int(t0), int(nframes), fmt,
+                                             C.c_void_p(out.data_ptr()), N.DEVICE))
+            if self._stream_ptr is None or moved:   # (the moved copies are freed when this call returns)
+                self.synchronize()
+            return out
+        a = np.empty((int(nframes), Cn), np.int16 if fmt == N.AUDIO_S16 else np.float32)
+        self._chk(self.L.uwspr_tx_render(self.h, sp, len(sig), C.byref(ch), Cn, int(t0), int(nframes), fmt,
+                                         C.c_void_p(a.ctypes.data), N.HOST))
+        return a
+
     # -- multi-GPU gather over RCCL (uwspr_dist_*) ---------------------------
     @staticmethod
     def dist_unique_id():
@@ -598,6 +680,96 @@ def c2_read(path):
     if rc != 0:
         raise N.UwsprError(rc, "cannot read %s" % path)
     return iq, freq.value, typ.value
+
+
+# ---- transmit side (no device needed up to the symbols) -------------------------------------------------------------
+def wspr_pack(text):
+    """WSPR message text ("CALL GRID4 dBm", "PFX/CALL dBm", "CALL/SFX dBm", "<CALL> GRID6 dBm") -> the 7 message bytes
+    (int8) that unpack_message turns back into text.  Invalid text raises UwsprError (UWSPR_ERR_ARG)."""
+    m = np.zeros(7, np.int8)
+    rc = N.lib().uwspr_wspr_pack(str(text).encode("ascii", "replace"), C.c_void_p(m.ctypes.data))
+    if rc != 0:
+        raise N.UwsprError(rc, "not a WSPR message: %r" % (text,))
+    return m
+
+
+def nhash(key, initval=146):
+    """lookup3 hashlittle() of a byte string (the type 3 callsign hash is nhash(call) & 32767)"""
+    k = key.encode() if isinstance(key, str) else bytes(key)
+    return int(N.lib().uwspr_nhash(k, len(k), int(initval) & 0xFFFFFFFF))
+
+
+def wspr_symbols(text_or_message):
+    """The 162 channel symbols (uint8, 0..3) wsprsim transmits for a message: text, or the 7 bytes of wspr_pack"""
+    m = wspr_pack(text_or_message) if isinstance(text_or_message, str) else \
+        np.ascontiguousarray(text_or_message, dtype=np.int8).reshape(7)
+    sym = np.zeros(N.NSYM, np.uint8)
+    N.lib().uwspr_wspr_symbols(C.c_void_p(m.ctypes.data), C.c_void_p(sym.ctypes.data))
+    return sym
+
+
+def write_c2(path, iq, dial_freq=10.1387, type=2):
+    """45000 (I,Q) pairs as a .c2 file that c2_read returns unchanged (the file holds Q negated, as wsprsim writes it)"""
+    a = np.ascontiguousarray(iq, np.float32).reshape(-1, 2)
+    rc = N.lib().uwspr_c2_write(str(path).encode(), C.c_void_p(a.ctypes.data), a.shape[0], float(dial_freq), int(type))
+    if rc != 0:
+        raise N.UwsprError(rc, "cannot write %s (%d samples; a .c2 file holds 45000)" % (path, a.shape[0]))
+
+
+def tx_signals(signals):
+    """A list of transmissions -> the uwspr_tx_signal array.  Each is a dict: "text" (or "message": 7 bytes, or
+    "symbols": 162), "channel" (0), "start" (baseband sample of the first symbol, 375), "f0" (Hz, 0), "drift" (Hz over the
+    transmission, 0), "phase0" (rad, 0), "gain" (1)."""
+    signals = list(signals)
+    arr = (N.TxSignal * max(len(signals), 1))()
+    for i, s in enumerate(signals):
+        if "symbols" in s:
+            sym = np.asarray(s["symbols"], np.uint8).reshape(N.NSYM)
+        else:
+            sym = wspr_symbols(s["text"] if "text" in s else s["message"])
+        C.memmove(arr[i].symbols, sym.ctypes.data, N.NSYM)
+        arr[i].channel = int(s.get("channel", 0))
+        arr[i].start = int(s.get("start", 375))
+        arr[i].f0_hz, arr[i].drift_hz = float(s.get("f0", 0.0)), float(s.get("drift", 0.0))
+        arr[i].phase0, arr[i].gain = float(s.get("phase0", 0.0)), float(s.get("gain", 1.0))
+    return arr if signals else (N.TxSignal * 0)()
+
+
+def tx_sigma(snr_db, gain=1.0):
+    """AWGN sigma (per 12 kS/s audio sample) that puts a transmission of baseband amplitude `gain` at snr_db in 2500 Hz
+    at the transmit chain's output: the chain makes it a real tone of amplitude gain / 32 (the interpolation filter has
+    unit gain), of power (gain / 32)^2 / 2 against sigma^2 2500 / 6000 of noise in 2500 Hz."""
+    a = float(gain) / 32.0
+    return float(np.sqrt(0.5 * a * a * (AUDIO_RATE / 2.0) / 2500.0 * 10.0 ** (-float(snr_db) / 10.0)))
+
+
+def encode_wav(path, schedule, channels=1, snr_db=None, seed=0, gain=1.0, seconds=None, piece_s=60, ctx=None):
+    """c2ToWaveFile from text: a 16-bit 12 kS/s WAV of `channels` channels carrying the schedule's transmissions.
+    schedule: (text, channel, start_s, f0) entries; start_s is the start of the entry's 2-minute slot (its first symbol
+    is 1 s later, as in a .c2 file) and f0 the offset in Hz (the transmission is centred on 1500 + f0 Hz).  snr_db: AWGN per channel (seed + channel) for that SNR in 2500 Hz, None = none.  The file is rendered
+    in pieces of piece_s seconds and lasts `seconds` (default: until the last slot's frame is complete)."""
+    import wave
+    sig = [{"text": t, "channel": int(c), "start": int(round(375 * float(s0))) + 375, "f0": float(f0), "gain": gain}
+           for (t, c, s0, f0) in schedule]
+    if seconds is None:
+        seconds = max([float(e[2]) for e in schedule] + [0.0]) + 121.0
+    n = int(round(seconds * AUDIO_RATE))
+    own = ctx is None
+    ctx = Context() if own else ctx
+    sigma = 0.0 if snr_db is None else tx_sigma(snr_db, gain)
+    try:
+        with wave.open(str(path), "wb") as w:
+            w.setnchannels(int(channels))
+            w.setsampwidth(2)
+            w.setframerate(AUDIO_RATE)
+            step = int(piece_s * AUDIO_RATE)
+            for k in range(0, n, step):
+                x = ctx.tx_render(sig, min(step, n - k), t0=k, channels=channels, sigma=sigma,
+                                  seed=[int(seed) + c for c in range(int(channels))], format="s16")
+                w.writeframes(x.astype("<i2").tobytes())
+    finally:
+        if own:
+            ctx.close()
 
 
 class Pipe:

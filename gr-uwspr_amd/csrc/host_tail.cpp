@@ -508,3 +508,229 @@ extern "C" int uwspr_c2_read(const char *path, float *iq, double *dial_freq, int
   if (type) *type = ntrmin;
   return UWSPR_OK;
 }
+
+// ---- WSPR message pack, channel symbols, .c2 writer (the sender: wsprsim) -----------------------------------------
+// The inverse of uwspr_unpack_message above: 28 callsign bits n1 and 22 bits n2 of grid / type / power, 50 bits in 7
+// bytes.  Type 1 "CALL GRID4 dBm": n2 = 128 ngrid + dBm + 64.  Type 2 "PFX/CALL dBm" or "CALL/SFX dBm": the prefix /
+// suffix number m (15 bits + the nadd carry) and n2 = 128 m + dBm + 1 + nadd + 64.  Type 3 "<CALL> GRID6 dBm": n1 packs
+// the locator rotated by one character (FN25AB -> N25ABF) as a callsign, n2 = 128 hash - (dBm + 1) + 64.
+namespace {
+
+int char_code(char c) {   // 0-9, A-Z -> 0..35; space -> 36; anything else -> -1
+  if (c >= '0' && c <= '9') return c - '0';
+  if (c >= 'A' && c <= 'Z') return c - 'A' + 10;
+  if (c == ' ') return 36;
+  return -1;
+}
+
+bool is_digit(char c) { return c >= '0' && c <= '9'; }
+bool is_letter(char c) { return c >= 'A' && c <= 'Z'; }
+
+// callsign -> n1: aligned so that its digit is the third of six characters (" K1ABC"); 1..2 characters before the
+// digit, 1..3 letters after it
+bool pack_call(const char *call, int32_t *n1) {
+  const size_t len = strlen(call);
+  if (len < 3 || len > 6) return false;
+  char c6[7] = "      ";
+  if (is_digit(call[2])) memcpy(c6, call, len);
+  else if (is_digit(call[1]) && len <= 5) memcpy(c6 + 1, call, len);
+  else return false;
+  if (!(c6[0] == ' ' || is_digit(c6[0]) || is_letter(c6[0])) || !(is_digit(c6[1]) || is_letter(c6[1])) || !is_digit(c6[2]))
+    return false;
+  if (!is_letter(c6[3])) return false;
+  for (int i = 4; i < 6; i++)
+    if (!(is_letter(c6[i]) || (c6[i] == ' ' && (i == 5 || c6[i + 1] == ' ')))) return false;
+  int32_t n = char_code(c6[0]);
+  n = n * 36 + char_code(c6[1]);
+  n = n * 10 + char_code(c6[2]);
+  for (int i = 3; i < 6; i++) n = n * 27 + char_code(c6[i]) - 10;
+  *n1 = n;
+  return true;
+}
+
+bool pack_grid4(const char *g, int32_t *ngrid) {
+  if (strlen(g) != 4 || g[0] < 'A' || g[0] > 'R' || g[1] < 'A' || g[1] > 'R' || !is_digit(g[2]) || !is_digit(g[3])) return false;
+  *ngrid = 180 * (179 - 10 * (g[0] - 'A') - (g[2] - '0')) + 10 * (g[1] - 'A') + (g[3] - '0');
+  return true;
+}
+
+bool power_ok(const char *s, int *dbm) {
+  const size_t len = strlen(s);
+  if (len < 1 || len > 2) return false;
+  for (size_t i = 0; i < len; i++) if (!is_digit(s[i])) return false;
+  const int v = atoi(s);
+  const int u = v % 10;
+  if (v > 60 || !(u == 0 || u == 3 || u == 7)) return false;
+  *dbm = v;
+  return true;
+}
+
+bool alnum_only(const char *s, size_t len) {
+  for (size_t i = 0; i < len; i++) if (!(is_digit(s[i]) || is_letter(s[i]))) return false;
+  return true;
+}
+
+void put50(int32_t n1, int32_t n2, int8_t *m) {
+  uint8_t *d = (uint8_t *)m;
+  d[0] = (uint8_t)(n1 >> 20); d[1] = (uint8_t)(n1 >> 12); d[2] = (uint8_t)(n1 >> 4);
+  d[3] = (uint8_t)(((n1 & 15) << 4) | ((n2 >> 18) & 15));
+  d[4] = (uint8_t)(n2 >> 10); d[5] = (uint8_t)(n2 >> 2); d[6] = (uint8_t)((n2 & 3) << 6);
+}
+
+// "PFX/CALL" or "CALL/SFX" -> (n1, m, nadd): the number unpack_prefix() takes apart is m + 32768 nadd
+bool pack_compound(const char *call, int32_t *n1, int32_t *m, int *nadd) {
+  const char *slash = strchr(call, '/');
+  if (!slash || strchr(slash + 1, '/')) return false;
+  const size_t a = (size_t)(slash - call), b = strlen(slash + 1);
+  char base[8];
+  if (b >= 1 && b <= 2 && a >= 3) {               // suffix: one character, or two digits 10..99
+    if (a > 6) return false;
+    memcpy(base, call, a); base[a] = 0;
+    if (!pack_call(base, n1)) return false;
+    const char *s = slash + 1;
+    int32_t v;
+    if (b == 1) {
+      if (char_code(s[0]) < 0 || s[0] == ' ') return false;
+      v = char_code(s[0]);
+    } else {
+      if (!is_digit(s[0]) || !is_digit(s[1]) || s[0] == '0') return false;
+      v = 26 + 10 * (s[0] - '0') + (s[1] - '0');
+    }
+    *m = 60000 - 32768 + v; *nadd = 1;
+    return true;
+  }
+  if (a < 1 || a > 3 || b > 6 || !alnum_only(call, a)) return false;   // prefix: 1..3 characters
+  memcpy(base, slash + 1, b); base[b] = 0;
+  if (!pack_call(base, n1)) return false;
+  int32_t v = 0;
+  for (size_t i = a; i < 3; i++) v = 37 * v + 36;    // leading spaces
+  for (size_t i = 0; i < a; i++) v = 37 * v + char_code(call[i]);
+  *nadd = 0;
+  if (v >= 32768) { v -= 32768; *nadd = 1; }
+  *m = v;
+  return true;
+}
+
+}  // namespace
+
+// lookup3.c hashlittle() (Bob Jenkins, 2006, public domain), the byte-at-a-time form: the same value as the word-reading
+// paths on a little-endian host
+extern "C" uint32_t uwspr_nhash(const void *key, size_t length, uint32_t initval) {
+#define UW_ROT(x, k) (((x) << (k)) | ((x) >> (32 - (k))))
+  uint32_t a, b, c;
+  a = b = c = 0xdeadbeefu + (uint32_t)length + initval;
+  const uint8_t *k = (const uint8_t *)key;
+  while (length > 12) {
+    a += k[0] + ((uint32_t)k[1] << 8) + ((uint32_t)k[2] << 16) + ((uint32_t)k[3] << 24);
+    b += k[4] + ((uint32_t)k[5] << 8) + ((uint32_t)k[6] << 16) + ((uint32_t)k[7] << 24);
+    c += k[8] + ((uint32_t)k[9] << 8) + ((uint32_t)k[10] << 16) + ((uint32_t)k[11] << 24);
+    a -= c; a ^= UW_ROT(c, 4); c += b;   // mix()
+    b -= a; b ^= UW_ROT(a, 6); a += c;
+    c -= b; c ^= UW_ROT(b, 8); b += a;
+    a -= c; a ^= UW_ROT(c, 16); c += b;
+    b -= a; b ^= UW_ROT(a, 19); a += c;
+    c -= b; c ^= UW_ROT(b, 4); b += a;
+    length -= 12;
+    k += 12;
+  }
+  switch (length) {   // the last block, zero-padded
+    case 12: c += (uint32_t)k[11] << 24; /* fall through */
+    case 11: c += (uint32_t)k[10] << 16; /* fall through */
+    case 10: c += (uint32_t)k[9] << 8; /* fall through */
+    case 9: c += k[8]; /* fall through */
+    case 8: b += (uint32_t)k[7] << 24; /* fall through */
+    case 7: b += (uint32_t)k[6] << 16; /* fall through */
+    case 6: b += (uint32_t)k[5] << 8; /* fall through */
+    case 5: b += k[4]; /* fall through */
+    case 4: a += (uint32_t)k[3] << 24; /* fall through */
+    case 3: a += (uint32_t)k[2] << 16; /* fall through */
+    case 2: a += (uint32_t)k[1] << 8; /* fall through */
+    case 1: a += k[0]; break;
+    case 0: return c;
+  }
+  c ^= b; c -= UW_ROT(b, 14);   // final()
+  a ^= c; a -= UW_ROT(c, 11);
+  b ^= a; b -= UW_ROT(a, 25);
+  c ^= b; c -= UW_ROT(b, 16);
+  a ^= c; a -= UW_ROT(c, 4);
+  b ^= a; b -= UW_ROT(a, 14);
+  c ^= b; c -= UW_ROT(b, 24);
+#undef UW_ROT
+  return c;
+}
+
+extern "C" int uwspr_wspr_pack(const char *text, int8_t *message7) {
+  if (!text || !message7) return UWSPR_ERR_ARG;
+  char buf[64];
+  const size_t len = strlen(text);
+  if (len >= sizeof(buf)) return UWSPR_ERR_ARG;
+  for (size_t i = 0; i <= len; i++) buf[i] = (text[i] >= 'a' && text[i] <= 'z') ? (char)(text[i] - 32) : text[i];
+  char *tok[4];
+  int nt = 0;
+  char *save = nullptr;   // (strtok_r: the call stays reentrant)
+  for (char *p = strtok_r(buf, " \t", &save); p; p = strtok_r(nullptr, " \t", &save)) {
+    if (nt == 3) return UWSPR_ERR_ARG;
+    tok[nt++] = p;
+  }
+  int dbm = 0;
+  int32_t n1 = 0, n2 = 0;
+  if (nt == 3 && tok[0][0] == '<') {               // type 3: <CALL> GRID6 dBm
+    const size_t cl = strlen(tok[0]);
+    if (cl < 3 || cl > 14 || tok[0][cl - 1] != '>' || !power_ok(tok[2], &dbm)) return UWSPR_ERR_ARG;
+    const char *call = tok[0] + 1;
+    const size_t k = cl - 2;
+    for (size_t i = 0; i < k; i++) if (!(is_digit(call[i]) || is_letter(call[i]) || call[i] == '/')) return UWSPR_ERR_ARG;
+    const char *g = tok[1];
+    if (strlen(g) != 6 || g[0] < 'A' || g[0] > 'R' || g[1] < 'A' || g[1] > 'R' || !is_digit(g[2]) || !is_digit(g[3]) ||
+        g[4] < 'A' || g[4] > 'X' || g[5] < 'A' || g[5] > 'X')
+      return UWSPR_ERR_ARG;
+    char rot[7];
+    memcpy(rot, g + 1, 5); rot[5] = g[0]; rot[6] = 0;
+    if (!pack_call(rot, &n1)) return UWSPR_ERR_ARG;
+    const int32_t ihash = (int32_t)(uwspr_nhash(call, k, 146) & 32767u);
+    n2 = 128 * ihash - (dbm + 1) + 64;
+  } else if (nt == 3) {                            // type 1: CALL GRID4 dBm
+    int32_t ng;
+    if (!pack_call(tok[0], &n1) || !pack_grid4(tok[1], &ng) || !power_ok(tok[2], &dbm)) return UWSPR_ERR_ARG;
+    n2 = 128 * ng + dbm + 64;
+  } else if (nt == 2) {                            // type 2: PFX/CALL dBm, CALL/SFX dBm
+    int32_t m;
+    int nadd;
+    if (!pack_compound(tok[0], &n1, &m, &nadd) || !power_ok(tok[1], &dbm)) return UWSPR_ERR_ARG;
+    n2 = 128 * m + dbm + 1 + nadd + 64;
+  } else {
+    return UWSPR_ERR_ARG;
+  }
+  put50(n1, n2, message7);
+  return UWSPR_OK;
+}
+
+// wsprsim's channel symbols: the 7 bytes zero-padded to 11, convolutionally encoded (the first 162 of its 176 bits),
+// interleaved by bit reversal (the inverse of uwspr_deinterleave), each symbol pr3[j] + 2 bit
+extern "C" int uwspr_wspr_symbols(const int8_t *message7, uint8_t *sym162) {
+  if (!message7 || !sym162) return UWSPR_ERR_ARG;
+  uint8_t data[11] = {0}, enc[176];
+  memcpy(data, message7, 7);
+  uwspr_fano_encode(enc, data, 11);
+  static const uint32_t pr3[6] = {0x07a47103u, 0x58b340a4u, 0x56349558u, 0xe2cdc904u, 0x63580ca0u, 0x00000000u};
+  for (int p = 0; p < UWSPR_NSYM; p++) {
+    const int j = kDeint.src[p];
+    sym162[j] = (uint8_t)(((pr3[j >> 5] >> (j & 31)) & 1u) + 2 * enc[p]);
+  }
+  return UWSPR_OK;
+}
+
+extern "C" int uwspr_c2_write(const char *path, const float *iq, int nsamples, double dial_freq, int32_t type) {
+  if (!path || !iq || nsamples != 45000) return UWSPR_ERR_ARG;
+  char name[14];
+  memset(name, 0, sizeof(name));
+  const char *base = strrchr(path, '/');
+  strncpy(name, base ? base + 1 : path, sizeof(name) - 1);
+  std::vector<float> v(iq, iq + 2 * (size_t)nsamples);
+  for (int i = 0; i < nsamples; i++) v[2 * i + 1] = -v[2 * i + 1];   // uwspr_c2_read negates Q on load
+  FILE *fp = fopen(path, "wb");
+  if (!fp) return UWSPR_ERR_ARG;
+  const bool ok = fwrite(name, 1, 14, fp) == 14 && fwrite(&type, 4, 1, fp) == 1 && fwrite(&dial_freq, 8, 1, fp) == 1 &&
+                  fwrite(v.data(), sizeof(float), v.size(), fp) == v.size();
+  return (fclose(fp) == 0 && ok) ? UWSPR_OK : UWSPR_ERR_ARG;
+}

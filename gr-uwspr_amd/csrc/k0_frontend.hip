@@ -211,6 +211,9 @@ static std::vector<float> gr_firdes(double gain, double fs, double lo, double hi
   for (int i = 0; i < ntaps; i++) taps[i] = (float)(taps[i] * gain);
   return taps;
 }
+std::vector<float> lowpass_hamming(double fs, double cutoff, double tw) {
+  return gr_firdes(1.0, fs, -1.0, cutoff, tw, WIN_HAMMING, 6.76);
+}
 // gr-filter/python/filter/rational_resampler.py: design_filter(interp, decim, fractional_bw = 0.4 when none is given)
 static std::vector<float> gr_resampler_taps(int interp, int decim) {
   const double fractional_bw = 0.4, beta = 7.0, halfband = 0.5;

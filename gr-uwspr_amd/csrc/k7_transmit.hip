@@ -1,0 +1,508 @@
+// K7 -- the transmitter: WSPR channel symbols -> 375 S/s complex baseband -> 12 kS/s audio.
+//
+// The reference's sender is two programs.  wsprsim writes a .c2 file: unit-amplitude continuous-phase 4-FSK at 375 S/s,
+// tone s at (s - 1.5) 375/256 Hz (as uwspr_c2_read returns the file), 256 samples per symbol, the phase accumulated
+// exclusively from 0 (theta[i + 1] = theta[i] + 2 pi f[i] / 375), the first symbol at sample 375.  examples/c2ToWaveFile.grc turns that into
+// 12 kS/s audio with GNU Radio blocks: zero-stuff x32 with h1 = low_pass(1, 12000, 200, 10, HAMMING) (2891 taps), then
+// h2 = low_pass(1, 12000, 2500, 100, HAMMING) (289 taps) rotated to 1500 Hz, the output mixed by e^{-j 2 pi 1500 n / 12000}
+// and its real part taken.  Every stage is linear and the mixer's period (8 samples) divides 32, so the chain is ONE
+// causal complex FIR on the 375 S/s input -- the transpose of K0:
+//
+//     audio[n] = Re sum_j g[n - 32 j] x[j],     g[q] = e^{-j pi q / 4} sum_k h2[k] e^{+j pi k / 4} h1[q - k]   (3179 taps)
+//
+// Output phase p = n mod 32 meets the taps g[p + 32 i], i = 0..99 (padded to K7_T = 104): two FMAs per tap, since only
+// the real part is wanted.  The file holds e^{-j theta} (uwspr_c2_read's conjugate) and the chain inverts the spectrum
+// once more, so a tone at f Hz as uwspr_c2_read sees the baseband is audio 1500 + f Hz.
+//
+// Mapping (K0's, transposed).  A 1024-thread workgroup owns 16384 consecutive audio samples of ONE channel, i.e. 512
+// baseband steps m = mb .. mb + 511.  It renders the 616 baseband samples they read (x[mb - 104 .. mb + 511]: every
+// signal of the channel, in ascending signal index) straight into LDS -- no baseband in HBM.  Wavefront w owns output
+// phases 2w and 2w + 1, a lane owns EIGHT consecutive steps of a phase, so one staged sample read feeds 16 FMAs (a
+// sliding window of 16 samples lives in registers) and the taps come as wave-uniform LDS reads.  Baseband column col is
+// stored at [col mod 8][col div 8], so the 64 lanes of a read hit consecutive words.  The results go through LDS once
+// more to be written in sample order, after the channel's noise and background are added and the value quantised.
+// An output's arithmetic does not depend on where it falls in a workgroup or a launch: renders of any pieces
+// concatenate to the same bytes.  1.44 M outputs x 100 taps x 2 FMAs = 0.58 GFLOP per 2-minute channel record.
+#include <math.h>
+#include <stdarg.h>
+#include <stdio.h>
+#include <string.h>
+
+#include <algorithm>
+#include <complex>
+#include <vector>
+
+#include "uwspr_internal.h"
+
+namespace uwspr {
+
+constexpr int K7_DEC = 32;
+constexpr int K7_NT = 3179;                      // composite taps (2891 + 289 - 1)
+constexpr int K7_T = 104;                        // taps per output phase: ceil(3179 / 32) = 100, padded to 13 x 8
+constexpr int K7_WG = 1024;                      // 16 wavefronts x 2 output phases
+constexpr int K7_R = 8;                          // baseband steps per lane and phase
+constexpr int K7_M = 64 * K7_R;                  // baseband steps per workgroup (512)
+constexpr int K7_OUT = K7_DEC * K7_M;            // audio samples per workgroup (16384)
+constexpr int K7_G = K7_M / 8 + K7_T / 8;        // LDS column groups of 8 baseband samples (77)
+constexpr int K7_NX = 8 * K7_G;                  // baseband samples a workgroup reads (616)
+constexpr int K7_YP = K7_M + 1;                  // output staging: floats per phase row (+1: reads in sample order hit 32 banks)
+constexpr int K7_NSYM = UWSPR_NSYM, K7_SPB = 256, K7_NTX = K7_NSYM * K7_SPB;   // 41472 samples per transmission
+constexpr double K7_FS = 375.0;
+constexpr double K7_TWO_PI = 6.283185307179586476925286766559;
+
+static size_t k7_lds_bytes() {
+  return (size_t)K7_NX * sizeof(float2) + (size_t)K7_DEC * K7_T * sizeof(float2) + (size_t)K7_DEC * K7_YP * sizeof(float);
+}
+
+// One signal as the kernels read it.  Phase of sample k = 256 q + r (symbol q) of the transmission, binary64:
+//     theta = ph[q] + r (2 pi (sym[q] - 1.5) / 256 + wf) + wd (r (256 q - (N - 1) / 2) + r (r - 1) / 2)
+// = phase0 + sum_{u < k} 2 pi f[u] / 375 with f[u] = f0 + (s - 1.5) 375/256 + drift (u - (N - 1) / 2) / (N - 1): the
+// exclusive accumulation, evaluated from per-symbol prefix sums so that any window renders without a sequential scan.
+struct tx_dsig {
+  long long start;      // baseband index of the first symbol's first sample
+  int channel;
+  float gain;
+  double wf;            // 2 pi f0 / 375 (rad per sample)
+  double wd;            // 2 pi drift / ((N - 1) 375) (rad per sample^2)
+  double ph[K7_NSYM];   // phase at the first sample of each symbol, phase0 included
+  uint8_t sym[K7_NSYM];
+  uint8_t _pad[6];
+};
+static_assert(sizeof(tx_dsig) % 8 == 0, "tx_dsig is 8-byte aligned in arrays");
+
+struct tx_dchan {
+  float sigma, bg_gain;
+  unsigned long long seed;
+  const void *bg;       // device memory, or null
+  long long bg_len;
+  int bg_s16;
+  int sig0, nsig;       // the channel's signals: sigs[sig0 .. sig0 + nsig) (sorted by channel, index order kept)
+  int _pad;
+};
+
+// ---------------------------------------------------------------- device side
+__device__ __forceinline__ void tx_add(const tx_dsig &s, long long j, float &re, float &im) {
+  const long long k = j - s.start;
+  if (k < 0 || k >= K7_NTX) return;
+  const int q = (int)(k >> 8);
+  const double r = (double)(int)(k & 255);
+  const double th = s.ph[q] + r * (K7_TWO_PI * ((double)s.sym[q] - 1.5) / 256.0 + s.wf) +
+                    s.wd * (r * ((double)(256 * q) - 0.5 * (K7_NTX - 1)) + 0.5 * r * (r - 1.0));
+  double sn, cs;
+  sincos(th, &sn, &cs);
+  re += s.gain * (float)cs;
+  im -= s.gain * (float)sn;
+}
+
+// baseband sample j of a channel in the file's orientation (I + jQ = gain e^{-j theta}: what wsprsim writes and
+// c2ToWaveFile reads), signals in ascending index
+__device__ __forceinline__ float2 tx_baseband_at(const tx_dsig *__restrict__ sigs, int nsig, int ch, long long j) {
+  float re = 0.0f, im = 0.0f;
+  for (int s = 0; s < nsig; s++)
+    if (sigs[s].channel == ch) tx_add(sigs[s], j, re, im);
+  return make_float2(re, im);
+}
+
+// Philox4x32-10 (Salmon et al., SC'11): counter-based, so a sample's noise depends on (seed, channel, index) only
+__device__ __forceinline__ uint4 philox4x32_10(uint4 c, uint2 k) {
+#pragma unroll
+  for (int i = 0; i < 10; i++) {
+    const uint32_t lo0 = 0xD2511F53u * c.x, hi0 = __umulhi(0xD2511F53u, c.x);
+    const uint32_t lo1 = 0xCD9E8D57u * c.z, hi1 = __umulhi(0xCD9E8D57u, c.z);
+    c = make_uint4(hi1 ^ c.y ^ k.x, lo1, hi0 ^ c.w ^ k.y, lo0);
+    k.x += 0x9E3779B9u; k.y += 0xBB67AE85u;
+  }
+  return c;
+}
+
+// one standard normal per (seed, channel, audio index): Box-Muller on the first two words
+__device__ __forceinline__ float tx_gauss(unsigned long long seed, int ch, long long n) {
+  const uint4 r = philox4x32_10(make_uint4((uint32_t)n, (uint32_t)((unsigned long long)n >> 32), (uint32_t)ch, 0u),
+                                make_uint2((uint32_t)seed, (uint32_t)(seed >> 32)));
+  const float u1 = ((float)(r.x >> 8) + 0.5f) * (1.0f / 16777216.0f);   // (0, 1)
+  const float u2 = (float)(r.y >> 8) * (1.0f / 16777216.0f);            // [0, 1)
+  return sqrtf(-2.0f * logf(u1)) * cospif(2.0f * u2);
+}
+
+__device__ __forceinline__ int16_t tx_s16(float v) {   // round(32767 x), saturated
+  const float q = fminf(fmaxf(32767.0f * v, -32768.0f), 32767.0f);
+  return (int16_t)(int)rintf(q);
+}
+
+// 8 taps against the 16-sample window S = A ++ B: acc[r] += Re(g[u] x[m + r - u]) = g.x * S.x + g.y * S.y,
+// S[8 + r - u] being x[m + r - u] (g.y holds -Im g)
+__device__ __forceinline__ void k7_block(float (&acc)[K7_R], const float2 (&A)[8], const float2 (&B)[8],
+                                         const float2 *__restrict__ g) {
+#pragma unroll
+  for (int u = 0; u < 8; u++) {
+    const float2 t = g[u];
+#pragma unroll
+    for (int r = 0; r < K7_R; r++) {
+      const float2 s = r < u ? A[8 + r - u] : B[r - u];
+      acc[r] = fmaf(t.x, s.x, acc[r]);
+      acc[r] = fmaf(t.y, s.y, acc[r]);
+    }
+  }
+}
+
+// Workgroup b renders audio [32 mb, 32 mb + 16384) of channel b mod C, mb = nb0 + 512 (b div C), and writes the
+// samples that fall in [t0, t0 + nframes) to out[(n - t0) C + ch].
+template <bool S16>
+__global__ __launch_bounds__(K7_WG) void k7_render(const tx_dsig *__restrict__ sigs, int nsig,
+                                                   const tx_dchan *__restrict__ chans, int C,
+                                                   const float2 *__restrict__ taps, long long t0, long long nframes,
+                                                   long long nb0, void *__restrict__ out) {
+  extern __shared__ __align__(16) float k7_lds[];
+  float2 *xs = reinterpret_cast<float2 *>(k7_lds);          // [8][K7_G]
+  float2 *tp = xs + K7_NX;                                  // [32][K7_T]
+  float *ys = reinterpret_cast<float *>(tp + K7_DEC * K7_T); // [32][K7_YP]
+  const int ch = (int)(blockIdx.x % (unsigned)C);
+  const long long mb = nb0 + (long long)(blockIdx.x / (unsigned)C) * K7_M;
+  const int tid = threadIdx.x;
+  const tx_dchan cz = chans[ch];
+  for (int col = tid; col < K7_NX; col += K7_WG)
+    xs[(col & 7) * K7_G + (col >> 3)] = tx_baseband_at(sigs + cz.sig0, cz.nsig, ch, mb - K7_T + col);
+  for (int i = tid; i < K7_DEC * K7_T; i += K7_WG) tp[i] = taps[i];
+  __syncthreads();
+
+  // lane l, phase p: steps m = mb + 8 l + r.  Tap block t (taps 8t .. 8t+7) reads columns 8 (l + 12 - t) .. +15,
+  // i.e. groups l + 12 - t (A) and l + 13 - t (B); the next block's B is this block's A.
+  const int w = tid >> 6, l = tid & 63;
+  for (int h = 0; h < 2; h++) {
+    const int p = 2 * w + h;
+    const float2 *g = tp + p * K7_T;
+    float acc[K7_R];
+#pragma unroll
+    for (int r = 0; r < K7_R; r++) acc[r] = 0.0f;
+    float2 A[8], B[8];
+#pragma unroll
+    for (int v = 0; v < 8; v++) { B[v] = xs[v * K7_G + l + 13]; A[v] = xs[v * K7_G + l + 12]; }
+    k7_block(acc, A, B, g);
+    for (int t = 1; t < K7_T / 8; t += 2) {    // two blocks per trip: the window's halves swap roles, no copies
+#pragma unroll
+      for (int v = 0; v < 8; v++) B[v] = xs[v * K7_G + l + 12 - t];
+      k7_block(acc, B, A, g + 8 * t);
+#pragma unroll
+      for (int v = 0; v < 8; v++) A[v] = xs[v * K7_G + l + 11 - t];
+      k7_block(acc, A, B, g + 8 * t + 8);
+    }
+#pragma unroll
+    for (int r = 0; r < K7_R; r++) ys[p * K7_YP + 8 * l + r] = acc[r];
+  }
+  __syncthreads();
+
+  const long long n0 = (long long)K7_DEC * mb;
+  for (int e = tid; e < K7_OUT; e += K7_WG) {
+    const long long n = n0 + e;
+    if (n < t0 || n - t0 >= nframes) continue;
+    float v = ys[(e & 31) * K7_YP + (e >> 5)];
+    if (cz.sigma > 0.0f) v += cz.sigma * tx_gauss(cz.seed, ch, n);
+    if (cz.bg) {
+      const long long i = n % cz.bg_len;
+      const float b = cz.bg_s16 ? (float)static_cast<const int16_t *>(cz.bg)[i] * (1.0f / 32768)
+                                : static_cast<const float *>(cz.bg)[i];
+      v += cz.bg_gain * b;
+    }
+    const size_t o = (size_t)(n - t0) * (size_t)C + (size_t)ch;
+    if constexpr (S16) static_cast<int16_t *>(out)[o] = tx_s16(v);
+    else static_cast<float *>(out)[o] = v;
+  }
+}
+
+// baseband samples [t0, t0 + n) of one channel, as uwspr_c2_read returns a .c2 file (Q negated against the file:
+// gain e^{+j theta})
+__global__ void k7_baseband(const tx_dsig *__restrict__ sigs, int nsig, int ch, long long t0, int n,
+                            float2 *__restrict__ out) {
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+    const float2 x = tx_baseband_at(sigs, nsig, ch, t0 + i);
+    out[i] = make_float2(x.x, -x.y);
+  }
+}
+
+// ---------------------------------------------------------------- host side
+struct tx_state {
+  float2 *d_taps = nullptr;                     // [32][K7_T] (Re g, -Im g)
+  tx_dsig *d_sig = nullptr; size_t cap_sig = 0;
+  tx_dchan *d_chan = nullptr;
+  void *d_out = nullptr; size_t cap_out = 0;    // host-output staging (bytes)
+  void *d_bg = nullptr; size_t cap_bg = 0;      // host backgrounds staged (bytes)
+};
+
+void tx_release(uwspr_ctx *c) {
+  if (!c || !c->tx) return;
+  tx_state *t = c->tx;
+  void *bufs[] = {t->d_taps, t->d_sig, t->d_chan, t->d_out, t->d_bg};
+  for (void *b : bufs) if (b) (void)hipFree(b);
+  delete t;
+  c->tx = nullptr;
+}
+
+static int tx_fail(uwspr_ctx *c, int status, const char *fmt, ...) {
+  if (c) {
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(c->err, sizeof(c->err), fmt, ap);
+    va_end(ap);
+  }
+  return status;
+}
+
+#define TXCHK(c, call)                                                                                  \
+  do {                                                                                                  \
+    hipError_t e_ = (call);                                                                             \
+    if (e_ != hipSuccess)                                                                               \
+      return tx_fail((c), UWSPR_ERR_HIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); \
+  } while (0)
+
+static int tx_grow(uwspr_ctx *c, void **buf, size_t *cap, size_t bytes) {
+  if (bytes <= *cap && *buf) return UWSPR_OK;
+  if (*buf) { TXCHK(c, hipFree(*buf)); *buf = nullptr; *cap = 0; }
+  const size_t n = bytes > 256 ? bytes : 256;
+  const hipError_t e = hipMalloc(buf, n);
+  if (e != hipSuccess) return tx_fail(c, UWSPR_ERR_NOMEM, "hipMalloc(%zu bytes): %s", n, hipGetErrorString(e));
+  *cap = n;
+  return UWSPR_OK;
+}
+
+static std::complex<double> tx_octant(long k) {   // e^{+j k pi / 4}, exact octant values
+  static const double r = sqrt(0.5);
+  static const double cs[8] = {1, r, 0, -r, -1, -r, 0, r}, sn[8] = {0, r, 1, r, 0, -r, -1, -r};
+  const int q = (int)(((k % 8) + 8) % 8);
+  return std::complex<double>(cs[q], sn[q]);
+}
+
+// g[q] = e^{-j pi q/4} sum_k h2r[k] h1[q - k], h2r = the rotated taps as freq_xlating_fir_filter holds them (binary32
+// pairs); designed in binary64
+static std::vector<std::complex<double>> tx_composite() {
+  const std::vector<float> h1 = lowpass_hamming(12000.0, 200.0, 10.0);     // 2891 taps
+  const std::vector<float> h2 = lowpass_hamming(12000.0, 2500.0, 100.0);   // 289 taps
+  std::vector<std::complex<double>> g(h1.size() + h2.size() - 1, std::complex<double>(0, 0));
+  for (size_t k = 0; k < h2.size(); k++) {
+    const std::complex<double> z = (double)h2[k] * tx_octant((long)k);
+    const std::complex<double> zr((double)(float)z.real(), (double)(float)z.imag());
+    for (size_t i = 0; i < h1.size(); i++) g[k + i] += zr * (double)h1[i];
+  }
+  for (size_t q = 0; q < g.size(); q++) g[q] *= std::conj(tx_octant((long)q));
+  return g;
+}
+
+static int tx_begin(uwspr_ctx *c) {
+  if (!c) return UWSPR_ERR_ARG;
+  if (!c->own_stream) return tx_fail(c, UWSPR_ERR_NODEVICE, "context has no device (creation failed: %s)", c->err);
+  TXCHK(c, hipSetDevice(c->device));
+  if (!c->tx) c->tx = new tx_state();
+  TXCHK(c, hipStreamSynchronize(c->stream));   // the scratch below may still be read by the previous call's kernels
+  if (!c->tx->d_taps) {
+    const std::vector<std::complex<double>> g = tx_composite();
+    if ((int)g.size() != K7_NT) return tx_fail(c, UWSPR_ERR_HIP, "transmit taps: %zu, expected %d", g.size(), K7_NT);
+    std::vector<float2> img((size_t)K7_DEC * K7_T, make_float2(0.0f, 0.0f));
+    for (int p = 0; p < K7_DEC; p++)
+      for (int i = 0; i < K7_T; i++) {
+        const int q = p + K7_DEC * i;
+        if (q < K7_NT) img[(size_t)p * K7_T + i] = make_float2((float)g[q].real(), (float)-g[q].imag());
+      }
+    if (hipFuncSetAttribute(reinterpret_cast<const void *>(k7_render<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)k7_lds_bytes()) != hipSuccess ||
+        hipFuncSetAttribute(reinterpret_cast<const void *>(k7_render<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)k7_lds_bytes()) != hipSuccess)
+      return tx_fail(c, UWSPR_ERR_HIP, "transmit kernel: %zu bytes of LDS refused", k7_lds_bytes());
+    float2 *d = nullptr;
+    TXCHK(c, hipMalloc((void **)&d, img.size() * sizeof(float2)));
+    c->tx->d_taps = d;
+    TXCHK(c, hipMemcpy(d, img.data(), img.size() * sizeof(float2), hipMemcpyHostToDevice));
+  }
+  return UWSPR_OK;
+}
+
+// The context's device and [p, p + bytes) inside one device allocation of it: what a kernel may touch with XNACK off.
+// Pageable host memory, another device's memory and ranges past an allocation's end are refused here, before any launch.
+static bool tx_device_range(uwspr_ctx *c, const void *p, size_t bytes) {
+  hipPointerAttribute_t a;
+  memset(&a, 0, sizeof(a));
+  const hipError_t e = hipPointerGetAttributes(&a, p);
+  (void)hipGetLastError();   // a refused query leaves no error behind for the calls that follow
+  if (e != hipSuccess || a.type != hipMemoryTypeDevice || a.device != c->device) return false;
+  hipDeviceptr_t base = nullptr;
+  size_t size = 0;
+  if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)p) != hipSuccess) { (void)hipGetLastError(); return false; }
+  const char *b = (const char *)base, *q = (const char *)p;
+  return q >= b && bytes <= size && (size_t)(q - b) <= size - bytes;
+}
+
+static int tx_device_ready(uwspr_ctx *c) {
+  if (!c->own_stream) return tx_fail(c, UWSPR_ERR_NODEVICE, "context has no device (creation failed: %s)", c->err);
+  TXCHK(c, hipSetDevice(c->device));
+  return UWSPR_OK;
+}
+
+static bool tx_finite(double v) { return v == v && v - v == 0.0; }
+
+// check the records (channel < C when C > 0) and build the device form of those that pass `keep`
+template <typename Keep>
+static int tx_prepare(uwspr_ctx *c, const uwspr_tx_signal *sig, int nsig, int C, Keep keep, std::vector<tx_dsig> &out) {
+  if (nsig < 0 || (nsig > 0 && !sig)) return tx_fail(c, UWSPR_ERR_ARG, "uwspr_tx: signals %p, nsig %d", (const void *)sig, nsig);
+  out.clear();
+  for (int i = 0; i < nsig; i++) {
+    const uwspr_tx_signal &s = sig[i];
+    for (int k = 0; k < K7_NSYM; k++)
+      if (s.symbols[k] > 3) return tx_fail(c, UWSPR_ERR_ARG, "uwspr_tx: signal %d symbol %d = %d (0..3)", i, k, s.symbols[k]);
+    if (s.channel < 0 || (C > 0 && s.channel >= C)) return tx_fail(c, UWSPR_ERR_ARG, "uwspr_tx: signal %d channel %d", i, s.channel);
+    if (!tx_finite(s.f0_hz) || !tx_finite(s.drift_hz) || !tx_finite(s.phase0) || !tx_finite((double)s.gain))
+      return tx_fail(c, UWSPR_ERR_ARG, "uwspr_tx: signal %d has a non-finite f0 / drift / phase / gain", i);
+    if (s.start < -(1LL << 50) || s.start > (1LL << 50)) return tx_fail(c, UWSPR_ERR_ARG, "uwspr_tx: signal %d start %lld", i, (long long)s.start);
+    if (!keep(s)) continue;
+    tx_dsig d;
+    memset(&d, 0, sizeof(d));
+    d.start = s.start; d.channel = s.channel; d.gain = s.gain;
+    d.wf = K7_TWO_PI * s.f0_hz / K7_FS;
+    d.wd = K7_TWO_PI * s.drift_hz / ((double)(K7_NTX - 1) * K7_FS);
+    double ph = s.phase0;
+    for (int q = 0; q < K7_NSYM; q++) {
+      d.ph[q] = ph;
+      d.sym[q] = s.symbols[q];
+      const double r = 256.0;
+      ph += r * (K7_TWO_PI * ((double)s.symbols[q] - 1.5) / 256.0 + d.wf) +
+            d.wd * (r * ((double)(256 * q) - 0.5 * (K7_NTX - 1)) + 0.5 * r * (r - 1.0));
+    }
+    out.push_back(d);
+  }
+  return UWSPR_OK;
+}
+
+static int tx_upload_signals(uwspr_ctx *c, const std::vector<tx_dsig> &v) {
+  tx_state *t = c->tx;
+  int rc = tx_grow(c, (void **)&t->d_sig, &t->cap_sig, v.size() * sizeof(tx_dsig));
+  if (rc) return rc;
+  if (!v.empty()) TXCHK(c, hipMemcpyAsync(t->d_sig, v.data(), v.size() * sizeof(tx_dsig), hipMemcpyHostToDevice, c->stream));
+  return UWSPR_OK;
+}
+
+}  // namespace uwspr
+
+using namespace uwspr;
+
+extern "C" int uwspr_tx_baseband(uwspr_ctx *c, const uwspr_tx_signal *sig, int nsig, int channel, long long t0, int n,
+                                 float *iq, int where) {
+  if (!c) return UWSPR_ERR_ARG;
+  if (n < 0 || (n > 0 && !iq) || channel < 0 || (where != UWSPR_HOST && where != UWSPR_DEVICE))
+    return tx_fail(c, UWSPR_ERR_ARG, "uwspr_tx_baseband: n %d, iq %p, channel %d, where %d", n, (void *)iq, channel, where);
+  std::vector<tx_dsig> v;
+  int rc = tx_prepare(c, sig, nsig, 0, [&](const uwspr_tx_signal &s) {
+    return s.channel == channel && s.start < t0 + n && s.start + K7_NTX > t0;
+  }, v);
+  if (rc) return rc;
+  if (n == 0) return UWSPR_OK;
+  if ((rc = tx_device_ready(c))) return rc;
+  if (where == UWSPR_DEVICE && !tx_device_range(c, iq, (size_t)n * sizeof(float2)))
+    return tx_fail(c, UWSPR_ERR_ARG, "uwspr_tx_baseband: iq %p is not %zu bytes of this device's memory", (void *)iq, (size_t)n * sizeof(float2));
+  if ((rc = tx_begin(c))) return rc;
+  if ((rc = tx_upload_signals(c, v))) return rc;
+  tx_state *t = c->tx;
+  float2 *dst = (float2 *)iq;
+  if (where == UWSPR_HOST) {
+    if ((rc = tx_grow(c, &t->d_out, &t->cap_out, (size_t)n * sizeof(float2)))) return rc;
+    dst = (float2 *)t->d_out;
+  }
+  TXCHK(c, hipStreamSynchronize(c->stream));   // (the records live on this call's stack)
+  const int blocks = (n + 255) / 256 < 2048 ? (n + 255) / 256 : 2048;
+  hipLaunchKernelGGL(k7_baseband, dim3(blocks), dim3(256), 0, c->stream, t->d_sig, (int)v.size(), channel, t0, n, dst);
+  TXCHK(c, hipGetLastError());
+  if (where == UWSPR_HOST) {
+    TXCHK(c, hipMemcpyAsync(iq, dst, (size_t)n * sizeof(float2), hipMemcpyDeviceToHost, c->stream));
+    TXCHK(c, hipStreamSynchronize(c->stream));
+  }
+  return UWSPR_OK;
+}
+
+extern "C" int uwspr_tx_render(uwspr_ctx *c, const uwspr_tx_signal *sig, int nsig, const uwspr_tx_channel *chan, int C,
+                               long long t0, long long nframes, int format, void *out, int where) {
+  if (!c) return UWSPR_ERR_ARG;
+  if (C < 1 || C > UWSPR_PIPE_MAX_CHANNELS || !chan || t0 < 0 || nframes < 0 || (nframes > 0 && !out) ||
+      (format != UWSPR_AUDIO_F32 && format != UWSPR_AUDIO_S16) || (where != UWSPR_HOST && where != UWSPR_DEVICE))
+    return tx_fail(c, UWSPR_ERR_ARG, "uwspr_tx_render: C %d, chan %p, t0 %lld, nframes %lld, out %p, format %d, where %d",
+                   C, (const void *)chan, t0, nframes, out, format, where);
+  if (nframes > (1LL << 40) / C) return tx_fail(c, UWSPR_ERR_ARG, "uwspr_tx_render: %lld frames x %d channels", nframes, C);
+  for (int k = 0; k < C; k++) {
+    const uwspr_tx_channel &z = chan[k];
+    if (!tx_finite(z.sigma) || z.sigma < 0 || !tx_finite((double)z.background_gain) ||
+        (z.background && (z.background_len <= 0 || (z.background_format != UWSPR_AUDIO_F32 && z.background_format != UWSPR_AUDIO_S16))))
+      return tx_fail(c, UWSPR_ERR_ARG, "uwspr_tx_render: channel %d: sigma %g, background %p len %lld format %d gain %g", k,
+                     z.sigma, z.background, (long long)z.background_len, z.background_format, (double)z.background_gain);
+  }
+  // signals that reach [t0, t0 + nframes): audio 32 start .. 32 (start + N - 1) + 3178 (the others add exact zeros)
+  std::vector<tx_dsig> v;
+  int rc = tx_prepare(c, sig, nsig, C, [&](const uwspr_tx_signal &s) {
+    return K7_DEC * s.start < t0 + nframes && K7_DEC * (s.start + K7_NTX - 1) + K7_NT - 1 >= t0;
+  }, v);
+  if (rc) return rc;
+  if (nframes == 0) return UWSPR_OK;
+  const size_t esz = format == UWSPR_AUDIO_S16 ? 2 : 4;
+  if ((rc = tx_device_ready(c))) return rc;
+  if (where == UWSPR_DEVICE) {   // device pointers must be device memory: a host pointer would fault the kernel
+    if (!tx_device_range(c, out, (size_t)nframes * C * esz))
+      return tx_fail(c, UWSPR_ERR_ARG, "uwspr_tx_render: out %p is not %zu bytes of this device's memory", out, (size_t)nframes * C * esz);
+    for (int k = 0; k < C; k++)
+      if (chan[k].background &&
+          !tx_device_range(c, chan[k].background, (size_t)chan[k].background_len * (chan[k].background_format == UWSPR_AUDIO_S16 ? 2 : 4)))
+        return tx_fail(c, UWSPR_ERR_ARG, "uwspr_tx_render: channel %d: background %p is not %lld samples of this device's memory", k,
+                       chan[k].background, (long long)chan[k].background_len);
+  }
+  // the kernel walks only its channel's signals: sorted by channel, ascending index within one (the order they add up in)
+  std::stable_sort(v.begin(), v.end(), [](const tx_dsig &a, const tx_dsig &b) { return a.channel < b.channel; });
+  if ((rc = tx_begin(c))) return rc;
+  tx_state *t = c->tx;
+  if ((rc = tx_upload_signals(c, v))) return rc;
+  // channels: host backgrounds are staged behind each other
+  std::vector<tx_dchan> dc(C);
+  size_t bg_bytes = 0;
+  for (int k = 0; k < C; k++)
+    if (chan[k].background && where == UWSPR_HOST)
+      bg_bytes += ((size_t)chan[k].background_len * (chan[k].background_format == UWSPR_AUDIO_S16 ? 2 : 4) + 255) / 256 * 256;
+  if (bg_bytes && (rc = tx_grow(c, &t->d_bg, &t->cap_bg, bg_bytes))) return rc;
+  size_t off = 0;
+  for (int k = 0; k < C; k++) {
+    const uwspr_tx_channel &z = chan[k];
+    tx_dchan &d = dc[k];
+    memset(&d, 0, sizeof(d));
+    d.sigma = (float)z.sigma; d.bg_gain = z.background_gain; d.seed = z.seed;
+    d.sig0 = (int)(std::lower_bound(v.begin(), v.end(), k, [](const tx_dsig &a, int ch) { return a.channel < ch; }) - v.begin());
+    d.nsig = (int)(std::upper_bound(v.begin(), v.end(), k, [](int ch, const tx_dsig &a) { return ch < a.channel; }) - v.begin()) - d.sig0;
+    if (z.background) {
+      d.bg_len = z.background_len; d.bg_s16 = z.background_format == UWSPR_AUDIO_S16;
+      if (where == UWSPR_HOST) {
+        const size_t b = (size_t)z.background_len * (d.bg_s16 ? 2 : 4);
+        TXCHK(c, hipMemcpyAsync((char *)t->d_bg + off, z.background, b, hipMemcpyHostToDevice, c->stream));
+        d.bg = (char *)t->d_bg + off;
+        off += (b + 255) / 256 * 256;
+      } else {
+        d.bg = z.background;
+      }
+    }
+  }
+  if (!t->d_chan) TXCHK(c, hipMalloc((void **)&t->d_chan, UWSPR_PIPE_MAX_CHANNELS * sizeof(tx_dchan)));
+  TXCHK(c, hipMemcpyAsync(t->d_chan, dc.data(), C * sizeof(tx_dchan), hipMemcpyHostToDevice, c->stream));
+  TXCHK(c, hipStreamSynchronize(c->stream));   // (the records above live on this call's stack)
+
+  // device output: one launch; host output: pieces of at most 2^24 samples through a staging buffer (the render of any
+  // piece is the same bytes as that part of a whole render)
+  const long long piece = where == UWSPR_DEVICE ? nframes : std::max<long long>(K7_OUT, (1LL << 24) / C / K7_OUT * K7_OUT);
+  if (where == UWSPR_HOST && (rc = tx_grow(c, &t->d_out, &t->cap_out, (size_t)std::min(piece, nframes) * C * esz))) return rc;
+  for (long long k = 0; k < nframes; k += piece) {
+    const long long a = t0 + k, len = std::min(piece, nframes - k);
+    const long long nb0 = a / K7_DEC;
+    const long long nblk = (a + len - K7_DEC * nb0 + K7_OUT - 1) / K7_OUT;
+    if (nblk * C > 0x7fffffffLL) return tx_fail(c, UWSPR_ERR_ARG, "uwspr_tx_render: %lld workgroups", nblk * C);
+    void *dst = where == UWSPR_HOST ? t->d_out : (void *)((char *)out + (size_t)k * C * esz);
+    const dim3 grid((unsigned)(nblk * C));
+    if (format == UWSPR_AUDIO_S16)
+      hipLaunchKernelGGL(k7_render<true>, grid, dim3(K7_WG), k7_lds_bytes(), c->stream, t->d_sig, (int)v.size(),
+                         t->d_chan, C, t->d_taps, a, len, nb0, dst);
+    else
+      hipLaunchKernelGGL(k7_render<false>, grid, dim3(K7_WG), k7_lds_bytes(), c->stream, t->d_sig, (int)v.size(),
+                         t->d_chan, C, t->d_taps, a, len, nb0, dst);
+    TXCHK(c, hipGetLastError());
+    if (where == UWSPR_HOST) {
+      TXCHK(c, hipMemcpyAsync((char *)out + (size_t)k * C * esz, dst, (size_t)len * C * esz, hipMemcpyDeviceToHost, c->stream));
+      TXCHK(c, hipStreamSynchronize(c->stream));
+    }
+  }
+  return UWSPR_OK;
+}

@@ -135,6 +135,8 @@ struct fdr_consts {
 };
 
 struct ev_pair { hipEvent_t a, b; int kind; int64_t units; };
+struct tx_state;
+void tx_release(uwspr_ctx *c);   // k7_transmit.hip: frees what the uwspr_tx_* calls made
 
 }  // namespace uwspr
 
@@ -220,6 +222,8 @@ struct uwspr_ctx {
   size_t cap_slab; uint8_t *d_slab;
   // multi-GPU gather (dist.hip): RCCL communicator of this rank, or null (single rank / not initialised)
   void *dist_comm; int dist_rank, dist_world;
+  // transmitter (k7_transmit.hip): composite taps and call scratch, made by the first uwspr_tx_* call
+  uwspr::tx_state *tx;
 
   int prof_mask;
   std::vector<uwspr::ev_pair> prof_events;
@@ -231,6 +235,8 @@ namespace uwspr {
 // ---- launchers (each enqueues on ctx->stream) ------------------------------
 int frontend_design(int mode, int stage, std::vector<double> &out, int *delay);
 int frontend_tap_image(int mode, std::vector<float> &img, int *J, int *dcols);
+// firdes::low_pass(1, fs, cutoff, tw, WIN_HAMMING) as GNU Radio 3.7 designs it (binary32 taps; k0_frontend.hip)
+std::vector<float> lowpass_hamming(double fs, double cutoff, double tw);
 int frontend_prepare();
 void launch_frontend(uwspr_ctx *c, const float *audio, int B, int nin, float2 *out, int nout);
 void launch_spectrogram(uwspr_ctx *c, const float *frames, int B);

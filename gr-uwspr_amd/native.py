@@ -26,7 +26,7 @@ LIBPATH = os.path.join(LIBDIR, "libuwspr_hip_exp_%s.so" % _EXTRA_TAG if _EXTRA e
 HOSTLIB = os.path.join(LIBDIR, "libuwspr_blocks.so")
 
 SOURCES = ["uwspr_api.hip", "k0_frontend.hip", "k1_spectrogram.hip", "k2_spectrum.hip", "k3_coarse.hip",
-           "k4_tonecorr.hip", "k4_grid.hip", "k4_pair.hip", "k4_jig.hip", "k5_fold_schedule.hip", "k6_sched.hip", "pipe.hip", "dist.hip", "host_tail.cpp"]
+           "k4_tonecorr.hip", "k4_grid.hip", "k4_pair.hip", "k4_jig.hip", "k5_fold_schedule.hip", "k6_sched.hip", "k7_transmit.hip", "pipe.hip", "dist.hip", "host_tail.cpp"]
 HIPFLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off",
             "-fno-slp-vectorize", "-fhip-fp32-correctly-rounded-divide-sqrt", "-fPIC", "-Wall", "-Wno-unused-function"]
 
@@ -209,6 +209,20 @@ assert DECODE_DTYPE.itemsize == 112 and DECODE_DTYPE.fields["channel"][1] == 108
 PIPE_MAX_CHANNELS = 64
 
 
+class TxSignal(C.Structure):
+    _fields_ = [("symbols", C.c_uint8 * NSYM), ("_pad", C.c_uint8 * 2), ("channel", C.c_int32), ("start", C.c_int64),
+                ("f0_hz", C.c_double), ("drift_hz", C.c_double), ("phase0", C.c_double), ("gain", C.c_float),
+                ("_pad2", C.c_int32)]
+
+
+class TxChannel(C.Structure):
+    _fields_ = [("sigma", C.c_double), ("seed", C.c_uint64), ("background", C.c_void_p), ("background_len", C.c_int64),
+                ("background_format", C.c_int32), ("background_gain", C.c_float)]
+
+
+assert C.sizeof(TxSignal) == 208 and C.sizeof(TxChannel) == 40
+
+
 class PipeOpts(C.Structure):
     _fields_ = [(k, C.c_int32) for k in ("hop", "batch_frames", "max_per_frame", "lanes", "host_threads", "eager",
                                          "sched_form", "spare_after_us")]
@@ -239,6 +253,7 @@ ABI_SYMBOLS = [
     "uwspr_pipeline_batch", "uwspr_set_tries", "uwspr_set_option", "uwspr_get_option", "uwspr_demod_resume", "uwspr_pack_slabs", "uwspr_pipeline_slabs", "uwspr_prof_enable", "uwspr_prof_read", "uwspr_prof_intervals", "uwspr_deinterleave",
     "uwspr_fano_decode", "uwspr_fano_encode", "uwspr_decode_candidate", "uwspr_host_threads", "uwspr_host_set_ranks", "uwspr_decode_batch", "uwspr_unpack_message",
     "uwspr_c2_read",
+    "uwspr_wspr_pack", "uwspr_nhash", "uwspr_wspr_symbols", "uwspr_c2_write", "uwspr_tx_baseband", "uwspr_tx_render",
     "uwspr_dist_unique_id", "uwspr_dist_init", "uwspr_dist_gather", "uwspr_dist_finalize",
     "uwspr_pipe_open", "uwspr_pipe_close", "uwspr_pipe_last_error", "uwspr_pipe_acquire", "uwspr_pipe_commit",
     "uwspr_pipe_push", "uwspr_pipe_push_audio", "uwspr_pipe_push_audio_channels", "uwspr_pipe_submit_device", "uwspr_pipe_flush", "uwspr_pipe_collect", "uwspr_pipe_get_stats",
@@ -327,6 +342,13 @@ def lib():
     L.uwspr_host_set_ranks.argtypes = [ip]
     L.uwspr_unpack_message.argtypes = [vp, C.c_char_p, C.c_size_t]
     L.uwspr_c2_read.argtypes = [C.c_char_p, vp, C.POINTER(C.c_double), C.POINTER(C.c_int32)]
+    L.uwspr_wspr_pack.argtypes = [C.c_char_p, vp]
+    L.uwspr_nhash.argtypes = [C.c_char_p, C.c_size_t, C.c_uint32]
+    L.uwspr_nhash.restype = C.c_uint32
+    L.uwspr_wspr_symbols.argtypes = [vp, vp]
+    L.uwspr_c2_write.argtypes = [C.c_char_p, vp, ip, C.c_double, C.c_int32]
+    L.uwspr_tx_baseband.argtypes = [vp, vp, ip, ip, C.c_longlong, ip, vp, ip]
+    L.uwspr_tx_render.argtypes = [vp, vp, ip, vp, ip, C.c_longlong, C.c_longlong, ip, vp, ip]
     L.uwspr_dist_unique_id.argtypes = [vp]
     L.uwspr_dist_init.argtypes = [vp, ip, ip, vp]
     L.uwspr_dist_gather.argtypes = [vp, vp, C.c_size_t, vp, ip, ip]

@@ -36,7 +36,8 @@ extern "C" {
                                  5: uwspr_host_set_ranks (the host's CPU share divided between the ranks of a node);
                                  6: audio streams: uwspr_stream_push_audio, uwspr_pipe_push_audio; multichannel
                                     audio into one pipe: uwspr_pipe_push_audio_channels, uwspr_decode.channel (carved
-                                    out of the padding: the record stays 112 bytes) */
+                                    out of the padding: the record stays 112 bytes); the transmit side: uwspr_wspr_pack,
+                                    uwspr_nhash, uwspr_wspr_symbols, uwspr_c2_write, uwspr_tx_baseband, uwspr_tx_render */
 
 typedef enum {
   UWSPR_OK = 0,
@@ -543,6 +544,69 @@ int uwspr_unpack_message(const int8_t *message7, char *out, size_t out_len);
 /* .c2 reader, lib/c2file_source_impl.cc:80-96 (Q negated on load).
  * iq: 2*45000 floats. */
 int uwspr_c2_read(const char *path, float *iq, double *dial_freq, int32_t *type);
+
+/* ---- transmit side: the reference's sender (README "Sender": wsprsim, examples/c2ToWaveFile.grc) ---------------- */
+/* Message text -> the 50 bits uwspr_unpack_message takes apart, in its 7-byte layout.  Three forms (lower case is taken
+ * as upper case): type 1 "CALL GRID4 dBm" (callsign of 1-2 characters, a digit, 1-3 letters); type 2 "PFX/CALL dBm"
+ * (1-3 character prefix) or "CALL/SFX dBm" (one character, or two digits 10..99); type 3 "<CALL> GRID6 dBm" (15-bit
+ * hash of CALL, uwspr_nhash(call, len, 146) & 32767).  dBm is 0..60 ending in 0, 3 or 7.  Anything else: UWSPR_ERR_ARG
+ * and message7 untouched. */
+int uwspr_wspr_pack(const char *text, int8_t *message7);
+/* lookup3 hashlittle() (the reference's nhash, lib/helpers.cc:151-319) */
+uint32_t uwspr_nhash(const void *key, size_t length, uint32_t initval);
+/* wsprsim's 162 channel symbols of a message: the 7 bytes zero-padded to 11 -> uwspr_fano_encode (first 162 bits) ->
+ * bit-reversal interleave (the inverse of uwspr_deinterleave) -> symbol j = pr3[j] + 2 bit[j] */
+int uwspr_wspr_symbols(const int8_t *message7, uint8_t *sym162);
+/* .c2 writer, the inverse of uwspr_c2_read: 14-byte NUL-padded name (the file's base name), int32 type, float64 dial
+ * frequency, then the nsamples = 45000 (I,Q) binary32 pairs with Q negated (uwspr_c2_read negates it back). */
+int uwspr_c2_write(const char *path, const float *iq, int nsamples, double dial_freq, int32_t type);
+
+/* One transmission.  Baseband (375 S/s) sample start + k, k = 0 .. 162*256 - 1, of its channel is
+ *     gain e^{j theta(k)},  theta(k) = phase0 + sum_{u < k} 2 pi f(u) / 375,
+ *     f(u) = f0_hz + (symbols[u / 256] - 1.5) 375/256 + drift_hz (u - (N - 1)/2) / (N - 1),  N = 41472
+ * (wsprsim's signal: the exclusive phase accumulation, a linear drift centred on the transmission as synth.make_frames
+ * has it), zero elsewhere; the signals of a channel add up in ascending index.  theta is evaluated in binary64 from
+ * per-symbol prefix sums, so any window renders without a sequential scan. */
+typedef struct uwspr_tx_signal {
+  uint8_t symbols[UWSPR_NSYM];   /* 0..3 */
+  uint8_t _pad[2];
+  int32_t channel;
+  int64_t start;                 /* baseband samples (audio sample 32 start) */
+  double f0_hz, drift_hz, phase0;
+  float gain;
+  int32_t _pad2;
+} uwspr_tx_signal;
+/* What a channel of a rendered recording adds to its signals: AWGN of standard deviation sigma (Philox4x32-10 keyed by
+ * (seed, channel, absolute audio index) + Box-Muller: the same samples however the recording is cut into calls), and
+ * background[n mod background_len] x background_gain (format UWSPR_AUDIO_F32 / S16 = s / 32768; the flowgraph's
+ * repeating wavfile_source; NULL: none).  background is memory of the call's `where`: with UWSPR_DEVICE, out and every
+ * background must lie inside a device allocation of the context's device, else the call fails with UWSPR_ERR_ARG before
+ * any launch (a host pointer would fault the kernel). */
+typedef struct uwspr_tx_channel {
+  double sigma;
+  uint64_t seed;
+  const void *background;
+  int64_t background_len;
+  int32_t background_format;
+  float background_gain;
+} uwspr_tx_channel;
+/* Baseband samples [t0, t0 + n) of one channel, the signals above, as uwspr_c2_read returns a .c2 file (the file itself
+ * holds the conjugate): the VE3EMB symbols at start 375, f0 0, gain 1 are examples/VE3EMB.c2.  iq: n (I,Q) pairs per `where`. */
+int uwspr_tx_baseband(uwspr_ctx *ctx, const uwspr_tx_signal *sig, int nsig, int channel, long long t0, int n, float *iq,
+                      int where);
+/* Audio frames [t0, t0 + nframes) of a C-channel 12 kS/s recording (K7, k7_transmit.hip), interleaved [nframes][C] as
+ * uwspr_pipe_push_audio_channels takes it: channel c's sample n is
+ *     Re sum_j g[n - 32 j] x_c[j] + sigma_c noise + background_gain_c background_c[n mod len]
+ * x_c being the channel's baseband as the .c2 file holds it (the conjugate of uwspr_tx_baseband's) and g the 3179-tap
+ * composite of c2ToWaveFile.grc's chain (zero-stuff x32, low_pass(1, 12000, 200, 10, HAMMING), low_pass(1, 12000, 2500,
+ * 100, HAMMING) at 1500 Hz, real part): a tone at f Hz of uwspr_tx_baseband's output comes out at 1500 + f Hz, a unit
+ * baseband as a tone of amplitude ~1/32.  format UWSPR_AUDIO_F32, or UWSPR_AUDIO_S16
+ * = round(32767 x) saturated.  Renders of consecutive pieces concatenate to the bytes of one render; host and device
+ * output are the same bytes.  chan [C], 1 <= C <= UWSPR_PIPE_MAX_CHANNELS, t0 >= 0; every signal's channel < C.  Bad
+ * arguments fail the call with UWSPR_ERR_ARG before any device use.  where: UWSPR_HOST (complete on return) or
+ * UWSPR_DEVICE (asynchronous on the context's stream). */
+int uwspr_tx_render(uwspr_ctx *ctx, const uwspr_tx_signal *sig, int nsig, const uwspr_tx_channel *chan, int C,
+                    long long t0, long long nframes, int format, void *out, int where);
 
 #ifdef __cplusplus
 }
