@@ -438,9 +438,13 @@ class Context:
     # -- transmit side (K7: uwspr_tx_*) ------------------------------------
     def tx_baseband(self, signals, n=45000, t0=0, channel=0, out=None):
         """375 S/s baseband samples [t0, t0 + n) of one channel's signals (tx_signals), as c2_read returns a .c2 file:
-        numpy [n, 2] float32, or written into `out` (a torch CUDA float32 tensor of n pairs)."""
-        sig = tx_signals(signals)
+        numpy [n, 2] float32, or written into `out` (a torch CUDA float32 tensor of n pairs).  A signal with a "motion"
+        (tx_motions) sends the call through uwspr_tx_baseband_moving."""
+        signals = list(signals)
+        sig, mot = tx_signals(signals), tx_motions(signals)
         sp = C.c_void_p(C.addressof(sig)) if len(sig) else None
+        call = self.L.uwspr_tx_baseband if mot is None else \
+            (lambda h, *a: self.L.uwspr_tx_baseband_moving(h, a[0], C.c_void_p(C.addressof(mot)), *a[1:]))
         if out is not None and _is_torch(out):
             import torch
             if not (out.is_cuda and out.is_contiguous() and out.dtype == torch.float32 and out.numel() >= 2 * n):
@@ -448,14 +452,12 @@ class Context:
                                 % (2 * n, out.dtype, tuple(out.shape)))
             if self._stream_ptr is None:
                 torch.cuda.current_stream(out.device).synchronize()
-            self._chk(self.L.uwspr_tx_baseband(self.h, sp, len(sig), int(channel), int(t0), int(n),
-                                               C.c_void_p(out.data_ptr()), N.DEVICE))
+            self._chk(call(self.h, sp, len(sig), int(channel), int(t0), int(n), C.c_void_p(out.data_ptr()), N.DEVICE))
             if self._stream_ptr is None:
                 self.synchronize()
             return out
         iq = np.empty((n, 2), np.float32)
-        self._chk(self.L.uwspr_tx_baseband(self.h, sp, len(sig), int(channel), int(t0), int(n),
-                                           C.c_void_p(iq.ctypes.data), N.HOST))
+        self._chk(call(self.h, sp, len(sig), int(channel), int(t0), int(n), C.c_void_p(iq.ctypes.data), N.HOST))
         return iq
 
     def tx_render(self, signals, nframes, t0=0, channels=1, sigma=0.0, seed=0, background=None, background_gain=1.0,
@@ -465,8 +467,12 @@ class Context:
         shape and dtype (what stream_push_audio / a pipe takes, with no PCIe crossing).  sigma, seed, background
         (a 1-D float32 / int16 numpy array or torch tensor, or None) and background_gain are one value for every channel
         or a list of one per channel.  A background is moved to where the output is made: to out's device for device
-        output (once per call: keep it there for repeated renders), to host memory for host output."""
-        sig = tx_signals(signals)
+        output (once per call: keep it there for repeated renders), to host memory for host output.  A signal with a
+        "motion" (tx_motions) sends the call through uwspr_tx_render_moving."""
+        signals = list(signals)
+        sig, mot = tx_signals(signals), tx_motions(signals)
+        call = self.L.uwspr_tx_render if mot is None else \
+            (lambda h, *a: self.L.uwspr_tx_render_moving(h, a[0], C.c_void_p(C.addressof(mot)), *a[1:]))
         dev_out = out is not None and _is_torch(out)
         if dev_out and not out.is_cuda:
             raise TypeError("tx_render: out must be a CUDA tensor (or None for a numpy result)")
@@ -507,14 +513,14 @@ class Context:
                                 % ("int16" if fmt == N.AUDIO_S16 else "float32", int(nframes) * Cn, out.dtype, tuple(out.shape)))
             if self._stream_ptr is None or moved:   # (a moved background was copied on torch's stream)
                 torch.cuda.current_stream(out.device).synchronize()
-            self._chk(self.L.uwspr_tx_render(self.h, sp, len(sig), C.byref(ch), Cn, int(t0), int(nframes), fmt,
-                                             C.c_void_p(out.data_ptr()), N.DEVICE))
+            self._chk(call(self.h, sp, len(sig), C.byref(ch), Cn, int(t0), int(nframes), fmt,
+                           C.c_void_p(out.data_ptr()), N.DEVICE))
             if self._stream_ptr is None or moved:   # (the moved copies are freed when this call returns)
                 self.synchronize()
             return out
         a = np.empty((int(nframes), Cn), np.int16 if fmt == N.AUDIO_S16 else np.float32)
-        self._chk(self.L.uwspr_tx_render(self.h, sp, len(sig), C.byref(ch), Cn, int(t0), int(nframes), fmt,
-                                         C.c_void_p(a.ctypes.data), N.HOST))
+        self._chk(call(self.h, sp, len(sig), C.byref(ch), Cn, int(t0), int(nframes), fmt,
+                       C.c_void_p(a.ctypes.data), N.HOST))
         return a
 
     # -- multi-GPU gather over RCCL (uwspr_dist_*) ---------------------------
@@ -719,7 +725,7 @@ def write_c2(path, iq, dial_freq=10.1387, type=2):
 def tx_signals(signals):
     """A list of transmissions -> the uwspr_tx_signal array.  Each is a dict: "text" (or "message": 7 bytes, or
     "symbols": 162), "channel" (0), "start" (baseband sample of the first symbol, 375), "f0" (Hz, 0), "drift" (Hz over the
-    transmission, 0), "phase0" (rad, 0), "gain" (1)."""
+    transmission, 0), "phase0" (rad, 0), "gain" (1), and optionally "motion" (tx_motions)."""
     signals = list(signals)
     arr = (N.TxSignal * max(len(signals), 1))()
     for i, s in enumerate(signals):
@@ -735,6 +741,64 @@ def tx_signals(signals):
     return arr if signals else (N.TxSignal * 0)()
 
 
+_TX_MODELS = {"static": N.TX_STATIC, "doppler": N.TX_DOPPLER, "delay": N.TX_DELAY}
+
+
+def tx_motions(signals):
+    """The uwspr_tx_motion array of a list of transmissions (tx_signals' dicts), or None when none has a "motion".  A
+    motion is a dict: "v" (V1, V2) m/s, "p" (p1, p2) m (the source at (V1 t + p1, V2 t + p2), the hydrophone at the
+    origin: slm.cc's straight-line model), "t" (trajectory time of the transmission's first sample, s, 0), "model"
+    ("doppler": the carrier Doppler alone, the receiver's model; "delay": propagation delay as well; "static"),
+    "absolute" (False: delay and phase relative to R(t_first); True: R / c, `start` being the emission time) and
+    "spreading" (False; True: amplitude R(t_first) / R(t)).  include/uwspr_hip.h states the model."""
+    signals = list(signals)
+    if not any(s.get("motion") is not None for s in signals):
+        return None
+    arr = (N.TxMotion * len(signals))()
+    for i, s in enumerate(signals):
+        m = s.get("motion")
+        if m is None:
+            continue
+        unknown = set(m) - {"v", "p", "t", "model", "absolute", "spreading"}
+        if unknown:
+            raise ValueError("motion: unknown keys %s" % sorted(unknown))
+        v, p = m.get("v", (0.0, 0.0)), m.get("p", (0.0, 0.0))
+        arr[i].v1, arr[i].v2 = float(v[0]), float(v[1])
+        arr[i].p1, arr[i].p2 = float(p[0]), float(p[1])
+        arr[i].t_first = float(m.get("t", 0.0))
+        model = m.get("model", "doppler")
+        arr[i].model = _TX_MODELS[model] if isinstance(model, str) else int(model)
+        arr[i].flags = (N.TX_ABSOLUTE if m.get("absolute", False) else 0) | (N.TX_SPREADING if m.get("spreading", False) else 0)
+    return arr
+
+
+def slm_trajectories():
+    """The receiver's 125 straight-line-model trajectories, [125, 4] float64 (V1, V2, p1, p2), in slmGenerator's order
+    (lib/slm.cc:76-116): p2 = 50 .. 850 step 200 fastest, then V1 = -2 .. 2, then V2 = -2 .. 2 (m/s); p1 = 0."""
+    out = np.zeros((125, 4), np.float64)
+    i = 0
+    for v2 in range(-2, 3):
+        for v1 in range(-2, 3):
+            for p2 in range(50, 851, 200):
+                out[i] = (v1, v2, 0.0, p2)
+                i += 1
+    return out
+
+
+def slm_drift(traj, t, cf=1500.0):
+    """The straight-line-model Doppler in Hz, binary64: slmFrequencyDrift (lib/slm.cc:36-73) = -(cf / c) dR/dt with
+    R(t) = |(V1 t + p1, V2 t + p2)| and c = 1500 m/s (0 where R = 0).  traj: (V1, V2, p1, p2) or an [..., 4] array; t in
+    seconds; the result broadcasts traj[..., 0] against t."""
+    a = np.asarray(traj, np.float64)
+    V1, V2, p1, p2 = a[..., 0], a[..., 1], a[..., 2], a[..., 3]
+    t = np.asarray(t, np.float64)
+    q1, q2 = V1 * t + p1, V2 * t + p2
+    R = np.hypot(q1, q2)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        d = np.where(R > 0, -(V1 * q1 + V2 * q2) / np.where(R > 0, R, 1.0) * (float(cf) / 1500.0), 0.0)
+    return d
+
+
 def tx_sigma(snr_db, gain=1.0):
     """AWGN sigma (per 12 kS/s audio sample) that puts a transmission of baseband amplitude `gain` at snr_db in 2500 Hz
     at the transmit chain's output: the chain makes it a real tone of amplitude gain / 32 (the interpolation filter has
@@ -746,13 +810,21 @@ def tx_sigma(snr_db, gain=1.0):
 def encode_wav(path, schedule, channels=1, snr_db=None, seed=0, gain=1.0, seconds=None, piece_s=60, ctx=None):
     """c2ToWaveFile from text: a 16-bit 12 kS/s WAV of `channels` channels carrying the schedule's transmissions.
     schedule: (text, channel, start_s, f0) entries; start_s is the start of the entry's 2-minute slot (its first symbol
-    is 1 s later, as in a .c2 file) and f0 the offset in Hz (the transmission is centred on 1500 + f0 Hz).  snr_db: AWGN per channel (seed + channel) for that SNR in 2500 Hz, None = none.  The file is rendered
+    is 1 s later, as in a .c2 file) and f0 the offset in Hz (the transmission is centred on 1500 + f0 Hz).  An entry may
+    also be a tx_signals dict (a moving source: its "motion"), its gain `gain` unless it names one.  snr_db: AWGN per channel (seed + channel) for that SNR in 2500 Hz, None = none.  The file is rendered
     in pieces of piece_s seconds and lasts `seconds` (default: until the last slot's frame is complete)."""
     import wave
-    sig = [{"text": t, "channel": int(c), "start": int(round(375 * float(s0))) + 375, "f0": float(f0), "gain": gain}
-           for (t, c, s0, f0) in schedule]
+    sig, slots = [], []
+    for e in schedule:
+        if isinstance(e, dict):
+            sig.append(dict({"gain": gain}, **e))
+            slots.append((int(e.get("start", 375)) - 375) / 375.0)
+        else:
+            t, c, s0, f0 = e
+            sig.append({"text": t, "channel": int(c), "start": int(round(375 * float(s0))) + 375, "f0": float(f0), "gain": gain})
+            slots.append(float(s0))
     if seconds is None:
-        seconds = max([float(e[2]) for e in schedule] + [0.0]) + 121.0
+        seconds = max(slots + [0.0]) + 121.0
     n = int(round(seconds * AUDIO_RATE))
     own = ctx is None
     ctx = Context() if own else ctx

@@ -23,6 +23,13 @@
 // more to be written in sample order, after the channel's noise and background are added and the value quantised.
 // An output's arithmetic does not depend on where it falls in a workgroup or a launch: renders of any pieces
 // concatenate to the same bytes.  1.44 M outputs x 100 taps x 2 FMAs = 0.58 GFLOP per 2-minute channel record.
+//
+// Moving sources (uwspr_tx_*_moving, the straight-line model of include/uwspr_hip.h): a signal with a motion gets one
+// more binary64 hypot per baseband sample, R(t) of its trajectory, folded into the same single sincos; in DELAY mode the
+// symbol lookup takes the fractional index k' = k - 375 D(t).  Those launches are the <MOVING = true> instances of the
+// kernels, so static renders run the code they ran before.  R(t_first) is evaluated once per signal ON THE DEVICE
+// (k7_motion_prep), with the hypot the samples use: a zero-velocity trajectory has D = 0 exactly, so k' = k and the
+// phase are the static ones bit for bit.
 #include <math.h>
 #include <stdarg.h>
 #include <stdio.h>
@@ -70,6 +77,18 @@ struct tx_dsig {
 };
 static_assert(sizeof(tx_dsig) % 8 == 0, "tx_dsig is 8-byte aligned in arrays");
 
+// A signal's motion as the kernels read it, beside its tx_dsig (same index).  r0 and rref are filled in on the device.
+struct tx_dmot {
+  double v1, v2, p1, p2, t_first;
+  double r0;            // R(t_first)
+  double rref;          // R(t_first), or 0 with UWSPR_TX_ABSOLUTE: D(t) = (R(t) - rref) / c
+  long long lo, hi;     // k = j - start outside [lo, hi) adds nothing (DELAY: a conservative bound on the support)
+  int model;            // UWSPR_TX_STATIC / DOPPLER / DELAY
+  int flags;
+};
+static_assert(sizeof(tx_dmot) % 8 == 0, "tx_dmot is 8-byte aligned in arrays");
+constexpr double K7_C = 1500.0, K7_FC = 1500.0;   // sound speed (slm.cc), the chain's carrier
+
 struct tx_dchan {
   float sigma, bg_gain;
   unsigned long long seed;
@@ -94,13 +113,54 @@ __device__ __forceinline__ void tx_add(const tx_dsig &s, long long j, float &re,
   im -= s.gain * (float)sn;
 }
 
+// tx_add for a signal with a motion.  theta at k' = 256 q + r (r fractional in DELAY mode) is tx_add's expression; with
+// D = 0 (zero velocity, no ABSOLUTE) k' = k and every operation below repeats tx_add's on the same values.
+__device__ __forceinline__ void tx_add_moving(const tx_dsig &s, const tx_dmot &m, long long j, float &re, float &im) {
+  if (m.model == UWSPR_TX_STATIC) { tx_add(s, j, re, im); return; }
+  const long long k = j - s.start;
+  if (k < m.lo || k >= m.hi) return;
+  const double t = m.t_first + (double)k / K7_FS;
+  const double R = hypot(m.v1 * t + m.p1, m.v2 * t + m.p2);
+  const double d = (R - m.rref) / K7_C;                      // D(t), s
+  double kp = (double)k;
+  if (m.model == UWSPR_TX_DELAY) {
+    kp -= K7_FS * d;
+    if (!(kp >= 0.0 && kp < (double)K7_NTX)) return;
+  }
+  const int q = (int)floor(kp * (1.0 / 256.0));
+  const double r = kp - 256.0 * (double)q;
+  const double th = s.ph[q] + r * (K7_TWO_PI * ((double)s.sym[q] - 1.5) / 256.0 + s.wf) +
+                    s.wd * (r * ((double)(256 * q) - 0.5 * (K7_NTX - 1)) + 0.5 * r * (r - 1.0)) -
+                    (K7_TWO_PI * K7_FC) * d;
+  const float g = (m.flags & UWSPR_TX_SPREADING) ? (float)((double)s.gain * (m.r0 / R)) : s.gain;
+  double sn, cs;
+  sincos(th, &sn, &cs);
+  re += g * (float)cs;
+  im -= g * (float)sn;
+}
+
 // baseband sample j of a channel in the file's orientation (I + jQ = gain e^{-j theta}: what wsprsim writes and
 // c2ToWaveFile reads), signals in ascending index
-__device__ __forceinline__ float2 tx_baseband_at(const tx_dsig *__restrict__ sigs, int nsig, int ch, long long j) {
+template <bool MOVING>
+__device__ __forceinline__ float2 tx_baseband_at(const tx_dsig *__restrict__ sigs, const tx_dmot *__restrict__ mots,
+                                                 int nsig, int ch, long long j) {
   float re = 0.0f, im = 0.0f;
   for (int s = 0; s < nsig; s++)
-    if (sigs[s].channel == ch) tx_add(sigs[s], j, re, im);
+    if (sigs[s].channel == ch) {
+      if constexpr (MOVING) tx_add_moving(sigs[s], mots[s], j, re, im);
+      else tx_add(sigs[s], j, re, im);
+    }
   return make_float2(re, im);
+}
+
+// R(t_first) of every motion, with the hypot tx_add_moving uses (one thread per signal, before the render)
+__global__ void k7_motion_prep(tx_dmot *__restrict__ mots, int nsig) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= nsig) return;
+  tx_dmot &m = mots[i];
+  const double r0 = hypot(m.v1 * m.t_first + m.p1, m.v2 * m.t_first + m.p2);
+  m.r0 = r0;
+  m.rref = (m.flags & UWSPR_TX_ABSOLUTE) ? 0.0 : r0;
 }
 
 // Philox4x32-10 (Salmon et al., SC'11): counter-based, so a sample's noise depends on (seed, channel, index) only
@@ -147,8 +207,8 @@ __device__ __forceinline__ void k7_block(float (&acc)[K7_R], const float2 (&A)[8
 
 // Workgroup b renders audio [32 mb, 32 mb + 16384) of channel b mod C, mb = nb0 + 512 (b div C), and writes the
 // samples that fall in [t0, t0 + nframes) to out[(n - t0) C + ch].
-template <bool S16>
-__global__ __launch_bounds__(K7_WG) void k7_render(const tx_dsig *__restrict__ sigs, int nsig,
+template <bool S16, bool MOVING>
+__global__ __launch_bounds__(K7_WG) void k7_render(const tx_dsig *__restrict__ sigs, const tx_dmot *__restrict__ mots, int nsig,
                                                    const tx_dchan *__restrict__ chans, int C,
                                                    const float2 *__restrict__ taps, long long t0, long long nframes,
                                                    long long nb0, void *__restrict__ out) {
@@ -160,8 +220,10 @@ __global__ __launch_bounds__(K7_WG) void k7_render(const tx_dsig *__restrict__ s
   const long long mb = nb0 + (long long)(blockIdx.x / (unsigned)C) * K7_M;
   const int tid = threadIdx.x;
   const tx_dchan cz = chans[ch];
+  const tx_dmot *mz = nullptr;
+  if constexpr (MOVING) mz = mots + cz.sig0;
   for (int col = tid; col < K7_NX; col += K7_WG)
-    xs[(col & 7) * K7_G + (col >> 3)] = tx_baseband_at(sigs + cz.sig0, cz.nsig, ch, mb - K7_T + col);
+    xs[(col & 7) * K7_G + (col >> 3)] = tx_baseband_at<MOVING>(sigs + cz.sig0, mz, cz.nsig, ch, mb - K7_T + col);
   for (int i = tid; i < K7_DEC * K7_T; i += K7_WG) tp[i] = taps[i];
   __syncthreads();
 
@@ -211,10 +273,11 @@ __global__ __launch_bounds__(K7_WG) void k7_render(const tx_dsig *__restrict__ s
 
 // baseband samples [t0, t0 + n) of one channel, as uwspr_c2_read returns a .c2 file (Q negated against the file:
 // gain e^{+j theta})
-__global__ void k7_baseband(const tx_dsig *__restrict__ sigs, int nsig, int ch, long long t0, int n,
-                            float2 *__restrict__ out) {
+template <bool MOVING>
+__global__ void k7_baseband(const tx_dsig *__restrict__ sigs, const tx_dmot *__restrict__ mots, int nsig, int ch,
+                            long long t0, int n, float2 *__restrict__ out) {
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
-    const float2 x = tx_baseband_at(sigs, nsig, ch, t0 + i);
+    const float2 x = tx_baseband_at<MOVING>(sigs, mots, nsig, ch, t0 + i);
     out[i] = make_float2(x.x, -x.y);
   }
 }
@@ -223,6 +286,7 @@ __global__ void k7_baseband(const tx_dsig *__restrict__ sigs, int nsig, int ch, 
 struct tx_state {
   float2 *d_taps = nullptr;                     // [32][K7_T] (Re g, -Im g)
   tx_dsig *d_sig = nullptr; size_t cap_sig = 0;
+  tx_dmot *d_mot = nullptr; size_t cap_mot = 0;
   tx_dchan *d_chan = nullptr;
   void *d_out = nullptr; size_t cap_out = 0;    // host-output staging (bytes)
   void *d_bg = nullptr; size_t cap_bg = 0;      // host backgrounds staged (bytes)
@@ -231,7 +295,7 @@ struct tx_state {
 void tx_release(uwspr_ctx *c) {
   if (!c || !c->tx) return;
   tx_state *t = c->tx;
-  void *bufs[] = {t->d_taps, t->d_sig, t->d_chan, t->d_out, t->d_bg};
+  void *bufs[] = {t->d_taps, t->d_sig, t->d_mot, t->d_chan, t->d_out, t->d_bg};
   for (void *b : bufs) if (b) (void)hipFree(b);
   delete t;
   c->tx = nullptr;
@@ -301,8 +365,10 @@ static int tx_begin(uwspr_ctx *c) {
         const int q = p + K7_DEC * i;
         if (q < K7_NT) img[(size_t)p * K7_T + i] = make_float2((float)g[q].real(), (float)-g[q].imag());
       }
-    if (hipFuncSetAttribute(reinterpret_cast<const void *>(k7_render<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)k7_lds_bytes()) != hipSuccess ||
-        hipFuncSetAttribute(reinterpret_cast<const void *>(k7_render<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)k7_lds_bytes()) != hipSuccess)
+    if (hipFuncSetAttribute(reinterpret_cast<const void *>(k7_render<false, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)k7_lds_bytes()) != hipSuccess ||
+        hipFuncSetAttribute(reinterpret_cast<const void *>(k7_render<true, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)k7_lds_bytes()) != hipSuccess ||
+        hipFuncSetAttribute(reinterpret_cast<const void *>(k7_render<false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)k7_lds_bytes()) != hipSuccess ||
+        hipFuncSetAttribute(reinterpret_cast<const void *>(k7_render<true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)k7_lds_bytes()) != hipSuccess)
       return tx_fail(c, UWSPR_ERR_HIP, "transmit kernel: %zu bytes of LDS refused", k7_lds_bytes());
     float2 *d = nullptr;
     TXCHK(c, hipMalloc((void **)&d, img.size() * sizeof(float2)));
@@ -335,11 +401,62 @@ static int tx_device_ready(uwspr_ctx *c) {
 
 static bool tx_finite(double v) { return v == v && v - v == 0.0; }
 
-// check the records (channel < C when C > 0) and build the device form of those that pass `keep`
+static double tx_range_r(const uwspr_tx_motion &m, double t) { return hypot(m.v1 * t + m.p1, m.v2 * t + m.p2); }
+
+// R over trajectory times [ta, tb]: R is convex, so its maximum is at an end and its minimum at the closest approach
+// clipped to the interval
+static void tx_r_range(const uwspr_tx_motion &m, double ta, double tb, double *rmin, double *rmax) {
+  const double ra = tx_range_r(m, ta), rb = tx_range_r(m, tb), vv = m.v1 * m.v1 + m.v2 * m.v2;
+  const double tc = vv > 0.0 ? std::min(std::max(-(m.v1 * m.p1 + m.v2 * m.p2) / vv, ta), tb) : ta;
+  *rmax = std::max(ra, rb);
+  *rmin = std::min(std::min(ra, rb), tx_range_r(m, tc));
+}
+
+// Check a motion and bound the k = j - start where its signal can be non-zero: [0, N) unless DELAY.  In DELAY mode
+// k' = k - 375 D(t(k)) increases with k (|dR/dt| <= 100 m/s < c), so an interval [a, b] with a <= 375 min D - 2 and
+// b >= N + 375 max D + 2 (extremes over [a, b] itself) holds the whole support: k' < -2 at a, k' > N + 2 at b.  It is
+// found by widening [0, N] until it holds (a contraction: each widening is at most 1/15 of the last).
+static int tx_motion_check(uwspr_ctx *c, int i, const uwspr_tx_motion &m, long long *lo, long long *hi) {
+  *lo = 0; *hi = K7_NTX;
+  if (!tx_finite(m.v1) || !tx_finite(m.v2) || !tx_finite(m.p1) || !tx_finite(m.p2) || !tx_finite(m.t_first))
+    return tx_fail(c, UWSPR_ERR_ARG, "uwspr_tx: motion %d has a non-finite field", i);
+  if (m.model < UWSPR_TX_STATIC || m.model > UWSPR_TX_DELAY || (m.flags & ~(UWSPR_TX_ABSOLUTE | UWSPR_TX_SPREADING)))
+    return tx_fail(c, UWSPR_ERR_ARG, "uwspr_tx: motion %d: model %d, flags 0x%x", i, m.model, (unsigned)m.flags);
+  if (hypot(m.v1, m.v2) > 100.0 || fabs(m.t_first) > 1e6 || fabs(m.p1) > 1e9 || fabs(m.p2) > 1e9)
+    return tx_fail(c, UWSPR_ERR_ARG, "uwspr_tx: motion %d: |v| %g m/s (<= 100), t_first %g s (|.| <= 1e6), p (%g, %g) m "
+                   "(|.| <= 1e9)", i, hypot(m.v1, m.v2), m.t_first, m.p1, m.p2);
+  if (m.model == UWSPR_TX_STATIC) return UWSPR_OK;
+  double a = 0.0, b = (double)K7_NTX;
+  if (m.model == UWSPR_TX_DELAY) {
+    const double ref = (m.flags & UWSPR_TX_ABSOLUTE) ? 0.0 : tx_range_r(m, m.t_first);
+    int it = 0;
+    for (;; it++) {
+      double rmin, rmax;
+      tx_r_range(m, m.t_first + a / K7_FS, m.t_first + b / K7_FS, &rmin, &rmax);
+      const double na = K7_FS * (rmin - ref) / K7_C - 2.0, nb = K7_NTX + K7_FS * (rmax - ref) / K7_C + 2.0;
+      if ((a <= na && b >= nb) || it == 200) break;
+      a = std::min(a, na); b = std::max(b, nb);
+    }
+    if (it == 200 || !(fabs(a) < 1e15 && fabs(b) < 1e15))
+      return tx_fail(c, UWSPR_ERR_ARG, "uwspr_tx: motion %d: no bound on the delayed support", i);
+    *lo = (long long)floor(a); *hi = (long long)ceil(b) + 1;
+  }
+  if (m.flags & UWSPR_TX_SPREADING) {   // R(t_first) / R(t) over the transmission
+    double rmin, rmax;
+    tx_r_range(m, m.t_first + (double)*lo / K7_FS, m.t_first + (double)(*hi - 1) / K7_FS, &rmin, &rmax);
+    if (!(rmin >= 1.0)) return tx_fail(c, UWSPR_ERR_ARG, "uwspr_tx: motion %d: SPREADING with R down to %g m (>= 1)", i, rmin);
+  }
+  return UWSPR_OK;
+}
+
+// check the records (channel < C when C > 0; motions, when given) and build the device form of those that pass
+// keep(s, lo, hi) ([start + lo, start + hi): where the signal may be non-zero)
 template <typename Keep>
-static int tx_prepare(uwspr_ctx *c, const uwspr_tx_signal *sig, int nsig, int C, Keep keep, std::vector<tx_dsig> &out) {
+static int tx_prepare(uwspr_ctx *c, const uwspr_tx_signal *sig, const uwspr_tx_motion *mot, int nsig, int C, Keep keep,
+                      std::vector<tx_dsig> &out, std::vector<tx_dmot> *mout) {
   if (nsig < 0 || (nsig > 0 && !sig)) return tx_fail(c, UWSPR_ERR_ARG, "uwspr_tx: signals %p, nsig %d", (const void *)sig, nsig);
   out.clear();
+  if (mout) mout->clear();
   for (int i = 0; i < nsig; i++) {
     const uwspr_tx_signal &s = sig[i];
     for (int k = 0; k < K7_NSYM; k++)
@@ -348,7 +465,22 @@ static int tx_prepare(uwspr_ctx *c, const uwspr_tx_signal *sig, int nsig, int C,
     if (!tx_finite(s.f0_hz) || !tx_finite(s.drift_hz) || !tx_finite(s.phase0) || !tx_finite((double)s.gain))
       return tx_fail(c, UWSPR_ERR_ARG, "uwspr_tx: signal %d has a non-finite f0 / drift / phase / gain", i);
     if (s.start < -(1LL << 50) || s.start > (1LL << 50)) return tx_fail(c, UWSPR_ERR_ARG, "uwspr_tx: signal %d start %lld", i, (long long)s.start);
-    if (!keep(s)) continue;
+    long long lo = 0, hi = K7_NTX;
+    if (mot) {
+      const int rc = tx_motion_check(c, i, mot[i], &lo, &hi);
+      if (rc) return rc;
+      if (s.start + lo < -(1LL << 52) || s.start + hi > (1LL << 52))
+        return tx_fail(c, UWSPR_ERR_ARG, "uwspr_tx: signal %d: delayed support [%lld, %lld)", i, s.start + lo, s.start + hi);
+    }
+    if (!keep(s, lo, hi)) continue;
+    if (mout) {
+      const uwspr_tx_motion &m = mot[i];
+      tx_dmot dm;
+      memset(&dm, 0, sizeof(dm));
+      dm.v1 = m.v1; dm.v2 = m.v2; dm.p1 = m.p1; dm.p2 = m.p2; dm.t_first = m.t_first;
+      dm.lo = lo; dm.hi = hi; dm.model = m.model; dm.flags = m.flags;
+      mout->push_back(dm);
+    }
     tx_dsig d;
     memset(&d, 0, sizeof(d));
     d.start = s.start; d.channel = s.channel; d.gain = s.gain;
@@ -375,19 +507,38 @@ static int tx_upload_signals(uwspr_ctx *c, const std::vector<tx_dsig> &v) {
   return UWSPR_OK;
 }
 
+static bool tx_any_moving(const std::vector<tx_dmot> &m) {
+  for (const tx_dmot &d : m)
+    if (d.model != UWSPR_TX_STATIC) return true;
+  return false;
+}
+
+// the motions beside the signals, R(t_first) filled in on the device
+static int tx_upload_motions(uwspr_ctx *c, const std::vector<tx_dmot> &m) {
+  tx_state *t = c->tx;
+  int rc = tx_grow(c, (void **)&t->d_mot, &t->cap_mot, m.size() * sizeof(tx_dmot));
+  if (rc) return rc;
+  if (m.empty()) return UWSPR_OK;
+  TXCHK(c, hipMemcpyAsync(t->d_mot, m.data(), m.size() * sizeof(tx_dmot), hipMemcpyHostToDevice, c->stream));
+  hipLaunchKernelGGL(k7_motion_prep, dim3((unsigned)((m.size() + 63) / 64)), dim3(64), 0, c->stream, t->d_mot, (int)m.size());
+  TXCHK(c, hipGetLastError());
+  return UWSPR_OK;
+}
+
 }  // namespace uwspr
 
 using namespace uwspr;
 
-extern "C" int uwspr_tx_baseband(uwspr_ctx *c, const uwspr_tx_signal *sig, int nsig, int channel, long long t0, int n,
-                                 float *iq, int where) {
+static int tx_baseband(uwspr_ctx *c, const uwspr_tx_signal *sig, const uwspr_tx_motion *mot, int nsig, int channel,
+                       long long t0, int n, float *iq, int where) {
   if (!c) return UWSPR_ERR_ARG;
   if (n < 0 || (n > 0 && !iq) || channel < 0 || (where != UWSPR_HOST && where != UWSPR_DEVICE))
     return tx_fail(c, UWSPR_ERR_ARG, "uwspr_tx_baseband: n %d, iq %p, channel %d, where %d", n, (void *)iq, channel, where);
   std::vector<tx_dsig> v;
-  int rc = tx_prepare(c, sig, nsig, 0, [&](const uwspr_tx_signal &s) {
-    return s.channel == channel && s.start < t0 + n && s.start + K7_NTX > t0;
-  }, v);
+  std::vector<tx_dmot> mv;
+  int rc = tx_prepare(c, sig, mot, nsig, 0, [&](const uwspr_tx_signal &s, long long lo, long long hi) {
+    return s.channel == channel && s.start + lo < t0 + n && s.start + hi > t0;
+  }, v, mot ? &mv : nullptr);
   if (rc) return rc;
   if (n == 0) return UWSPR_OK;
   if ((rc = tx_device_ready(c))) return rc;
@@ -395,6 +546,8 @@ extern "C" int uwspr_tx_baseband(uwspr_ctx *c, const uwspr_tx_signal *sig, int n
     return tx_fail(c, UWSPR_ERR_ARG, "uwspr_tx_baseband: iq %p is not %zu bytes of this device's memory", (void *)iq, (size_t)n * sizeof(float2));
   if ((rc = tx_begin(c))) return rc;
   if ((rc = tx_upload_signals(c, v))) return rc;
+  const bool moving = tx_any_moving(mv);
+  if (moving && (rc = tx_upload_motions(c, mv))) return rc;
   tx_state *t = c->tx;
   float2 *dst = (float2 *)iq;
   if (where == UWSPR_HOST) {
@@ -403,7 +556,10 @@ extern "C" int uwspr_tx_baseband(uwspr_ctx *c, const uwspr_tx_signal *sig, int n
   }
   TXCHK(c, hipStreamSynchronize(c->stream));   // (the records live on this call's stack)
   const int blocks = (n + 255) / 256 < 2048 ? (n + 255) / 256 : 2048;
-  hipLaunchKernelGGL(k7_baseband, dim3(blocks), dim3(256), 0, c->stream, t->d_sig, (int)v.size(), channel, t0, n, dst);
+  if (moving)
+    hipLaunchKernelGGL(k7_baseband<true>, dim3(blocks), dim3(256), 0, c->stream, t->d_sig, t->d_mot, (int)v.size(), channel, t0, n, dst);
+  else
+    hipLaunchKernelGGL(k7_baseband<false>, dim3(blocks), dim3(256), 0, c->stream, t->d_sig, (const tx_dmot *)nullptr, (int)v.size(), channel, t0, n, dst);
   TXCHK(c, hipGetLastError());
   if (where == UWSPR_HOST) {
     TXCHK(c, hipMemcpyAsync(iq, dst, (size_t)n * sizeof(float2), hipMemcpyDeviceToHost, c->stream));
@@ -412,8 +568,8 @@ extern "C" int uwspr_tx_baseband(uwspr_ctx *c, const uwspr_tx_signal *sig, int n
   return UWSPR_OK;
 }
 
-extern "C" int uwspr_tx_render(uwspr_ctx *c, const uwspr_tx_signal *sig, int nsig, const uwspr_tx_channel *chan, int C,
-                               long long t0, long long nframes, int format, void *out, int where) {
+static int tx_render(uwspr_ctx *c, const uwspr_tx_signal *sig, const uwspr_tx_motion *mot, int nsig,
+                     const uwspr_tx_channel *chan, int C, long long t0, long long nframes, int format, void *out, int where) {
   if (!c) return UWSPR_ERR_ARG;
   if (C < 1 || C > UWSPR_PIPE_MAX_CHANNELS || !chan || t0 < 0 || nframes < 0 || (nframes > 0 && !out) ||
       (format != UWSPR_AUDIO_F32 && format != UWSPR_AUDIO_S16) || (where != UWSPR_HOST && where != UWSPR_DEVICE))
@@ -427,11 +583,13 @@ extern "C" int uwspr_tx_render(uwspr_ctx *c, const uwspr_tx_signal *sig, int nsi
       return tx_fail(c, UWSPR_ERR_ARG, "uwspr_tx_render: channel %d: sigma %g, background %p len %lld format %d gain %g", k,
                      z.sigma, z.background, (long long)z.background_len, z.background_format, (double)z.background_gain);
   }
-  // signals that reach [t0, t0 + nframes): audio 32 start .. 32 (start + N - 1) + 3178 (the others add exact zeros)
+  // signals that reach [t0, t0 + nframes): audio 32 (start + lo) .. 32 (start + hi - 1) + 3178, [lo, hi) = [0, N)
+  // unless delayed (the others add exact zeros)
   std::vector<tx_dsig> v;
-  int rc = tx_prepare(c, sig, nsig, C, [&](const uwspr_tx_signal &s) {
-    return K7_DEC * s.start < t0 + nframes && K7_DEC * (s.start + K7_NTX - 1) + K7_NT - 1 >= t0;
-  }, v);
+  std::vector<tx_dmot> mv;
+  int rc = tx_prepare(c, sig, mot, nsig, C, [&](const uwspr_tx_signal &s, long long lo, long long hi) {
+    return K7_DEC * (s.start + lo) < t0 + nframes && K7_DEC * (s.start + hi - 1) + K7_NT - 1 >= t0;
+  }, v, mot ? &mv : nullptr);
   if (rc) return rc;
   if (nframes == 0) return UWSPR_OK;
   const size_t esz = format == UWSPR_AUDIO_S16 ? 2 : 4;
@@ -446,10 +604,23 @@ extern "C" int uwspr_tx_render(uwspr_ctx *c, const uwspr_tx_signal *sig, int nsi
                        chan[k].background, (long long)chan[k].background_len);
   }
   // the kernel walks only its channel's signals: sorted by channel, ascending index within one (the order they add up in)
-  std::stable_sort(v.begin(), v.end(), [](const tx_dsig &a, const tx_dsig &b) { return a.channel < b.channel; });
+  // (a motion moves with its signal)
+  const bool moving = tx_any_moving(mv);
+  if (moving) {
+    std::vector<int> ix(v.size());
+    for (size_t i = 0; i < ix.size(); i++) ix[i] = (int)i;
+    std::stable_sort(ix.begin(), ix.end(), [&](int a, int b) { return v[a].channel < v[b].channel; });
+    std::vector<tx_dsig> vs(v.size());
+    std::vector<tx_dmot> ms(v.size());
+    for (size_t i = 0; i < ix.size(); i++) { vs[i] = v[ix[i]]; ms[i] = mv[ix[i]]; }
+    v.swap(vs); mv.swap(ms);
+  } else {
+    std::stable_sort(v.begin(), v.end(), [](const tx_dsig &a, const tx_dsig &b) { return a.channel < b.channel; });
+  }
   if ((rc = tx_begin(c))) return rc;
   tx_state *t = c->tx;
   if ((rc = tx_upload_signals(c, v))) return rc;
+  if (moving && (rc = tx_upload_motions(c, mv))) return rc;
   // channels: host backgrounds are staged behind each other
   std::vector<tx_dchan> dc(C);
   size_t bg_bytes = 0;
@@ -492,11 +663,18 @@ extern "C" int uwspr_tx_render(uwspr_ctx *c, const uwspr_tx_signal *sig, int nsi
     if (nblk * C > 0x7fffffffLL) return tx_fail(c, UWSPR_ERR_ARG, "uwspr_tx_render: %lld workgroups", nblk * C);
     void *dst = where == UWSPR_HOST ? t->d_out : (void *)((char *)out + (size_t)k * C * esz);
     const dim3 grid((unsigned)(nblk * C));
-    if (format == UWSPR_AUDIO_S16)
-      hipLaunchKernelGGL(k7_render<true>, grid, dim3(K7_WG), k7_lds_bytes(), c->stream, t->d_sig, (int)v.size(),
+    const tx_dmot *dm = moving ? t->d_mot : nullptr;
+    if (format == UWSPR_AUDIO_S16 && moving)
+      hipLaunchKernelGGL((k7_render<true, true>), grid, dim3(K7_WG), k7_lds_bytes(), c->stream, t->d_sig, dm, (int)v.size(),
+                         t->d_chan, C, t->d_taps, a, len, nb0, dst);
+    else if (format == UWSPR_AUDIO_S16)
+      hipLaunchKernelGGL((k7_render<true, false>), grid, dim3(K7_WG), k7_lds_bytes(), c->stream, t->d_sig, dm, (int)v.size(),
+                         t->d_chan, C, t->d_taps, a, len, nb0, dst);
+    else if (moving)
+      hipLaunchKernelGGL((k7_render<false, true>), grid, dim3(K7_WG), k7_lds_bytes(), c->stream, t->d_sig, dm, (int)v.size(),
                          t->d_chan, C, t->d_taps, a, len, nb0, dst);
     else
-      hipLaunchKernelGGL(k7_render<false>, grid, dim3(K7_WG), k7_lds_bytes(), c->stream, t->d_sig, (int)v.size(),
+      hipLaunchKernelGGL((k7_render<false, false>), grid, dim3(K7_WG), k7_lds_bytes(), c->stream, t->d_sig, dm, (int)v.size(),
                          t->d_chan, C, t->d_taps, a, len, nb0, dst);
     TXCHK(c, hipGetLastError());
     if (where == UWSPR_HOST) {
@@ -505,4 +683,25 @@ extern "C" int uwspr_tx_render(uwspr_ctx *c, const uwspr_tx_signal *sig, int nsi
     }
   }
   return UWSPR_OK;
+}
+
+extern "C" int uwspr_tx_baseband(uwspr_ctx *c, const uwspr_tx_signal *sig, int nsig, int channel, long long t0, int n,
+                                 float *iq, int where) {
+  return tx_baseband(c, sig, nullptr, nsig, channel, t0, n, iq, where);
+}
+
+extern "C" int uwspr_tx_baseband_moving(uwspr_ctx *c, const uwspr_tx_signal *sig, const uwspr_tx_motion *motion, int nsig,
+                                        int channel, long long t0, int n, float *iq, int where) {
+  return tx_baseband(c, sig, motion, nsig, channel, t0, n, iq, where);
+}
+
+extern "C" int uwspr_tx_render(uwspr_ctx *c, const uwspr_tx_signal *sig, int nsig, const uwspr_tx_channel *chan, int C,
+                               long long t0, long long nframes, int format, void *out, int where) {
+  return tx_render(c, sig, nullptr, nsig, chan, C, t0, nframes, format, out, where);
+}
+
+extern "C" int uwspr_tx_render_moving(uwspr_ctx *c, const uwspr_tx_signal *sig, const uwspr_tx_motion *motion, int nsig,
+                                      const uwspr_tx_channel *chan, int C, long long t0, long long nframes, int format,
+                                      void *out, int where) {
+  return tx_render(c, sig, motion, nsig, chan, C, t0, nframes, format, out, where);
 }

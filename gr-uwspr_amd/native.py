@@ -220,7 +220,16 @@ class TxChannel(C.Structure):
                 ("background_format", C.c_int32), ("background_gain", C.c_float)]
 
 
-assert C.sizeof(TxSignal) == 208 and C.sizeof(TxChannel) == 40
+
+
+class TxMotion(C.Structure):
+    _fields_ = [("v1", C.c_double), ("v2", C.c_double), ("p1", C.c_double), ("p2", C.c_double), ("t_first", C.c_double),
+                ("model", C.c_int32), ("flags", C.c_int32)]
+
+
+assert C.sizeof(TxSignal) == 208 and C.sizeof(TxChannel) == 40 and C.sizeof(TxMotion) == 48
+TX_STATIC, TX_DOPPLER, TX_DELAY = 0, 1, 2
+TX_ABSOLUTE, TX_SPREADING = 1, 2
 
 
 class PipeOpts(C.Structure):
@@ -254,6 +263,7 @@ ABI_SYMBOLS = [
     "uwspr_fano_decode", "uwspr_fano_encode", "uwspr_decode_candidate", "uwspr_host_threads", "uwspr_host_set_ranks", "uwspr_decode_batch", "uwspr_unpack_message",
     "uwspr_c2_read",
     "uwspr_wspr_pack", "uwspr_nhash", "uwspr_wspr_symbols", "uwspr_c2_write", "uwspr_tx_baseband", "uwspr_tx_render",
+    "uwspr_tx_baseband_moving", "uwspr_tx_render_moving",
     "uwspr_dist_unique_id", "uwspr_dist_init", "uwspr_dist_gather", "uwspr_dist_finalize",
     "uwspr_pipe_open", "uwspr_pipe_close", "uwspr_pipe_last_error", "uwspr_pipe_acquire", "uwspr_pipe_commit",
     "uwspr_pipe_push", "uwspr_pipe_push_audio", "uwspr_pipe_push_audio_channels", "uwspr_pipe_submit_device", "uwspr_pipe_flush", "uwspr_pipe_collect", "uwspr_pipe_get_stats",
@@ -349,6 +359,8 @@ def lib():
     L.uwspr_c2_write.argtypes = [C.c_char_p, vp, ip, C.c_double, C.c_int32]
     L.uwspr_tx_baseband.argtypes = [vp, vp, ip, ip, C.c_longlong, ip, vp, ip]
     L.uwspr_tx_render.argtypes = [vp, vp, ip, vp, ip, C.c_longlong, C.c_longlong, ip, vp, ip]
+    L.uwspr_tx_baseband_moving.argtypes = [vp, vp, vp, ip, ip, C.c_longlong, ip, vp, ip]
+    L.uwspr_tx_render_moving.argtypes = [vp, vp, vp, ip, vp, ip, C.c_longlong, C.c_longlong, ip, vp, ip]
     L.uwspr_dist_unique_id.argtypes = [vp]
     L.uwspr_dist_init.argtypes = [vp, ip, ip, vp]
     L.uwspr_dist_gather.argtypes = [vp, vp, C.c_size_t, vp, ip, ip]

@@ -37,7 +37,8 @@ extern "C" {
                                  6: audio streams: uwspr_stream_push_audio, uwspr_pipe_push_audio; multichannel
                                     audio into one pipe: uwspr_pipe_push_audio_channels, uwspr_decode.channel (carved
                                     out of the padding: the record stays 112 bytes); the transmit side: uwspr_wspr_pack,
-                                    uwspr_nhash, uwspr_wspr_symbols, uwspr_c2_write, uwspr_tx_baseband, uwspr_tx_render */
+                                    uwspr_nhash, uwspr_wspr_symbols, uwspr_c2_write, uwspr_tx_baseband, uwspr_tx_render;
+                                    moving sources: uwspr_tx_motion, uwspr_tx_baseband_moving, uwspr_tx_render_moving */
 
 typedef enum {
   UWSPR_OK = 0,
@@ -607,6 +608,45 @@ int uwspr_tx_baseband(uwspr_ctx *ctx, const uwspr_tx_signal *sig, int nsig, int 
  * UWSPR_DEVICE (asynchronous on the context's stream). */
 int uwspr_tx_render(uwspr_ctx *ctx, const uwspr_tx_signal *sig, int nsig, const uwspr_tx_channel *chan, int C,
                     long long t0, long long nframes, int format, void *out, int where);
+
+/* A moving source: the straight-line model (SLM) of the receiver's nonlinear search (lib/slm.cc).  The hydrophone is
+ * at the origin and the source at q(t) = (v1 t + p1, v2 t + p2) metres, R(t) = |q(t)|, c = 1500 m/s, fc = 1500 Hz (the
+ * chain's carrier).  Baseband index start + k of a transmission has trajectory time t = t_first + k / 375 s.  With
+ * theta the static phase above (uwspr_tx_baseband's orientation, gain e^{+j theta}) and D(t) = (R(t) - R(t_first)) / c,
+ * or R(t) / c with UWSPR_TX_ABSOLUTE:
+ *   UWSPR_TX_STATIC   the signal as uwspr_tx_baseband makes it (the motion is ignored);
+ *   UWSPR_TX_DOPPLER  y(k) = gain e^{+j [theta(k) - 2 pi fc D(t)]}, 0 <= k < N: the carrier Doppler alone.  The added
+ *                     frequency is -(fc / c) dR/dt = slmFrequencyDrift(m_nl, 1500, t): a trajectory of the receiver's
+ *                     grid with t_first = 0 is the hypothesis K3 scores (t = floor(k 111 / 162) s from the first symbol);
+ *   UWSPR_TX_DELAY    propagation: k' = k - 375 D(t), y(k) = gain e^{+j [theta(k') - 2 pi fc D(t)]} for 0 <= k' < N, theta
+ *                     at a fractional index being the per-symbol quadratic with fractional r.  This adds the time
+ *                     compression to the carrier Doppler.  With UWSPR_TX_ABSOLUTE, start is the emission time and the
+ *                     whole travel time R / c delays the signal.
+ * R is evaluated at the reception time t, not at the emission (retarded) time: an error of first order in v / c.
+ * UWSPR_TX_SPREADING multiplies the amplitude by R(t_first) / R(t) (spherical spreading).  Everything is binary64 per
+ * sample, in closed form: any window renders alone.  A zero-velocity motion without ABSOLUTE or SPREADING gives the bytes
+ * of no motion in either model.  Refused with UWSPR_ERR_ARG before any launch, the output untouched: a non-finite field,
+ * an unknown model or flag bit, |(v1, v2)| > 100 m/s, |t_first| > 1e6 s, |p1| or |p2| > 1e9 m, SPREADING with R < 1 m somewhere in the
+ * transmission.  Multipath is several signals with their own start, gain and motion. */
+#define UWSPR_TX_STATIC 0
+#define UWSPR_TX_DOPPLER 1
+#define UWSPR_TX_DELAY 2
+#define UWSPR_TX_ABSOLUTE 1
+#define UWSPR_TX_SPREADING 2
+typedef struct uwspr_tx_motion {
+  double v1, v2;                 /* m/s */
+  double p1, p2;                 /* m, at t = 0 */
+  double t_first;                /* s: trajectory time of the transmission's first sample */
+  int32_t model;                 /* UWSPR_TX_STATIC / DOPPLER / DELAY */
+  int32_t flags;                 /* UWSPR_TX_ABSOLUTE | UWSPR_TX_SPREADING */
+} uwspr_tx_motion;
+/* uwspr_tx_baseband and uwspr_tx_render with a motion per signal: motion is NULL (every signal static) or has nsig
+ * entries.  Same outputs, chunking and host / device identities as the static calls. */
+int uwspr_tx_baseband_moving(uwspr_ctx *ctx, const uwspr_tx_signal *sig, const uwspr_tx_motion *motion, int nsig,
+                             int channel, long long t0, int n, float *iq, int where);
+int uwspr_tx_render_moving(uwspr_ctx *ctx, const uwspr_tx_signal *sig, const uwspr_tx_motion *motion, int nsig,
+                           const uwspr_tx_channel *chan, int C, long long t0, long long nframes, int format, void *out,
+                           int where);
 
 #ifdef __cplusplus
 }
