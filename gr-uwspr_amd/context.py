@@ -435,6 +435,37 @@ class Context:
                                           C.c_void_p(sync_t.data_ptr()),
                                           C.c_void_p(sym_t.data_ptr()) if sym_t is not None else None))
 
+    # -- known-symbol subtraction (K8: uwspr_subtract_batch) -----------------
+    def subtract(self, frames, items, refine=True, out=None):
+        """Take decoded transmissions out of their frames.  items: a SUB_ITEM_DTYPE array, or dicts with "frame", "shift",
+        "f" (Hz), "drift" (Hz, 0) and "symbols" (162 values 0..3) or "text" / "message"; sorted by frame, the items of one
+        frame applied in list order.  -> (frames_out, results): numpy [B, fl, 2] for host frames, a torch CUDA tensor for
+        device frames (`out`: the tensor to write, which may be `frames` itself), and a SUB_RESULT_DTYPE array."""
+        it = sub_items(items)
+        p, B, where, keep = self._frames(frames)
+        res = np.zeros(len(it), N.SUB_RESULT_DTYPE)
+        ip = C.c_void_p(it.ctypes.data) if len(it) else None
+        rp = C.c_void_p(res.ctypes.data) if len(it) else None
+        if where == N.DEVICE:
+            import torch
+            if _is_torch(frames):
+                if out is None:
+                    out = torch.empty((B, self.fl, 2), dtype=torch.float32, device=frames.device)
+                assert out.is_cuda and out.is_contiguous() and out.dtype == torch.float32 and out.numel() >= 2 * B * self.fl
+                op = C.c_void_p(out.data_ptr())
+            else:
+                assert out is not None, "subtract: a FrameView of device memory needs out"
+                op = C.c_void_p(out.data_ptr() if _is_torch(out) else int(out))
+            # (results to the host, the frames stay where they are)
+            self._chk(self.L.uwspr_subtract_batch(self.h, p, B, N.DEVICE_FRAMES, ip, len(it), 1 if refine else 0, op, rp))
+            return out, res
+        if out is None:
+            out = np.empty((B, self.fl, 2), np.float32)
+        assert out.dtype == np.float32 and out.flags.c_contiguous and out.size >= 2 * B * self.fl
+        self._chk(self.L.uwspr_subtract_batch(self.h, p, B, N.HOST, ip, len(it), 1 if refine else 0,
+                                              C.c_void_p(out.ctypes.data), rp))
+        return out, res
+
     # -- transmit side (K7: uwspr_tx_*) ------------------------------------
     def tx_baseband(self, signals, n=45000, t0=0, channel=0, out=None):
         """375 S/s baseband samples [t0, t0 + n) of one channel's signals (tx_signals), as c2_read returns a .c2 file:
@@ -722,6 +753,22 @@ def write_c2(path, iq, dial_freq=10.1387, type=2):
         raise N.UwsprError(rc, "cannot write %s (%d samples; a .c2 file holds 45000)" % (path, a.shape[0]))
 
 
+def sub_items(items):
+    """Subtraction items (Context.subtract) -> a SUB_ITEM_DTYPE array; arrays of that dtype pass through."""
+    if isinstance(items, np.ndarray) and items.dtype == N.SUB_ITEM_DTYPE:
+        return np.ascontiguousarray(items)
+    items = list(items)
+    arr = np.zeros(len(items), N.SUB_ITEM_DTYPE)
+    for i, s in enumerate(items):
+        arr[i]["frame"] = int(s["frame"])
+        arr[i]["shift"] = int(s["shift"])
+        arr[i]["f_hz"] = float(s["f"])
+        arr[i]["drift_hz"] = float(s.get("drift", 0.0))
+        sym = s["symbols"] if "symbols" in s else wspr_symbols(s["text"] if "text" in s else s["message"])
+        arr[i]["symbols"] = np.asarray(sym, np.uint8).reshape(N.NSYM)
+    return arr
+
+
 def tx_signals(signals):
     """A list of transmissions -> the uwspr_tx_signal array.  Each is a dict: "text" (or "message": 7 bytes, or
     "symbols": 162), "channel" (0), "start" (baseband sample of the first symbol, 375), "f0" (Hz, 0), "drift" (Hz over the
@@ -851,7 +898,7 @@ class Pipe:
 
     def __init__(self, fs=375, fl=45000, spb=256, maxdrift=0, maxfreqs=200, halfbandwidth=10, cf=1500,
                  threshold=10, device=0, hop=3375, batch_frames=256, max_per_frame=1, lanes=0,
-                 host_threads=0, eager=False, sched=None, spare_after_us=0):
+                 host_threads=0, eager=False, sched=None, spare_after_us=0, passes=1):
         self.L = N.lib()
         self.h = C.c_void_p()
         self.fl = fl
@@ -866,6 +913,12 @@ class Pipe:
             self.h = None
             raise N.UwsprError(rc, msg)
         self.batch_frames, self.hop = batch_frames, hop
+        if passes != 1:   # 2: what decodes is subtracted and the residual searched again (records with pass = 1)
+            try:
+                self.set_option("passes", passes)
+            except N.UwsprError:
+                self.close()
+                raise
 
     def _chk(self, rc):
         if rc < 0:
@@ -974,8 +1027,9 @@ def read_wav(path, channels=None):
 def decode_wav(path, channels=None, **pipe_opts):
     """Decode a 12 kS/s recording as the receiver flowgraph does (examples/AudioSourceDecode.grc): the file through a
     Pipe's push_audio -> one dict per decoded record, in frame order: frame, t (stream_pos / 375 s), the coarse freq
-    and snr, and the unpacked text.  channels="all": every channel of the file through one pipe, records in (take,
-    channel, frame) order, each dict with its "channel"."""
+    and snr, the unpacked text and "pass" (1: found by the second pass of passes=2, under a decoded signal; else 0).
+    channels="all": every channel of the file through one pipe, records in (take, channel, frame) order, each dict with
+    its "channel"."""
     x, _ = read_wav(path, channels)
     pipe = Pipe(**pipe_opts)
     try:
@@ -992,7 +1046,7 @@ def decode_wav(path, channels=None, **pipe_opts):
             continue
         d = {"frame": int(r["frame"]), "t": int(r["stream_pos"]) / 375.0,
              "freq": float(r["coarse"]["freq"]), "snr": float(r["coarse"]["snr"]),
-             "text": unpack_message(r["message"])[1]}
+             "text": unpack_message(r["message"])[1], "pass": int(r["pass"])}
         if channels == "all":
             d["channel"] = int(r["channel"])
         out.append(d)

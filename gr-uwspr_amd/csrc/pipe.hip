@@ -15,6 +15,7 @@
 // Reference: the flowgraph chain sliding_window_stream_to_pdu -> FDR -> sync_and_demodulate
 // (lib/sliding_window_stream_to_pdu_impl.cc:97-138, lib/FDR_impl.cc:214-456,
 // lib/sync_and_demodulate_impl.cc:315-534; the lazy tries are cc:457-490's early exit).
+#include <math.h>
 #include <stdarg.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -61,6 +62,17 @@ struct pipe_lane {
   std::vector<int> tasks;            // (record << 5) | try: the resumed tries, decoded in parallel
   std::vector<uint8_t> task_ok;
   std::vector<int8_t> task_msg;
+  // second pass (option "passes" = 2): the frames that decoded, with their decoded signals taken out, [slots][fl]
+  float *d_res2 = nullptr; size_t cap_res2 = 0;
+  std::vector<int> slot_frame;           // slot -> frame of the batch
+  std::vector<uwspr_sub_item> items;     // the decoded records as subtraction items (frame = slot)
+  std::vector<uwspr_decode> extra;       // the second pass's records, frame = index in the batch until they are merged
+};
+
+// what the host tails of a batch add to the pipe's statistics
+struct tail_acc {
+  long long calls = 0, fails = 0, resumed = 0;
+  double gpu_wait_s = 0.0, fano_s = 0.0, resume_s = 0.0;
 };
 
 double now_s() {
@@ -73,6 +85,7 @@ struct uwspr_pipe {
   uwspr_params p;
   uwspr_pipe_opts o;
   int device = 0, fl = 0, maxfreqs = 0, per = 1;
+  int passes = 1;   // uwspr_pipe_set_option("passes"): 2 = subtract what decoded and search the residual again
   char err[512];
   // Sticky status of the first RUNTIME failure (HIP, a lane's context), written by coordinators and the producer, read
   // by both without the lock.  Argument errors are not sticky: the call that made them returns UWSPR_ERR_ARG (with
@@ -140,14 +153,16 @@ static int parg(uwspr_pipe *q, const char *fmt, ...) {
   } while (0)
 
 // ---- coordinator: finishes the batches in launch order ------------------------------------------
-static int finish_batch(uwspr_pipe *q, pipe_lane &L) {
-  const int per = q->per, B = L.B, nrec = B * per;
-  L.recs.clear();   // (a failure below emits nothing for this batch)
+// The host tail of one search of B frames (the batch itself, first = true; or its second pass over the residual frames):
+// waits for the lane's event, runs Fano on what the GPU produced, resumes what try 0 did not decode.  Leaves L.dec /
+// L.idt / L.msg for the B * per records of L.h_out.
+static int host_tail(uwspr_pipe *q, pipe_lane &L, const float *frames, int B, bool first, tail_acc &ta) {
+  const int per = q->per, nrec = B * per;
   double t0 = now_s();
   PHIP(q, hipEventSynchronize(L.ev_done));
-  if (q->inject_where.load() == 1 && L.seq == q->inject_seq.load()) return pfail(q, UWSPR_ERR_HIP, "injected failure in the host tail of batch %lld", (long long)L.seq);
+  if (first && q->inject_where.load() == 1 && L.seq == q->inject_seq.load()) return pfail(q, UWSPR_ERR_HIP, "injected failure in the host tail of batch %lld", (long long)L.seq);
   double t1 = now_s();
-  {
+  if (first) {
     std::lock_guard<std::mutex> lk(q->m);
     L.host_since = t1;   // the host tail of this batch starts: the producer may open a spare lane if it lasts (take_lane)
   }
@@ -185,7 +200,7 @@ static int finish_batch(uwspr_pipe *q, pipe_lane &L) {
   if (!L.redo.empty()) {
     // the other 16 tries of those candidates, then Fano from try 1 on
     PHIP(q, hipMemcpyAsync(L.d_need, L.h_need, (size_t)nrec, hipMemcpyHostToDevice, L.stream));
-    int rc = uwspr_demod_resume(L.ctx, L.frames, B, UWSPR_DEVICE, L.d_need, per, L.d_out);
+    int rc = uwspr_demod_resume(L.ctx, frames, B, UWSPR_DEVICE, L.d_need, per, L.d_out);
     if (rc) return pfail(q, rc, "uwspr_demod_resume: %s", uwspr_last_error(L.ctx));
     if (L.redo.size() * 4 > (size_t)nrec) {
       PHIP(q, hipMemcpyAsync(L.h_out, L.d_out, (size_t)nrec * sizeof(uwspr_demod_out), hipMemcpyDeviceToHost, L.stream));
@@ -223,6 +238,22 @@ static int finish_batch(uwspr_pipe *q, pipe_lane &L) {
     }
   }
   double t4 = now_s();
+  ta.calls += calls.load(); ta.fails += fails.load();   // (tries run after a decoding one count as calls)
+  ta.resumed += (long long)L.redo.size();
+  ta.gpu_wait_s += (t1 - t0);
+  ta.fano_s += (t2 - t1) + (t4 - t3);
+  ta.resume_s += (t3 - t2);
+  return UWSPR_OK;
+}
+
+static int second_pass(uwspr_pipe *q, pipe_lane &L, tail_acc &ta, int *ncand, int *ndec);
+
+static int finish_batch(uwspr_pipe *q, pipe_lane &L) {
+  const int per = q->per, B = L.B;
+  L.recs.clear();   // (a failure below emits nothing for this batch)
+  tail_acc ta;
+  if (const int rc = host_tail(q, L, L.frames, B, true, ta)) return rc;
+  auto valid = [&](int i) { const int b = i / per, j = i - b * per; return j < L.h_npk[b] && j < q->maxfreqs; };
   int ncand = 0, ndec = 0;
   {
     for (int b = 0; b < B; b++) {
@@ -245,15 +276,117 @@ static int finish_batch(uwspr_pipe *q, pipe_lane &L) {
       }
     }
   }
+  if (q->passes == 2 && ndec > 0) {
+    const int rc = second_pass(q, L, ta, &ncand, &ndec);
+    if (rc) { L.recs.clear(); return rc; }
+  }
   {
     std::lock_guard<std::mutex> lk(q->m);
     q->st.frames += B; q->st.batches += 1; q->st.candidates += ncand; q->st.decoded += ndec;
-    q->st.resumed += (int64_t)L.redo.size();
-    q->st.fano_calls += calls.load(); q->st.fano_timeouts += fails.load();   // (tries run after a decoding one count as calls)
-    q->st.gpu_wait_s += (t1 - t0);
-    q->st.fano_s += (t2 - t1) + (t4 - t3);
-    q->st.resume_s += (t3 - t2);
+    q->st.resumed += (int64_t)ta.resumed;
+    q->st.fano_calls += ta.calls; q->st.fano_timeouts += ta.fails;
+    q->st.gpu_wait_s += ta.gpu_wait_s;
+    q->st.fano_s += ta.fano_s;
+    q->st.resume_s += ta.resume_s;
   }
+  return UWSPR_OK;
+}
+
+// Option "passes" = 2.  L.recs holds the batch's records; the frames with a decoded one go through K8 -- every decoded
+// record an item: the symbols of its message, its f1, the shift of the try that decoded, its drift1, refined against
+// the samples -- into the lane's own buffer (the ring is only read), and that buffer through FDR + schedule + Fano as the
+// batch itself went.  What decodes there and is not one of its frame's first-pass messages becomes a record with
+// pass = 1 behind the frame's first-pass records.
+// slmFrequencyDrift (lib/slm.cc:36-73) at t = 0: the constant the fine search adds to a nonlinear candidate's f0
+static float slm_at_zero(const uwspr_candidate &c, float cf) {
+  const double V1 = c.m_nonlinear.V1, V2 = c.m_nonlinear.V2, q1 = (double)c.m_nonlinear.p1, q2 = (double)c.m_nonlinear.p2;
+  const float sign = (float)(((q1 * V1 + q2 * V2) > 0) * 2 - 1);
+  const double num = fabs(V1 * q1 + V2 * q2), den = sqrt(q1 * q1 + q2 * q2);
+  if (den == 0) return 0.0f;
+  return (float)((double)(-sign) * num / den * (double)cf / 1500.0);
+}
+
+static int second_pass(uwspr_pipe *q, pipe_lane &L, tail_acc &ta, int *ncand, int *ndec) {
+  const int per = q->per, B = L.B;
+  L.slot_frame.clear(); L.items.clear(); L.extra.clear();
+  for (int b = 0; b < B; b++)
+    for (int j = 0; j < per; j++) {
+      const int i = b * per + j;
+      if (!(j < L.h_npk[b] && j < q->maxfreqs) || !L.dec[i]) continue;
+      if (L.slot_frame.empty() || L.slot_frame.back() != b) L.slot_frame.push_back(b);
+      const uwspr_demod_out &o = L.h_out[i];
+      uwspr_sub_item it;
+      memset(&it, 0, sizeof(it));
+      it.frame = (int32_t)L.slot_frame.size() - 1;
+      it.shift = o.jig_shift[L.idt[i] >= 0 && L.idt[i] < UWSPR_NJIG ? L.idt[i] : 0];
+      // the frequency model the fine search itself correlated with: f1 and drift1 for a LINEAR candidate; for a
+      // NONLINEAR one the constant f1 + slmFrequencyDrift(t = 0) (sync_and_demodulate_impl.cc:170-180 evaluates it at
+      // t = 0 for every symbol), without drift
+      const uwspr_candidate &cd = L.h_cands[(size_t)b * per + j];
+      if (cd.m_type == UWSPR_NONLINEAR) { it.f_hz = o.f1 + slm_at_zero(cd, (float)q->p.cf); it.drift_hz = 0.0f; }
+      else { it.f_hz = o.f1; it.drift_hz = o.drift1; }
+      if (uwspr_wspr_symbols(&L.msg[7 * (size_t)i], it.symbols)) return pfail(q, UWSPR_ERR_ARG, "second pass: symbols of a decoded message");
+      L.items.push_back(it);
+    }
+  const int ns = (int)L.slot_frame.size();
+  if (ns == 0) return UWSPR_OK;
+  std::vector<int32_t> npk1(ns);
+  for (int s = 0; s < ns; s++) npk1[s] = L.h_npk[L.slot_frame[s]];
+  const size_t need = (size_t)ns * q->fl * 2;
+  if (need > L.cap_res2) {
+    PHIP(q, hipStreamSynchronize(L.stream));
+    if (L.d_res2) { PHIP(q, hipFree(L.d_res2)); L.d_res2 = nullptr; L.cap_res2 = 0; }
+    if (hipMalloc((void **)&L.d_res2, need * sizeof(float)) != hipSuccess) { (void)hipGetLastError(); return pfail(q, UWSPR_ERR_NOMEM, "second pass: %zu bytes for %d residual frames", need * sizeof(float), ns); }
+    L.cap_res2 = need;
+  }
+  int rc = subtract_check(L.ctx, L.items.data(), (int)L.items.size(), ns);
+  if (!rc) rc = subtract_run(L.ctx, L.frames, (size_t)L.stride, ns, L.slot_frame.data(), L.items.data(), (int)L.items.size(), 1, L.d_res2);
+  if (rc) return pfail(q, rc, "second pass, subtraction: %s", uwspr_last_error(L.ctx));
+  rc = uwspr_set_frame_stride(L.ctx, 0);
+  if (!rc) rc = uwspr_set_tries(L.ctx, q->o.eager ? UWSPR_NJIG : 1);
+  if (!rc) rc = uwspr_pipeline_batch(L.ctx, L.d_res2, ns, UWSPR_DEVICE, per, L.d_cands, L.d_npk, L.d_out);
+  if (rc) return pfail(q, rc, "second pass, uwspr_pipeline_batch: %s", uwspr_last_error(L.ctx));
+  PHIP(q, hipMemcpyAsync(L.h_npk, L.d_npk, (size_t)ns * sizeof(int32_t), hipMemcpyDeviceToHost, L.stream));
+  PHIP(q, hipMemcpy2DAsync(L.h_cands, (size_t)per * sizeof(uwspr_candidate), L.d_cands,
+                           (size_t)q->maxfreqs * sizeof(uwspr_candidate), (size_t)per * sizeof(uwspr_candidate), ns,
+                           hipMemcpyDeviceToHost, L.stream));
+  PHIP(q, hipMemcpyAsync(L.h_out, L.d_out, (size_t)ns * per * sizeof(uwspr_demod_out), hipMemcpyDeviceToHost, L.stream));
+  PHIP(q, hipEventRecord(L.ev_done, L.stream));
+  if ((rc = host_tail(q, L, L.d_res2, ns, false, ta))) return rc;
+  // merge: the records of frame b, then what the second pass adds to it
+  std::vector<uwspr_decode> merged;
+  merged.reserve(L.recs.size() + (size_t)ns * per);
+  size_t r0 = 0;
+  for (int s = 0; s < ns; s++) {
+    const int64_t fr = L.frame0 + L.slot_frame[s];
+    while (r0 < L.recs.size() && L.recs[r0].frame < fr) merged.push_back(L.recs[r0++]);
+    const size_t first = r0, mfirst = merged.size();   // the frame's first record in L.recs / in merged
+    while (r0 < L.recs.size() && L.recs[r0].frame == fr) merged.push_back(L.recs[r0++]);
+    int cand = (int)(r0 - first);
+    for (int j = 0; j < per; j++) {
+      const int i = s * per + j;
+      if (!(j < L.h_npk[s] && j < q->maxfreqs) || !L.dec[i]) continue;
+      bool known = false;   // one of the frame's first-pass messages, or of the second-pass records already made for it
+      for (size_t r = mfirst; r < merged.size() && !known; r++) known = merged[r].decoded && !memcmp(merged[r].message, &L.msg[7 * (size_t)i], 7);
+      if (known) continue;
+      uwspr_decode d;
+      memset(&d, 0, sizeof(d));
+      d.frame = fr;
+      d.channel = (int16_t)L.channel;
+      d.stream_pos = L.pos0 >= 0 ? L.pos0 + (int64_t)L.slot_frame[s] * L.stride : -1;
+      d.cand = cand++; d.npk = npk1[s];
+      d.coarse = L.h_cands[(size_t)s * per + j];
+      const uwspr_demod_out &o = L.h_out[i];
+      d.f1 = o.f1; d.drift1 = o.drift1; d.sync1 = o.sync1; d.shift1 = o.shift1; d.worth_a_try = o.worth_a_try;
+      d.decoded = 1; d.idt = L.idt[i];
+      memcpy(d.message, &L.msg[7 * (size_t)i], 7);
+      d.pass = 1;
+      merged.push_back(d);
+      (*ncand)++; (*ndec)++;
+    }
+  }
+  while (r0 < L.recs.size()) merged.push_back(L.recs[r0++]);
+  L.recs.swap(merged);
   return UWSPR_OK;
 }
 
@@ -398,7 +531,7 @@ extern "C" void uwspr_pipe_close(uwspr_pipe *q) {
   for (auto &L : q->lanes)   // lanes beyond the stream count ran on another lane's stream: back to their own before any is destroyed
     if (L.ctx && L.stream != L.ctx->own_stream) { (void)uwspr_set_stream(L.ctx, nullptr); L.stream = L.ctx->own_stream; }
   for (auto &L : q->lanes) {
-    void *dev[] = {L.d_cands, L.d_npk, L.d_out, L.d_need};
+    void *dev[] = {L.d_cands, L.d_npk, L.d_out, L.d_need, L.d_res2};
     for (void *b : dev) if (b) (void)hipFree(b);
     void *host[] = {L.h_cands, L.h_npk, L.h_out, L.h_need};
     for (void *b : host) if (b) (void)hipHostFree(b);
@@ -633,6 +766,14 @@ extern "C" int uwspr_pipe_set_option(uwspr_pipe *q, const char *name, int value)
   if (!q || !name) return UWSPR_ERR_ARG;
   if (const int f = q->failed.load()) return f;
   if (!strcmp(name, "sched")) return parg(q, "uwspr_pipe_set_option: \"sched\" belongs to uwspr_pipe_opts.sched_form");
+  if (!strcmp(name, "passes")) {   // the pipe's own: 1 (default), or 2 = subtract what decoded and search the residual
+    if (value != 1 && value != 2) return parg(q, "uwspr_pipe_set_option: \"passes\" is 1 or 2, not %d", value);
+    std::lock_guard<std::mutex> lk(q->m);
+    for (auto &L : q->lanes)
+      if (L.busy) { snprintf(q->err, sizeof(q->err), "uwspr_pipe_set_option(passes): batches in flight (flush first)"); return UWSPR_ERR_ARG; }
+    q->passes = value;
+    return UWSPR_OK;
+  }
   // checked AND applied under q->m: a lane is marked busy under the same lock when a batch is launched on it, so no
   // batch starts between the check and the last lane's option (the producer is single-threaded by contract, the
   // coordinators are not)

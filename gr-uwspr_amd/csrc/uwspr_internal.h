@@ -137,6 +137,8 @@ struct fdr_consts {
 struct ev_pair { hipEvent_t a, b; int kind; int64_t units; };
 struct tx_state;
 void tx_release(uwspr_ctx *c);   // k7_transmit.hip: frees what the uwspr_tx_* calls made
+struct sub_state;
+void sub_release(uwspr_ctx *c);  // k8_subtract.hip: frees what uwspr_subtract_batch / the pipe's second pass made
 
 }  // namespace uwspr
 
@@ -224,6 +226,8 @@ struct uwspr_ctx {
   void *dist_comm; int dist_rank, dist_world;
   // transmitter (k7_transmit.hip): composite taps and call scratch, made by the first uwspr_tx_* call
   uwspr::tx_state *tx;
+  // subtraction (k8_subtract.hip): window tables and call scratch, made by the first use
+  uwspr::sub_state *sub;
 
   int prof_mask;
   std::vector<uwspr::ev_pair> prof_events;
@@ -231,6 +235,15 @@ struct uwspr_ctx {
 };
 
 namespace uwspr {
+
+// frames of a batch call -> device pointer (host frames are staged in the context; uwspr_api.hip)
+int api_frames_on_device(uwspr_ctx *c, const float *frames, int B, int where, const float **dev);
+// K8 (k8_subtract.hip): slot s of dst [nslots][fl] = input frame slot_frame[s] (null: s) with the items whose `frame` is s
+// taken out, in list order; items are host records that passed subtract_check (sorted by frame, frames in [0, nframes),
+// symbols 0..3, finite f / drift, bounded shift: UWSPR_ERR_ARG with a message otherwise)
+int subtract_check(uwspr_ctx *c, const uwspr_sub_item *items, int nitems, int nframes);
+int subtract_run(uwspr_ctx *c, const float *src, size_t stride, int nslots, const int *slot_frame, const uwspr_sub_item *items,
+                 int nitems, int refine, float *dst);
 
 // ---- launchers (each enqueues on ctx->stream) ------------------------------
 int frontend_design(int mode, int stage, std::vector<double> &out, int *delay);

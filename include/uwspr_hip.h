@@ -38,7 +38,9 @@ extern "C" {
                                     audio into one pipe: uwspr_pipe_push_audio_channels, uwspr_decode.channel (carved
                                     out of the padding: the record stays 112 bytes); the transmit side: uwspr_wspr_pack,
                                     uwspr_nhash, uwspr_wspr_symbols, uwspr_c2_write, uwspr_tx_baseband, uwspr_tx_render;
-                                    moving sources: uwspr_tx_motion, uwspr_tx_baseband_moving, uwspr_tx_render_moving */
+                                    moving sources: uwspr_tx_motion, uwspr_tx_baseband_moving, uwspr_tx_render_moving;
+                                    known-symbol subtraction: uwspr_sub_item, uwspr_sub_result, uwspr_subtract_batch, the pipe
+                                    option "passes", uwspr_decode.pass (carved out of the padding as well) */
 
 typedef enum {
   UWSPR_OK = 0,
@@ -428,7 +430,8 @@ typedef struct uwspr_decode {
   int8_t message[7];
   uint8_t _pad0;
   int16_t channel;        /* the audio channel of a multichannel pipe (uwspr_pipe_push_audio_channels); 0 otherwise */
-  uint8_t _pad[2];
+  uint8_t pass;           /* 1: found by the second pass (option "passes" = 2), in the frame with its decoded signals taken out; 0 otherwise */
+  uint8_t _pad;
 } uwspr_decode;
 typedef struct uwspr_pipe_stats {
   int64_t frames, batches, candidates, decoded, resumed;   /* resumed: records whose other tries were produced */
@@ -477,7 +480,18 @@ int uwspr_pipe_collect(uwspr_pipe *pipe, uwspr_decode *out, int cap, int wait);
 int uwspr_pipe_get_stats(uwspr_pipe *pipe, uwspr_pipe_stats *st);
 /* uwspr_set_option on every lane's context (e.g. "fast_search").  Only while nothing is in flight (after
  * uwspr_pipe_flush / before the first batch): UWSPR_ERR_ARG otherwise, and for "sched", which the pipe chooses by its
- * lane count (uwspr_pipe_opts.sched_form). */
+ * lane count (uwspr_pipe_opts.sched_form).
+ * "passes" is the pipe's own option: 1 (default) or 2, anything else UWSPR_ERR_ARG.  With 2 a batch's host tail is followed
+ * by a second pass on its lane: the frames that hold a decoded record go through uwspr_subtract_batch's kernels (refine =
+ * 1) into a buffer of the lane -- one item per decoded record in candidate order: the symbols of its message
+ * (uwspr_wspr_symbols), its f1, the jig_shift of the try that decoded, its drift1 (a NONLINEAR candidate: the constant
+ * the fine search correlated with, f1 + slmFrequencyDrift at t = 0, and no drift) -- and those residual frames through FDR +
+ * schedule + Fano with the same options.  A second-pass record is emitted directly behind its frame's first-pass records,
+ * only if it decoded and its message is not one of that frame's first-pass messages (nor that of a second-pass record
+ * already emitted for the frame: a new message appears once): pass = 1, cand counting on from the
+ * frame's first-pass records, npk that of the first pass, coarse / f1 / ... what the second search found.  Frame and
+ * channel order stay; the stream is read, never written.  Stats: frames and batches as with 1; candidates and decoded
+ * count the emitted records, the Fano and resume figures include the second pass.  With 1 nothing changes. */
 int uwspr_pipe_set_option(uwspr_pipe *pipe, const char *name, int value);
 /* Error behaviour.  An argument error (too many samples, a bad B or stride) fails THAT call with UWSPR_ERR_ARG and
  * its message; the pipe goes on.  A runtime failure (HIP, a lane's context) is sticky: the batch it hit emits
@@ -647,6 +661,46 @@ int uwspr_tx_baseband_moving(uwspr_ctx *ctx, const uwspr_tx_signal *sig, const u
 int uwspr_tx_render_moving(uwspr_ctx *ctx, const uwspr_tx_signal *sig, const uwspr_tx_motion *motion, int nsig,
                            const uwspr_tx_channel *chan, int C, long long t0, long long nframes, int format, void *out,
                            int where);
+
+/* ---- known-symbol subtraction (K8, k8_subtract.hip) --------------------------------------------------------------- */
+/* A decoded transmission is rebuilt from its 162 channel symbols, fitted to the samples and taken out of them, so that a
+ * weaker one within a tone spacing of it can be found in what is left.  The reference has no counterpart; binary32 with
+ * fused multiply-adds, phases in binary64.  N = 41472, df = 375/256.  An item models symbol i at the frequency of the
+ * receiver's LINEAR hypothesis,
+ *     f_i = f_hz + (drift_hz / 2)(i - 81) / 81 + (symbols[i] - 1.5) df.
+ * Refinement (refine != 0): over the lags l = -24..24 and the offsets q = -4..4,
+ *     M(l, q) = sum_i | sum_{k < 256} x[shift + l + 256 i + k] e^{-j 2 pi (f_i + 0.0125 q) k / 375} |
+ * (samples outside [0, fl) count as 0); the first maximum in (q, l) order -- q ascending, then l -- gives shift' = shift + l,
+ * f' = f_hz + 0.0125 q (formed in binary64, rounded to the binary32 of the result record) and metric = M.  refine = 0: f' =
+ * f_hz, shift' = shift, metric = 0.  A call with refine = 0 on (f', shift') removes what the refining call removed.
+ * Cancellation, for k in [0, N) with shift' + k inside [0, fl) (nothing else is touched):
+ *     r[k] = e^{j theta(k)}, theta(k) = 2 pi sum_{u < k} f_{u div 256} / 375      (f_i with f' in the place of f_hz)
+ *     c[k] = x[shift' + k] conj r[k]                                         (0 for any other k)
+ *     a[k] = sum_m w[m] c[k + m - 511] / sum_m w[m] v[k + m - 511],   m = 0..1022
+ *     out[shift' + k] = x[shift' + k] - a[k] r[k]
+ * w being the 1023-tap Hann window 0.5 - 0.5 cos(2 pi (m + 1) / 1024) and v = 1 where c is defined, 0 elsewhere: the
+ * amplitude is a weighted mean over the samples that exist.  removed = sum |a r|^2.
+ * Items of one frame apply in list order, each refined and fitted on the residual the one before left.
+ * frames: B frames per `where` and uwspr_set_frame_stride; frames_out: contiguous [B][fl], host memory with UWSPR_HOST,
+ * device memory with UWSPR_DEVICE and UWSPR_DEVICE_FRAMES; frames without an item are copied.  frames_out == frames is
+ * allowed when the stride is 0 or fl; any other overlap of the two is refused.  items: HOST memory whatever `where` says
+ * (call records), sorted by frame, frame in [0, B), symbols <= 3, f_hz and drift_hz finite (|f| <= 1e4, |drift| <= 1e3),
+ * |shift| <= 2^20: anything else returns UWSPR_ERR_ARG before any launch, the output untouched.  res: nitems records in
+ * item order (device memory with UWSPR_DEVICE, else host), or NULL.  Host and device calls give the same bytes. */
+typedef struct uwspr_sub_item {
+  int32_t frame, shift;
+  float f_hz, drift_hz;
+  uint8_t symbols[UWSPR_NSYM];   /* 0..3 */
+  uint8_t _pad[2];
+} uwspr_sub_item;
+typedef struct uwspr_sub_result {
+  float f_hz;       /* f' */
+  int32_t shift;    /* shift' */
+  float metric;     /* M at the maximum (0 without refinement) */
+  float removed;    /* sum |a r|^2: the energy taken out */
+} uwspr_sub_result;
+int uwspr_subtract_batch(uwspr_ctx *ctx, const float *frames, int B, int where, const uwspr_sub_item *items, int nitems,
+                         int refine, float *frames_out, uwspr_sub_result *res);
 
 #ifdef __cplusplus
 }
