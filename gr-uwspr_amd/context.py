@@ -466,6 +466,28 @@ class Context:
                                               C.c_void_p(out.ctypes.data), rp))
         return out, res
 
+    # -- ordered-statistics decoding (K9: uwspr_osd_batch) -------------------
+    def osd(self, symbols, order=2):
+        """Ordered-statistics decoding of soft-symbol vectors as uwspr_demod_out.symbols[idt] holds them: [n, 162] uint8, a
+        numpy array or a torch CUDA tensor (read in place).  -> an OSD_RESULT_DTYPE array: dmin, dnext, nhard, nflip and
+        the 7 message bytes per vector (include/uwspr_hip.h states the definition)."""
+        if _is_torch(symbols):
+            import torch
+            assert symbols.is_cuda and symbols.is_contiguous() and symbols.dtype == torch.uint8
+            n = symbols.numel() // N.NSYM
+            out = torch.zeros(max(n, 1) * N.OSD_RESULT_DTYPE.itemsize, dtype=torch.uint8, device=symbols.device)
+            if self._stream_ptr is None:
+                torch.cuda.current_stream(symbols.device).synchronize()
+            self._chk(self.L.uwspr_osd_batch(self.h, C.c_void_p(symbols.data_ptr()), n, N.DEVICE, int(order),
+                                             C.c_void_p(out.data_ptr())))
+            self.synchronize()
+            return out.cpu().numpy()[:n * N.OSD_RESULT_DTYPE.itemsize].view(N.OSD_RESULT_DTYPE).copy()
+        a = np.ascontiguousarray(symbols, dtype=np.uint8).reshape(-1, N.NSYM)
+        res = np.zeros(len(a), N.OSD_RESULT_DTYPE)
+        self._chk(self.L.uwspr_osd_batch(self.h, C.c_void_p(a.ctypes.data) if len(a) else None, len(a), N.HOST, int(order),
+                                         C.c_void_p(res.ctypes.data) if len(a) else None))
+        return res
+
     # -- transmit side (K7: uwspr_tx_*) ------------------------------------
     def tx_baseband(self, signals, n=45000, t0=0, channel=0, out=None):
         """375 S/s baseband samples [t0, t0 + n) of one channel's signals (tx_signals), as c2_read returns a .c2 file:
@@ -898,7 +920,7 @@ class Pipe:
 
     def __init__(self, fs=375, fl=45000, spb=256, maxdrift=0, maxfreqs=200, halfbandwidth=10, cf=1500,
                  threshold=10, device=0, hop=3375, batch_frames=256, max_per_frame=1, lanes=0,
-                 host_threads=0, eager=False, sched=None, spare_after_us=0, passes=1):
+                 host_threads=0, eager=False, sched=None, spare_after_us=0, passes=1, osd=0, osd_gap=None):
         self.L = N.lib()
         self.h = C.c_void_p()
         self.fl = fl
@@ -913,12 +935,16 @@ class Pipe:
             self.h = None
             raise N.UwsprError(rc, msg)
         self.batch_frames, self.hop = batch_frames, hop
-        if passes != 1:   # 2: what decodes is subtracted and the residual searched again (records with pass = 1)
-            try:
+        try:
+            if passes != 1:   # 2: what decodes is subtracted and the residual searched again (records with pass = 1)
                 self.set_option("passes", passes)
-            except N.UwsprError:
-                self.close()
-                raise
+            if osd:           # 1, 2: ordered-statistics decoding of that order on what Fano timed out on (records with osd = 1)
+                self.set_option("osd", osd)
+            if osd_gap is not None:
+                self.set_option("osd_gap", osd_gap)
+        except N.UwsprError:
+            self.close()
+            raise
 
     def _chk(self, rc):
         if rc < 0:
@@ -1027,7 +1053,8 @@ def read_wav(path, channels=None):
 def decode_wav(path, channels=None, **pipe_opts):
     """Decode a 12 kS/s recording as the receiver flowgraph does (examples/AudioSourceDecode.grc): the file through a
     Pipe's push_audio -> one dict per decoded record, in frame order: frame, t (stream_pos / 375 s), the coarse freq
-    and snr, the unpacked text and "pass" (1: found by the second pass of passes=2, under a decoded signal; else 0).
+    and snr, the unpacked text, "pass" (1: found by the second pass of passes=2, under a decoded signal; else 0) and
+    "osd" (1: Fano timed out and ordered-statistics decoding gave the message, osd=1 or 2; else 0).
     channels="all": every channel of the file through one pipe, records in (take, channel, frame) order, each dict with
     its "channel"."""
     x, _ = read_wav(path, channels)
@@ -1046,7 +1073,7 @@ def decode_wav(path, channels=None, **pipe_opts):
             continue
         d = {"frame": int(r["frame"]), "t": int(r["stream_pos"]) / 375.0,
              "freq": float(r["coarse"]["freq"]), "snr": float(r["coarse"]["snr"]),
-             "text": unpack_message(r["message"])[1], "pass": int(r["pass"])}
+             "text": unpack_message(r["message"])[1], "pass": int(r["pass"]), "osd": int(r["osd"])}
         if channels == "all":
             d["channel"] = int(r["channel"])
         out.append(d)

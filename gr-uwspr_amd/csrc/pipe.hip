@@ -67,6 +67,11 @@ struct pipe_lane {
   std::vector<int> slot_frame;           // slot -> frame of the batch
   std::vector<uwspr_sub_item> items;     // the decoded records as subtraction items (frame = slot)
   std::vector<uwspr_decode> extra;       // the second pass's records, frame = index in the batch until they are merged
+  // ordered-statistics decoding (option "osd"): the records Fano gave up on, one item each
+  std::vector<uint8_t> osdf;                 // [B*per] 1: decoded by K9
+  std::vector<int> osd_rec, osd_idt;         // item -> record, try
+  std::vector<unsigned long long> osd_off;   // item -> byte offset of its symbols in d_out
+  std::vector<uwspr_osd_result> osd_res;
 };
 
 // what the host tails of a batch add to the pipe's statistics
@@ -86,6 +91,7 @@ struct uwspr_pipe {
   uwspr_pipe_opts o;
   int device = 0, fl = 0, maxfreqs = 0, per = 1;
   int passes = 1;   // uwspr_pipe_set_option("passes"): 2 = subtract what decoded and search the residual again
+  int osd = 0, osd_gap = UWSPR_OSD_GAP_DEFAULT;   // uwspr_pipe_set_option("osd" / "osd_gap"): K9 on what Fano timed out on
   char err[512];
   // Sticky status of the first RUNTIME failure (HIP, a lane's context), written by coordinators and the producer, read
   // by both without the lock.  Argument errors are not sticky: the call that made them returns UWSPR_ERR_ARG (with
@@ -156,6 +162,8 @@ static int parg(uwspr_pipe *q, const char *fmt, ...) {
 // The host tail of one search of B frames (the batch itself, first = true; or its second pass over the residual frames):
 // waits for the lane's event, runs Fano on what the GPU produced, resumes what try 0 did not decode.  Leaves L.dec /
 // L.idt / L.msg for the B * per records of L.h_out.
+static int osd_tail(uwspr_pipe *q, pipe_lane &L, int nrec, tail_acc &ta);
+
 static int host_tail(uwspr_pipe *q, pipe_lane &L, const float *frames, int B, bool first, tail_acc &ta) {
   const int per = q->per, nrec = B * per;
   double t0 = now_s();
@@ -243,6 +251,49 @@ static int host_tail(uwspr_pipe *q, pipe_lane &L, const float *frames, int B, bo
   ta.gpu_wait_s += (t1 - t0);
   ta.fano_s += (t2 - t1) + (t4 - t3);
   ta.resume_s += (t3 - t2);
+  memset(L.osdf.data(), 0, (size_t)nrec);
+  if (q->osd > 0) return osd_tail(q, L, nrec, ta);
+  return UWSPR_OK;
+}
+
+// Option "osd".  The records that were worth a try and that Fano did not decode have all 17 tries in L.d_out by now (the
+// resume, or the eager first pass).  Each with a gated try (cc:470) is one K9 item: the gated try with the largest
+// jig_sync, the first one on ties, its symbols read in place in the lane's device records.  An item whose runner-up is
+// at least osd_gap behind and whose bytes unpack makes its record a decoded one.  Its time counts as resume time.
+static int osd_tail(uwspr_pipe *q, pipe_lane &L, int nrec, tail_acc &ta) {
+  const float minsync2 = 0.12f, minrms = (float)(52.0 * (50 / 64.0));   // the gates of decode_try (host_tail.cpp)
+  const int per = q->per;
+  L.osd_rec.clear(); L.osd_idt.clear(); L.osd_off.clear();
+  for (int i = 0; i < nrec; i++) {
+    const int b = i / per, j = i - b * per;
+    if (!(j < L.h_npk[b] && j < q->maxfreqs) || !L.h_out[i].worth_a_try || L.dec[i]) continue;
+    const uwspr_demod_out &o = L.h_out[i];
+    int pick = -1;
+    for (int idt = 0; idt < UWSPR_NJIG; idt++)
+      if (o.jig_sync[idt] > minsync2 && o.jig_rms[idt] > minrms && (pick < 0 || o.jig_sync[idt] > o.jig_sync[pick])) pick = idt;
+    if (pick < 0) continue;
+    L.osd_rec.push_back(i); L.osd_idt.push_back(pick);
+    L.osd_off.push_back((unsigned long long)((const char *)&L.d_out[i].symbols[pick][0] - (const char *)L.d_out));
+  }
+  const int n = (int)L.osd_rec.size();
+  if (n == 0) return UWSPR_OK;
+  const double t0 = now_s();
+  uwspr_osd_result *d_res = nullptr;
+  const int rc = osd_run(L.ctx, (const uint8_t *)L.d_out, L.osd_off.data(), n, q->osd, nullptr, &d_res);
+  if (rc) return pfail(q, rc, "ordered-statistics decoding: %s", uwspr_last_error(L.ctx));
+  L.osd_res.resize((size_t)n);
+  PHIP(q, hipMemcpyAsync(L.osd_res.data(), d_res, (size_t)n * sizeof(uwspr_osd_result), hipMemcpyDeviceToHost, L.stream));
+  PHIP(q, hipEventRecord(L.ev_done, L.stream));
+  PHIP(q, hipEventSynchronize(L.ev_done));
+  for (int k = 0; k < n; k++) {
+    const uwspr_osd_result &r = L.osd_res[k];
+    char text[32];
+    if ((long long)r.dnext - (long long)r.dmin < (long long)q->osd_gap || uwspr_unpack_message(r.message, text, sizeof(text)) != 0) continue;
+    const int i = L.osd_rec[k];
+    L.dec[i] = 1; L.idt[i] = L.osd_idt[k]; L.osdf[i] = 1;
+    memcpy(&L.msg[7 * (size_t)i], r.message, 7);
+  }
+  ta.resume_s += now_s() - t0;
   return UWSPR_OK;
 }
 
@@ -271,6 +322,7 @@ static int finish_batch(uwspr_pipe *q, pipe_lane &L) {
         d.f1 = o.f1; d.drift1 = o.drift1; d.sync1 = o.sync1; d.shift1 = o.shift1; d.worth_a_try = o.worth_a_try;
         d.decoded = L.dec[i]; d.idt = L.idt[i];
         memcpy(d.message, &L.msg[7 * (size_t)i], 7);
+        d.osd = L.osdf[i];
         L.recs.push_back(d);
         ncand++; ndec += L.dec[i];
       }
@@ -381,6 +433,7 @@ static int second_pass(uwspr_pipe *q, pipe_lane &L, tail_acc &ta, int *ncand, in
       d.decoded = 1; d.idt = L.idt[i];
       memcpy(d.message, &L.msg[7 * (size_t)i], 7);
       d.pass = 1;
+      d.osd = L.osdf[i];
       merged.push_back(d);
       (*ncand)++; (*ndec)++;
     }
@@ -598,6 +651,7 @@ extern "C" int uwspr_pipe_open(const uwspr_params *p, int device, const uwspr_pi
     // the coordinator sleeps on this event (it does not spin: the cores belong to the Fano pool)
     PHIP(q, hipEventCreateWithFlags(&L.ev_done, hipEventDisableTiming | hipEventBlockingSync));
     L.dec.resize((size_t)Bm * per); L.idt.resize((size_t)Bm * per); L.msg.resize((size_t)Bm * per * 7);
+    L.osdf.resize((size_t)Bm * per);
   }
   // pushed streams: the device ring and the page-locked staging buffers are made by the first acquire (open_ingest):
   // a pipe that only takes device frames (uwspr_pipe_submit_device) never pays their 2 x 83 MB of HBM + 4 x 6.9 MB page-locked (hop 3375; 2.2 GB + 0.37 GB at hop 0 = the frame length)
@@ -772,6 +826,16 @@ extern "C" int uwspr_pipe_set_option(uwspr_pipe *q, const char *name, int value)
     for (auto &L : q->lanes)
       if (L.busy) { snprintf(q->err, sizeof(q->err), "uwspr_pipe_set_option(passes): batches in flight (flush first)"); return UWSPR_ERR_ARG; }
     q->passes = value;
+    return UWSPR_OK;
+  }
+  if (!strcmp(name, "osd") || !strcmp(name, "osd_gap")) {   // the pipe's own: K9 on the records Fano gave up on
+    const bool gap = name[3] != 0;
+    if (gap ? value < 0 : (value < 0 || value > 2))
+      return parg(q, gap ? "uwspr_pipe_set_option: \"osd_gap\" is >= 0, not %d" : "uwspr_pipe_set_option: \"osd\" is 0, 1 or 2, not %d", value);
+    std::lock_guard<std::mutex> lk(q->m);
+    for (auto &L : q->lanes)
+      if (L.busy) { snprintf(q->err, sizeof(q->err), "uwspr_pipe_set_option(%s): batches in flight (flush first)", name); return UWSPR_ERR_ARG; }
+    (gap ? q->osd_gap : q->osd) = value;
     return UWSPR_OK;
   }
   // checked AND applied under q->m: a lane is marked busy under the same lock when a batch is launched on it, so no

@@ -139,6 +139,8 @@ struct tx_state;
 void tx_release(uwspr_ctx *c);   // k7_transmit.hip: frees what the uwspr_tx_* calls made
 struct sub_state;
 void sub_release(uwspr_ctx *c);  // k8_subtract.hip: frees what uwspr_subtract_batch / the pipe's second pass made
+struct osd_state;
+void osd_release(uwspr_ctx *c);  // k9_osd.hip: frees what uwspr_osd_batch / the pipe's option "osd" made
 
 }  // namespace uwspr
 
@@ -228,6 +230,8 @@ struct uwspr_ctx {
   uwspr::tx_state *tx;
   // subtraction (k8_subtract.hip): window tables and call scratch, made by the first use
   uwspr::sub_state *sub;
+  // ordered-statistics decoding (k9_osd.hip): the generator / de-interleave table and call scratch, made by the first use
+  uwspr::osd_state *osd;
 
   int prof_mask;
   std::vector<uwspr::ev_pair> prof_events;
@@ -244,6 +248,12 @@ int api_frames_on_device(uwspr_ctx *c, const float *frames, int B, int where, co
 int subtract_check(uwspr_ctx *c, const uwspr_sub_item *items, int nitems, int nframes);
 int subtract_run(uwspr_ctx *c, const float *src, size_t stride, int nslots, const int *slot_frame, const uwspr_sub_item *items,
                  int nitems, int refine, float *dst);
+
+// K9 (k9_osd.hip): n items on the context's stream, item i = the 162 interleaved soft symbols at base + off[i] (off: host
+// array, null = 162 i; base: device memory); results to res (device memory), or with res null to a buffer of the context
+// handed back through *res_out.  order 0..2 (the caller checks it).
+int osd_run(uwspr_ctx *c, const uint8_t *base, const unsigned long long *off, int n, int order, uwspr_osd_result *res,
+            uwspr_osd_result **res_out);
 
 // ---- launchers (each enqueues on ctx->stream) ------------------------------
 int frontend_design(int mode, int stage, std::vector<double> &out, int *delay);

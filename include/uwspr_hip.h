@@ -40,7 +40,9 @@ extern "C" {
                                     uwspr_nhash, uwspr_wspr_symbols, uwspr_c2_write, uwspr_tx_baseband, uwspr_tx_render;
                                     moving sources: uwspr_tx_motion, uwspr_tx_baseband_moving, uwspr_tx_render_moving;
                                     known-symbol subtraction: uwspr_sub_item, uwspr_sub_result, uwspr_subtract_batch, the pipe
-                                    option "passes", uwspr_decode.pass (carved out of the padding as well) */
+                                    option "passes", uwspr_decode.pass (carved out of the padding as well);
+                                    ordered-statistics decoding: uwspr_osd_result, uwspr_osd_batch, the pipe options "osd" and
+                                    "osd_gap", uwspr_decode.osd (the last byte of the padding) */
 
 typedef enum {
   UWSPR_OK = 0,
@@ -431,7 +433,7 @@ typedef struct uwspr_decode {
   uint8_t _pad0;
   int16_t channel;        /* the audio channel of a multichannel pipe (uwspr_pipe_push_audio_channels); 0 otherwise */
   uint8_t pass;           /* 1: found by the second pass (option "passes" = 2), in the frame with its decoded signals taken out; 0 otherwise */
-  uint8_t _pad;
+  uint8_t osd;            /* 1: Fano timed out on every gated try and ordered-statistics decoding gave the message (option "osd"); 0 otherwise */
 } uwspr_decode;
 typedef struct uwspr_pipe_stats {
   int64_t frames, batches, candidates, decoded, resumed;   /* resumed: records whose other tries were produced */
@@ -491,7 +493,15 @@ int uwspr_pipe_get_stats(uwspr_pipe *pipe, uwspr_pipe_stats *st);
  * already emitted for the frame: a new message appears once): pass = 1, cand counting on from the
  * frame's first-pass records, npk that of the first pass, coarse / f1 / ... what the second search found.  Frame and
  * channel order stay; the stream is read, never written.  Stats: frames and batches as with 1; candidates and decoded
- * count the emitted records, the Fano and resume figures include the second pass.  With 1 nothing changes. */
+ * count the emitted records, the Fano and resume figures include the second pass.  With 1 nothing changes.
+ * "osd" and "osd_gap" are the pipe's own as well.  "osd" = 0 (default), 1 or 2 (anything else UWSPR_ERR_ARG): with 1 or 2, K9
+ * (uwspr_osd_batch below, that order) runs on the batch's lane behind its host tail, resumed tries included -- and behind
+ * the second pass's host tail with "passes" = 2 -- for every record with worth_a_try in which at least one try passed the
+ * gates of cc:470 and none decoded: one item per such record, the gated try with the largest jig_sync (the first one on
+ * ties), its symbols read where they lie in the lane's device records.  An item with dnext - dmin >= "osd_gap" (>= 0;
+ * default UWSPR_OSD_GAP_DEFAULT) whose bytes uwspr_unpack_message accepts turns the record into a decoded one: decoded = 1,
+ * idt = that try, message set, osd = 1.  It is an ordinary decoded record from there on: counted in the stats' decoded,
+ * subtracted by "passes" = 2.  With "osd" = 0 every byte and statistic is what it is without the option. */
 int uwspr_pipe_set_option(uwspr_pipe *pipe, const char *name, int value);
 /* Error behaviour.  An argument error (too many samples, a bad B or stride) fails THAT call with UWSPR_ERR_ARG and
  * its message; the pipe goes on.  A runtime failure (HIP, a lane's context) is sticky: the batch it hit emits
@@ -701,6 +711,36 @@ typedef struct uwspr_sub_result {
 } uwspr_sub_result;
 int uwspr_subtract_batch(uwspr_ctx *ctx, const float *frames, int B, int where, const uwspr_sub_item *items, int nitems,
                          int refine, float *frames_out, uwspr_sub_result *res);
+
+/* ---- ordered-statistics decoding (K9, k9_osd.hip) -------------------------------------------------------------------- */
+/* What a try that Fano timed out on can still give: the transmission as the (162, 50) linear block code it is.  The
+ * reference has no counterpart (every WSPR decoder in use has this fall-back); all integers, so host, device and the test's
+ * restatement give the same bytes.
+ * Input: one 162-byte soft-symbol vector as uwspr_demod_out.symbols[idt] holds it (interleaved).  With s[i] the byte at
+ * de-interleaved position i (uwspr_deinterleave's table): hard bit h[i] = s[i] >= 128, reliability r[i] = |2 s[i] - 255|
+ * (odd, 1..255).  G (50 x 162 over GF(2)): row j = uwspr_fano_encode of the 81-bit input with only bit j set.
+ *   1. The positions are ordered by r descending, ties by ascending index.
+ *   2. Gauss-Jordan elimination walks the columns of G in that order: the pivot of a column is the first not-yet-pivoted row
+ *      with a 1; a column with no such row is skipped; at rank 50 it stops, the pivot columns being the information set.  A
+ *      50 x 50 identity is carried alongside, so that message bits can be read back.
+ *   3. The order-0 codeword c0 is the reduced rows combined by the hard bits at the 50 pivot positions.
+ *   4. Candidates: c0 with every set of at most `order` pivot bits flipped (1, 51, 1276 candidates at order 0, 1, 2).
+ *   5. D(c) = sum of r[i] over the positions where c[i] != h[i].
+ *   6. The winner has the least D; ties go to fewer flips, then to the lexicographically smaller flip set in pivot order.
+ *   7. dmin = its D; dnext = the least D among the other candidates (INT32_MAX at order 0); nflip; nhard = the positions
+ *      where it differs from h; message = its 50 message bits packed as uwspr_fano_decode fills data[0..6].
+ *   8. Accepted (the pipe's rule, not this call's) means dnext - dmin >= gap and uwspr_unpack_message accepts the bytes.
+ * UWSPR_OSD_GAP_DEFAULT: profiles/osd.txt says where the number comes from.
+ * symbols [n][162], res [n]: host memory (UWSPR_HOST, complete on return) or device memory (UWSPR_DEVICE, asynchronous on
+ * the context's stream; both must lie inside device allocations of the context's device, else UWSPR_ERR_ARG before any
+ * launch).  order 0..2, anything else UWSPR_ERR_ARG; n = 0 is fine. */
+#define UWSPR_OSD_GAP_DEFAULT 485
+typedef struct uwspr_osd_result {
+  int32_t dmin, dnext, nhard;
+  uint8_t nflip;
+  int8_t message[7];
+} uwspr_osd_result;
+int uwspr_osd_batch(uwspr_ctx *ctx, const uint8_t *symbols /*[n][162]*/, int n, int where, int order, uwspr_osd_result *res);
 
 #ifdef __cplusplus
 }

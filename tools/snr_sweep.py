@@ -4,7 +4,7 @@ committed as tests/golden/150613_1920_int16.npz) + AWGN over an SNR sweep, decod
 to end: K0 front-end -> FDR -> S0..S5 schedule (GPU) -> deinterleave + Fano + unpack
 (host), beside the CPU path (oracle kernels + the same host tail) on the same frames.
 
-usage: snr_sweep.py [seeds_per_snr] [--json out.json]      (bench.py calls run() for its configs4_n1 key)
+usage: snr_sweep.py [seeds_per_snr] [--json out.json] [--osd 1|2]      (bench.py calls run() for its configs4_n1 key)
 Prints one row per SNR: decode rate of `VE3EMB FN42 33`, GPU and CPU decode sets equal?,
 GPU and CPU seconds.  SNR is referred to 2500 Hz like WSPR reports; the recording's own
 SNR is estimated from its 375 S/s spectrum and noise is added up to the target.
@@ -61,12 +61,16 @@ def cpu_decode(fdr, frame):
     return texts
 
 
-def run(seeds=8, cpu_seeds=None, quiet=False, rank=0, world=1):
+def run(seeds=8, cpu_seeds=None, quiet=False, rank=0, world=1, osd=0):
     """The sweep; the CPU leg (and the GPU == CPU comparison) covers the first cpu_seeds frames of every SNR.
     rank / world (bench.py --gpus N): the `seeds` noisy copies of every SNR are sharded round-robin like the frames of the
     search path (copy s on rank s mod world, its noise a function of s: the union over the ranks is the one-rank sweep);
     this rank's rows count ITS copies, the caller adds them up; host threads = this rank's share of the host
-    (uwspr_host_set_ranks)."""
+    (uwspr_host_set_ranks).
+    osd = 1, 2 (--osd): on the same noisy copies, the records Fano decoded on no try also go through ordered-statistics
+    decoding of that order under the pipe's rules (the gated try with the largest jig_sync, the default gap, the bytes must
+    unpack); every row gains osd_decoded / osd_other_decodes: the frames with the message and the other texts, Fano's included.
+    With osd = 0 rows and output are what they were."""
     mine = list(range(rank, seeds, world))
     cpu_seeds = len(mine) if cpu_seeds is None else min(cpu_seeds, len(mine))
     say = (lambda *a: None) if quiet else print
@@ -115,6 +119,22 @@ def run(seeds=8, cpu_seeds=None, quiet=False, rank=0, world=1):
             gpu_texts.append([G.unpack_message(msg[b * PER + j])[1] for j in range(min(PER, len(cands[b])))
                               if okv[b * PER + j]])
         tg = time.time() - t0
+        osd_texts = [list(t) for t in gpu_texts]
+        if osd:
+            flat = out.reshape(-1)
+            items = []
+            for b in range(seeds_l):
+                for j in range(min(PER, len(cands[b]))):
+                    r = flat[b * PER + j]
+                    g = [t for t in range(17) if r["jig_sync"][t] > np.float32(0.12) and r["jig_rms"][t] > np.float32(52.0 * (50 / 64.0))]
+                    if r["worth_a_try"] and not okv[b * PER + j] and g:
+                        items.append((b, r["symbols"][max(g, key=lambda t: (r["jig_sync"][t], -t))]))
+            if items:
+                res = ctx.osd(np.stack([v for _, v in items]), order=osd)
+                for (b, _), q in zip(items, res):
+                    rc, text = G.unpack_message(q["message"])
+                    if int(q["dnext"]) - int(q["dmin"]) >= G.native.OSD_GAP_DEFAULT and rc == 0:
+                        osd_texts[b].append(text)
         # lazy flow: uwspr_set_tries(1) -> Fano on try 0 -> uwspr_demod_resume for what did not decode
         t0 = time.time()
         frames_l = lazy.frontend(audio)
@@ -147,6 +167,10 @@ def run(seeds=8, cpu_seeds=None, quiet=False, rank=0, world=1):
                      "records": int((out_l["worth_a_try"] != 0).sum()), "cpu_s": tc, "cpu_frames": cpu_seeds,
                      "cpu_threads": nw, "gpu_frames_per_s": seeds_l / tg, "gpu_lazy_frames_per_s": seeds_l / tl,
                      "cpu_frames_per_s": cpu_seeds / tc})
+        if osd:
+            rows[-1]["osd_decoded"] = sum(WANT in t for t in osd_texts)
+            rows[-1]["osd_other_decodes"] = sum(len([u for u in t if u != WANT]) for t in osd_texts)
+            say("SNR %5.1f dB, osd=%d: %2d/%d decoded, %d other decodes" % (snr, osd, rows[-1]["osd_decoded"], seeds_l, rows[-1]["osd_other_decodes"]))
         say("SNR %5.1f dB: %2d/%d decoded, %d other decodes, GPU==lazy==CPU %s, GPU %.1f ms eager / %.1f ms lazy "
               "(%d of %d records resumed) (host audio in, front-end + search + Fano), CPU %.1f ms on %d threads "
               "(search + Fano, no front-end)"
@@ -160,7 +184,7 @@ def run(seeds=8, cpu_seeds=None, quiet=False, rank=0, world=1):
 def main():
     seeds = int(sys.argv[1]) if len(sys.argv) > 1 and not sys.argv[1].startswith("-") else 8
     jpath = sys.argv[sys.argv.index("--json") + 1] if "--json" in sys.argv else None
-    res = run(seeds)
+    res = run(seeds, osd=int(sys.argv[sys.argv.index("--osd") + 1]) if "--osd" in sys.argv else 0)
     if jpath:
         json.dump(res, open(jpath, "w"), indent=1)
     print("mismatches:", sum(not r["gpu_equals_cpu"] for r in res["rows"]))
