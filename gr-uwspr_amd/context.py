@@ -488,6 +488,25 @@ class Context:
                                          C.c_void_p(res.ctypes.data) if len(a) else None))
         return res
 
+    # -- block demodulation (K10: uwspr_blockdemod_batch) ---------------------
+    def blockdemod(self, frames, items):
+        """Soft symbols coherent over 1, 2 and 3 symbols.  items: a BLOCK_ITEM_DTYPE array, or dicts with "frame", "shift",
+        "f" (Hz) and "drift" (Hz, 0), sorted by frame; frames: numpy, a torch CUDA tensor or a FrameView.  -> numpy
+        [n, 3, 162] uint8: per item the vectors of block length 1, 2, 3, each as uwspr_demod_out.symbols[idt] holds one
+        (include/uwspr_hip.h states the definition)."""
+        it = block_items(items)
+        p, B, where, keep = self._frames(frames)
+        ip = C.c_void_p(it.ctypes.data) if len(it) else None
+        if where == N.DEVICE:   # device frames: the bytes are written to device memory and copied back
+            import torch
+            dev = torch.zeros(max(3 * N.NSYM * len(it), 1), dtype=torch.uint8, device=frames.device)
+            torch.cuda.current_stream(dev.device).synchronize()
+            self._chk(self.L.uwspr_blockdemod_batch(self.h, p, B, N.DEVICE_FRAMES, ip, len(it), C.c_void_p(dev.data_ptr())))
+            return dev.cpu().numpy()[:3 * N.NSYM * len(it)].reshape(len(it), 3, N.NSYM).copy()
+        out = np.zeros((len(it), 3, N.NSYM), np.uint8)
+        self._chk(self.L.uwspr_blockdemod_batch(self.h, p, B, N.HOST, ip, len(it), C.c_void_p(out.ctypes.data) if len(it) else None))
+        return out
+
     # -- transmit side (K7: uwspr_tx_*) ------------------------------------
     def tx_baseband(self, signals, n=45000, t0=0, channel=0, out=None):
         """375 S/s baseband samples [t0, t0 + n) of one channel's signals (tx_signals), as c2_read returns a .c2 file:
@@ -791,6 +810,20 @@ def sub_items(items):
     return arr
 
 
+def block_items(items):
+    """Block-demodulation items (Context.blockdemod) -> a BLOCK_ITEM_DTYPE array; arrays of that dtype pass through."""
+    if isinstance(items, np.ndarray) and items.dtype == N.BLOCK_ITEM_DTYPE:
+        return np.ascontiguousarray(items)
+    items = list(items)
+    arr = np.zeros(len(items), N.BLOCK_ITEM_DTYPE)
+    for i, s in enumerate(items):
+        arr[i]["frame"] = int(s["frame"])
+        arr[i]["shift"] = int(s["shift"])
+        arr[i]["f_hz"] = float(s["f"])
+        arr[i]["drift_hz"] = float(s.get("drift", 0.0))
+    return arr
+
+
 def tx_signals(signals):
     """A list of transmissions -> the uwspr_tx_signal array.  Each is a dict: "text" (or "message": 7 bytes, or
     "symbols": 162), "channel" (0), "start" (baseband sample of the first symbol, 375), "f0" (Hz, 0), "drift" (Hz over the
@@ -920,7 +953,8 @@ class Pipe:
 
     def __init__(self, fs=375, fl=45000, spb=256, maxdrift=0, maxfreqs=200, halfbandwidth=10, cf=1500,
                  threshold=10, device=0, hop=3375, batch_frames=256, max_per_frame=1, lanes=0,
-                 host_threads=0, eager=False, sched=None, spare_after_us=0, passes=1, osd=0, osd_gap=None):
+                 host_threads=0, eager=False, sched=None, spare_after_us=0, passes=1, osd=0, osd_gap=None,
+                 block=0):
         self.L = N.lib()
         self.h = C.c_void_p()
         self.fl = fl
@@ -942,6 +976,8 @@ class Pipe:
                 self.set_option("osd", osd)
             if osd_gap is not None:
                 self.set_option("osd_gap", osd_gap)
+            if block:         # 2, 3: block demodulation up to that length on what Fano timed out on (records with block = 2, 3)
+                self.set_option("block", block)
         except N.UwsprError:
             self.close()
             raise
@@ -1054,7 +1090,8 @@ def decode_wav(path, channels=None, **pipe_opts):
     """Decode a 12 kS/s recording as the receiver flowgraph does (examples/AudioSourceDecode.grc): the file through a
     Pipe's push_audio -> one dict per decoded record, in frame order: frame, t (stream_pos / 375 s), the coarse freq
     and snr, the unpacked text, "pass" (1: found by the second pass of passes=2, under a decoded signal; else 0) and
-    "osd" (1: Fano timed out and ordered-statistics decoding gave the message, osd=1 or 2; else 0).
+    "osd" (1: Fano timed out and ordered-statistics decoding gave the message, osd=1 or 2; else 0) and "block" (2, 3: Fano
+    timed out and the soft symbols coherent over that many symbols decoded, block=2 or 3; else 0).
     channels="all": every channel of the file through one pipe, records in (take, channel, frame) order, each dict with
     its "channel"."""
     x, _ = read_wav(path, channels)
@@ -1073,7 +1110,8 @@ def decode_wav(path, channels=None, **pipe_opts):
             continue
         d = {"frame": int(r["frame"]), "t": int(r["stream_pos"]) / 375.0,
              "freq": float(r["coarse"]["freq"]), "snr": float(r["coarse"]["snr"]),
-             "text": unpack_message(r["message"])[1], "pass": int(r["pass"]), "osd": int(r["osd"])}
+             "text": unpack_message(r["message"])[1], "pass": int(r["pass"]), "osd": int(r["osd"]),
+             "block": int(r["block"])}
         if channels == "all":
             d["channel"] = int(r["channel"])
         out.append(d)

@@ -72,6 +72,13 @@ struct pipe_lane {
   std::vector<int> osd_rec, osd_idt;         // item -> record, try
   std::vector<unsigned long long> osd_off;   // item -> byte offset of its symbols in d_out
   std::vector<uwspr_osd_result> osd_res;
+  // block demodulation (option "block"): the same records, one K10 item each
+  std::vector<uint8_t> blkf;                 // [B*per] 2, 3: decoded from the soft symbols of that block length
+  std::vector<int> blk_rec, blk_idt;         // item -> record, try
+  std::vector<uwspr_block_item> blk_items;
+  std::vector<uint8_t> blk_sym;              // [items][3][162]
+  std::vector<uint8_t> blk_n;                // item -> the block length that decoded (0: none)
+  std::vector<int8_t> blk_msg;               // [items][7]
 };
 
 // what the host tails of a batch add to the pipe's statistics
@@ -92,6 +99,7 @@ struct uwspr_pipe {
   int device = 0, fl = 0, maxfreqs = 0, per = 1;
   int passes = 1;   // uwspr_pipe_set_option("passes"): 2 = subtract what decoded and search the residual again
   int osd = 0, osd_gap = UWSPR_OSD_GAP_DEFAULT;   // uwspr_pipe_set_option("osd" / "osd_gap"): K9 on what Fano timed out on
+  int block = 0;    // uwspr_pipe_set_option("block"): 2, 3 = K10's soft symbols of block lengths 2 .. block for those records
   char err[512];
   // Sticky status of the first RUNTIME failure (HIP, a lane's context), written by coordinators and the producer, read
   // by both without the lock.  Argument errors are not sticky: the call that made them returns UWSPR_ERR_ARG (with
@@ -163,6 +171,7 @@ static int parg(uwspr_pipe *q, const char *fmt, ...) {
 // waits for the lane's event, runs Fano on what the GPU produced, resumes what try 0 did not decode.  Leaves L.dec /
 // L.idt / L.msg for the B * per records of L.h_out.
 static int osd_tail(uwspr_pipe *q, pipe_lane &L, int nrec, tail_acc &ta);
+static int block_tail(uwspr_pipe *q, pipe_lane &L, const float *frames, int nrec, tail_acc &ta);
 
 static int host_tail(uwspr_pipe *q, pipe_lane &L, const float *frames, int B, bool first, tail_acc &ta) {
   const int per = q->per, nrec = B * per;
@@ -252,8 +261,24 @@ static int host_tail(uwspr_pipe *q, pipe_lane &L, const float *frames, int B, bo
   ta.fano_s += (t2 - t1) + (t4 - t3);
   ta.resume_s += (t3 - t2);
   memset(L.osdf.data(), 0, (size_t)nrec);
+  memset(L.blkf.data(), 0, (size_t)nrec);
+  if (q->block > 0)
+    if (const int rc = block_tail(q, L, frames, nrec, ta)) return rc;
   if (q->osd > 0) return osd_tail(q, L, nrec, ta);
   return UWSPR_OK;
+}
+
+// The item rule of the options "block" and "osd": record i is an item when it was worth a try, no try decoded and at least
+// one try passed the gates of cc:470; its try is the gated one with the largest jig_sync, the first one on ties (-1: no item).
+static int fallback_try(const uwspr_pipe *q, const pipe_lane &L, int i) {
+  const float minsync2 = 0.12f, minrms = (float)(52.0 * (50 / 64.0));   // the gates of decode_try (host_tail.cpp)
+  const int per = q->per, b = i / per, j = i - b * per;
+  if (!(j < L.h_npk[b] && j < q->maxfreqs) || !L.h_out[i].worth_a_try || L.dec[i]) return -1;
+  const uwspr_demod_out &o = L.h_out[i];
+  int pick = -1;
+  for (int idt = 0; idt < UWSPR_NJIG; idt++)
+    if (o.jig_sync[idt] > minsync2 && o.jig_rms[idt] > minrms && (pick < 0 || o.jig_sync[idt] > o.jig_sync[pick])) pick = idt;
+  return pick;
 }
 
 // Option "osd".  The records that were worth a try and that Fano did not decode have all 17 tries in L.d_out by now (the
@@ -261,16 +286,9 @@ static int host_tail(uwspr_pipe *q, pipe_lane &L, const float *frames, int B, bo
 // jig_sync, the first one on ties, its symbols read in place in the lane's device records.  An item whose runner-up is
 // at least osd_gap behind and whose bytes unpack makes its record a decoded one.  Its time counts as resume time.
 static int osd_tail(uwspr_pipe *q, pipe_lane &L, int nrec, tail_acc &ta) {
-  const float minsync2 = 0.12f, minrms = (float)(52.0 * (50 / 64.0));   // the gates of decode_try (host_tail.cpp)
-  const int per = q->per;
   L.osd_rec.clear(); L.osd_idt.clear(); L.osd_off.clear();
   for (int i = 0; i < nrec; i++) {
-    const int b = i / per, j = i - b * per;
-    if (!(j < L.h_npk[b] && j < q->maxfreqs) || !L.h_out[i].worth_a_try || L.dec[i]) continue;
-    const uwspr_demod_out &o = L.h_out[i];
-    int pick = -1;
-    for (int idt = 0; idt < UWSPR_NJIG; idt++)
-      if (o.jig_sync[idt] > minsync2 && o.jig_rms[idt] > minrms && (pick < 0 || o.jig_sync[idt] > o.jig_sync[pick])) pick = idt;
+    const int pick = fallback_try(q, L, i);
     if (pick < 0) continue;
     L.osd_rec.push_back(i); L.osd_idt.push_back(pick);
     L.osd_off.push_back((unsigned long long)((const char *)&L.d_out[i].symbols[pick][0] - (const char *)L.d_out));
@@ -293,6 +311,77 @@ static int osd_tail(uwspr_pipe *q, pipe_lane &L, int nrec, tail_acc &ta) {
     L.dec[i] = 1; L.idt[i] = L.osd_idt[k]; L.osdf[i] = 1;
     memcpy(&L.msg[7 * (size_t)i], r.message, 7);
   }
+  ta.resume_s += now_s() - t0;
+  return UWSPR_OK;
+}
+
+static float slm_at_zero(const uwspr_candidate &c, float cf);
+
+// Option "block".  The items are osd_tail's (fallback_try); K10 makes each one's soft symbols for the block lengths 1, 2, 3
+// from the frames the search itself read, at the try's jig_shift and the frequency model the fine search correlated with
+// (second_pass's).  On the host pool, per item: for n = 2 .. block, a vector above the rms gate of cc:470 goes through
+// Fano; the first that decodes to bytes that unpack makes the record a decoded one.  Its time counts as resume time.
+static int block_tail(uwspr_pipe *q, pipe_lane &L, const float *frames, int nrec, tail_acc &ta) {
+  const int per = q->per;
+  L.blk_rec.clear(); L.blk_idt.clear(); L.blk_items.clear();
+  for (int i = 0; i < nrec; i++) {
+    const int pick = fallback_try(q, L, i);
+    if (pick < 0) continue;
+    const uwspr_demod_out &o = L.h_out[i];
+    const uwspr_candidate &cd = L.h_cands[i];   // [B][per], as h_out
+    uwspr_block_item it;
+    it.frame = i / per;
+    it.shift = o.jig_shift[pick];
+    if (cd.m_type == UWSPR_NONLINEAR) { it.f_hz = o.f1 + slm_at_zero(cd, (float)q->p.cf); it.drift_hz = 0.0f; }
+    else { it.f_hz = o.f1; it.drift_hz = o.drift1; }
+    L.blk_rec.push_back(i); L.blk_idt.push_back(pick); L.blk_items.push_back(it);
+  }
+  const int n = (int)L.blk_rec.size();
+  if (n == 0) return UWSPR_OK;
+  const double t0 = now_s();
+  uint8_t *d_sym = nullptr;
+  int rc = blockdemod_check(L.ctx, L.blk_items.data(), n, (nrec + per - 1) / per);
+  if (!rc) rc = blockdemod_run(L.ctx, frames, (size_t)L.ctx->fstride, L.blk_items.data(), n, nullptr, &d_sym);
+  if (rc) return pfail(q, rc, "block demodulation: %s", uwspr_last_error(L.ctx));
+  L.blk_sym.resize((size_t)n * 3 * UWSPR_NSYM);
+  PHIP(q, hipMemcpyAsync(L.blk_sym.data(), d_sym, L.blk_sym.size(), hipMemcpyDeviceToHost, L.stream));
+  PHIP(q, hipEventRecord(L.ev_done, L.stream));
+  PHIP(q, hipEventSynchronize(L.ev_done));
+  L.blk_n.assign((size_t)n, 0);
+  L.blk_msg.assign((size_t)n * 7, 0);
+  std::atomic<long long> calls(0), fails(0);
+  const int nmax = q->block;
+  auto one = [&](int k) {
+    const float minrms = (float)(52.0 * (50 / 64.0));
+    for (int nb = 2; nb <= nmax; nb++) {
+      uint8_t sym[UWSPR_NSYM], data[11];
+      memcpy(sym, &L.blk_sym[((size_t)k * 3 + (nb - 1)) * UWSPR_NSYM], UWSPR_NSYM);
+      float sq = 0.0f;   // cc:469-474
+      for (int i = 0; i < UWSPR_NSYM; i++) { const float y = (float)((double)(float)sym[i] - 128.0); sq += y * y; }
+      if (!((float)sqrt((double)sq / 162.0) > minrms)) continue;
+      uwspr_deinterleave(sym);
+      memset(data, 0, sizeof(data));
+      uint32_t metric, cycles, maxnp;
+      calls.fetch_add(1, std::memory_order_relaxed);
+      if (uwspr_fano_decode(sym, data, &metric, &cycles, &maxnp, 60, 10000) != 0) { fails.fetch_add(1, std::memory_order_relaxed); continue; }
+      int8_t msg[7];
+      char text[32];
+      for (int i = 0; i < 7; i++) msg[i] = (int8_t)data[i];
+      if (uwspr_unpack_message(msg, text, sizeof(text)) != 0) continue;
+      L.blk_n[k] = (uint8_t)nb;
+      memcpy(&L.blk_msg[7 * (size_t)k], msg, 7);
+      return;
+    }
+  };
+  if (n <= 2) for (int k = 0; k < n; k++) one(k);
+  else q->pool->run(n, q->o.host_threads, one);
+  for (int k = 0; k < n; k++) {
+    if (!L.blk_n[k]) continue;
+    const int i = L.blk_rec[k];
+    L.dec[i] = 1; L.idt[i] = L.blk_idt[k]; L.blkf[i] = L.blk_n[k];
+    memcpy(&L.msg[7 * (size_t)i], &L.blk_msg[7 * (size_t)k], 7);
+  }
+  ta.calls += calls.load(); ta.fails += fails.load();
   ta.resume_s += now_s() - t0;
   return UWSPR_OK;
 }
@@ -323,6 +412,7 @@ static int finish_batch(uwspr_pipe *q, pipe_lane &L) {
         d.decoded = L.dec[i]; d.idt = L.idt[i];
         memcpy(d.message, &L.msg[7 * (size_t)i], 7);
         d.osd = L.osdf[i];
+        d.block = L.blkf[i];
         L.recs.push_back(d);
         ncand++; ndec += L.dec[i];
       }
@@ -434,6 +524,7 @@ static int second_pass(uwspr_pipe *q, pipe_lane &L, tail_acc &ta, int *ncand, in
       memcpy(d.message, &L.msg[7 * (size_t)i], 7);
       d.pass = 1;
       d.osd = L.osdf[i];
+      d.block = L.blkf[i];
       merged.push_back(d);
       (*ncand)++; (*ndec)++;
     }
@@ -652,6 +743,7 @@ extern "C" int uwspr_pipe_open(const uwspr_params *p, int device, const uwspr_pi
     PHIP(q, hipEventCreateWithFlags(&L.ev_done, hipEventDisableTiming | hipEventBlockingSync));
     L.dec.resize((size_t)Bm * per); L.idt.resize((size_t)Bm * per); L.msg.resize((size_t)Bm * per * 7);
     L.osdf.resize((size_t)Bm * per);
+    L.blkf.resize((size_t)Bm * per);
   }
   // pushed streams: the device ring and the page-locked staging buffers are made by the first acquire (open_ingest):
   // a pipe that only takes device frames (uwspr_pipe_submit_device) never pays their 2 x 83 MB of HBM + 4 x 6.9 MB page-locked (hop 3375; 2.2 GB + 0.37 GB at hop 0 = the frame length)
@@ -836,6 +928,14 @@ extern "C" int uwspr_pipe_set_option(uwspr_pipe *q, const char *name, int value)
     for (auto &L : q->lanes)
       if (L.busy) { snprintf(q->err, sizeof(q->err), "uwspr_pipe_set_option(%s): batches in flight (flush first)", name); return UWSPR_ERR_ARG; }
     (gap ? q->osd_gap : q->osd) = value;
+    return UWSPR_OK;
+  }
+  if (!strcmp(name, "block")) {   // the pipe's own: K10's block soft symbols for the records Fano gave up on
+    if (value != 0 && value != 2 && value != 3) return parg(q, "uwspr_pipe_set_option: \"block\" is 0, 2 or 3, not %d", value);
+    std::lock_guard<std::mutex> lk(q->m);
+    for (auto &L : q->lanes)
+      if (L.busy) { snprintf(q->err, sizeof(q->err), "uwspr_pipe_set_option(block): batches in flight (flush first)"); return UWSPR_ERR_ARG; }
+    q->block = value;
     return UWSPR_OK;
   }
   // checked AND applied under q->m: a lane is marked busy under the same lock when a batch is launched on it, so no

@@ -141,6 +141,8 @@ struct sub_state;
 void sub_release(uwspr_ctx *c);  // k8_subtract.hip: frees what uwspr_subtract_batch / the pipe's second pass made
 struct osd_state;
 void osd_release(uwspr_ctx *c);  // k9_osd.hip: frees what uwspr_osd_batch / the pipe's option "osd" made
+struct blk_state;
+void blk_release(uwspr_ctx *c);  // k10_blockdemod.hip: frees what uwspr_blockdemod_batch / the pipe's option "block" made
 
 }  // namespace uwspr
 
@@ -232,6 +234,8 @@ struct uwspr_ctx {
   uwspr::sub_state *sub;
   // ordered-statistics decoding (k9_osd.hip): the generator / de-interleave table and call scratch, made by the first use
   uwspr::osd_state *osd;
+  // block demodulation (k10_blockdemod.hip): call scratch, made by the first use
+  uwspr::blk_state *blk;
 
   int prof_mask;
   std::vector<uwspr::ev_pair> prof_events;
@@ -254,6 +258,14 @@ int subtract_run(uwspr_ctx *c, const float *src, size_t stride, int nslots, cons
 // handed back through *res_out.  order 0..2 (the caller checks it).
 int osd_run(uwspr_ctx *c, const uint8_t *base, const unsigned long long *off, int n, int order, uwspr_osd_result *res,
             uwspr_osd_result **res_out);
+
+// K10 (k10_blockdemod.hip): nitems > 0 items (host records that passed blockdemod_check against the frames of src: sorted by
+// frame, frames in [0, nframes), finite f / drift, bounded shift) on the context's stream; src: device frames, frame b at
+// src + 2 stride b floats; the [nitems][3][162] bytes go to out (device memory), or with out null to a buffer of the
+// context handed back through *out_dev
+int blockdemod_check(uwspr_ctx *c, const uwspr_block_item *items, int nitems, int nframes);
+int blockdemod_run(uwspr_ctx *c, const float *src, size_t stride, const uwspr_block_item *items, int nitems, uint8_t *out,
+                   uint8_t **out_dev);
 
 // ---- launchers (each enqueues on ctx->stream) ------------------------------
 int frontend_design(int mode, int stage, std::vector<double> &out, int *delay);

@@ -26,7 +26,7 @@ LIBPATH = os.path.join(LIBDIR, "libuwspr_hip_exp_%s.so" % _EXTRA_TAG if _EXTRA e
 HOSTLIB = os.path.join(LIBDIR, "libuwspr_blocks.so")
 
 SOURCES = ["uwspr_api.hip", "k0_frontend.hip", "k1_spectrogram.hip", "k2_spectrum.hip", "k3_coarse.hip",
-           "k4_tonecorr.hip", "k4_grid.hip", "k4_pair.hip", "k4_jig.hip", "k5_fold_schedule.hip", "k6_sched.hip", "k7_transmit.hip", "k8_subtract.hip", "k9_osd.hip", "pipe.hip", "dist.hip", "host_tail.cpp"]
+           "k4_tonecorr.hip", "k4_grid.hip", "k4_pair.hip", "k4_jig.hip", "k5_fold_schedule.hip", "k6_sched.hip", "k7_transmit.hip", "k8_subtract.hip", "k9_osd.hip", "k10_blockdemod.hip", "pipe.hip", "dist.hip", "host_tail.cpp"]
 HIPFLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off",
             "-fno-slp-vectorize", "-fhip-fp32-correctly-rounded-divide-sqrt", "-fPIC", "-Wall", "-Wno-unused-function"]
 
@@ -204,15 +204,17 @@ class Info(C.Structure):
 DECODE_DTYPE = np.dtype([("frame", "<i8"), ("stream_pos", "<i8"), ("cand", "<i4"), ("npk", "<i4"),
                          ("coarse", CAND_DTYPE), ("f1", "<f4"), ("drift1", "<f4"), ("sync1", "<f4"),
                          ("shift1", "<i4"), ("worth_a_try", "<i4"), ("decoded", "<i4"), ("idt", "<i4"),
-                         ("message", "i1", (7,)), ("_pad0", "u1"), ("channel", "<i2"), ("pass", "u1"), ("osd", "u1")])
+                         ("message", "i1", (7,)), ("block", "u1"), ("channel", "<i2"), ("pass", "u1"), ("osd", "u1")])
 assert DECODE_DTYPE.itemsize == 112 and DECODE_DTYPE.fields["channel"][1] == 108 and DECODE_DTYPE.fields["pass"][1] == 110
-assert DECODE_DTYPE.fields["osd"][1] == 111
+assert DECODE_DTYPE.fields["osd"][1] == 111 and DECODE_DTYPE.fields["block"][1] == 107
 SUB_ITEM_DTYPE = np.dtype([("frame", "<i4"), ("shift", "<i4"), ("f_hz", "<f4"), ("drift_hz", "<f4"),
                            ("symbols", "u1", (NSYM,)), ("_pad", "u1", (2,))])
 SUB_RESULT_DTYPE = np.dtype([("f_hz", "<f4"), ("shift", "<i4"), ("metric", "<f4"), ("removed", "<f4")])
 assert SUB_ITEM_DTYPE.itemsize == 180 and SUB_RESULT_DTYPE.itemsize == 16
 OSD_RESULT_DTYPE = np.dtype([("dmin", "<i4"), ("dnext", "<i4"), ("nhard", "<i4"), ("nflip", "u1"), ("message", "i1", (7,))])
 assert OSD_RESULT_DTYPE.itemsize == 20
+BLOCK_ITEM_DTYPE = np.dtype([("frame", "<i4"), ("shift", "<i4"), ("f_hz", "<f4"), ("drift_hz", "<f4")])
+assert BLOCK_ITEM_DTYPE.itemsize == 16
 OSD_GAP_DEFAULT = 485   # UWSPR_OSD_GAP_DEFAULT
 PIPE_MAX_CHANNELS = 64
 
@@ -271,7 +273,7 @@ ABI_SYMBOLS = [
     "uwspr_fano_decode", "uwspr_fano_encode", "uwspr_decode_candidate", "uwspr_host_threads", "uwspr_host_set_ranks", "uwspr_decode_batch", "uwspr_unpack_message",
     "uwspr_c2_read",
     "uwspr_wspr_pack", "uwspr_nhash", "uwspr_wspr_symbols", "uwspr_c2_write", "uwspr_tx_baseband", "uwspr_tx_render",
-    "uwspr_tx_baseband_moving", "uwspr_tx_render_moving", "uwspr_subtract_batch", "uwspr_osd_batch",
+    "uwspr_tx_baseband_moving", "uwspr_tx_render_moving", "uwspr_subtract_batch", "uwspr_osd_batch", "uwspr_blockdemod_batch",
     "uwspr_dist_unique_id", "uwspr_dist_init", "uwspr_dist_gather", "uwspr_dist_finalize",
     "uwspr_pipe_open", "uwspr_pipe_close", "uwspr_pipe_last_error", "uwspr_pipe_acquire", "uwspr_pipe_commit",
     "uwspr_pipe_push", "uwspr_pipe_push_audio", "uwspr_pipe_push_audio_channels", "uwspr_pipe_submit_device", "uwspr_pipe_flush", "uwspr_pipe_collect", "uwspr_pipe_get_stats",
@@ -371,6 +373,7 @@ def lib():
     L.uwspr_tx_render_moving.argtypes = [vp, vp, vp, ip, vp, ip, C.c_longlong, C.c_longlong, ip, vp, ip]
     L.uwspr_subtract_batch.argtypes = [vp, vp, ip, ip, vp, ip, ip, vp, vp]
     L.uwspr_osd_batch.argtypes = [vp, vp, ip, ip, ip, vp]
+    L.uwspr_blockdemod_batch.argtypes = [vp, vp, ip, ip, vp, ip, vp]
     L.uwspr_dist_unique_id.argtypes = [vp]
     L.uwspr_dist_init.argtypes = [vp, ip, ip, vp]
     L.uwspr_dist_gather.argtypes = [vp, vp, C.c_size_t, vp, ip, ip]

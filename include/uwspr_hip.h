@@ -42,7 +42,9 @@ extern "C" {
                                     known-symbol subtraction: uwspr_sub_item, uwspr_sub_result, uwspr_subtract_batch, the pipe
                                     option "passes", uwspr_decode.pass (carved out of the padding as well);
                                     ordered-statistics decoding: uwspr_osd_result, uwspr_osd_batch, the pipe options "osd" and
-                                    "osd_gap", uwspr_decode.osd (the last byte of the padding) */
+                                    "osd_gap", uwspr_decode.osd (the last byte of the padding);
+                                    block demodulation: uwspr_block_item, uwspr_blockdemod_batch, the pipe option "block",
+                                    uwspr_decode.block (the byte that was _pad0) */
 
 typedef enum {
   UWSPR_OK = 0,
@@ -430,7 +432,7 @@ typedef struct uwspr_decode {
   int32_t decoded;        /* 1: message holds the 7 bytes sync_and_demodulate publishes (cc:528-530) */
   int32_t idt;            /* the jiggered try that decoded (-1: none) */
   int8_t message[7];
-  uint8_t _pad0;
+  uint8_t block;          /* 2, 3: Fano timed out on every gated try and the soft symbols of that block length decoded (option "block"); 0 otherwise */
   int16_t channel;        /* the audio channel of a multichannel pipe (uwspr_pipe_push_audio_channels); 0 otherwise */
   uint8_t pass;           /* 1: found by the second pass (option "passes" = 2), in the frame with its decoded signals taken out; 0 otherwise */
   uint8_t osd;            /* 1: Fano timed out on every gated try and ordered-statistics decoding gave the message (option "osd"); 0 otherwise */
@@ -501,7 +503,19 @@ int uwspr_pipe_get_stats(uwspr_pipe *pipe, uwspr_pipe_stats *st);
  * ties), its symbols read where they lie in the lane's device records.  An item with dnext - dmin >= "osd_gap" (>= 0;
  * default UWSPR_OSD_GAP_DEFAULT) whose bytes uwspr_unpack_message accepts turns the record into a decoded one: decoded = 1,
  * idt = that try, message set, osd = 1.  It is an ordinary decoded record from there on: counted in the stats' decoded,
- * subtracted by "passes" = 2.  With "osd" = 0 every byte and statistic is what it is without the option. */
+ * subtracted by "passes" = 2.  With "osd" = 0 every byte and statistic is what it is without the option.
+ * "block" is the pipe's own too: 0 (default), 2 or 3 (anything else UWSPR_ERR_ARG).  With 2 or 3, K10
+ * (uwspr_blockdemod_batch below) runs on the batch's lane behind its host tail, resumed tries included, and before "osd" --
+ * and behind the second pass's host tail with "passes" = 2 -- on the records "osd" would take: one item per record with
+ * worth_a_try that decoded on no try and has a gated try, the gated try with the largest jig_sync (the first one on ties).
+ * The item is that try's jig_shift with the record's f1 and drift1 (a NONLINEAR candidate: the constant f1 +
+ * slmFrequencyDrift at t = 0, no drift, as "passes" = 2 models it), over the batch's own frames (the second pass: the
+ * residual frames).  For n = 2 .. "block" in that order: a vector whose rms (that of cc:469-474) is above the gate of
+ * cc:470 is de-interleaved and goes through uwspr_fano_decode(60, 10000) on the host pool; the first that decodes and
+ * whose bytes uwspr_unpack_message accepts turns the record into a decoded one: decoded = 1, idt = that try, message set,
+ * block = n.  It is an ordinary decoded record from there on (counted, subtracted by "passes" = 2, no item of "osd").
+ * These calls count in fano_calls / fano_timeouts, their time in resume_s.  With "block" = 0 every byte and statistic is
+ * what it is without the option. */
 int uwspr_pipe_set_option(uwspr_pipe *pipe, const char *name, int value);
 /* Error behaviour.  An argument error (too many samples, a bad B or stride) fails THAT call with UWSPR_ERR_ARG and
  * its message; the pipe goes on.  A runtime failure (HIP, a lane's context) is sticky: the batch it hit emits
@@ -741,6 +755,42 @@ typedef struct uwspr_osd_result {
   int8_t message[7];
 } uwspr_osd_result;
 int uwspr_osd_batch(uwspr_ctx *ctx, const uint8_t *symbols /*[n][162]*/, int n, int where, int order, uwspr_osd_result *res);
+
+/* ---- block demodulation (K10, k10_blockdemod.hip) -------------------------------------------------------------------- */
+/* Soft symbols from COMPLEX tone correlations summed coherently over n = 1, 2, 3 neighbouring symbols (the transmission is
+ * continuous-phase 4-FSK with a known sync bit per symbol), instead of the per-symbol magnitudes of the fine search's mode 2
+ * (sync_and_demodulate_impl.cc:240-254).  The reference has no counterpart (the -B mode of the WSPR decoders in use);
+ * binary32 with fused multiply-adds, phases in binary64.  df = 375/256.
+ * An item is (frame, shift s, f, drift): the fields of a uwspr_sub_item without the symbols; for a NONLINEAR candidate f
+ * is the constant the fine search correlated with (f1 + slmFrequencyDrift at t = 0) and drift = 0.  For symbol i = 0..161,
+ *     f_i = f + (drift / 2)(i - 81) / 81.
+ *   - z_i[j] = sum_{k < 256} x[s + 256 i + k] e^{-j 2 pi (f_i + (j - 1.5) df) k / 375}, tones j = 0..3.  A sample whose index
+ *     n = s + 256 i + k is not in 0 < n < min(fl, 45000) counts as 0: the fine search's own bound (cc:200; 45000 whatever
+ *     fl is, capped at fl where the reference would read past its arrays).  The phasor starts at (1, 0) in every symbol,
+ *     as the fine search's does (cc:188).
+ *   - Whatever the data, the carrier advances by theta_i = 2 pi f_i 256 / 375 + pi per symbol: every tone offset
+ *     (j - 1.5) df makes an odd number of half cycles in 256 samples.
+ *   - Block length n in {1, 2, 3}: block b covers the symbols i0 = n b .. i0 + n - 1 (162, 81, 54 blocks).  For every data
+ *     sequence d in {0,1}^n,
+ *         P(d) = | sum_{m < n} z_{i0+m}[pr3[i0+m] + 2 d_m] e^{-j psi_m} |,   psi_m = sum_{q < m} theta_{i0+q}.
+ *   - soft[i0+m] = max_{d: d_m = 1} P(d) - max_{d: d_m = 0} P(d).  With n = 1 this is mode 2's p[pr3 + 2] - p[pr3].
+ *   - Normalisation as in mode 2 (cc:240-254): fsum and f2sum the mean and the mean square of the 162 values, fac =
+ *     sqrt(f2sum - fsum^2), v = 50 soft / fac clipped to [-128, 127], byte = (uint8)(v + 128).  When fac is not a positive
+ *     finite number every byte is 128.
+ * Output per item: the three 162-byte vectors n = 1, 2, 3, each interleaved as uwspr_demod_out.symbols[idt] holds one; all
+ * three are always produced (the work is one set of z either way).  Every sum has one owner and a fixed order: an item's
+ * bytes depend neither on the rest of the batch nor on where the frames live.
+ * frames: B frames per `where` and uwspr_set_frame_stride.  items: HOST memory whatever `where` says, sorted by frame, frame
+ * in [0, B), f_hz and drift_hz finite (|f| <= 1e4, |drift| <= 1e3), |shift| <= 2^20: anything else returns UWSPR_ERR_ARG
+ * before any launch, the output untouched.  symbols: host memory with UWSPR_HOST (complete on return); device memory with
+ * UWSPR_DEVICE (asynchronous on the context's stream) and UWSPR_DEVICE_FRAMES (complete on return) -- it must lie inside a
+ * device allocation of the context's device, else UWSPR_ERR_ARG before any launch.  nitems = 0 is fine. */
+typedef struct uwspr_block_item {
+  int32_t frame, shift;
+  float f_hz, drift_hz;
+} uwspr_block_item;
+int uwspr_blockdemod_batch(uwspr_ctx *ctx, const float *frames, int B, int where, const uwspr_block_item *items, int nitems,
+                           uint8_t *symbols /*[nitems][3][162]*/);
 
 #ifdef __cplusplus
 }
