@@ -181,9 +181,12 @@ __global__ __launch_bounds__(64) void k8_pick(const uwspr_sub_item *__restrict__
   }
 }
 
+// NT taps of a block of eight: the last block has seven (there are 1023 taps, and a 1024th of weight 0 would still turn a
+// NaN or an infinite sample 512 behind the output into a NaN)
+template <int NT = 8>
 __device__ __forceinline__ void k8_block(float2 (&acc)[K8_CR], const float2 (&A)[8], const float2 (&B)[8], const float *__restrict__ wt) {
 #pragma unroll
-  for (int u = 0; u < 8; u++) {
+  for (int u = 0; u < NT; u++) {
     const float t = wt[u];
 #pragma unroll
     for (int r = 0; r < K8_CR; r++) {
@@ -235,13 +238,21 @@ __global__ __launch_bounds__(K8_CWG) void k8_cancel(const float2 *__restrict__ f
   for (int r = 0; r < K8_CR; r++) acc[r] = make_float2(0.0f, 0.0f);
 #pragma unroll
   for (int v = 0; v < 8; v++) A[v] = cs[v * K8_G + tid];
-  for (int b = 0; b < 128; b += 2) {   // two blocks per trip: the window's halves swap roles, no copies
+  for (int b = 0; b < 126; b += 2) {   // two blocks per trip: the window's halves swap roles, no copies
 #pragma unroll
     for (int v = 0; v < 8; v++) B[v] = cs[v * K8_G + tid + b + 1];
     k8_block(acc, A, B, wt + 8 * b);
 #pragma unroll
-    for (int v = 0; v < 8; v++) A[v] = cs[v * K8_G + tid + b + 2];   // (group <= 575 + 128 = 703)
+    for (int v = 0; v < 8; v++) A[v] = cs[v * K8_G + tid + b + 2];
     k8_block(acc, B, A, wt + 8 * b + 8);
+  }
+  {   // taps 1008 .. 1022
+#pragma unroll
+    for (int v = 0; v < 8; v++) B[v] = cs[v * K8_G + tid + 127];
+    k8_block(acc, A, B, wt + 8 * 126);
+#pragma unroll
+    for (int v = 0; v < 8; v++) A[v] = cs[v * K8_G + tid + 128];   // (group <= 575 + 128 = 703)
+    k8_block<7>(acc, B, A, wt + 8 * 127);
   }
   float rs = 0.0f;
 #pragma unroll
@@ -309,6 +320,9 @@ struct sub_state {
   bool timing = false;
   std::vector<hipEvent_t> ev;   // four per rank: before / after k8_refine, before / after k8_cancel
   size_t ev_used = 0;
+  // uwspr_debug_subtract_surface: what the last subtract_run left in d_part
+  int last_items = 0;
+  bool last_refine = false;
 };
 
 void sub_release(uwspr_ctx *c) {
@@ -406,6 +420,8 @@ int subtract_run(uwspr_ctx *c, const float *src, size_t stride, int nslots, cons
   if (rc) return rc;
   sub_state *t = c->sub;
   const int fl = c->fc.fl;
+  t->last_items = 0;
+  t->last_refine = false;
   std::vector<int> order;
   std::vector<int> rank_at;   // order[rank_at[r] .. rank_at[r + 1]): the items that are the r-th of their frame
   if (nitems > 0) {
@@ -465,6 +481,8 @@ int subtract_run(uwspr_ctx *c, const float *src, size_t stride, int nslots, cons
                        t->d_rem, t->d_res);
     SUBCHK(c, hipGetLastError());
   }
+  t->last_items = nitems;
+  t->last_refine = refine != 0;
   return UWSPR_OK;
 }
 
@@ -527,6 +545,29 @@ extern "C" int uwspr_debug_subtract_times(uwspr_ctx *c, int enable, double *refi
     }
     if (refine_ms) *refine_ms = a;
     if (cancel_ms) *cancel_ms = b;
+  }
+  return UWSPR_OK;
+}
+
+// Read-out of tests/test_gpu_subtract_edges.py (not part of the ABI either): the refine surface k8_pick saw for item `item`
+// of the last call, M[(q + 4) * 49 + (l + 24)].  Waits for the context's stream, copies the item's nine partial rows out of
+// d_part and adds them here in ascending part order in binary32 -- adds only, k8_pick's own operations on the same values,
+// so the 441 numbers are bit-equal to the pick's.  UWSPR_ERR_ARG when the last call did not refine or has no such item.
+extern "C" int uwspr_debug_subtract_surface(uwspr_ctx *c, int item, float *M) {
+  if (!c) return UWSPR_ERR_ARG;
+  sub_state *t = c->sub;
+  if (!M || !t || !t->last_refine || item < 0 || item >= t->last_items)
+    return sub_fail(c, UWSPR_ERR_ARG, "uwspr_debug_subtract_surface: item %d, M %p (the last call: %d items, refine %d)", item, (void *)M,
+                    t ? t->last_items : 0, t ? (int)t->last_refine : 0);
+  if (!c->own_stream) return sub_fail(c, UWSPR_ERR_NODEVICE, "context has no device (creation failed: %s)", c->err);
+  SUBCHK(c, hipSetDevice(c->device));
+  SUBCHK(c, hipStreamSynchronize(c->stream));
+  std::vector<float> part((size_t)K8_PARTS * K8_NHYP);
+  SUBCHK(c, hipMemcpy(part.data(), t->d_part + (size_t)item * K8_PARTS * K8_NHYP, part.size() * sizeof(float), hipMemcpyDeviceToHost));
+  for (int h = 0; h < K8_NHYP; h++) {
+    float s = 0.0f;
+    for (int p = 0; p < K8_PARTS; p++) s += part[(size_t)p * K8_NHYP + h];
+    M[h] = s;
   }
   return UWSPR_OK;
 }

@@ -697,6 +697,10 @@ int uwspr_tx_render_moving(uwspr_ctx *ctx, const uwspr_tx_signal *sig, const uws
  * (samples outside [0, fl) count as 0); the first maximum in (q, l) order -- q ascending, then l -- gives shift' = shift + l,
  * f' = f_hz + 0.0125 q (formed in binary64, rounded to the binary32 of the result record) and metric = M.  refine = 0: f' =
  * f_hz, shift' = shift, metric = 0.  A call with refine = 0 on (f', shift') removes what the refining call removed.
+ * NaN samples are accepted.  The pick walks M in (q, l) order from M(-24, -4) and moves on `>` alone, and a comparison with
+ * a NaN is false: a NaN M is never moved to, and a NaN M(-24, -4) is never left -- the result is then (q, l) = (-4, -24) with
+ * metric = NaN (one NaN sample inside every lag's windows does that).  In the cancellation a NaN or infinite sample makes
+ * NaN of the outputs whose 1023 taps reach it, |k - k0| <= 511, and of nothing else; other frames' bytes never depend on it.
  * Cancellation, for k in [0, N) with shift' + k inside [0, fl) (nothing else is touched):
  *     r[k] = e^{j theta(k)}, theta(k) = 2 pi sum_{u < k} f_{u div 256} / 375      (f_i with f' in the place of f_hz)
  *     c[k] = x[shift' + k] conj r[k]                                         (0 for any other k)

@@ -28,10 +28,13 @@ def frame_offset(seed):
     return np.random.Generator(np.random.Philox(0x05D7E87 + seed)).uniform(-6.0, 6.0)
 
 
-def clean_frame(G, text, seed):
-    """text_frame's signal without its noise"""
+def clean_frame(G, text, seed, off=None, drift=0.0):
+    """text_frame's signal without its noise (off: another frequency offset than the seed's; drift: the item model's
+    (drift / 2)(i - 81) / 81 per symbol on top of it)"""
     sym = G.wspr_symbols(text).astype(np.float64)
-    phase = 2.0 * np.pi * np.cumsum(np.repeat((sym - 1.5) * DF, 256) + frame_offset(seed)) / 375.0
+    off = frame_offset(seed) if off is None else off
+    fi = off + (drift / 2.0) * (np.arange(NSYM) - 81.0) / 81.0
+    phase = 2.0 * np.pi * np.cumsum(np.repeat((sym - 1.5) * DF + fi, 256)) / 375.0
     sig = np.zeros((NP, 2), np.float64)
     sig[375:375 + NSYM * 256, 0] = np.cos(phase)
     sig[375:375 + NSYM * 256, 1] = np.sin(phase)
@@ -149,6 +152,29 @@ def test_seventy_items_and_an_item_alone(G, ctx, data):
     assert np.array_equal(alone[0], got[5]) and np.array_equal(alone[1], got[40])
     for q in (17, 69):
         assert np.array_equal(ctx.blockdemod(data["frames"], [items[q]])[0], got[q]), q
+
+
+@pytest.mark.gpu
+def test_the_limits_of_the_item_parameters(G, ctx, data):
+    """|f| <= 1e4 Hz, |drift| <= 1e3 Hz, |shift| <= 2^20 are accepted: the noise-free signal at the alias of +-9999.7 Hz
+    (9999.7 - 27 x 375 = -125.3: the same samples), a noise-free signal that drifts by +-1000 Hz, and items all of whose
+    samples are missing.  The phases (up to 6800 turns within a symbol) are reduced in binary64 on both sides."""
+    wide = float(np.float32(9999.7))
+    frames = np.stack([clean_frame(G, TEXT, CLEAN_SEED, off=wide - 27 * 375.0), clean_frame(G, TEXT, CLEAN_SEED, off=27 * 375.0 - wide),
+                       clean_frame(G, TEXT, CLEAN_SEED, off=1.25, drift=1000.0), clean_frame(G, TEXT, CLEAN_SEED, off=-2.5, drift=-1000.0),
+                       data["frames"][0]])
+    items = [{"frame": 0, "shift": 375, "f": wide, "drift": 0.0}, {"frame": 1, "shift": 375, "f": -wide, "drift": 0.0},
+             {"frame": 2, "shift": 375, "f": 1.25, "drift": 1000.0}, {"frame": 3, "shift": 375, "f": -2.5, "drift": -1000.0},
+             {"frame": 4, "shift": 1 << 20, "f": data["offs"][0], "drift": 0.0}, {"frame": 4, "shift": -(1 << 20), "f": data["offs"][0], "drift": 2.0}]
+    want = np.stack([block_restate(frames[it["frame"]], it["shift"], it["f"], it["drift"], G.synth.PR3) for it in items])
+    got = ctx.blockdemod(frames, items)
+    _close(got[:4], want[:4], "f = +-9999.7 Hz and drift = +-1000 Hz")
+    sym = G.wspr_symbols(TEXT)
+    for q in range(4):       # the restatement and the kernel both still read the transmitted bits there
+        for nb in range(3):
+            assert np.array_equal(want[q][nb] >= 128, (sym >> 1).astype(bool)), (q, nb)
+            assert np.array_equal(got[q][nb] >= 128, (sym >> 1).astype(bool)), (q, nb)
+    assert (want[4:] == 128).all() and got[4:].tobytes() == bytes([128]) * (2 * 3 * NSYM)    # every sample missing
 
 
 @pytest.mark.gpu

@@ -51,10 +51,19 @@ def first_max(M):
     return h // 49 - 4, h % 49 - 24
 
 
-def cancel_ref(x, sym, f, shift, drift):
-    """-> (frame with the item taken out, removed), x complex128 [fl]; f, drift as the binary32 values of the call."""
-    fi = np.repeat(f_sym(f, drift, sym), SPB)
-    theta = 2.0 * np.pi * np.concatenate(([0.0], np.cumsum(fi / FS)[:-1]))
+def cancel_ref(x, sym, f, shift, drift, reduced=False):
+    """-> (frame with the item taken out, removed), x complex128 [fl]; f, drift as the binary32 values of the call.
+    reduced: the phase from per-symbol prefix sums taken mod 1 turn (tests/test_gpu_subtract_edges.py: at |f| = 1e4 Hz the
+    running sum over 41472 samples reaches 1e6 turns and loses what this form keeps -- good to 1e-9 turns)"""
+    if reduced:
+        w = f_sym(f, drift, sym) / FS                      # turns per sample
+        ph = np.zeros(NSYM)
+        for i in range(1, NSYM):
+            ph[i] = (ph[i - 1] + SPB * w[i - 1]) % 1.0
+        theta = 2.0 * np.pi * ((ph[:, None] + np.arange(SPB, dtype=np.float64)[None, :] * w[:, None]) % 1.0).reshape(N)
+    else:
+        fi = np.repeat(f_sym(f, drift, sym), SPB)
+        theta = 2.0 * np.pi * np.concatenate(([0.0], np.cumsum(fi / FS)[:-1]))
     r = np.exp(1j * theta)
     idx = shift + np.arange(N)
     ok = (idx >= 0) & (idx < len(x))

@@ -63,6 +63,17 @@ def main():
     err = np.max(np.abs(T.to_c(got) - case["ref"])) / np.max(np.abs(T.to_c(case["frames"])))
     lines += ["cancel, refine = 0, the test's 3 frames / 4 items: max |GPU - binary64 restatement| / max |x| = %.3e" % err,
               "(tests/test_gpu_subtract.py bounds it by 4 x this value)", ""]
+
+    import test_gpu_subtract_edges as E
+    s = E.build_surface_cases()
+    ctx.subtract(s["frames"], s["items"], refine=True)
+    lines.append("refine surface, tests/test_gpu_subtract_edges.py's cases: max over (q, l) of |M_gpu - binary64 restatement| / S_l")
+    worst = 0.0
+    for n, name in enumerate(s["names"]):
+        e = float(E.surface_error(E.read_surface(G, ctx, n), s["Mref"][n], s["S"][n]).max())
+        worst = max(worst, e)
+        lines.append("  %-24s %.3e" % (name, e))
+    lines += ["worst case %.3e (the test bounds every case by 4 x SURFACE_MEASURED)" % worst, ""]
     ctx.close()
 
     nf = a.frames
