@@ -131,6 +131,26 @@ class Context:
         self.synchronize()
         return out
 
+    LAUNCH_FORMS = ("flat_t1", "flat_t2", "flat_t4", "flat_fast", "fold_wave", "fold_lanes",
+                    "grid_nl1", "grid_nl2", "grid_nl4", "grid_nl5", "grid_nl6", "grid_nl8",
+                    "grid_wpw1", "grid_wpw2", "grid_wpw4", "grid_fallback",
+                    "fold_wave_soft", "fold_lanes_soft", "fold_wave_pwin", "fold_lanes_pwin")
+
+    def launch_forms(self):
+        """diagnostics: launches of the sweep kernels per form since the context was created (uwspr_debug_launch_forms:
+        host-side counters of launch_tonecorr, launch_fold, launch_grid_block and the fallback of uwspr_sync_grid) ->
+        {name: count}: the flat kernel by tones per lane, the fold by form (and, of those, the launches with soft
+        symbols and with the stage winner's magnitudes), the grid kernel by lags per block and by wavefronts per
+        workgroup, and the grid calls that fell back to the flat kernel."""
+        f = self.L.uwspr_debug_launch_forms
+        f.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+        f.restype = C.c_int
+        out = np.zeros(len(self.LAUNCH_FORMS), np.int64)
+        n = f(self.h, C.c_void_p(out.ctypes.data), out.size)
+        if n != out.size:
+            raise N.UwsprError(n if n < 0 else -1, "uwspr_debug_launch_forms: %d slots, this binding names %d" % (n, out.size))
+        return {k: int(v) for k, v in zip(self.LAUNCH_FORMS, out)}
+
     # -- front-end ---------------------------------------------------------
     def frontend(self, audio):
         """12 kS/s real audio [B, nin] -> frames [B, fl, 2] at 375 S/s (uwspr_frontend_batch)."""

@@ -216,6 +216,9 @@ bool launch_grid_block(uwspr_ctx *c, const float *frames, int nframes, int ncent
   const float2 *fr = (const float2 *)frames;
   float *po = (float *)p;
   const int NL = nv <= 1 ? 1 : nv <= 2 ? 2 : nv <= 4 ? 4 : nv <= 5 ? 5 : nv <= 6 ? 6 : 8;
+  c->launch_forms[NL == 1 ? UWSPR_FORM_GRID_NL1 : NL == 2 ? UWSPR_FORM_GRID_NL2 : NL == 4 ? UWSPR_FORM_GRID_NL4 :
+                  NL == 5 ? UWSPR_FORM_GRID_NL5 : NL == 6 ? UWSPR_FORM_GRID_NL6 : UWSPR_FORM_GRID_NL8]++;
+  c->launch_forms[wpw == 1 ? UWSPR_FORM_GRID_WPW1 : wpw == 2 ? UWSPR_FORM_GRID_WPW2 : UWSPR_FORM_GRID_WPW4]++;
   switch (NL) {
     case 1: launch_grid_t<1>(c, ps, fr, nframes, ncentres, centres, cframe, ga, wpw, po); break;
     case 2: launch_grid_t<2>(c, ps, fr, nframes, ncentres, centres, cframe, ga, wpw, po); break;

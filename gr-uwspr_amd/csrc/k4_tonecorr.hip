@@ -213,6 +213,7 @@ void launch_tonecorr(uwspr_ctx *c, const float *frames, int B, const dev_hyp *hy
   dim3 blk(64 * K4_WAVES);
   if (hyps_per_grp < 1) hyps_per_grp = 1;
   const int sp = skip_pairs && (H % 2 == 0) ? 1 : 0;
+  c->launch_forms[T == 1 ? (c->fast_now ? UWSPR_FORM_FLAT_FAST : UWSPR_FORM_FLAT_T1) : T == 2 ? UWSPR_FORM_FLAT_T2 : UWSPR_FORM_FLAT_T4]++;
   if (T == 1 && c->fast_now) launch_timed(c, ps, (k4_tonecorr<1, true>), dim3(blocks), blk, 0, fr, c->fstride, c->np, B, hyps, H, po, taken, hyps_per_grp, sp);
   else if (T == 1) launch_timed(c, ps, k4_tonecorr<1>, dim3(blocks), blk, 0, fr, c->fstride, c->np, B, hyps, H, po, taken, hyps_per_grp, sp);
   else if (T == 2) launch_timed(c, ps, k4_tonecorr<2>, dim3(blocks), blk, 0, fr, c->fstride, c->np, B, hyps, H, po, taken, hyps_per_grp, sp);

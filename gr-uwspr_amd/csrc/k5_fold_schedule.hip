@@ -231,6 +231,9 @@ void launch_fold(uwspr_ctx *c, const dev_hyp *hyps, const float4 *p, int H, floa
   const int forced = c->opt[UWSPR_OPT_K5_LANES];
   const bool lanes_form = forced >= 0 ? forced != 0 : H >= 32768;
   if (per_slot < 1) per_slot = 1;
+  c->launch_forms[lanes_form ? UWSPR_FORM_FOLD_LANES : UWSPR_FORM_FOLD_WAVE]++;
+  if (symbols) c->launch_forms[lanes_form ? UWSPR_FORM_FOLD_LANES_SOFT : UWSPR_FORM_FOLD_WAVE_SOFT]++;
+  if (pwin) c->launch_forms[lanes_form ? UWSPR_FORM_FOLD_LANES_PWIN : UWSPR_FORM_FOLD_WAVE_PWIN]++;
   if (!lanes_form) {
     dim3 g((H + K5W_WAVES - 1) / K5W_WAVES), b(64 * K5W_WAVES);
     if (symbols) hipLaunchKernelGGL(k5_fold_wave<true>, g, b, 0, c->stream, hyps, p, H, 50.0f, sync, symbols, pwin, per_slot);

@@ -726,6 +726,7 @@ extern "C" int uwspr_sync_grid(uwspr_ctx *c, const float *frames, int B, int whe
   HIPCHK(c, hipMemcpyAsync(ddl, dlag, (size_t)nlag * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
   if (!launch_tonecorr_grid(c, d, B, dcent, nf, df, ndrift, ddrift, nlag, dlag, ddl, c->d_hyps, c->d_p)) {
     // window scheme does not fit (huge lag span): the flat kernel on the same hypothesis list
+    c->launch_forms[UWSPR_FORM_GRID_FALLBACK]++;
     launch_tonecorr(c, d, B, c->d_hyps, (int)H, c->d_p);
   }
   launch_fold(c, c->d_hyps, c->d_p, (int)H, c->d_sync, soft ? c->d_sym : nullptr);
@@ -1263,5 +1264,36 @@ extern "C" int uwspr_prof_read(uwspr_ctx *c, uwspr_prof *o) {
     c->ev_pool.push_back(e.a); c->ev_pool.push_back(e.b);
   }
   c->prof_events.clear();
+  return UWSPR_OK;
+}
+
+// diagnostics (not part of the ABI header): launches of the sweep kernels per form since the context was created, counted
+// on the host where launch_tonecorr, launch_fold, launch_grid_block and uwspr_sync_grid choose.  out[0 .. n) in the order
+// of UWSPR_FORM_* (uwspr_internal.h):
+//    0..3   flat kernel k4_tonecorr<T>: T = 1, 2, 4, and the fast_search instance <1, true>
+//    4, 5   fold: wave form (k5_fold_wave), lanes form (k5_fold)
+//    6..11  k4_grid<NL>: NL = 1, 2, 4, 5, 6, 8
+//   12..14  k4_grid with 1, 2, 4 wavefronts per workgroup
+//   15      uwspr_sync_grid calls that fell back to the flat kernel (a lag block's windows did not fit LDS)
+//   16, 17  of slots 4, 5: the launches that wrote soft symbols
+//   18, 19  of slots 4, 5: the launches with the stage winner's magnitudes (pwin: stage 5 of the staged schedule)
+// Returns the number of slots that exist (20), or a negative status.
+extern "C" int uwspr_debug_launch_forms(uwspr_ctx *c, long long *out, int n) {
+  if (!c || !out || n < 0) return UWSPR_ERR_ARG;
+  for (int i = 0; i < n && i < UWSPR_NFORMS; i++) out[i] = c->launch_forms[i];
+  for (int i = UWSPR_NFORMS; i < n; i++) out[i] = 0;
+  return UWSPR_NFORMS;
+}
+
+// diagnostics (not part of the ABI header): rows [first, first + n) of the context's OWN metric and soft-symbol buffers
+// ([H] floats, [H][162] bytes: what the fold writes before the results are copied to the caller).  Rows behind the last
+// call's H still hold what an earlier, larger call left there: a fold that stored past its H would have damaged them.
+extern "C" int uwspr_debug_sweep_outputs(uwspr_ctx *c, int first, int n, float *sync, uint8_t *symbols) {
+  if (!c || first < 0 || n <= 0) return UWSPR_ERR_ARG;
+  if (sync && (!c->d_sync || (size_t)first + n > c->cap_sync)) return UWSPR_ERR_ARG;
+  if (symbols && (!c->d_sym || ((size_t)first + n) * UWSPR_NSYM > c->cap_sym)) return UWSPR_ERR_ARG;
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (sync) HIPCHK(c, hipMemcpy(sync, c->d_sync + first, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
+  if (symbols) HIPCHK(c, hipMemcpy(symbols, c->d_sym + (size_t)first * UWSPR_NSYM, (size_t)n * UWSPR_NSYM, hipMemcpyDeviceToHost));
   return UWSPR_OK;
 }

@@ -30,6 +30,32 @@ enum {
   UWSPR_NOPT
 };
 
+// Launch forms of the sweep kernels, counted on the host where the launchers choose (uwspr_ctx::launch_forms, read by
+// uwspr_debug_launch_forms: the slot layout of its `out`).  A test that forces a form reads here that it really ran.
+enum {
+  UWSPR_FORM_FLAT_T1 = 0,       // k4_tonecorr<1>
+  UWSPR_FORM_FLAT_T2,           // k4_tonecorr<2>
+  UWSPR_FORM_FLAT_T4,           // k4_tonecorr<4>
+  UWSPR_FORM_FLAT_FAST,         // k4_tonecorr<1, true> (fast_search)
+  UWSPR_FORM_FOLD_WAVE,         // k5_fold_wave, with or without soft symbols
+  UWSPR_FORM_FOLD_LANES,        // k5_fold
+  UWSPR_FORM_GRID_NL1,          // k4_grid<NL>: NL = 1, 2, 4, 5, 6, 8 in the next six slots
+  UWSPR_FORM_GRID_NL2,
+  UWSPR_FORM_GRID_NL4,
+  UWSPR_FORM_GRID_NL5,
+  UWSPR_FORM_GRID_NL6,
+  UWSPR_FORM_GRID_NL8,
+  UWSPR_FORM_GRID_WPW1,         // k4_grid with 1, 2, 4 wavefronts per workgroup
+  UWSPR_FORM_GRID_WPW2,
+  UWSPR_FORM_GRID_WPW4,
+  UWSPR_FORM_GRID_FALLBACK,     // uwspr_sync_grid: a lag block did not fit LDS, the whole call went through the flat kernel
+  UWSPR_FORM_FOLD_WAVE_SOFT,    // of the fold launches above: those that wrote soft symbols ...
+  UWSPR_FORM_FOLD_LANES_SOFT,
+  UWSPR_FORM_FOLD_WAVE_PWIN,    // ... and those that were given the stage winner's magnitudes (stage 5 of the schedule)
+  UWSPR_FORM_FOLD_LANES_PWIN,
+  UWSPR_NFORMS
+};
+
 namespace uwspr {
 
 // 162 WSPR sync bits (lib/pr3.h:5-13), LSB-first packed; a protocol constant.
@@ -194,6 +220,7 @@ struct uwspr_ctx {
   // Options (uwspr_set_option; defaults in uwspr_api.hip: kOptions).  The ones the launch sequences branch on:
   int opt[UWSPR_NOPT];
   bool opt_set[UWSPR_NOPT];   // set by the caller (environment or uwspr_set_option), not the default
+  long long launch_forms[UWSPR_NFORMS] = {};   // launches per form since the context was created (UWSPR_FORM_*)
   bool use_fused;        // "sched" = 1: one workgroup per candidate runs S0..S5 (k6_sched); 0: staged launches
   bool use_stage_kernels;   // "stage_kernels" >= 1: the staged form's packed / ring / rows kernels; 0: the flat kernel for every stage
   bool reuse_centre;     // "reuse": skip the stage-winner hypothesis in S1/S3/S4 and try 0 of S5 (0: recompute it)

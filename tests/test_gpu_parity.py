@@ -336,12 +336,12 @@ def test_options_are_checked(G, ctx):
     assert ctx.get_option("sched") in (0, 1)
 
 
-def test_schedule_forms_on_random_candidates(G, oracle):
-    """Hand-made candidates that the packed / table kernels must not trip over: frames with 0..5 candidates (dead
-    slots between live ones), shifts from before the frame start to the last one whose windows fit, drifting linear
-    models (no phasor table: the recurrence kernels take them) next to drift-free and straight-line ones in the same
-    workgroups.  Fused kernel, staged form and staged form with the flat kernel only: identical bytes;
-    a sample of the records against the oracle."""
+RANDOM_CANDIDATE_SAMPLE = ((0, 0), (0, 3), (2, 1), (3, 0), (5, 2))   # (frame, slot) of the records compared with the oracle
+
+
+def random_candidates(G, oracle):
+    """-> (frames [6, 45000, 2], candidate arrays per frame, slots per frame) of test_schedule_forms_on_random_candidates
+    (tests/test_gpu_sweep_forms.py sends the same set through the forced kernel forms)"""
     rng = np.random.default_rng(2024)
     frames = np.concatenate([G.synth.make_frames(4, seed=606, snr_db=-17.0),
                              (0.5 * rng.standard_normal((2, 45000, 2))).astype(np.float32)])
@@ -364,6 +364,16 @@ def test_schedule_forms_on_random_candidates(G, oracle):
                 c[j] = np.frombuffer(c[j].tobytes()[:24] + drift.tobytes() + c[j].tobytes()[28:], oracle.CAND_DTYPE)[0]
         cands.append(c)
     cands[0][0]["freq"] = frames.dtype.type(0.0)       # one candidate on the generated signal's grid
+    return frames, cands, per
+
+
+def test_schedule_forms_on_random_candidates(G, oracle):
+    """Hand-made candidates that the packed / table kernels must not trip over: frames with 0..5 candidates (dead
+    slots between live ones), shifts from before the frame start to the last one whose windows fit, drifting linear
+    models (no phasor table: the recurrence kernels take them) next to drift-free and straight-line ones in the same
+    workgroups.  Fused kernel, staged form and staged form with the flat kernel only: identical bytes;
+    a sample of the records against the oracle."""
+    frames, cands, per = random_candidates(G, oracle)
     outs = {}
     for name, opts in (("fused", {"sched": 1}),
                        ("staged", {"sched": 0}),
@@ -378,7 +388,7 @@ def test_schedule_forms_on_random_candidates(G, oracle):
             c.close()
     for name in ("staged", "staged-lds-ring", "staged-no-tables", "staged-no-tables-no-reuse", "staged-flat"):
         assert outs[name].tobytes() == outs["fused"].tobytes(), name
-    for b, j in ((0, 0), (0, 3), (2, 1), (3, 0), (5, 2)):
+    for b, j in RANDOM_CANDIDATE_SAMPLE:
         d = oracle.demod_candidate(cands[b][j], 1500, frames[b])
         o = outs["staged"][b, j]
         assert int(o["shift1"]) == d["shift1"] and int(o["worth_a_try"]) == d["worth_a_try"], (b, j)
