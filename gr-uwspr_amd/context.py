@@ -172,6 +172,39 @@ class Context:
                                               N.HOST, C.c_void_p(out.ctypes.data)))
         return out
 
+    def debug_frontend_launch(self, audio, in0, out, m_first, nch=1, plane=None, nout=None, nin=None):
+        """diagnostics: ONE launch of the stream form of K0 (uwspr_debug_frontend_launch; what a stream's audio push
+        runs) on torch CUDA tensors.  audio: float32 or int16, audio [in0, in0 + nin) -- nin samples, or nin frames of
+        nch interleaved channels (nin defaults to all of it); out: float32, receives outputs [m_first, m_first + nout)
+        of channel b at pair b * plane (nout defaults to what `out` holds per channel, plane to nout).  The tensors
+        must hold what the launch reads and writes: that is checked here, the library sees pointers only."""
+        import torch
+        fmt = {torch.float32: N.AUDIO_F32, torch.int16: N.AUDIO_S16}.get(audio.dtype)
+        if fmt is None or not audio.is_cuda or not audio.is_contiguous():
+            raise TypeError("debug_frontend_launch: a contiguous float32 or int16 CUDA tensor, not %s" % audio.dtype)
+        if out.dtype != torch.float32 or not out.is_cuda or not out.is_contiguous():
+            raise TypeError("debug_frontend_launch: out is a contiguous float32 CUDA tensor, not %s" % out.dtype)
+        nch = int(nch)
+        if nin is None:
+            nin = audio.numel() // max(nch, 1)
+        if nout is None:
+            if plane is not None:
+                raise ValueError("debug_frontend_launch: plane without nout")
+            nout = out.numel() // (2 * max(nch, 1))
+        if plane is None:
+            plane = nout
+        nin, nout, plane = int(nin), int(nout), int(plane)
+        if nin * nch > audio.numel() or 2 * ((nch - 1) * plane + nout) > out.numel():
+            raise ValueError("debug_frontend_launch: nin %d x nch %d / nout %d, plane %d do not fit the tensors" % (nin, nch, nout, plane))
+        f = self.L.uwspr_debug_frontend_launch
+        f.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_longlong, C.c_int, C.c_void_p, C.c_int,
+                      C.c_longlong, C.c_longlong]
+        f.restype = C.c_int
+        if self._stream_ptr is None:
+            torch.cuda.current_stream(audio.device).synchronize()
+        self._chk(f(self.h, C.c_void_p(audio.data_ptr()), fmt, nin, int(in0), nch, C.c_void_p(out.data_ptr()), nout,
+                    int(m_first), plane))
+
     # -- FDR ---------------------------------------------------------------
     def fdr_batch(self, frames):
         """-> list (per frame) of candidate record arrays, FDR_impl.cc:214-456."""

@@ -512,6 +512,21 @@ static int copy_out(uwspr_ctx *c, void *dst, const void *src, size_t bytes, int 
 }
 
 // -------------------------------------------------------------- front-end
+// the tap image of the context's `frontend` option on the device (built on first use and when the option changed)
+static int frontend_taps(uwspr_ctx *c) {
+  if (c->d_fe_taps && c->fe_mode == c->opt[UWSPR_OPT_FRONTEND]) return UWSPR_OK;
+  std::vector<float> img;
+  int J = 0, dcols = 0;
+  if (frontend_tap_image(c->opt[UWSPR_OPT_FRONTEND], img, &J, &dcols)) return fail(c, UWSPR_ERR_ARG, "front-end mode %d", c->opt[UWSPR_OPT_FRONTEND]);
+  if (frontend_prepare()) return fail(c, UWSPR_ERR_HIP, "front-end kernel: %zu bytes of LDS refused", (size_t)160 * 1024);
+  HIPCHK(c, hipStreamSynchronize(c->stream));          // (a launch with the other mode's taps may be in flight)
+  if (c->d_fe_taps) { HIPCHK(c, hipFree(c->d_fe_taps)); c->d_fe_taps = nullptr; }
+  HIPCHK(c, hipMalloc((void **)&c->d_fe_taps, img.size() * sizeof(float)));
+  HIPCHK(c, hipMemcpy(c->d_fe_taps, img.data(), img.size() * sizeof(float), hipMemcpyHostToDevice));
+  c->fe_mode = c->opt[UWSPR_OPT_FRONTEND]; c->fe_J = J; c->fe_dcols = dcols;
+  return UWSPR_OK;
+}
+
 extern "C" int uwspr_frontend_batch(uwspr_ctx *c, const float *audio, int B, int nin, int where,
                                     float *frames_out) {
   int rc = ready(c);
@@ -519,17 +534,7 @@ extern "C" int uwspr_frontend_batch(uwspr_ctx *c, const float *audio, int B, int
   const int nout = c->fc.fl;
   if (!audio || !frames_out || B <= 0 || nin <= 0) return fail(c, UWSPR_ERR_ARG, "uwspr_frontend_batch: audio/out/B/nin");
   if (c->p.fs != 375) return fail(c, UWSPR_ERR_UNSUPPORTED, "front-end is 12000 -> 375 S/s (fs=%d)", c->p.fs);
-  if (!c->d_fe_taps || c->fe_mode != c->opt[UWSPR_OPT_FRONTEND]) {
-    std::vector<float> img;
-    int J = 0, dcols = 0;
-    if (frontend_tap_image(c->opt[UWSPR_OPT_FRONTEND], img, &J, &dcols)) return fail(c, UWSPR_ERR_ARG, "front-end mode %d", c->opt[UWSPR_OPT_FRONTEND]);
-    if (frontend_prepare()) return fail(c, UWSPR_ERR_HIP, "front-end kernel: %zu bytes of LDS refused", (size_t)160 * 1024);
-    HIPCHK(c, hipStreamSynchronize(c->stream));          // (a launch with the other mode's taps may be in flight)
-    if (c->d_fe_taps) { HIPCHK(c, hipFree(c->d_fe_taps)); c->d_fe_taps = nullptr; }
-    HIPCHK(c, hipMalloc((void **)&c->d_fe_taps, img.size() * sizeof(float)));
-    HIPCHK(c, hipMemcpy(c->d_fe_taps, img.data(), img.size() * sizeof(float), hipMemcpyHostToDevice));
-    c->fe_mode = c->opt[UWSPR_OPT_FRONTEND]; c->fe_J = J; c->fe_dcols = dcols;
-  }
+  if ((rc = frontend_taps(c))) return rc;
   const float *da = audio;
   float *dout = frames_out;
   if (where == UWSPR_HOST) {
@@ -1283,6 +1288,26 @@ extern "C" int uwspr_debug_launch_forms(uwspr_ctx *c, long long *out, int n) {
   for (int i = 0; i < n && i < UWSPR_NFORMS; i++) out[i] = c->launch_forms[i];
   for (int i = UWSPR_NFORMS; i < n; i++) out[i] = 0;
   return UWSPR_NFORMS;
+}
+
+// diagnostics (not part of the ABI header): ONE launch of the stream form of K0 (launch_frontend_stream, what
+// stream_ring::push_audio calls) on device memory, with the taps of the context's `frontend` option, on the context's
+// stream, waited for.  audio_dev holds audio [in0, in0 + nin) -- nin samples, or with nch > 1 nin frames of nch
+// interleaved channels -- and out_dev receives outputs [m_first, m_first + nout) of channel b at out_dev + 2 * b * plane
+// floats (plane >= nout pairs; not read when nch == 1).  nch == 1 runs k0_frontend<T, false>, nch > 1 <T, true>.
+extern "C" int uwspr_debug_frontend_launch(uwspr_ctx *c, const void *audio_dev, int format, int nin, long long in0, int nch,
+                                           float *out_dev, int nout, long long m_first, long long plane) {
+  int rc = ready(c);
+  if (rc) return rc;
+  if (!audio_dev || !out_dev || nin < 1 || nout < 1 || nch < 1 || nch > UWSPR_PIPE_MAX_CHANNELS ||
+      (format != UWSPR_AUDIO_F32 && format != UWSPR_AUDIO_S16) || (nch > 1 && plane < nout))
+    return fail(c, UWSPR_ERR_ARG, "uwspr_debug_frontend_launch: audio/out/format %d/nin %d/nout %d/nch %d/plane %lld", format, nin, nout, nch, plane);
+  if ((rc = frontend_taps(c))) return rc;
+  launch_frontend_stream(c->stream, audio_dev, format == UWSPR_AUDIO_S16, nin, in0, c->d_fe_taps, c->fe_J, c->fe_dcols, out_dev,
+                         nout, m_first, nch, plane);
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return UWSPR_OK;
 }
 
 // diagnostics (not part of the ABI header): rows [first, first + n) of the context's OWN metric and soft-symbol buffers

@@ -140,6 +140,18 @@ def _close(got, ref):
     return np.abs(z - ref).max() / np.abs(ref).max()
 
 
+# 64 outputs of a full-size record: its first, a workgroup seam in its middle (40 x 512), its last
+EXACT_64 = np.concatenate([np.arange(16), np.arange(20464, 20496), np.arange(44984, 45000)])
+
+
+def _restated(G, mode, x):
+    """the outputs EXACT_64 of record x as the kernel's own binary32 sums give them (tests/frontend_exact.py, which
+    tests/test_gpu_frontend_exact.py holds K0 to at small shapes): ties the full-size record to those"""
+    import frontend_exact
+    g, D = G.frontend_design(mode, 0)
+    return frontend_exact.restate(g.astype(np.complex64), D, x, 0, EXACT_64)
+
+
 @pytest.mark.gpu
 def test_kernel_matches_the_float64_chain(G, FE):
     """uwspr_frontend_batch (grc mode, the default) against the oracle's stage-by-stage chain: white noise (a full
@@ -163,6 +175,7 @@ def test_kernel_matches_the_float64_chain(G, FE):
     assert _close(ys[0], FE.chain(x[0, :500000])) <= TOL
     assert not ys[0, (500000 + 6831) // 32 + 1:].any()      # nothing after the last tap has left the record
     assert _close(yr[0], FE.chain(rec)) <= TOL
+    assert y[0][EXACT_64].tobytes() == _restated(G, G.FRONTEND_GRC, x[0]).tobytes()
 
 
 @pytest.mark.gpu
@@ -187,6 +200,7 @@ def test_compact_kernel_matches_its_float64_formula(G):
     g0, _ = G.frontend_design(G.FRONTEND_GRC, 0)
     ref0 = ss.oaconvolve(x[0].astype(np.float64), g0)[:x.shape[1]][::32][:45000]
     assert _close(y0[0], ref0) <= TOL
+    assert y[0][EXACT_64].tobytes() == _restated(G, G.FRONTEND_COMPACT, x[0]).tobytes()
 
 
 @pytest.mark.gpu
