@@ -205,6 +205,67 @@ class Context:
         self._chk(f(self.h, C.c_void_p(audio.data_ptr()), fmt, nin, int(in0), nch, C.c_void_p(out.data_ptr()), nout,
                     int(m_first), plane))
 
+    # -- resampler (K11) ----------------------------------------------------
+    def resample(self, audio, rate, nout=None):
+        """Audio at `rate` S/s -> 12 kS/s float32 (uwspr_resample_batch): a 1-D [n] or 2-D [n, C] numpy float32 or
+        int16 array (zero outside it) -> [nout] or [nout, C]; nout defaults to ceil(n * 12000 / rate), the outputs
+        whose audio time lies inside the record.  A contiguous torch CUDA tensor of those shapes and types stays on the
+        device (-> a CUDA tensor)."""
+        if _is_torch(audio):
+            import torch
+            fmt = {torch.float32: N.AUDIO_F32, torch.int16: N.AUDIO_S16}.get(audio.dtype)
+            if fmt is None or audio.dim() not in (1, 2) or not audio.is_cuda or not audio.is_contiguous() or audio.shape[0] < 1:
+                raise TypeError("resample: a contiguous [n] or [n, C] float32 or int16 CUDA tensor, not %s %s" %
+                                (audio.dtype, tuple(audio.shape)))
+            nch = 1 if audio.dim() == 1 else audio.shape[1]
+            if nout is None:
+                nout = -(-audio.shape[0] * AUDIO_RATE // int(rate))
+            out = torch.empty((int(nout),) + tuple(audio.shape[1:]), dtype=torch.float32, device=audio.device)
+            if self._stream_ptr is None:
+                torch.cuda.current_stream(audio.device).synchronize()
+            self._chk(self.L.uwspr_resample_batch(self.h, C.c_void_p(audio.data_ptr()), audio.shape[0], nch, fmt, int(rate),
+                                                  N.DEVICE, C.c_void_p(out.data_ptr()), int(nout)))
+            if self._stream_ptr is None:
+                self.synchronize()
+            return out
+        a = np.asarray(audio)
+        if a.ndim not in (1, 2) or a.dtype not in (np.float32, np.int16) or a.shape[0] < 1:
+            raise TypeError("resample: a [n] or [n, C] float32 or int16 array, not %s %s" % (a.dtype, a.shape))
+        a = np.ascontiguousarray(a)
+        nch = 1 if a.ndim == 1 else a.shape[1]
+        if nout is None:
+            nout = -(-a.shape[0] * AUDIO_RATE // int(rate))
+        out = np.empty((int(nout),) + a.shape[1:], np.float32)
+        self._chk(self.L.uwspr_resample_batch(self.h, C.c_void_p(a.ctypes.data), a.shape[0], nch,
+                                              N.AUDIO_S16 if a.dtype == np.int16 else N.AUDIO_F32, int(rate), N.HOST,
+                                              C.c_void_p(out.ctypes.data), int(nout)))
+        return out
+
+    def debug_resample_launch(self, audio, rate, in0, out, j_first, nch=1, nin=None, nout=None):
+        """diagnostics: ONE launch of K11 (uwspr_debug_resample_launch) on torch CUDA tensors.  audio: float32 or int16,
+        frames [in0, in0 + nin) of nch interleaved samples (nin defaults to all of it); out: float32, receives outputs
+        [j_first, j_first + nout) as [nout, nch] (nout defaults to what it holds).  The input format picks the kernel's
+        instantiation.  The tensors must hold what the launch reads and writes: checked here."""
+        import torch
+        fmt = {torch.float32: N.AUDIO_F32, torch.int16: N.AUDIO_S16}.get(audio.dtype)
+        if fmt is None or not audio.is_cuda or not audio.is_contiguous():
+            raise TypeError("debug_resample_launch: a contiguous float32 or int16 CUDA tensor, not %s" % audio.dtype)
+        if out.dtype != torch.float32 or not out.is_cuda or not out.is_contiguous():
+            raise TypeError("debug_resample_launch: out is a contiguous float32 CUDA tensor, not %s" % out.dtype)
+        nch = int(nch)
+        nin = audio.numel() // nch if nin is None else int(nin)
+        nout = out.numel() // nch if nout is None else int(nout)
+        if nin * nch > audio.numel() or nout * nch > out.numel():
+            raise ValueError("debug_resample_launch: nin %d / nout %d x nch %d do not fit the tensors" % (nin, nout, nch))
+        f = self.L.uwspr_debug_resample_launch
+        f.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_longlong, C.c_longlong, C.c_int, C.c_int, C.c_void_p,
+                      C.c_longlong, C.c_longlong]
+        f.restype = C.c_int
+        if self._stream_ptr is None:
+            torch.cuda.current_stream(audio.device).synchronize()
+        self._chk(f(self.h, C.c_void_p(audio.data_ptr()), fmt, nin, int(in0), nch, int(rate), C.c_void_p(out.data_ptr()),
+                    nout, int(j_first)))
+
     # -- FDR ---------------------------------------------------------------
     def fdr_batch(self, frames):
         """-> list (per frame) of candidate record arrays, FDR_impl.cc:214-456."""
@@ -803,6 +864,29 @@ def frontend_design(mode=FRONTEND_GRC, stage=0):
     return g
 
 
+def resample_design(rate):
+    """uwspr_resample_design: the prototype low-pass of the resampler for `rate` S/s -> (taps float64 [N], L, M, T, D);
+    ValueError for an unsupported rate."""
+    L = N.lib()
+    v = [C.c_int(0) for _ in range(4)]
+    n = L.uwspr_resample_design(int(rate), None, 0, *[C.byref(q) for q in v])
+    if n < 0:
+        raise ValueError("audio rate %d S/s is not supported (8000 .. 192000 S/s with 12000 / gcd(rate, 12000) <= 160)" % int(rate))
+    taps = np.zeros(n, np.float64)
+    L.uwspr_resample_design(int(rate), C.c_void_p(taps.ctypes.data), n, *[C.byref(q) for q in v])
+    return (taps,) + tuple(q.value for q in v)
+
+
+def resample_launch_counts():
+    """diagnostics: launches of K11 since the process started -> (with float32 input, with int16 input)"""
+    f = N.lib().uwspr_debug_resample_counts
+    f.argtypes = [C.c_void_p]
+    f.restype = C.c_int
+    out = np.zeros(2, np.int64)
+    f(C.c_void_p(out.ctypes.data))
+    return int(out[0]), int(out[1])
+
+
 def c2_read(path):
     iq = np.zeros((45000, 2), np.float32)
     freq, typ = C.c_double(), C.c_int32()
@@ -1007,7 +1091,7 @@ class Pipe:
     def __init__(self, fs=375, fl=45000, spb=256, maxdrift=0, maxfreqs=200, halfbandwidth=10, cf=1500,
                  threshold=10, device=0, hop=3375, batch_frames=256, max_per_frame=1, lanes=0,
                  host_threads=0, eager=False, sched=None, spare_after_us=0, passes=1, osd=0, osd_gap=None,
-                 block=0):
+                 block=0, audio_rate=None):
         self.L = N.lib()
         self.h = C.c_void_p()
         self.fl = fl
@@ -1031,6 +1115,8 @@ class Pipe:
                 self.set_option("osd_gap", osd_gap)
             if block:         # 2, 3: block demodulation up to that length on what Fano timed out on (records with block = 2, 3)
                 self.set_option("block", block)
+            if audio_rate is not None and int(audio_rate) != AUDIO_RATE:   # push_audio takes audio at that rate (K11 ahead of the front-end)
+                self.set_option("audio_rate", audio_rate)
         except N.UwsprError:
             self.close()
             raise
@@ -1056,8 +1142,9 @@ class Pipe:
         self._chk(self.L.uwspr_pipe_push(self.h, C.c_void_p(a.ctypes.data), a.size // 2))
 
     def push_audio(self, x):
-        """12 kS/s real audio: a 1-D numpy float32 or int16 array of any length (uwspr_pipe_push_audio), or a 2-D
-        [n, C] one of C interleaved channels (uwspr_pipe_push_audio_channels; the first push fixes C)"""
+        """Real audio at the pipe's audio_rate (default 12 kS/s): a 1-D numpy float32 or int16 array of any length
+        (uwspr_pipe_push_audio), or a 2-D [n, C] one of C interleaved channels (uwspr_pipe_push_audio_channels; the
+        first push fixes C)"""
         a = np.asarray(x)
         if a.ndim == 2:
             if a.dtype not in (np.float32, np.int16):
@@ -1115,10 +1202,17 @@ class Pipe:
 AUDIO_RATE = 12000
 
 
-def read_wav(path, channels=None):
+def supported_rate(rate):
+    """whether the resampler takes audio at `rate` S/s (include/uwspr_hip.h; 12000 = no resampler)"""
+    rate = int(rate)
+    return 8000 <= rate <= 192000 and AUDIO_RATE // int(np.gcd(rate, AUDIO_RATE)) <= 160
+
+
+def read_wav(path, channels=None, any_rate=False):
     """A 16-bit PCM WAV (stdlib wave) -> (channel 0 as int16, rate); channels="all": ([n, C] int16, rate), every
     channel.  Anything else -- another sample width, a float WAV, a rate other than the front-end's 12000 S/s --
-    raises ValueError."""
+    raises ValueError.  any_rate=True: every rate the resampler supports (Pipe(audio_rate=rate) takes it); ValueError
+    naming the rate otherwise."""
     if channels not in (None, "all"):
         raise ValueError("read_wav: channels=None (channel 0) or \"all\", not %r" % (channels,))
     import wave
@@ -1130,7 +1224,9 @@ def read_wav(path, channels=None):
         width, nch, rate, n = w.getsampwidth(), w.getnchannels(), w.getframerate(), w.getnframes()
         if width != 2:
             raise ValueError("%s: %d-bit samples; 16-bit PCM only" % (path, 8 * width))
-        if rate != AUDIO_RATE:
+        if any_rate and not supported_rate(rate):
+            raise ValueError("%s: %d S/s is not a supported rate (8000 .. 192000 S/s with 12000 / gcd(rate, 12000) <= 160)" % (path, rate))
+        if rate != AUDIO_RATE and not any_rate:
             raise ValueError("%s: %d S/s; the front-end takes %d S/s" % (path, rate, AUDIO_RATE))
         raw = w.readframes(n)
     x = np.frombuffer(raw, dtype="<i2").reshape(-1, nch)
@@ -1140,17 +1236,18 @@ def read_wav(path, channels=None):
 
 
 def decode_wav(path, channels=None, **pipe_opts):
-    """Decode a 12 kS/s recording as the receiver flowgraph does (examples/AudioSourceDecode.grc): the file through a
+    """Decode a recording (12 kS/s, or any rate read_wav(any_rate=True) returns: the pipe's audio_rate is set from the
+    file) as the receiver flowgraph does (examples/AudioSourceDecode.grc): the file through a
     Pipe's push_audio -> one dict per decoded record, in frame order: frame, t (stream_pos / 375 s), the coarse freq
     and snr, the unpacked text, "pass" (1: found by the second pass of passes=2, under a decoded signal; else 0) and
     "osd" (1: Fano timed out and ordered-statistics decoding gave the message, osd=1 or 2; else 0) and "block" (2, 3: Fano
     timed out and the soft symbols coherent over that many symbols decoded, block=2 or 3; else 0).
     channels="all": every channel of the file through one pipe, records in (take, channel, frame) order, each dict with
     its "channel"."""
-    x, _ = read_wav(path, channels)
-    pipe = Pipe(**pipe_opts)
+    x, rate = read_wav(path, channels, any_rate=True)
+    pipe = Pipe(audio_rate=rate, **pipe_opts)
     try:
-        piece = 12000 * 60
+        piece = rate * 60
         for k in range(0, x.shape[0], piece):
             pipe.push_audio(x[k:k + piece])
         pipe.flush()

@@ -158,7 +158,7 @@ __global__ __launch_bounds__(K0_WG) void k0_frontend(const T *__restrict__ audio
 
 // ---------------------------------------------------------------- tap designs (host, binary64)
 // GNU Radio 3.7 gr-fft/lib/window.cc
-static double gr_izero(double x) {             // Izero(): I0 by its power series, terms down to 1e-21 of the sum
+double gr_izero(double x) {             // Izero(): I0 by its power series, terms down to 1e-21 of the sum
   double sum = 1.0, u = 1.0;
   const double halfx = x / 2.0;
   int n = 1;

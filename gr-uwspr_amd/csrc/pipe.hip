@@ -100,6 +100,7 @@ struct uwspr_pipe {
   int passes = 1;   // uwspr_pipe_set_option("passes"): 2 = subtract what decoded and search the residual again
   int osd = 0, osd_gap = UWSPR_OSD_GAP_DEFAULT;   // uwspr_pipe_set_option("osd" / "osd_gap"): K9 on what Fano timed out on
   int block = 0;    // uwspr_pipe_set_option("block"): 2, 3 = K10's soft symbols of block lengths 2 .. block for those records
+  int audio_rate = 12000;   // uwspr_pipe_set_option("audio_rate"): the rate of the pushed audio (12000: no resampler, else K11 ahead of K0)
   char err[512];
   // Sticky status of the first RUNTIME failure (HIP, a lane's context), written by coordinators and the producer, read
   // by both without the lock.  Argument errors are not sticky: the call that made them returns UWSPR_ERR_ARG (with
@@ -857,27 +858,40 @@ extern "C" int uwspr_pipe_push_audio_channels(uwspr_pipe *q, const void *audio, 
   const int mode = q->lanes[0].ctx->opt[UWSPR_OPT_FRONTEND];
   if (r.kind == RING_AUDIO && mode != r.au.mode)
     return parg(q, "uwspr_pipe_push_audio: option frontend changed to %d while the audio stream runs in mode %d", mode, r.au.mode);
+  // option "audio_rate": latched like the front-end mode; any other rate than 12000 goes through K11 first
+  const int rate = q->audio_rate;
+  const bool rs_on = rate != 12000;
+  const int running = r.kind == RING_AUDIO ? (r.rs.rate ? r.rs.rate : 12000) : 0;
+  if (running && rate != running)
+    return parg(q, "uwspr_pipe_push_audio: option audio_rate changed to %d while the audio stream runs at %d S/s", rate, running);
   (void)hipSetDevice(q->device);
   if (const int rc = open_ingest(q, nchannels)) return rc;
-  if (r.kind != RING_AUDIO && !r.audio_latch(mode, s16))
+  if (r.kind != RING_AUDIO && rs_on && !r.resample_latch(rate, s16))
+    return pfail(q, r.err == hipErrorOutOfMemory ? UWSPR_ERR_NOMEM : UWSPR_ERR_HIP, "resampler set-up (%d S/s, %d channels): %s",
+                 rate, nchannels, hipGetErrorString(r.err));
+  if (r.kind != RING_AUDIO && !r.audio_latch(mode, s16 && !rs_on))
     return pfail(q, r.err == hipErrorOutOfMemory ? UWSPR_ERR_NOMEM : UWSPR_ERR_HIP, "audio stream set-up (%d channels): %s",
                  nchannels, hipGetErrorString(r.err));
   const size_t es = (s16 ? 2 : 4) * (size_t)nchannels;   // bytes per frame
   size_t piece = q->stage_samples * 2 * sizeof(float) / es;
   // several channels: whole K0 workgroups per piece (32 * 512 frames), so a launch has no ragged last output block
   constexpr size_t kBlockFrames = 32 * 512;
-  if (nchannels > 1 && piece >= kBlockFrames) piece = piece / kBlockFrames * kBlockFrames;
+  if (!rs_on && nchannels > 1 && piece >= kBlockFrames) piece = piece / kBlockFrames * kBlockFrames;
+  // a rate below 12000 makes more 12 kS/s samples than it is given: a piece yields no more of them than a 12 kS/s piece
+  if (rs_on && r.rs.pl.L > r.rs.pl.M) piece = piece * (size_t)r.rs.pl.M / (size_t)r.rs.pl.L;
+  if (piece < 1) piece = 1;
   for (size_t off = 0; off < (size_t)nframes;) {
     const size_t n = (size_t)nframes - off < piece ? (size_t)nframes - off : piece;
     const int s = q->stage_next;
     if (q->stage_busy[s]) { PHIP(q, hipEventSynchronize(q->stage_ev[s])); q->stage_busy[s] = false; }
     memcpy(q->h_stage[s], (const char *)audio + off * es, n * es);
-    const size_t nout = (size_t)r.audio_outputs(n, mode);
+    const size_t nout = (size_t)r.audio_outputs((size_t)r.resample_outputs(n, rate), mode);   // (12 kS/s samples the piece makes)
     while (r.have + nout > r.cap && r.ready() > 0) {
       const int rc = launch_from_ring(q, r.ready() < q->o.batch_frames ? r.ready() : q->o.batch_frames);
       if (rc) return rc;
     }
-    if (!r.push_audio(q->h_stage[s], n, s16, false)) return pfail(q, UWSPR_ERR_HIP, "audio stream: %s", hipGetErrorString(r.err));
+    if (!(rs_on ? r.push_resampled(q->h_stage[s], n, s16, false) : r.push_audio(q->h_stage[s], n, s16, false)))
+      return pfail(q, UWSPR_ERR_HIP, "audio stream: %s", hipGetErrorString(r.err));
     PHIP(q, hipEventRecord(q->stage_ev[s], r.copy));
     q->stage_busy[s] = true;
     q->stage_next = (s + 1) % uwspr_pipe::NSTAGE;
@@ -928,6 +942,15 @@ extern "C" int uwspr_pipe_set_option(uwspr_pipe *q, const char *name, int value)
     for (auto &L : q->lanes)
       if (L.busy) { snprintf(q->err, sizeof(q->err), "uwspr_pipe_set_option(%s): batches in flight (flush first)", name); return UWSPR_ERR_ARG; }
     (gap ? q->osd_gap : q->osd) = value;
+    return UWSPR_OK;
+  }
+  if (!strcmp(name, "audio_rate")) {   // the pipe's own: the rate of the audio its pushes carry, latched by the first push
+    resample_plan pl;
+    if (resample_design(value, pl)) return parg(q, "uwspr_pipe_set_option: \"audio_rate\" = %d is not a supported rate", value);
+    if (q->ring.kind == RING_AUDIO && value != (q->ring.rs.rate ? q->ring.rs.rate : 12000))
+      return parg(q, "uwspr_pipe_set_option: \"audio_rate\" = %d while the audio stream runs at %d S/s", value,
+                  q->ring.rs.rate ? q->ring.rs.rate : 12000);
+    q->audio_rate = value;
     return UWSPR_OK;
   }
   if (!strcmp(name, "block")) {   // the pipe's own: K10's block soft symbols for the records Fano gave up on

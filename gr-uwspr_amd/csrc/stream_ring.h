@@ -35,6 +35,16 @@ void launch_frontend_stream(hipStream_t s, const void *audio, bool s16, int nin,
                             int J, int dcols, float *out, int nout, long long m_first, int nch, long long plane);
 void launch_widen_s16(hipStream_t s, const int16_t *in, float *out, size_t n);
 
+// K11, the rational resampler ahead of K0 (k11_resample.hip; the definition: include/uwspr_hip.h)
+struct resample_plan {
+  int rate = 0, L = 0, M = 0, T = 0, N = 0, D = 0;
+  std::vector<double> h;               // T * L taps in binary64 (zero from N on)
+};
+int resample_design(int rate, resample_plan &out);
+void resample_tap_image(const resample_plan &pl, std::vector<float> &img, int *TP);
+hipError_t launch_resample(hipStream_t s, const void *audio, bool s16, long long nin, long long in0, int nch, const float *taps,
+                           const resample_plan &pl, int TP, float *out, long long nout, long long j_first);
+
 enum { RING_EMPTY = 0, RING_IQ = 1, RING_AUDIO = 2 };   // what the stream is, decided by its first push
 
 struct stream_ring {
@@ -75,6 +85,26 @@ struct stream_ring {
     size_t hist = 0;                   // frames held in d_buf[cur]: audio [a0, a0 + hist)
     long long m_next = 0;              // stream index of the next output
   } au;
+  // Audio at another rate (option "audio_rate" != 12000): the pushed frames go through K11 into a device buffer of
+  // 12 kS/s float frames, which push_audio takes as a device source on the same stream.  Output j of the resampler is
+  // complete as soon as input floor((j M + D) / L) has been pushed; the device buffer holds [history | new frames], the
+  // history being the inputs from floor((j_next M + D) / L) - (T - 1) on (at most T - 1 frames, zero before the first).
+  // Counters restart at 0 with every open / reset: K0 sees output j as 12 kS/s sample 32 pos + j.
+  struct resample_state {
+    int rate = 0;                      // latched by the first audio push after open / reset (0: none yet; 12000: no resampler)
+    int taps_rate = 0, TP = 0;
+    resample_plan pl;                  // of taps_rate
+    float *d_taps = nullptr;           // [L][TP]
+    int s16 = 0;                       // the input buffer holds int16 frames (every push so far was int16)
+    char *d_in[2] = {nullptr, nullptr};
+    size_t in_bytes = 0;
+    int cur = 0;
+    long long i_base = 0;              // input index of d_in[cur][0]
+    size_t hist = 0;                   // frames held: inputs [i_base, i_base + hist)
+    long long n_in = 0, j_next = 0;    // inputs pushed, next output
+    float *d_out = nullptr;            // [out_frames][nch]
+    size_t out_frames = 0;
+  } rs;
   // most new samples per K0 launch: AUDIO_PIECE / nch frames (one channel: 131072 outputs, 256 workgroups), so the
   // history buffers hold at most (32 J + 32) nch + AUDIO_PIECE samples whatever the channel count
   static constexpr size_t AUDIO_PIECE = 4u << 20;
@@ -91,6 +121,10 @@ struct stream_ring {
     for (int k = 0; k < 2; k++) if (au.d_buf[k]) { (void)hipFree(au.d_buf[k]); au.d_buf[k] = nullptr; }
     if (au.d_taps) { (void)hipFree(au.d_taps); au.d_taps = nullptr; }
     au = audio_state();
+    for (int k = 0; k < 2; k++) if (rs.d_in[k]) (void)hipFree(rs.d_in[k]);
+    if (rs.d_out) (void)hipFree(rs.d_out);
+    if (rs.d_taps) (void)hipFree(rs.d_taps);
+    rs = resample_state();
     if (copy) { (void)hipStreamDestroy(copy); copy = nullptr; }
     cap = 0; plane = 0; nch = 1; have = 0; base = 0; up_pending = false;
   }
@@ -122,7 +156,7 @@ struct stream_ring {
   // drop what is buffered.  Kernels may still be reading views of the current buffer, so the next append
   // goes through make_room() (base = cap: nothing fits) to the OTHER buffer, behind its readers.
   // An audio stream starts again at audio index 32 p with a zero history.
-  void reset(long long p) { have = 0; base = cap; pos = p; kind = RING_EMPTY; au.mode = -1; au.m_next = p; }
+  void reset(long long p) { have = 0; base = cap; pos = p; kind = RING_EMPTY; au.mode = -1; au.m_next = p; rs.rate = 0; }
 
   // make space for n more samples behind the unconsumed ones
   bool make_room(size_t n) {
@@ -290,6 +324,122 @@ struct stream_ring {
       }
       off += k;
     }
+    if (n && (err = hipEventRecord(ev_up, copy)) != hipSuccess) return false;
+    if (n) up_pending = true;
+    return true;
+  }
+
+  // ---- audio at another rate (K11 ahead of K0)
+  // one past the last resampler output that n_in pushed inputs complete
+  static long long resample_complete(long long n_in, const resample_plan &pl) {
+    const long long t = n_in * pl.L - 1 - pl.D;
+    return t >= 0 ? t / pl.M + 1 : 0;
+  }
+  // 12 kS/s samples a push of n frames at `rate` would add (rate: the latched one, or the one the push would latch);
+  // -1: the rate is not supported
+  long long resample_outputs(size_t n, int rate) const {
+    if (rate == 12000) return (long long)n;
+    resample_plan tmp;
+    const resample_plan *pl = &rs.pl;
+    if (rs.taps_rate != rate) { if (resample_design(rate, tmp)) return -1; pl = &tmp; }
+    const bool running = rs.rate == rate;
+    const long long j = resample_complete((running ? rs.n_in : 0) + (long long)n, *pl);
+    const long long jn = running ? rs.j_next : 0;
+    return j > jn ? j - jn : 0;
+  }
+  // most input frames per K11 launch: its outputs fit d_out (audio_piece_frames() frames, one K0 piece) whatever L / M is
+  size_t resample_piece_frames() const {
+    const size_t outp = audio_piece_frames();
+    const size_t by_out = (size_t)((long long)(outp - 2) * rs.pl.M / rs.pl.L);
+    return by_out < outp ? by_out : outp;
+  }
+
+  // The first audio push after open / reset at a rate other than 12000: taps and buffers of `rate`, zero history,
+  // counters at 0.  (The caller latches K0's side with audio_latch(mode, false): the resampler delivers float frames.)
+  bool resample_latch(int rate, bool s16) {
+    if (rs.taps_rate != rate) {
+      resample_plan pl;
+      std::vector<float> img;
+      int TP = 0;
+      if (resample_design(rate, pl)) { err = hipErrorInvalidValue; return false; }
+      resample_tap_image(pl, img, &TP);
+      if ((err = hipStreamSynchronize(copy)) != hipSuccess) return false;   // (launches with the old taps)
+      if (rs.d_taps) { (void)hipFree(rs.d_taps); rs.d_taps = nullptr; rs.taps_rate = 0; }
+      if ((err = hipMalloc((void **)&rs.d_taps, img.size() * sizeof(float))) != hipSuccess) { rs.d_taps = nullptr; return false; }
+      if ((err = hipMemcpy(rs.d_taps, img.data(), img.size() * sizeof(float), hipMemcpyHostToDevice)) != hipSuccess) return false;
+      rs.taps_rate = rate; rs.pl = pl; rs.TP = TP;
+    }
+    const size_t C = (size_t)nch, outp = audio_piece_frames();
+    const size_t need = ((size_t)rs.pl.T + resample_piece_frames()) * C * sizeof(float);
+    if (rs.in_bytes < need || rs.out_frames < outp) {
+      if ((err = hipStreamSynchronize(copy)) != hipSuccess) return false;
+      for (int k = 0; k < 2; k++) {
+        if (rs.d_in[k]) { (void)hipFree(rs.d_in[k]); rs.d_in[k] = nullptr; }
+        rs.in_bytes = 0;
+        if ((err = hipMalloc((void **)&rs.d_in[k], need)) != hipSuccess) { rs.d_in[k] = nullptr; return false; }
+      }
+      rs.in_bytes = need;
+      if (rs.d_out) { (void)hipFree(rs.d_out); rs.d_out = nullptr; }
+      rs.out_frames = 0;
+      if ((err = hipMalloc((void **)&rs.d_out, outp * C * sizeof(float))) != hipSuccess) { rs.d_out = nullptr; return false; }
+      rs.out_frames = outp;
+    }
+    rs.rate = rate; rs.s16 = s16;
+    rs.i_base = 0; rs.hist = 0; rs.n_in = 0; rs.j_next = 0;   // (inputs before 0 read as zero in the kernel)
+    return true;
+  }
+
+  // n frames of nch samples at the latched rate: behind the resampler's history, K11 for the outputs that became
+  // complete, those into push_audio as a device source on the copy stream.  Formats mix as in push_audio.  The caller
+  // has latched both sides and checked room() against audio_outputs(resample_outputs(n)).
+  bool push_resampled(const void *src, size_t n, bool s16_in, bool on_device, hipEvent_t src_ready = nullptr) {
+    const size_t C = (size_t)nch;
+    bool direct = false;
+    if (n && rs.s16 && !s16_in) {
+      launch_widen_s16(copy, (const int16_t *)rs.d_in[rs.cur], (float *)rs.d_in[rs.cur ^ 1], rs.hist * C);
+      if ((err = hipGetLastError()) != hipSuccess) return false;
+      rs.cur ^= 1; rs.s16 = 0;
+    }
+    const bool widen = s16_in && !rs.s16;
+    const size_t es = (rs.s16 ? 2 : 4) * C, es_in = (s16_in ? 2 : 4) * C;
+    const size_t piece = resample_piece_frames();
+    for (size_t off = 0; off < n;) {
+      const size_t k = n - off < piece ? n - off : piece;
+      char *b = rs.d_in[rs.cur];
+      last_direct = false;
+      if (widen) {
+        char *tmp = rs.d_in[rs.cur ^ 1];
+        if (!upload(tmp, (const char *)src + off * es_in, k * es_in, on_device, src_ready)) return false;
+        launch_widen_s16(copy, (const int16_t *)tmp, (float *)(b + rs.hist * es), k * C);
+        if ((err = hipGetLastError()) != hipSuccess) return false;
+      } else if (!upload(b + rs.hist * es, (const char *)src + off * es_in, k * es_in, on_device, src_ready)) {
+        return false;
+      }
+      direct = direct || last_direct;
+      rs.n_in += (long long)k;
+      const long long j_end = resample_complete(rs.n_in, rs.pl);
+      if (j_end > rs.j_next) {
+        const long long nout = j_end - rs.j_next;
+        if ((size_t)nout > rs.out_frames) { err = hipErrorInvalidValue; return false; }
+        if ((err = launch_resample(copy, b, rs.s16 != 0, (long long)(rs.hist + k), rs.i_base, nch, rs.d_taps, rs.pl, rs.TP,
+                                   rs.d_out, nout, rs.j_next)) != hipSuccess) return false;
+        rs.j_next = j_end;
+        if (!push_audio(rs.d_out, (size_t)nout, false, true, nullptr)) return false;
+      }
+      // keep the inputs the next output's window starts at
+      long long keep = (rs.j_next * rs.pl.M + rs.pl.D) / rs.pl.L - (rs.pl.T - 1);
+      if (keep > rs.n_in) keep = rs.n_in;
+      if (keep < rs.i_base) keep = rs.i_base;
+      const size_t nh = (size_t)(rs.n_in - keep);
+      if (keep != rs.i_base) {   // the tail to the front of the other buffer
+        if (nh && (err = hipMemcpyAsync(rs.d_in[rs.cur ^ 1], b + (size_t)(keep - rs.i_base) * es, nh * es,
+                                        hipMemcpyDeviceToDevice, copy)) != hipSuccess) return false;
+        rs.cur ^= 1; rs.i_base = keep;
+      }
+      rs.hist = nh;
+      off += k;
+    }
+    last_direct = direct;
     if (n && (err = hipEventRecord(ev_up, copy)) != hipSuccess) return false;
     if (n) up_pending = true;
     return true;

@@ -104,6 +104,7 @@ static const struct { const char *name; int dflt, lo, hi; } kOptions[UWSPR_NOPT]
     {"dist_force_comm", 0, 0, 1},   // tests: a one-rank communicator is really created
     {"frontend", 0, 0, 1},          // K0: 0 the flowgraph's GNU Radio chain as one polyphase FIR (grc:303-400,840-956,1767-1808), 1 compact single stage
     {"k4_forms", 1, 0, 255},        // staged form: bit 0 = S5 (k4_ring<6,8>) keeps its sample pairs in a register ring
+    {"audio_rate", 12000, 8000, 192000},   // uwspr_stream_push_audio: the rate of the pushed audio (12000: no resampler, else K11 ahead of K0)
 };
 
 static void refresh_options(uwspr_ctx *c) {
@@ -132,6 +133,11 @@ extern "C" int uwspr_set_option(uwspr_ctx *c, const char *name, int value) {
     return fail(c, UWSPR_ERR_ARG, "option '%s' shapes the context when it is created: UWSPR_OPTIONS=%s=%d", name, name, value);
   if (value < kOptions[i].lo || value > kOptions[i].hi)
     return fail(c, UWSPR_ERR_ARG, "option '%s' = %d: allowed %d .. %d", name, value, kOptions[i].lo, kOptions[i].hi);
+  if (i == UWSPR_OPT_AUDIO_RATE) {
+    resample_plan pl;
+    if (resample_design(value, pl))
+      return fail(c, UWSPR_ERR_ARG, "option 'audio_rate' = %d: not a supported rate (12000 / gcd(rate, 12000) <= 160)", value);
+  }
   c->opt[i] = value; c->opt_set[i] = true;
   refresh_options(c);
   return UWSPR_OK;
@@ -211,6 +217,7 @@ extern "C" int uwspr_ctx_create(const uwspr_params *p, int device, uwspr_ctx **o
   c->sub = nullptr;
   c->osd = nullptr;
   c->blk = nullptr;
+  c->rs = nullptr;
   c->dist_comm = nullptr; c->dist_rank = 0; c->dist_world = 0;
   c->cap_tmpc = 0; c->d_tmpc = nullptr; c->cap_tmpn = 0; c->d_tmpn = nullptr;
   c->h_pin = nullptr; c->pin_busy[0] = c->pin_busy[1] = false;
@@ -377,6 +384,7 @@ extern "C" void uwspr_ctx_destroy(uwspr_ctx *c) {
   sub_release(c);
   osd_release(c);
   blk_release(c);
+  rs_release(c);
   void *bufs[] = {c->d_window, c->d_twiddle, c->d_k3_tile, c->d_off, c->d_umap, c->d_fe_taps, c->d_audio, c->d_frames, c->d_ps, c->d_psavg, c->d_smraw,
                   c->d_smspec, c->d_noise, c->d_cands, c->d_npk, c->d_work, c->d_syncgrid, c->d_hyps, c->d_grps, c->d_cent,
                   c->d_abi_hyps, c->d_p, c->d_sync, c->d_sym, c->d_state, c->d_dout, c->d_slab, c->d_tabs, c->d_counter, c->d_sched_stamps, c->d_pwin, c->d_ptab, c->d_need, c->d_stream_frames, c->d_tmpc, c->d_tmpn};
@@ -569,6 +577,31 @@ extern "C" int uwspr_frontend_design(int mode, int stage, double *taps, int cap,
     for (int i = 0; i < k; i++) taps[i] = g[i];
   }
   return n;
+}
+
+// -------------------------------------------------------------- resampler (K11)
+extern "C" int uwspr_resample_design(int rate, double *taps, int cap, int *L, int *M, int *T, int *delay) {
+  resample_plan pl;
+  const int rc = resample_design(rate, pl);
+  if (rc) return rc;
+  if (L) *L = pl.L;
+  if (M) *M = pl.M;
+  if (T) *T = pl.T;
+  if (delay) *delay = pl.D;
+  if (taps)
+    for (int i = 0; i < pl.N && i < cap; i++) taps[i] = pl.h[i];
+  return pl.N;
+}
+
+extern "C" int uwspr_resample_batch(uwspr_ctx *c, const void *audio, long long nin, int nchannels, int format, int rate, int where,
+                                    float *out, long long nout) {
+  int rc = ready(c);
+  if (rc) return rc;
+  if (!audio || !out || nin <= 0 || nout <= 0 || nchannels < 1 || nchannels > UWSPR_PIPE_MAX_CHANNELS ||
+      (format != UWSPR_AUDIO_F32 && format != UWSPR_AUDIO_S16))
+    return fail(c, UWSPR_ERR_ARG, "uwspr_resample_batch: audio/out/nin %lld/nout %lld/nchannels %d/format %d", nin, nout, nchannels, format);
+  if (where != UWSPR_HOST && where != UWSPR_DEVICE) return fail(c, UWSPR_ERR_ARG, "where=%d", where);
+  return rs_batch(c, audio, nin, nchannels, format == UWSPR_AUDIO_S16, rate, where, out, nout);
 }
 
 // -------------------------------------------------------------------- FDR
@@ -1054,18 +1087,30 @@ extern "C" int uwspr_stream_push_audio(uwspr_ctx *c, const void *audio, int nsam
   if (nsamples > 0 && r.kind == RING_IQ) return fail(c, UWSPR_ERR_ARG, "uwspr_stream_push_audio on an (I,Q) stream (reset it first)");
   if (nsamples > 0 && r.kind == RING_AUDIO && mode != r.au.mode)
     return fail(c, UWSPR_ERR_ARG, "option frontend changed to %d while the audio stream runs in mode %d (reset it first)", mode, r.au.mode);
-  const long long nout = r.audio_outputs((size_t)nsamples, mode);
+  // option "audio_rate": latched like the front-end mode; any other rate than 12000 goes through K11 first
+  const int rate = c->opt[UWSPR_OPT_AUDIO_RATE];
+  const int running = r.kind == RING_AUDIO ? (r.rs.rate ? r.rs.rate : 12000) : 0;
+  if (nsamples > 0 && running && rate != running)
+    return fail(c, UWSPR_ERR_ARG, "option audio_rate changed to %d while the audio stream runs at %d S/s (reset it first)", rate, running);
+  const long long n12 = r.resample_outputs((size_t)nsamples, rate);
+  if (n12 < 0) return fail(c, UWSPR_ERR_ARG, "option audio_rate = %d: not a supported rate", rate);
+  const bool rs_on = rate != 12000;
+  const long long nout = r.audio_outputs((size_t)n12, mode);
   if (r.have + (size_t)nout > r.cap)
     return fail(c, UWSPR_ERR_ARG, "stream buffer full (%zu + %lld > %zu samples): take frames first", r.have, nout, r.cap);
   if (nsamples > 0) {
-    if (r.kind != RING_AUDIO && !r.audio_latch(mode, format == UWSPR_AUDIO_S16))
+    const bool s16 = format == UWSPR_AUDIO_S16;
+    if (r.kind != RING_AUDIO && rs_on && !r.resample_latch(rate, s16))
+      return fail(c, r.err == hipErrorOutOfMemory ? UWSPR_ERR_NOMEM : UWSPR_ERR_HIP, "resampler set-up (%d S/s): %s", rate, hipGetErrorString(r.err));
+    if (r.kind != RING_AUDIO && !r.audio_latch(mode, s16 && !rs_on))
       return fail(c, UWSPR_ERR_HIP, "audio stream set-up: %s", hipGetErrorString(r.err));
     bool ok;
     if (where == UWSPR_DEVICE) {   // produced by work on the context's stream
       HIPCHK(c, hipEventRecord(c->ring_ev, c->stream));
-      ok = r.push_audio(audio, (size_t)nsamples, format == UWSPR_AUDIO_S16, true, c->ring_ev);
+      ok = rs_on ? r.push_resampled(audio, (size_t)nsamples, s16, true, c->ring_ev)
+                 : r.push_audio(audio, (size_t)nsamples, s16, true, c->ring_ev);
     } else {
-      ok = r.push_audio(audio, (size_t)nsamples, format == UWSPR_AUDIO_S16, false);
+      ok = rs_on ? r.push_resampled(audio, (size_t)nsamples, s16, false) : r.push_audio(audio, (size_t)nsamples, s16, false);
       if (ok && where == UWSPR_HOST && r.last_direct) ok = r.wait_uploads();   // as uwspr_stream_push
     }
     if (!ok) return fail(c, UWSPR_ERR_HIP, "audio stream: %s", hipGetErrorString(r.err));
@@ -1307,6 +1352,29 @@ extern "C" int uwspr_debug_frontend_launch(uwspr_ctx *c, const void *audio_dev, 
                          nout, m_first, nch, plane);
   HIPCHK(c, hipGetLastError());
   HIPCHK(c, hipStreamSynchronize(c->stream));
+  return UWSPR_OK;
+}
+
+// diagnostics (not part of the ABI header): ONE launch of K11 (launch_resample, what uwspr_resample_batch and a stream's
+// push at another rate run) on device memory, with the taps of `rate`, on the context's stream, waited for.  audio_dev
+// holds frames [in0, in0 + nin) of nch interleaved samples, out_dev receives outputs [j_first, j_first + nout) of every
+// channel, [nout][nch].  The kernel has one instantiation per input format; `format` picks it.
+extern "C" int uwspr_debug_resample_launch(uwspr_ctx *c, const void *audio_dev, int format, long long nin, long long in0, int nch,
+                                           int rate, float *out_dev, long long nout, long long j_first) {
+  int rc = ready(c);
+  if (rc) return rc;
+  if (!audio_dev || !out_dev || nin < 1 || nout < 1 || nch < 1 || nch > UWSPR_PIPE_MAX_CHANNELS || in0 < -(1LL << 46) ||
+      in0 > (1LL << 46) || j_first < 0 || j_first > (1LL << 41) || nout > (1LL << 22) ||
+      (format != UWSPR_AUDIO_F32 && format != UWSPR_AUDIO_S16))
+    return fail(c, UWSPR_ERR_ARG, "uwspr_debug_resample_launch: audio/out/format %d/nin %lld/in0 %lld/nout %lld/j_first %lld/nch %d", format,
+                nin, in0, nout, j_first, nch);
+  return rs_debug_launch(c, audio_dev, format == UWSPR_AUDIO_S16, nin, in0, nch, rate, out_dev, nout, j_first);
+}
+
+// launches of K11 since the process started, per instantiation: out[0] float32 input, out[1] int16 input
+extern "C" int uwspr_debug_resample_counts(long long *out) {
+  if (!out) return UWSPR_ERR_ARG;
+  out[0] = resample_launch_count(0); out[1] = resample_launch_count(1);
   return UWSPR_OK;
 }
 

@@ -27,6 +27,7 @@ enum {
   UWSPR_OPT_DIST_FORCE_COMM,    // tests: a one-rank communicator is really created
   UWSPR_OPT_FRONTEND,           // K0 taps: 0 the flowgraph's three-stage GNU Radio chain (default), 1 the compact single stage
   UWSPR_OPT_K4_FORMS,           // staged form, bit mask of kernel forms (default: all that won their A/B): bit 0 = S5 register ring
+  UWSPR_OPT_AUDIO_RATE,         // rate of the audio uwspr_stream_push_audio takes (default 12000: no resampler; else K11 ahead of K0)
   UWSPR_NOPT
 };
 
@@ -169,6 +170,8 @@ struct osd_state;
 void osd_release(uwspr_ctx *c);  // k9_osd.hip: frees what uwspr_osd_batch / the pipe's option "osd" made
 struct blk_state;
 void blk_release(uwspr_ctx *c);  // k10_blockdemod.hip: frees what uwspr_blockdemod_batch / the pipe's option "block" made
+struct rs_state;
+void rs_release(uwspr_ctx *c);   // k11_resample.hip: frees what uwspr_resample_batch made
 
 }  // namespace uwspr
 
@@ -263,6 +266,8 @@ struct uwspr_ctx {
   uwspr::osd_state *osd;
   // block demodulation (k10_blockdemod.hip): call scratch, made by the first use
   uwspr::blk_state *blk;
+  // resampler (k11_resample.hip): the batch call's taps and staging, made by the first use
+  uwspr::rs_state *rs;
 
   int prof_mask;
   std::vector<uwspr::ev_pair> prof_events;
@@ -300,6 +305,13 @@ int frontend_tap_image(int mode, std::vector<float> &img, int *J, int *dcols);
 // firdes::low_pass(1, fs, cutoff, tw, WIN_HAMMING) as GNU Radio 3.7 designs it (binary32 taps; k0_frontend.hip)
 std::vector<float> lowpass_hamming(double fs, double cutoff, double tw);
 int frontend_prepare();
+double gr_izero(double x);   // I0 as K0's Kaiser windows compute it (k0_frontend.hip)
+// K11 (k11_resample.hip): the batch call and the one-launch door behind uwspr_resample_batch / uwspr_debug_resample_launch
+// (arguments checked by the callers); launches of the kernel per input format since the process started
+int rs_batch(uwspr_ctx *c, const void *audio, long long nin, int nch, int s16, int rate, int where, float *out, long long nout);
+int rs_debug_launch(uwspr_ctx *c, const void *audio_dev, int s16, long long nin, long long in0, int nch, int rate, float *out_dev,
+                    long long nout, long long j_first);
+long long resample_launch_count(int s16);
 void launch_frontend(uwspr_ctx *c, const float *audio, int B, int nin, float2 *out, int nout);
 void launch_spectrogram(uwspr_ctx *c, const float *frames, int B);
 void launch_spectrum(uwspr_ctx *c, int B);

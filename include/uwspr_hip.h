@@ -44,7 +44,9 @@ extern "C" {
                                     ordered-statistics decoding: uwspr_osd_result, uwspr_osd_batch, the pipe options "osd" and
                                     "osd_gap", uwspr_decode.osd (the last byte of the padding);
                                     block demodulation: uwspr_block_item, uwspr_blockdemod_batch, the pipe option "block",
-                                    uwspr_decode.block (the byte that was _pad0) */
+                                    uwspr_decode.block (the byte that was _pad0);
+                                    audio at other rates: uwspr_resample_design, uwspr_resample_batch, the option
+                                    "audio_rate" of contexts and pipes */
 
 typedef enum {
   UWSPR_OK = 0,
@@ -233,6 +235,51 @@ int uwspr_stream_reset(uwspr_ctx *ctx, long long pos);
  * wavfile_source), exactly, so pushes of either format may follow each other: the outputs are the same bytes. */
 enum { UWSPR_AUDIO_F32 = 0, UWSPR_AUDIO_S16 = 1 };
 int uwspr_stream_push_audio(uwspr_ctx *ctx, const void *audio, int nsamples, int format, int where, int *nready);
+/* ---- audio at other rates: a rational resampler ahead of the front-end (K11) ------------------------------------
+ * Sound cards and recorders deliver 44.1, 48, 96 or 192 kS/s (loggers 8, 16, 32 kS/s), the front-end takes 12 kS/s.
+ * A rate R (S/s) is supported when 8000 <= R <= 192000 and, with g = gcd(R, 12000), L = 12000 / g, M = R / g, L <= 160:
+ * 8000, 9600, 10000, 11025, 16000, 22050, 24000, 32000, 44100, 48000, 64000, 88200, 96000, 176400 and 192000 among
+ * them.  R = 12000 means "no resampler" (the design call reports the identity: one tap 1, L = M = T = 1, D = 0).
+ * The reference has no such stage; this is the project's own definition, and it is exact:
+ *   Prototype low-pass, designed on the host in binary64 at the rate F = L R: pass edge fp = 2400 Hz, stop edge
+ *   fs = min(R, 12000) - 2400 Hz, cut-off fc = (fp + fs) / 2; Kaiser window with A = 100 dB, beta = 0.1102 (A - 8.7);
+ *   dw = 2 pi (fs - fp) / F, N0 = ceil((A - 8) / (2.285 dw)) + 1, N = N0 rounded up to odd, T = ceil(N / L) taps per
+ *   phase (taps N .. T L - 1 are zero);
+ *     h[k] = (2 fc / F) sinc((2 fc / F) (k - (N - 1) / 2)) w[k],  sinc(x) = sin(pi x) / (pi x),
+ *     w[k] = I0(beta sqrt(1 - (2 k / (N - 1) - 1)^2)) / I0(beta),
+ *   scaled so that sum h = L; delay D = (N - 1) / 2.  The taps are rounded to binary32 once: hp[p][t] = (float) h[p + t L].
+ *   Output j (12 kS/s index; audio time j / 12000 s exactly, the delay being compensated):
+ *     q = j M + D (64-bit integer), i0 = floor(q / L), p = q mod L,
+ *     acc = 0; for t = T - 1 .. 0: acc = fmaf(hp[p][t], x[i0 - t], acc)      (binary32; y[j] = acc)
+ *   x being zero before the first sample (and, in the batch call, behind the last), int16 samples counting as s / 32768
+ *   exactly.  y[j] is complete as soon as x[i0] has been pushed.  One owner and one order per output: its bytes do
+ *   not depend on the batch, the launch, the channel count or the cuts of a stream.
+ * Pass band: 0 - 2400 Hz within 2.2e-5 of unity, stop band from fs on at -97.6 dB or below, for every rate above
+ * (T = 12 at 11025 S/s .. 173 at 192000 S/s, L T <= 1920).  0 - 2400 Hz is what every "frontend" mode reads (1490 -
+ * 1510 Hz, or +- 100 Hz around 1500 Hz in the compact mode): this is NOT a general-purpose 6 kHz audio resampler.
+ *   uwspr_resample_design    the design: returns the tap count N (taps may be NULL; at most cap are written) and
+ *                            L, M, T, D through the pointers that are not NULL; < 0 for an unsupported rate.
+ *   uwspr_resample_batch     a whole record: audio [nin][nchannels] interleaved (format UWSPR_AUDIO_F32 / _S16,
+ *                            1..UWSPR_PIPE_MAX_CHANNELS channels), zero outside it -> out [nout][nchannels] float,
+ *                            outputs 0 .. nout - 1.  where = UWSPR_HOST (complete on return) or UWSPR_DEVICE
+ *                            (asynchronous on the context's stream).
+ * Streams: option "audio_rate" (uwspr_set_option; default 12000) is the rate of what uwspr_stream_push_audio is given.
+ * It is latched by the first audio push after open / reset, as "frontend" is; a change while the stream runs fails that
+ * push with UWSPR_ERR_ARG (the stream is unharmed: set the old rate again and go on), an unsupported value fails
+ * uwspr_set_option with UWSPR_ERR_ARG.  At another rate than 12000 a push uploads the new frames behind the resampler's
+ * own history (at most T - 1 frames in the pushed format, widened once when the formats mix), runs K11 on the copy
+ * stream for the outputs that became complete and hands those 12 kS/s float frames to the front-end on the same
+ * stream, exactly as a device push of them would.  After open or uwspr_stream_reset(ctx, pos) the next pushed sample
+ * sits at audio time pos / 375 s, the resampler's counters restart at 0 with a zero history, and its output j is 12 kS/s
+ * sample 32 pos + j of the front-end; first_pos / 375 stays audio time in seconds.  The buffer-full check counts the
+ * 12 kS/s samples a push will produce.  With "audio_rate" = 12000 K11 never runs, none of its buffers exists, an int16
+ * stream stays int16, and every byte is what it was before this option existed.
+ * Device memory the resampler adds to a stream, made by the first push at another rate: the taps (L (T | 1) floats),
+ * two input buffers of (T + P) * nchannels samples (4 bytes) with P = min(Q, (Q - 2) M / L) frames and Q = 4 Mi /
+ * nchannels, and one output buffer of Q * nchannels floats: at most 3 x 16 MB. */
+int uwspr_resample_design(int rate, double *taps, int cap, int *L, int *M, int *T, int *delay);
+int uwspr_resample_batch(uwspr_ctx *ctx, const void *audio, long long nin, int nchannels, int format, int rate, int where,
+                         float *out, long long nout);
 /* device memory for callers without a HIP runtime of their own (the block mirror's frame hand-over) */
 int uwspr_device_alloc(size_t bytes, void **ptr);
 void uwspr_device_free(void *ptr);
@@ -470,7 +517,12 @@ int uwspr_pipe_push_audio(uwspr_pipe *pipe, const void *audio, int nsamples, int
  * buffers of nchannels planes of (ceil(lanes / nchannels) + 3) * batch_frames * hop + fl (I,Q) pairs (8 bytes; each
  * plane rounded up to 64 pairs when nchannels > 1), plus two audio buffers of ((32 J + 32) * nchannels + 4 Mi)
  * samples (4 bytes; J = 216 taps per phase in the default "grc" front-end, 32 in "compact").  Defaults (hop 3375,
- * batch_frames 256, 9 lanes): 2 x 83 MB for one channel, 2 x 28 MB per channel from 9 channels on. */
+ * batch_frames 256, 9 lanes): 2 x 83 MB for one channel, 2 x 28 MB per channel from 9 channels on.
+ * Audio at another rate: "audio_rate" is the pipe's own option (uwspr_pipe_set_option; default 12000, any rate
+ * uwspr_resample_design supports, else UWSPR_ERR_ARG), latched by the first audio push; setting another value once the
+ * audio stream runs is UWSPR_ERR_ARG.  The pieces then go through K11 and the front-end as described at
+ * uwspr_resample_batch, the pipe makes room for the 12 kS/s samples a piece will produce, and the resampler's buffers
+ * (see there) come on top of the figures above.  nframes counts frames at that rate; stream_pos / 375 stays seconds. */
 #define UWSPR_PIPE_MAX_CHANNELS 64
 int uwspr_pipe_push_audio_channels(uwspr_pipe *pipe, const void *audio, int nframes, int nchannels, int format);
 /* B frames already in device memory (frame b at frames + 2*stride*b floats, stride 0 = fl): searched as one
