@@ -266,6 +266,90 @@ class Context:
         self._chk(f(self.h, C.c_void_p(audio.data_ptr()), fmt, nin, int(in0), nch, int(rate), C.c_void_p(out.data_ptr()),
                     nout, int(j_first)))
 
+    # -- blanker (K12) ------------------------------------------------------
+    def blank(self, x, blank=24, guard=2):
+        """Impulses out of audio at any rate (uwspr_blank_batch): a 1-D [n] or 2-D [n, C] numpy float32 or int16 array
+        -> (y float32 of the same shape, med float32 [nblocks] or [nblocks, C]: the level of every complete block of
+        4096 samples, nzero int32 of that shape: the outputs of the block set to zero).  A contiguous torch CUDA tensor
+        of those shapes and types stays on the device (-> CUDA tensors)."""
+        if _is_torch(x):
+            import torch
+            fmt = {torch.float32: N.AUDIO_F32, torch.int16: N.AUDIO_S16}.get(x.dtype)
+            if fmt is None or x.dim() not in (1, 2) or not x.is_cuda or not x.is_contiguous() or x.shape[0] < 1:
+                raise TypeError("blank: a contiguous [n] or [n, C] float32 or int16 CUDA tensor, not %s %s" % (x.dtype, tuple(x.shape)))
+            nch = 1 if x.dim() == 1 else x.shape[1]
+            nb = -(-x.shape[0] // BLANK_BLOCK)
+            y = torch.empty(tuple(x.shape), dtype=torch.float32, device=x.device)
+            med = torch.empty((nb,) + tuple(x.shape[1:]), dtype=torch.float32, device=x.device)
+            nz = torch.empty((nb,) + tuple(x.shape[1:]), dtype=torch.int32, device=x.device)
+            if self._stream_ptr is None:
+                torch.cuda.current_stream(x.device).synchronize()
+            self._chk(self.L.uwspr_blank_batch(self.h, C.c_void_p(x.data_ptr()), x.shape[0], nch, fmt, N.DEVICE, int(blank),
+                                               int(guard), C.c_void_p(y.data_ptr()), C.c_void_p(med.data_ptr()),
+                                               C.c_void_p(nz.data_ptr())))
+            if self._stream_ptr is None:
+                self.synchronize()
+            return y, med, nz
+        a = np.asarray(x)
+        if a.ndim not in (1, 2) or a.dtype not in (np.float32, np.int16) or a.shape[0] < 1:
+            raise TypeError("blank: a [n] or [n, C] float32 or int16 array, not %s %s" % (a.dtype, a.shape))
+        a = np.ascontiguousarray(a)
+        nch = 1 if a.ndim == 1 else a.shape[1]
+        nb = -(-a.shape[0] // BLANK_BLOCK)
+        y = np.empty(a.shape, np.float32)
+        med = np.empty((nb,) + a.shape[1:], np.float32)
+        nz = np.empty((nb,) + a.shape[1:], np.int32)
+        self._chk(self.L.uwspr_blank_batch(self.h, C.c_void_p(a.ctypes.data), a.shape[0], nch,
+                                           N.AUDIO_S16 if a.dtype == np.int16 else N.AUDIO_F32, N.HOST, int(blank), int(guard),
+                                           C.c_void_p(y.ctypes.data), C.c_void_p(med.ctypes.data), C.c_void_p(nz.ctypes.data)))
+        return y, med, nz
+
+    def stream_blank_stats(self, channels=1):
+        """uwspr_stream_blank_stats: per channel, (samples output, samples set to zero) by the stream's blanker since
+        open / reset -> two int64 arrays [channels]; zeros when option "blank" is 0"""
+        s, z = np.zeros(int(channels), np.int64), np.zeros(int(channels), np.int64)
+        rc = self.L.uwspr_stream_blank_stats(self.h, C.c_void_p(s.ctypes.data), C.c_void_p(z.ctypes.data), int(channels))
+        if rc < 0:   # (>= 0: the stream's channel count)
+            self._chk(rc)
+        return s, z
+
+    def debug_blank_launch(self, audio, in0, lev, blk0, level_first, level_n, blank, guard, out, y_first, nz, nch=1, nin=None,
+                           nout=None):
+        """diagnostics: ONE launch of each K12 kernel (uwspr_debug_blank_launch) on torch CUDA tensors.  audio: float32
+        or int16, frames [in0, in0 + nin) of nch interleaved samples (nin defaults to all of it); lev: float32 level
+        table [rows, nch] whose row 0 is block blk0; k12_level writes the levels of blocks [level_first, level_first +
+        level_n) into it (level_n = 0: no launch), then k12_apply makes outputs [y_first, y_first + nout) into out
+        (float32 [nout, nch]; nout defaults to what it holds, 0 or out=None: no launch) and their zero counts into nz
+        (int32 [blocks touched, nch]).  The tensors must hold what the launches read and write: checked here."""
+        import torch
+        fmt = {torch.float32: N.AUDIO_F32, torch.int16: N.AUDIO_S16}.get(audio.dtype)
+        if fmt is None or not audio.is_cuda or not audio.is_contiguous():
+            raise TypeError("debug_blank_launch: a contiguous float32 or int16 CUDA tensor, not %s" % audio.dtype)
+        if lev.dtype != torch.float32 or not lev.is_cuda or not lev.is_contiguous():
+            raise TypeError("debug_blank_launch: lev is a contiguous float32 CUDA tensor")
+        nch = int(nch)
+        nin = audio.numel() // nch if nin is None else int(nin)
+        nlev = lev.numel() // nch
+        if out is None:
+            nout = 0
+        else:
+            if out.dtype != torch.float32 or not out.is_cuda or not out.is_contiguous() or nz.dtype != torch.int32 or not nz.is_cuda or not nz.is_contiguous():
+                raise TypeError("debug_blank_launch: out / nz are contiguous float32 / int32 CUDA tensors")
+            nout = out.numel() // nch if nout is None else int(nout)
+        nblk = (int(y_first) + nout - 1) // BLANK_BLOCK - int(y_first) // BLANK_BLOCK + 1 if nout > 0 else 0
+        if nin * nch > audio.numel() or (nout > 0 and (nout * nch > out.numel() or nblk * nch > nz.numel())):
+            raise ValueError("debug_blank_launch: nin %d / nout %d x nch %d do not fit the tensors" % (nin, nout, nch))
+        f = self.L.uwspr_debug_blank_launch
+        ll = C.c_longlong
+        f.argtypes = [C.c_void_p, C.c_void_p, C.c_int, ll, ll, C.c_int, C.c_void_p, ll, ll, ll, ll, C.c_int, C.c_int, C.c_void_p, ll, ll,
+                      C.c_void_p]
+        f.restype = C.c_int
+        if self._stream_ptr is None:
+            torch.cuda.current_stream(audio.device).synchronize()
+        self._chk(f(self.h, C.c_void_p(audio.data_ptr()), fmt, nin, int(in0), nch, C.c_void_p(lev.data_ptr()), nlev, int(blk0),
+                    int(level_first), int(level_n), int(blank), int(guard), C.c_void_p(out.data_ptr() if nout > 0 else None), nout,
+                    int(y_first), C.c_void_p(nz.data_ptr() if nout > 0 else None)))
+
     # -- FDR ---------------------------------------------------------------
     def fdr_batch(self, frames):
         """-> list (per frame) of candidate record arrays, FDR_impl.cc:214-456."""
@@ -887,6 +971,17 @@ def resample_launch_counts():
     return int(out[0]), int(out[1])
 
 
+def blank_launch_counts():
+    """diagnostics: launches of K12 since the process started -> (k12_level with float32 input, with int16 input,
+    k12_apply with float32 input, with int16 input)"""
+    f = N.lib().uwspr_debug_blank_counts
+    f.argtypes = [C.c_void_p]
+    f.restype = C.c_int
+    out = np.zeros(4, np.int64)
+    f(C.c_void_p(out.ctypes.data))
+    return tuple(int(v) for v in out)
+
+
 def c2_read(path):
     iq = np.zeros((45000, 2), np.float32)
     freq, typ = C.c_double(), C.c_int32()
@@ -1091,7 +1186,7 @@ class Pipe:
     def __init__(self, fs=375, fl=45000, spb=256, maxdrift=0, maxfreqs=200, halfbandwidth=10, cf=1500,
                  threshold=10, device=0, hop=3375, batch_frames=256, max_per_frame=1, lanes=0,
                  host_threads=0, eager=False, sched=None, spare_after_us=0, passes=1, osd=0, osd_gap=None,
-                 block=0, audio_rate=None):
+                 block=0, audio_rate=None, blank=0, blank_guard=None):
         self.L = N.lib()
         self.h = C.c_void_p()
         self.fl = fl
@@ -1117,6 +1212,10 @@ class Pipe:
                 self.set_option("block", block)
             if audio_rate is not None and int(audio_rate) != AUDIO_RATE:   # push_audio takes audio at that rate (K11 ahead of the front-end)
                 self.set_option("audio_rate", audio_rate)
+            if blank:         # 4 .. 1024: the noise blanker K12 ahead of everything push_audio feeds, threshold blank / 4 block medians
+                self.set_option("blank", blank)
+            if blank_guard is not None:
+                self.set_option("blank_guard", blank_guard)
         except N.UwsprError:
             self.close()
             raise
@@ -1192,6 +1291,13 @@ class Pipe:
         """uwspr_pipe_set_option: an option of every lane's context; only while nothing is in flight"""
         self._chk(self.L.uwspr_pipe_set_option(self.h, name.encode(), int(value)))
 
+    def blank_stats(self, channels=1):
+        """uwspr_pipe_blank_stats: per channel, (samples output, samples set to zero) by the pipe's blanker -> two int64
+        arrays [channels]; zeros when the pipe's "blank" is 0"""
+        s, z = np.zeros(int(channels), np.int64), np.zeros(int(channels), np.int64)
+        self._chk(self.L.uwspr_pipe_blank_stats(self.h, C.c_void_p(s.ctypes.data), C.c_void_p(z.ctypes.data), int(channels)))
+        return s, z
+
     def stats(self):
         st = N.PipeStats()
         self._chk(self.L.uwspr_pipe_get_stats(self.h, C.byref(st)))
@@ -1200,6 +1306,7 @@ class Pipe:
 
 # ---- recordings ---------------------------------------------------------------------------------------------------
 AUDIO_RATE = 12000
+BLANK_BLOCK = 4096   # UWSPR_BLANK_BLOCK: samples per block of the blanker's level
 
 
 def supported_rate(rate):

@@ -101,6 +101,7 @@ struct uwspr_pipe {
   int osd = 0, osd_gap = UWSPR_OSD_GAP_DEFAULT;   // uwspr_pipe_set_option("osd" / "osd_gap"): K9 on what Fano timed out on
   int block = 0;    // uwspr_pipe_set_option("block"): 2, 3 = K10's soft symbols of block lengths 2 .. block for those records
   int audio_rate = 12000;   // uwspr_pipe_set_option("audio_rate"): the rate of the pushed audio (12000: no resampler, else K11 ahead of K0)
+  int blank = 0, blank_guard = 2;   // uwspr_pipe_set_option("blank" / "blank_guard"): K12 ahead of K11 / K0 (blank 0: off)
   char err[512];
   // Sticky status of the first RUNTIME failure (HIP, a lane's context), written by coordinators and the producer, read
   // by both without the lock.  Argument errors are not sticky: the call that made them returns UWSPR_ERR_ARG (with
@@ -864,19 +865,28 @@ extern "C" int uwspr_pipe_push_audio_channels(uwspr_pipe *q, const void *audio, 
   const int running = r.kind == RING_AUDIO ? (r.rs.rate ? r.rs.rate : 12000) : 0;
   if (running && rate != running)
     return parg(q, "uwspr_pipe_push_audio: option audio_rate changed to %d while the audio stream runs at %d S/s", rate, running);
+  // options "blank" / "blank_guard": latched in the same way; "blank" != 0 puts K12 ahead of both
+  const int blank = q->blank, guard = q->blank_guard;
+  const bool bk_on = blank != 0;
+  if (r.kind == RING_AUDIO && (blank != r.bk.blank || (bk_on && guard != r.bk.guard)))
+    return parg(q, "uwspr_pipe_push_audio: options blank / blank_guard changed to %d / %d while the audio stream runs with %d / %d",
+                blank, guard, r.bk.blank, r.bk.blank ? r.bk.guard : guard);
   (void)hipSetDevice(q->device);
   if (const int rc = open_ingest(q, nchannels)) return rc;
-  if (r.kind != RING_AUDIO && rs_on && !r.resample_latch(rate, s16))
+  if (r.kind != RING_AUDIO && bk_on && !r.blank_latch(blank, guard, s16))
+    return pfail(q, r.err == hipErrorOutOfMemory ? UWSPR_ERR_NOMEM : UWSPR_ERR_HIP, "blanker set-up (%d channels): %s", nchannels,
+                 hipGetErrorString(r.err));
+  if (r.kind != RING_AUDIO && rs_on && !r.resample_latch(rate, s16 && !bk_on))
     return pfail(q, r.err == hipErrorOutOfMemory ? UWSPR_ERR_NOMEM : UWSPR_ERR_HIP, "resampler set-up (%d S/s, %d channels): %s",
                  rate, nchannels, hipGetErrorString(r.err));
-  if (r.kind != RING_AUDIO && !r.audio_latch(mode, s16 && !rs_on))
+  if (r.kind != RING_AUDIO && !r.audio_latch(mode, s16 && !rs_on && !bk_on))
     return pfail(q, r.err == hipErrorOutOfMemory ? UWSPR_ERR_NOMEM : UWSPR_ERR_HIP, "audio stream set-up (%d channels): %s",
                  nchannels, hipGetErrorString(r.err));
   const size_t es = (s16 ? 2 : 4) * (size_t)nchannels;   // bytes per frame
   size_t piece = q->stage_samples * 2 * sizeof(float) / es;
   // several channels: whole K0 workgroups per piece (32 * 512 frames), so a launch has no ragged last output block
   constexpr size_t kBlockFrames = 32 * 512;
-  if (!rs_on && nchannels > 1 && piece >= kBlockFrames) piece = piece / kBlockFrames * kBlockFrames;
+  if (!rs_on && !bk_on && nchannels > 1 && piece >= kBlockFrames) piece = piece / kBlockFrames * kBlockFrames;
   // a rate below 12000 makes more 12 kS/s samples than it is given: a piece yields no more of them than a 12 kS/s piece
   if (rs_on && r.rs.pl.L > r.rs.pl.M) piece = piece * (size_t)r.rs.pl.M / (size_t)r.rs.pl.L;
   if (piece < 1) piece = 1;
@@ -885,12 +895,15 @@ extern "C" int uwspr_pipe_push_audio_channels(uwspr_pipe *q, const void *audio, 
     const int s = q->stage_next;
     if (q->stage_busy[s]) { PHIP(q, hipEventSynchronize(q->stage_ev[s])); q->stage_busy[s] = false; }
     memcpy(q->h_stage[s], (const char *)audio + off * es, n * es);
-    const size_t nout = (size_t)r.audio_outputs((size_t)r.resample_outputs(n, rate), mode);   // (12 kS/s samples the piece makes)
+    // (the samples the blanker will complete, the 12 kS/s samples those make)
+    const size_t nout = (size_t)r.audio_outputs((size_t)r.resample_outputs((size_t)r.blank_outputs(n, blank, guard), rate), mode);
     while (r.have + nout > r.cap && r.ready() > 0) {
       const int rc = launch_from_ring(q, r.ready() < q->o.batch_frames ? r.ready() : q->o.batch_frames);
       if (rc) return rc;
     }
-    if (!(rs_on ? r.push_resampled(q->h_stage[s], n, s16, false) : r.push_audio(q->h_stage[s], n, s16, false)))
+    if (!(bk_on   ? r.push_blanked(q->h_stage[s], n, s16, false, rs_on)
+          : rs_on ? r.push_resampled(q->h_stage[s], n, s16, false)
+                  : r.push_audio(q->h_stage[s], n, s16, false)))
       return pfail(q, UWSPR_ERR_HIP, "audio stream: %s", hipGetErrorString(r.err));
     PHIP(q, hipEventRecord(q->stage_ev[s], r.copy));
     q->stage_busy[s] = true;
@@ -953,6 +966,16 @@ extern "C" int uwspr_pipe_set_option(uwspr_pipe *q, const char *name, int value)
     q->audio_rate = value;
     return UWSPR_OK;
   }
+  if (!strcmp(name, "blank") || !strcmp(name, "blank_guard")) {   // the pipe's own: K12 ahead of K11 / K0, latched by the first push
+    const bool g = name[5] != 0;
+    if (g ? (value < 0 || value > 64) : (value != 0 && (value < 4 || value > 1024)))
+      return parg(q, g ? "uwspr_pipe_set_option: \"blank_guard\" is 0 .. 64, not %d" : "uwspr_pipe_set_option: \"blank\" is 0 or 4 .. 1024, not %d", value);
+    if (q->ring.kind == RING_AUDIO && (g ? (q->ring.bk.blank && value != q->ring.bk.guard) : value != q->ring.bk.blank))
+      return parg(q, "uwspr_pipe_set_option: \"%s\" = %d while the audio stream runs with blank %d, guard %d", name, value,
+                  q->ring.bk.blank, q->ring.bk.guard);
+    (g ? q->blank_guard : q->blank) = value;
+    return UWSPR_OK;
+  }
   if (!strcmp(name, "block")) {   // the pipe's own: K10's block soft symbols for the records Fano gave up on
     if (value != 0 && value != 2 && value != 3) return parg(q, "uwspr_pipe_set_option: \"block\" is 0, 2 or 3, not %d", value);
     std::lock_guard<std::mutex> lk(q->m);
@@ -1006,6 +1029,16 @@ extern "C" int uwspr_pipe_collect(uwspr_pipe *q, uwspr_decode *out, int cap, int
   int n = 0;
   while (n < cap && !q->done.empty()) { out[n++] = q->done.front(); q->done.pop_front(); }
   return n;
+}
+
+extern "C" int uwspr_pipe_blank_stats(uwspr_pipe *q, long long *samples, long long *zeroed, int cap) {
+  if (!q) return UWSPR_ERR_ARG;
+  if (const int f = q->failed.load()) return f;
+  (void)hipSetDevice(q->device);
+  const int rc = ring_blank_stats(q->ring, samples, zeroed, cap);
+  if (rc == UWSPR_ERR_ARG) return parg(q, "uwspr_pipe_blank_stats: samples/zeroed/cap %d", cap);
+  if (rc < 0) return pfail(q, rc, "uwspr_pipe_blank_stats: %s", hipGetErrorString(q->ring.err));
+  return rc;
 }
 
 extern "C" int uwspr_pipe_get_stats(uwspr_pipe *q, uwspr_pipe_stats *st) {

@@ -45,6 +45,14 @@ void resample_tap_image(const resample_plan &pl, std::vector<float> &img, int *T
 hipError_t launch_resample(hipStream_t s, const void *audio, bool s16, long long nin, long long in0, int nch, const float *taps,
                            const resample_plan &pl, int TP, float *out, long long nout, long long j_first);
 
+// K12, the noise blanker ahead of K11 and K0 (k12_blank.hip; the definition: include/uwspr_hip.h)
+hipError_t launch_blank_level(hipStream_t s, const void *audio, bool s16, long long nin, long long in0, int nch, float *lev,
+                              long long nblk, long long blk_first);
+hipError_t launch_blank_apply(hipStream_t s, const void *audio, bool s16, long long nin, long long in0, int nch, const float *lev,
+                              long long nlev, long long blk0, int blank, int guard, float *out, long long nout, long long y_first,
+                              int *nz);
+long long blank_blocks_of(long long y_first, long long nout);
+
 enum { RING_EMPTY = 0, RING_IQ = 1, RING_AUDIO = 2 };   // what the stream is, decided by its first push
 
 struct stream_ring {
@@ -105,6 +113,32 @@ struct stream_ring {
     float *d_out = nullptr;            // [out_frames][nch]
     size_t out_frames = 0;
   } rs;
+  // Impulsive noise (option "blank" != 0): the pushed frames go through K12 into a device buffer of float frames at the
+  // same rate, which push_resampled or push_audio takes as a device source on the same stream.  Output i is complete as
+  // soon as input i + G has been pushed.  The device buffer holds [history | new frames]: the history is whatever is
+  // not yet output plus its guard (inputs from y_next - G on) and the incomplete block (from (n_in div N) N on), at
+  // most N + 2 G frames.  The level table holds the last three complete blocks ahead of the ones a push completes.
+  // The per-block zero counts go to the host through a page-locked queue and are summed there (blank_drain).
+  struct blank_state {
+    int blank = 0, guard = 0;          // latched by the first audio push after open / reset (blank 0: no blanker)
+    int s16 = 0;                       // the input buffer holds int16 frames (every push so far was int16)
+    char *d_in[2] = {nullptr, nullptr};
+    size_t in_bytes = 0;
+    int cur = 0;
+    long long i_base = 0;              // input index of d_in[cur][0]
+    size_t hist = 0;                   // frames held: inputs [i_base, i_base + hist)
+    long long n_in = 0, y_next = 0;    // inputs pushed, next output
+    float *d_out = nullptr;            // [out_frames][nch]
+    size_t out_frames = 0;
+    float *d_lev[2] = {nullptr, nullptr};   // [lev_rows][nch]: the levels of blocks lev0 .. blk_done - 1
+    size_t lev_rows = 0;
+    int lcur = 0;
+    long long lev0 = 0, blk_done = 0;  // first block of the table, complete blocks so far
+    int *d_nz = nullptr, *h_nz = nullptr;   // zero counts [..][nch] of the launches since the last drain, device and page-locked host
+    size_t nz_cap = 0, nz_used = 0;    // in ints (multiples of nch)
+    std::vector<long long> zeroed;     // per channel, drained so far
+    bool stale = false;                // a reset left counts in flight: drained and dropped by the next latch
+  } bk;
   // most new samples per K0 launch: AUDIO_PIECE / nch frames (one channel: 131072 outputs, 256 workgroups), so the
   // history buffers hold at most (32 J + 32) nch + AUDIO_PIECE samples whatever the channel count
   static constexpr size_t AUDIO_PIECE = 4u << 20;
@@ -125,6 +159,11 @@ struct stream_ring {
     if (rs.d_out) (void)hipFree(rs.d_out);
     if (rs.d_taps) (void)hipFree(rs.d_taps);
     rs = resample_state();
+    for (int k = 0; k < 2; k++) { if (bk.d_in[k]) (void)hipFree(bk.d_in[k]); if (bk.d_lev[k]) (void)hipFree(bk.d_lev[k]); }
+    if (bk.d_out) (void)hipFree(bk.d_out);
+    if (bk.d_nz) (void)hipFree(bk.d_nz);
+    if (bk.h_nz) (void)hipHostFree(bk.h_nz);
+    bk = blank_state();
     if (copy) { (void)hipStreamDestroy(copy); copy = nullptr; }
     cap = 0; plane = 0; nch = 1; have = 0; base = 0; up_pending = false;
   }
@@ -156,7 +195,9 @@ struct stream_ring {
   // drop what is buffered.  Kernels may still be reading views of the current buffer, so the next append
   // goes through make_room() (base = cap: nothing fits) to the OTHER buffer, behind its readers.
   // An audio stream starts again at audio index 32 p with a zero history.
-  void reset(long long p) { have = 0; base = cap; pos = p; kind = RING_EMPTY; au.mode = -1; au.m_next = p; rs.rate = 0; }
+  void reset(long long p) { have = 0; base = cap; pos = p; kind = RING_EMPTY; au.mode = -1; au.m_next = p; rs.rate = 0;
+    if (bk.blank) { bk.blank = 0; bk.stale = true; }
+  }
 
   // make space for n more samples behind the unconsumed ones
   bool make_room(size_t n) {
@@ -437,6 +478,138 @@ struct stream_ring {
         rs.cur ^= 1; rs.i_base = keep;
       }
       rs.hist = nh;
+      off += k;
+    }
+    last_direct = direct;
+    if (n && (err = hipEventRecord(ev_up, copy)) != hipSuccess) return false;
+    if (n) up_pending = true;
+    return true;
+  }
+
+  // ---- impulsive noise (K12 ahead of K11 and K0)
+  static constexpr long long BLANK_N = UWSPR_BLANK_BLOCK;
+  // samples a push of n frames would complete, for the blanker that runs or the one the push would latch (blank 0: n)
+  long long blank_outputs(size_t n, int blank, int guard) const {
+    if (!blank) return (long long)n;
+    const bool running = bk.blank != 0;
+    const long long y = (running ? bk.n_in : 0) + (long long)n - guard, yn = running ? bk.y_next : 0;
+    return y > yn ? y - yn : 0;
+  }
+  size_t blank_piece_frames() const { return audio_piece_frames(); }
+
+  // The first audio push after open / reset with "blank" != 0: buffers, an empty history, counters at 0.  (The caller
+  // latches the stages behind with float input: the blanker delivers float frames.)
+  bool blank_latch(int blank, int guard, bool s16) {
+    const size_t C = (size_t)nch, piece = blank_piece_frames();
+    const size_t need = ((size_t)BLANK_N + 2 * 64 + piece) * C * sizeof(float);
+    const size_t rows = piece / (size_t)BLANK_N + 6, nzc = (piece / (size_t)BLANK_N + 2) * C * 64;
+    if (bk.stale && (err = hipStreamSynchronize(copy)) != hipSuccess) return false;   // (counts of the stream before the reset)
+    bk.stale = false;
+    if (bk.in_bytes < need || bk.out_frames < piece || bk.lev_rows < rows || bk.nz_cap < nzc) {
+      if ((err = hipStreamSynchronize(copy)) != hipSuccess) return false;
+      for (int k = 0; k < 2; k++) {
+        if (bk.d_in[k]) { (void)hipFree(bk.d_in[k]); bk.d_in[k] = nullptr; }
+        if (bk.d_lev[k]) { (void)hipFree(bk.d_lev[k]); bk.d_lev[k] = nullptr; }
+      }
+      if (bk.d_out) { (void)hipFree(bk.d_out); bk.d_out = nullptr; }
+      if (bk.d_nz) { (void)hipFree(bk.d_nz); bk.d_nz = nullptr; }
+      if (bk.h_nz) { (void)hipHostFree(bk.h_nz); bk.h_nz = nullptr; }
+      bk.in_bytes = 0; bk.out_frames = 0; bk.lev_rows = 0; bk.nz_cap = 0;
+      for (int k = 0; k < 2; k++) {
+        if ((err = hipMalloc((void **)&bk.d_in[k], need)) != hipSuccess) { bk.d_in[k] = nullptr; return false; }
+        if ((err = hipMalloc((void **)&bk.d_lev[k], rows * C * sizeof(float))) != hipSuccess) { bk.d_lev[k] = nullptr; return false; }
+      }
+      if ((err = hipMalloc((void **)&bk.d_out, piece * C * sizeof(float))) != hipSuccess) { bk.d_out = nullptr; return false; }
+      if ((err = hipMalloc((void **)&bk.d_nz, nzc * sizeof(int))) != hipSuccess) { bk.d_nz = nullptr; return false; }
+      if ((err = hipHostMalloc((void **)&bk.h_nz, nzc * sizeof(int), hipHostMallocDefault)) != hipSuccess) { bk.h_nz = nullptr; return false; }
+      bk.in_bytes = need; bk.out_frames = piece; bk.lev_rows = rows; bk.nz_cap = nzc;
+    }
+    bk.blank = blank; bk.guard = guard; bk.s16 = s16;
+    bk.i_base = 0; bk.hist = 0; bk.n_in = 0; bk.y_next = 0; bk.lev0 = 0; bk.blk_done = 0; bk.nz_used = 0;
+    bk.zeroed.assign(C, 0);
+    return true;
+  }
+
+  // the zero counts the launches so far have written: wait for the copy stream, add them up per channel
+  bool blank_drain() {
+    if (!bk.nz_used) return true;
+    if ((err = hipStreamSynchronize(copy)) != hipSuccess) return false;
+    for (size_t i = 0; i < bk.nz_used; i++) bk.zeroed[i % (size_t)nch] += bk.h_nz[i];
+    bk.nz_used = 0;
+    return true;
+  }
+
+  // n frames of nch samples: behind the blanker's history, k12_level for the blocks the push completes, k12_apply for
+  // the outputs it completes, those into push_resampled (rs_on) or push_audio as a device source on the copy stream.
+  // Formats mix as in push_audio.  The caller has latched every stage and checked room() against what the outputs make.
+  bool push_blanked(const void *src, size_t n, bool s16_in, bool on_device, bool rs_on, hipEvent_t src_ready = nullptr) {
+    const size_t C = (size_t)nch;
+    const long long G = bk.guard;
+    bool direct = false;
+    if (n && bk.s16 && !s16_in) {
+      launch_widen_s16(copy, (const int16_t *)bk.d_in[bk.cur], (float *)bk.d_in[bk.cur ^ 1], bk.hist * C);
+      if ((err = hipGetLastError()) != hipSuccess) return false;
+      bk.cur ^= 1; bk.s16 = 0;
+    }
+    const bool widen = s16_in && !bk.s16;
+    const size_t es = (bk.s16 ? 2 : 4) * C, es_in = (s16_in ? 2 : 4) * C;
+    const size_t piece = blank_piece_frames();
+    for (size_t off = 0; off < n;) {
+      const size_t k = n - off < piece ? n - off : piece;
+      char *b = bk.d_in[bk.cur];
+      last_direct = false;
+      if (widen) {
+        char *tmp = bk.d_in[bk.cur ^ 1];
+        if (!upload(tmp, (const char *)src + off * es_in, k * es_in, on_device, src_ready)) return false;
+        launch_widen_s16(copy, (const int16_t *)tmp, (float *)(b + bk.hist * es), k * C);
+        if ((err = hipGetLastError()) != hipSuccess) return false;
+      } else if (!upload(b + bk.hist * es, (const char *)src + off * es_in, k * es_in, on_device, src_ready)) {
+        return false;
+      }
+      direct = direct || last_direct;
+      bk.n_in += (long long)k;
+      const long long held = (long long)(bk.hist + k);
+      // the blocks this piece completes
+      const long long done = bk.n_in / BLANK_N;
+      if (done > bk.blk_done) {
+        if ((size_t)(done - bk.lev0) > bk.lev_rows) { err = hipErrorInvalidValue; return false; }
+        if ((err = launch_blank_level(copy, b, bk.s16 != 0, held, bk.i_base, nch, bk.d_lev[bk.lcur] + (size_t)(bk.blk_done - bk.lev0) * C,
+                                      done - bk.blk_done, bk.blk_done)) != hipSuccess) return false;
+        bk.blk_done = done;
+      }
+      // the outputs it completes
+      const long long y_end = bk.n_in - G;
+      if (y_end > bk.y_next) {
+        const long long nout = y_end - bk.y_next;
+        const size_t nzn = (size_t)blank_blocks_of(bk.y_next, nout) * C;
+        if ((size_t)nout > bk.out_frames || nzn > bk.nz_cap) { err = hipErrorInvalidValue; return false; }
+        if (bk.nz_used + nzn > bk.nz_cap && !blank_drain()) return false;
+        if ((err = launch_blank_apply(copy, b, bk.s16 != 0, held, bk.i_base, nch, bk.d_lev[bk.lcur], bk.blk_done - bk.lev0, bk.lev0,
+                                      bk.blank, bk.guard, bk.d_out, nout, bk.y_next, bk.d_nz + bk.nz_used)) != hipSuccess) return false;
+        if ((err = hipMemcpyAsync(bk.h_nz + bk.nz_used, bk.d_nz + bk.nz_used, nzn * sizeof(int), hipMemcpyDeviceToHost, copy)) != hipSuccess)
+          return false;
+        bk.nz_used += nzn;
+        bk.y_next = y_end;
+        if (!(rs_on ? push_resampled(bk.d_out, (size_t)nout, false, true, nullptr) : push_audio(bk.d_out, (size_t)nout, false, true, nullptr)))
+          return false;
+      }
+      // the level table keeps the last three complete blocks
+      const long long lev0n = bk.blk_done > 3 ? bk.blk_done - 3 : 0;
+      if (lev0n != bk.lev0) {
+        if ((err = hipMemcpyAsync(bk.d_lev[bk.lcur ^ 1], bk.d_lev[bk.lcur] + (size_t)(lev0n - bk.lev0) * C,
+                                  (size_t)(bk.blk_done - lev0n) * C * sizeof(float), hipMemcpyDeviceToDevice, copy)) != hipSuccess) return false;
+        bk.lcur ^= 1; bk.lev0 = lev0n;
+      }
+      // keep what is not yet output with its guard, and the incomplete block
+      long long keep = bk.y_next - G < bk.blk_done * BLANK_N ? bk.y_next - G : bk.blk_done * BLANK_N;
+      if (keep < bk.i_base) keep = bk.i_base;
+      const size_t nh = (size_t)(bk.n_in - keep);
+      if (keep != bk.i_base) {   // the tail to the front of the other buffer
+        if (nh && (err = hipMemcpyAsync(bk.d_in[bk.cur ^ 1], b + (size_t)(keep - bk.i_base) * es, nh * es,
+                                        hipMemcpyDeviceToDevice, copy)) != hipSuccess) return false;
+        bk.cur ^= 1; bk.i_base = keep;
+      }
+      bk.hist = nh;
       off += k;
     }
     last_direct = direct;

@@ -105,6 +105,8 @@ static const struct { const char *name; int dflt, lo, hi; } kOptions[UWSPR_NOPT]
     {"frontend", 0, 0, 1},          // K0: 0 the flowgraph's GNU Radio chain as one polyphase FIR (grc:303-400,840-956,1767-1808), 1 compact single stage
     {"k4_forms", 1, 0, 255},        // staged form: bit 0 = S5 (k4_ring<6,8>) keeps its sample pairs in a register ring
     {"audio_rate", 12000, 8000, 192000},   // uwspr_stream_push_audio: the rate of the pushed audio (12000: no resampler, else K11 ahead of K0)
+    {"blank", 0, 0, 1024},          // uwspr_stream_push_audio: K12 ahead of K11 / K0, threshold in quarters of the block median (0: off; 4 .. 1024)
+    {"blank_guard", 2, 0, 64},      // K12: samples zeroed either side of a flagged one
 };
 
 static void refresh_options(uwspr_ctx *c) {
@@ -138,6 +140,8 @@ extern "C" int uwspr_set_option(uwspr_ctx *c, const char *name, int value) {
     if (resample_design(value, pl))
       return fail(c, UWSPR_ERR_ARG, "option 'audio_rate' = %d: not a supported rate (12000 / gcd(rate, 12000) <= 160)", value);
   }
+  if (i == UWSPR_OPT_BLANK && value != 0 && value < 4)
+    return fail(c, UWSPR_ERR_ARG, "option 'blank' = %d: 0 (off) or 4 .. 1024 quarters of the median", value);
   c->opt[i] = value; c->opt_set[i] = true;
   refresh_options(c);
   return UWSPR_OK;
@@ -180,6 +184,7 @@ static int options_from_environment(uwspr_ctx *c) {
       const long v = strtol(eq + 1, &vend, 10);
       if (vend == eq + 1 || *vend || errno || v < kOptions[i].lo || v > kOptions[i].hi)
         return fail(c, UWSPR_ERR_ARG, "UWSPR_OPTIONS: %s='%s' is not an integer in %d .. %d", tok, eq + 1, kOptions[i].lo, kOptions[i].hi);
+      if (i == UWSPR_OPT_BLANK && v != 0 && v < 4) return fail(c, UWSPR_ERR_ARG, "UWSPR_OPTIONS: blank=%ld is not 0 or 4 .. 1024", v);
       c->opt[i] = (int)v; c->opt_set[i] = true;
       if (last) break;
       tok = end + 1;
@@ -218,6 +223,7 @@ extern "C" int uwspr_ctx_create(const uwspr_params *p, int device, uwspr_ctx **o
   c->osd = nullptr;
   c->blk = nullptr;
   c->rs = nullptr;
+  c->bk = nullptr;
   c->dist_comm = nullptr; c->dist_rank = 0; c->dist_world = 0;
   c->cap_tmpc = 0; c->d_tmpc = nullptr; c->cap_tmpn = 0; c->d_tmpn = nullptr;
   c->h_pin = nullptr; c->pin_busy[0] = c->pin_busy[1] = false;
@@ -385,6 +391,7 @@ extern "C" void uwspr_ctx_destroy(uwspr_ctx *c) {
   osd_release(c);
   blk_release(c);
   rs_release(c);
+  bk_release(c);
   void *bufs[] = {c->d_window, c->d_twiddle, c->d_k3_tile, c->d_off, c->d_umap, c->d_fe_taps, c->d_audio, c->d_frames, c->d_ps, c->d_psavg, c->d_smraw,
                   c->d_smspec, c->d_noise, c->d_cands, c->d_npk, c->d_work, c->d_syncgrid, c->d_hyps, c->d_grps, c->d_cent,
                   c->d_abi_hyps, c->d_p, c->d_sync, c->d_sym, c->d_state, c->d_dout, c->d_slab, c->d_tabs, c->d_counter, c->d_sched_stamps, c->d_pwin, c->d_ptab, c->d_need, c->d_stream_frames, c->d_tmpc, c->d_tmpn};
@@ -602,6 +609,41 @@ extern "C" int uwspr_resample_batch(uwspr_ctx *c, const void *audio, long long n
     return fail(c, UWSPR_ERR_ARG, "uwspr_resample_batch: audio/out/nin %lld/nout %lld/nchannels %d/format %d", nin, nout, nchannels, format);
   if (where != UWSPR_HOST && where != UWSPR_DEVICE) return fail(c, UWSPR_ERR_ARG, "where=%d", where);
   return rs_batch(c, audio, nin, nchannels, format == UWSPR_AUDIO_S16, rate, where, out, nout);
+}
+
+// -------------------------------------------------------------- blanker (K12)
+extern "C" int uwspr_blank_batch(uwspr_ctx *c, const void *audio, long long nin, int nchannels, int format, int where, int blank,
+                                 int guard, float *out, float *med, int *nzero) {
+  int rc = ready(c);
+  if (rc) return rc;
+  if (!audio || !out || nin <= 0 || nchannels < 1 || nchannels > UWSPR_PIPE_MAX_CHANNELS ||
+      (format != UWSPR_AUDIO_F32 && format != UWSPR_AUDIO_S16))
+    return fail(c, UWSPR_ERR_ARG, "uwspr_blank_batch: audio/out/nin %lld/nchannels %d/format %d", nin, nchannels, format);
+  if (blank < 4 || blank > 1024 || guard < 0 || guard > 64)
+    return fail(c, UWSPR_ERR_ARG, "uwspr_blank_batch: blank %d (4 .. 1024) / guard %d (0 .. 64)", blank, guard);
+  if (where != UWSPR_HOST && where != UWSPR_DEVICE) return fail(c, UWSPR_ERR_ARG, "where=%d", where);
+  return bk_batch(c, audio, nin, nchannels, format == UWSPR_AUDIO_S16, where, blank, guard, out, med, nzero);
+}
+
+// per-channel totals of a ring's blanker since open / reset (shared with uwspr_pipe_blank_stats)
+int uwspr::ring_blank_stats(stream_ring &r, long long *samples, long long *zeroed, int cap) {
+  if (cap < 0 || (cap > 0 && (!samples || !zeroed))) return UWSPR_ERR_ARG;
+  const int C = r.is_open() ? r.nch : 1;
+  if (r.bk.blank && !r.blank_drain()) return UWSPR_ERR_HIP;
+  for (int k = 0; k < C && k < cap; k++) {
+    samples[k] = r.bk.blank ? r.bk.y_next : 0;
+    zeroed[k] = r.bk.blank ? r.bk.zeroed[(size_t)k] : 0;
+  }
+  return C;
+}
+
+extern "C" int uwspr_stream_blank_stats(uwspr_ctx *c, long long *samples, long long *zeroed, int cap) {
+  int rc = ready(c);
+  if (rc) return rc;
+  rc = ring_blank_stats(c->ring, samples, zeroed, cap);
+  if (rc == UWSPR_ERR_ARG) return fail(c, UWSPR_ERR_ARG, "uwspr_stream_blank_stats: samples/zeroed/cap %d", cap);
+  if (rc < 0) return fail(c, rc, "uwspr_stream_blank_stats: %s", hipGetErrorString(c->ring.err));
+  return rc;
 }
 
 // -------------------------------------------------------------------- FDR
@@ -1092,7 +1134,13 @@ extern "C" int uwspr_stream_push_audio(uwspr_ctx *c, const void *audio, int nsam
   const int running = r.kind == RING_AUDIO ? (r.rs.rate ? r.rs.rate : 12000) : 0;
   if (nsamples > 0 && running && rate != running)
     return fail(c, UWSPR_ERR_ARG, "option audio_rate changed to %d while the audio stream runs at %d S/s (reset it first)", rate, running);
-  const long long n12 = r.resample_outputs((size_t)nsamples, rate);
+  // options "blank" / "blank_guard": latched in the same way; "blank" != 0 puts K12 ahead of both
+  const int blank = c->opt[UWSPR_OPT_BLANK], guard = c->opt[UWSPR_OPT_BLANK_GUARD];
+  const bool bk_on = blank != 0;
+  if (nsamples > 0 && r.kind == RING_AUDIO && (blank != r.bk.blank || (bk_on && guard != r.bk.guard)))
+    return fail(c, UWSPR_ERR_ARG, "options blank / blank_guard changed to %d / %d while the audio stream runs with %d / %d (reset it first)",
+                blank, guard, r.bk.blank, r.bk.blank ? r.bk.guard : guard);
+  const long long n12 = r.resample_outputs((size_t)r.blank_outputs((size_t)nsamples, blank, guard), rate);
   if (n12 < 0) return fail(c, UWSPR_ERR_ARG, "option audio_rate = %d: not a supported rate", rate);
   const bool rs_on = rate != 12000;
   const long long nout = r.audio_outputs((size_t)n12, mode);
@@ -1100,17 +1148,22 @@ extern "C" int uwspr_stream_push_audio(uwspr_ctx *c, const void *audio, int nsam
     return fail(c, UWSPR_ERR_ARG, "stream buffer full (%zu + %lld > %zu samples): take frames first", r.have, nout, r.cap);
   if (nsamples > 0) {
     const bool s16 = format == UWSPR_AUDIO_S16;
-    if (r.kind != RING_AUDIO && rs_on && !r.resample_latch(rate, s16))
+    if (r.kind != RING_AUDIO && bk_on && !r.blank_latch(blank, guard, s16))
+      return fail(c, r.err == hipErrorOutOfMemory ? UWSPR_ERR_NOMEM : UWSPR_ERR_HIP, "blanker set-up: %s", hipGetErrorString(r.err));
+    if (r.kind != RING_AUDIO && rs_on && !r.resample_latch(rate, s16 && !bk_on))
       return fail(c, r.err == hipErrorOutOfMemory ? UWSPR_ERR_NOMEM : UWSPR_ERR_HIP, "resampler set-up (%d S/s): %s", rate, hipGetErrorString(r.err));
-    if (r.kind != RING_AUDIO && !r.audio_latch(mode, s16 && !rs_on))
+    if (r.kind != RING_AUDIO && !r.audio_latch(mode, s16 && !rs_on && !bk_on))
       return fail(c, UWSPR_ERR_HIP, "audio stream set-up: %s", hipGetErrorString(r.err));
     bool ok;
     if (where == UWSPR_DEVICE) {   // produced by work on the context's stream
       HIPCHK(c, hipEventRecord(c->ring_ev, c->stream));
-      ok = rs_on ? r.push_resampled(audio, (size_t)nsamples, s16, true, c->ring_ev)
-                 : r.push_audio(audio, (size_t)nsamples, s16, true, c->ring_ev);
+      ok = bk_on   ? r.push_blanked(audio, (size_t)nsamples, s16, true, rs_on, c->ring_ev)
+           : rs_on ? r.push_resampled(audio, (size_t)nsamples, s16, true, c->ring_ev)
+                   : r.push_audio(audio, (size_t)nsamples, s16, true, c->ring_ev);
     } else {
-      ok = rs_on ? r.push_resampled(audio, (size_t)nsamples, s16, false) : r.push_audio(audio, (size_t)nsamples, s16, false);
+      ok = bk_on   ? r.push_blanked(audio, (size_t)nsamples, s16, false, rs_on)
+           : rs_on ? r.push_resampled(audio, (size_t)nsamples, s16, false)
+                   : r.push_audio(audio, (size_t)nsamples, s16, false);
       if (ok && where == UWSPR_HOST && r.last_direct) ok = r.wait_uploads();   // as uwspr_stream_push
     }
     if (!ok) return fail(c, UWSPR_ERR_HIP, "audio stream: %s", hipGetErrorString(r.err));
@@ -1369,6 +1422,38 @@ extern "C" int uwspr_debug_resample_launch(uwspr_ctx *c, const void *audio_dev, 
     return fail(c, UWSPR_ERR_ARG, "uwspr_debug_resample_launch: audio/out/format %d/nin %lld/in0 %lld/nout %lld/j_first %lld/nch %d", format,
                 nin, in0, nout, j_first, nch);
   return rs_debug_launch(c, audio_dev, format == UWSPR_AUDIO_S16, nin, in0, nch, rate, out_dev, nout, j_first);
+}
+
+// diagnostics (not part of the ABI header): ONE launch of each K12 kernel (what uwspr_blank_batch and a stream's push
+// with "blank" != 0 run) on device memory, on the context's stream, waited for.  audio_dev holds frames [in0, in0 + nin)
+// of nch interleaved samples.  lev_dev is a level table [nlev][nch] whose row 0 is block blk0.  k12_level (when level_n
+// > 0) writes the levels of blocks [level_first, level_first + level_n) into their rows of it -- they must lie inside
+// the table; samples outside the buffer count as pattern 0 -- then k12_apply (when nout > 0) makes outputs [y_first,
+// y_first + nout) of every channel into out_dev [nout][nch] and their zero counts into nz_dev [blocks touched][nch].
+// Each kernel has one instantiation per input format; `format` picks it.
+extern "C" int uwspr_debug_blank_launch(uwspr_ctx *c, const void *audio_dev, int format, long long nin, long long in0, int nch,
+                                        float *lev_dev, long long nlev, long long blk0, long long level_first, long long level_n,
+                                        int blank, int guard, float *out_dev, long long nout, long long y_first, int *nz_dev) {
+  int rc = ready(c);
+  if (rc) return rc;
+  const long long lim = 1LL << 46;
+  if (!audio_dev || !lev_dev || nin < 1 || nch < 1 || nch > UWSPR_PIPE_MAX_CHANNELS || in0 < 0 || in0 > lim || nlev < 0 ||
+      nlev > (1LL << 22) || blk0 < 0 || blk0 > lim / UWSPR_BLANK_BLOCK || level_n < 0 || nout < 0 || nout > (1LL << 26) || y_first < 0 ||
+      y_first > lim || (level_n > 0 && (level_first < blk0 || level_first + level_n > blk0 + nlev)) ||
+      (nout > 0 && (!out_dev || !nz_dev)) || blank < 4 || blank > 1024 || guard < 0 || guard > 64 ||
+      (format != UWSPR_AUDIO_F32 && format != UWSPR_AUDIO_S16))
+    return fail(c, UWSPR_ERR_ARG, "uwspr_debug_blank_launch: audio/lev/out/nz/format %d/nin %lld/in0 %lld/nch %d/nlev %lld/blk0 %lld/"
+                "level %lld+%lld/blank %d/guard %d/nout %lld/y_first %lld", format, nin, in0, nch, nlev, blk0, level_first, level_n,
+                blank, guard, nout, y_first);
+  return bk_debug_launch(c, audio_dev, format == UWSPR_AUDIO_S16, nin, in0, nch, lev_dev, nlev, blk0, level_first, level_n, blank,
+                         guard, out_dev, nout, y_first, nz_dev);
+}
+
+// launches of K12 since the process started, per instantiation: k12_level float32, int16; k12_apply float32, int16
+extern "C" int uwspr_debug_blank_counts(long long *out) {
+  if (!out) return UWSPR_ERR_ARG;
+  for (int k = 0; k < 4; k++) out[k] = blank_launch_count(k);
+  return UWSPR_OK;
 }
 
 // launches of K11 since the process started, per instantiation: out[0] float32 input, out[1] int16 input

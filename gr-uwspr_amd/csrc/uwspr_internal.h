@@ -28,6 +28,8 @@ enum {
   UWSPR_OPT_FRONTEND,           // K0 taps: 0 the flowgraph's three-stage GNU Radio chain (default), 1 the compact single stage
   UWSPR_OPT_K4_FORMS,           // staged form, bit mask of kernel forms (default: all that won their A/B): bit 0 = S5 register ring
   UWSPR_OPT_AUDIO_RATE,         // rate of the audio uwspr_stream_push_audio takes (default 12000: no resampler; else K11 ahead of K0)
+  UWSPR_OPT_BLANK,              // uwspr_stream_push_audio: K12's threshold in quarters of the block median (default 0: no blanker)
+  UWSPR_OPT_BLANK_GUARD,        // K12's guard G: samples zeroed either side of a flagged one (default 2)
   UWSPR_NOPT
 };
 
@@ -172,6 +174,8 @@ struct blk_state;
 void blk_release(uwspr_ctx *c);  // k10_blockdemod.hip: frees what uwspr_blockdemod_batch / the pipe's option "block" made
 struct rs_state;
 void rs_release(uwspr_ctx *c);   // k11_resample.hip: frees what uwspr_resample_batch made
+struct bk_state;
+void bk_release(uwspr_ctx *c);   // k12_blank.hip: frees what uwspr_blank_batch made
 
 }  // namespace uwspr
 
@@ -268,6 +272,8 @@ struct uwspr_ctx {
   uwspr::blk_state *blk;
   // resampler (k11_resample.hip): the batch call's taps and staging, made by the first use
   uwspr::rs_state *rs;
+  // blanker (k12_blank.hip): the batch call's staging and tables, made by the first use
+  uwspr::bk_state *bk;
 
   int prof_mask;
   std::vector<uwspr::ev_pair> prof_events;
@@ -312,6 +318,15 @@ int rs_batch(uwspr_ctx *c, const void *audio, long long nin, int nch, int s16, i
 int rs_debug_launch(uwspr_ctx *c, const void *audio_dev, int s16, long long nin, long long in0, int nch, int rate, float *out_dev,
                     long long nout, long long j_first);
 long long resample_launch_count(int s16);
+// K12 (k12_blank.hip): the batch call and the one-launch door behind uwspr_blank_batch / uwspr_debug_blank_launch
+// (arguments checked by the callers); launches per kernel and input format (0, 1: k12_level float, int16; 2, 3: k12_apply)
+int bk_batch(uwspr_ctx *c, const void *audio, long long nin, int nch, int s16, int where, int blank, int guard, float *out,
+             float *med, int *nzero);
+int bk_debug_launch(uwspr_ctx *c, const void *audio_dev, int s16, long long nin, long long in0, int nch, float *lev_dev,
+                    long long nlev, long long blk0, long long level_first, long long level_n, int blank, int guard, float *out_dev,
+                    long long nout, long long y_first, int *nz_dev);
+long long blank_launch_count(int which);
+int ring_blank_stats(stream_ring &r, long long *samples, long long *zeroed, int cap);   // uwspr_api.hip
 void launch_frontend(uwspr_ctx *c, const float *audio, int B, int nin, float2 *out, int nout);
 void launch_spectrogram(uwspr_ctx *c, const float *frames, int B);
 void launch_spectrum(uwspr_ctx *c, int B);

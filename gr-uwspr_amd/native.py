@@ -26,7 +26,7 @@ LIBPATH = os.path.join(LIBDIR, "libuwspr_hip_exp_%s.so" % _EXTRA_TAG if _EXTRA e
 HOSTLIB = os.path.join(LIBDIR, "libuwspr_blocks.so")
 
 SOURCES = ["uwspr_api.hip", "k0_frontend.hip", "k1_spectrogram.hip", "k2_spectrum.hip", "k3_coarse.hip",
-           "k4_tonecorr.hip", "k4_grid.hip", "k4_pair.hip", "k4_jig.hip", "k5_fold_schedule.hip", "k6_sched.hip", "k7_transmit.hip", "k8_subtract.hip", "k9_osd.hip", "k10_blockdemod.hip", "k11_resample.hip", "pipe.hip", "dist.hip", "host_tail.cpp"]
+           "k4_tonecorr.hip", "k4_grid.hip", "k4_pair.hip", "k4_jig.hip", "k5_fold_schedule.hip", "k6_sched.hip", "k7_transmit.hip", "k8_subtract.hip", "k9_osd.hip", "k10_blockdemod.hip", "k11_resample.hip", "k12_blank.hip", "pipe.hip", "dist.hip", "host_tail.cpp"]
 HIPFLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off",
             "-fno-slp-vectorize", "-fhip-fp32-correctly-rounded-divide-sqrt", "-fPIC", "-Wall", "-Wno-unused-function"]
 
@@ -264,7 +264,7 @@ class Prof(C.Structure):
 ABI_SYMBOLS = [
     "uwspr_ctx_create", "uwspr_ctx_destroy", "uwspr_last_error", "uwspr_status_string",
     "uwspr_get_info", "uwspr_set_stream", "uwspr_synchronize", "uwspr_frontend_batch",
-    "uwspr_frontend_design", "uwspr_resample_design", "uwspr_resample_batch", "uwspr_set_frame_stride", "uwspr_stream_open", "uwspr_stream_push", "uwspr_stream_push_audio", "uwspr_stream_wait_uploads",
+    "uwspr_frontend_design", "uwspr_resample_design", "uwspr_resample_batch", "uwspr_blank_batch", "uwspr_stream_blank_stats", "uwspr_pipe_blank_stats", "uwspr_set_frame_stride", "uwspr_stream_open", "uwspr_stream_push", "uwspr_stream_push_audio", "uwspr_stream_wait_uploads",
     "uwspr_stream_take_view", "uwspr_stream_take", "uwspr_stream_reset",
     "uwspr_device_alloc", "uwspr_device_free", "uwspr_host_alloc", "uwspr_host_free", "uwspr_fdr_batch",
     "uwspr_fdr_read_spectrum", "uwspr_fdr_keep_syncgrid", "uwspr_fdr_read_syncgrid",
@@ -320,6 +320,9 @@ def lib():
     L.uwspr_frontend_design.argtypes = [ip, ip, vp, ip, vp]
     L.uwspr_resample_design.argtypes = [ip, vp, ip, vp, vp, vp, vp]
     L.uwspr_resample_batch.argtypes = [vp, vp, C.c_longlong, ip, ip, ip, ip, vp, C.c_longlong]
+    L.uwspr_blank_batch.argtypes = [vp, vp, C.c_longlong, ip, ip, ip, ip, ip, vp, vp, vp]
+    L.uwspr_stream_blank_stats.argtypes = [vp, vp, vp, ip]
+    L.uwspr_pipe_blank_stats.argtypes = [vp, vp, vp, ip]
     L.uwspr_stream_open.argtypes = [vp, ip, ip]
     L.uwspr_stream_push.argtypes = [vp, vp, ip, ip, C.POINTER(C.c_int)]
     L.uwspr_stream_push_audio.argtypes = [vp, vp, ip, ip, ip, C.POINTER(C.c_int)]

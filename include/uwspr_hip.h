@@ -46,7 +46,9 @@ extern "C" {
                                     block demodulation: uwspr_block_item, uwspr_blockdemod_batch, the pipe option "block",
                                     uwspr_decode.block (the byte that was _pad0);
                                     audio at other rates: uwspr_resample_design, uwspr_resample_batch, the option
-                                    "audio_rate" of contexts and pipes */
+                                    "audio_rate" of contexts and pipes;
+                                    impulsive noise: uwspr_blank_batch, uwspr_stream_blank_stats, uwspr_pipe_blank_stats,
+                                    the options "blank" and "blank_guard" of contexts and pipes */
 
 typedef enum {
   UWSPR_OK = 0,
@@ -280,6 +282,61 @@ int uwspr_stream_push_audio(uwspr_ctx *ctx, const void *audio, int nsamples, int
 int uwspr_resample_design(int rate, double *taps, int cap, int *L, int *M, int *T, int *delay);
 int uwspr_resample_batch(uwspr_ctx *ctx, const void *audio, long long nin, int nchannels, int format, int rate, int where,
                          float *out, long long nout);
+/* ---- impulsive noise: a median-gated blanker ahead of the resampler and the front-end (K12) ------------------------
+ * The underwater channel is impulsive (snapping shrimp, clicks, mooring and electrical spikes).  K0 reads +-10 Hz, so
+ * its impulse response is about half a second long: a click of 0.1 ms that reaches it is smeared over that half second
+ * and its whole energy lands in the band, while zeroing the click ahead of K0 costs 0.1 ms of signal.  The reference
+ * has no such stage; this is the project's own definition, and it is exact.  It is OFF by default; with it off nothing
+ * of it runs or is allocated and every byte is what it was before the option existed.
+ *   Audio is taken at the rate it is pushed at, ahead of K11 and K0, each channel on its own, int16 samples counting
+ *   as s / 32768 exactly; the output is always float32.  Let N = UWSPR_BLANK_BLOCK = 4096.  Block b holds audio indices
+ *   b N .. b N + N - 1, counted from the stream's first sample after open / reset, or from the start of the record in
+ *   the batch call.
+ *   Level of a COMPLETE block: with u(i) the bit pattern of x[i] with the sign cleared, as an unsigned 32-bit integer,
+ *     med(b) = the value of rank N / 2 - 1 (0-based, ascending) among the N patterns of block b
+ *   (a selection: exact, ties need no rule).
+ *   Threshold: the samples of block b >= 1 use
+ *     thr(b) = fl32(fl32((float) blank * med(b - 1)) * 0.25f)      (two binary32 multiplies, subnormals kept).
+ *   Block 0 has no threshold, nor has a block whose med(b - 1) has pattern 0 or >= 0x7f800000 (infinity, NaN).
+ *   Causal: a sample never waits for audio behind it, except for the guard.
+ *   Flag: sample i is flagged iff its block has a threshold and u(i) > bits(thr(block(i))) as unsigned integers (so a
+ *   NaN sample in a block with a threshold is flagged; in a block without one, nothing is).
+ *   Output: y[i] = +0.0f if any j with |j - i| <= G is flagged, else x[i] unchanged (the float value of an int16
+ *   sample).  G is the guard; j is limited to samples that exist (j >= 0; in the batch call j < nin); the guard crosses
+ *   block edges and each j is judged by its OWN block's threshold.
+ *   Completeness: in a stream y[i] is complete as soon as x[i + G] has been pushed.  Like K0 there is no flush and no
+ *   padding: the last G samples of a stream that ends are never produced.  A stream's bytes do not depend on how the
+ *   audio was cut, on the sample format of a piece or on the channel count, and on every index both produce they are
+ *   the batch call's.
+ * What the design costs: a level step of more than blank / 4 between neighbouring blocks is blanked for up to one
+ * block (0.34 s at 12 kS/s) -- a signal that switches on is judged by the silence before it -- and block 0 passes
+ * untouched (the first 0.34 s of a stream are not protected).
+ * Options: "blank" is the threshold in quarters of the median: 0 = off (default), 4 .. 1024 = on (24 means 6 x the
+ * median of |x|, about 4.05 sigma of Gaussian noise); "blank_guard" is G, 0 .. 64, default 2.  Anything else is
+ * UWSPR_ERR_ARG.  Both are options of the context (uwspr_set_option) for uwspr_stream_push_audio, and the pipe's own
+ * in uwspr_pipe_set_option, as "audio_rate" is.  Both are latched by the first audio push after open / reset; a change
+ * while the stream runs fails that push with UWSPR_ERR_ARG (the stream is unharmed: set the old values again and go on).
+ * With "blank" != 0 a push uploads the new frames behind the blanker's own history (what is not yet output, its guard
+ * and the incomplete block: at most N + 2 G frames), runs the level kernel for the blocks the push completes and the
+ * apply kernel for the outputs it completes on the copy stream, and hands those float frames to the resampler or the
+ * front-end on the same stream, exactly as a device push of them would; the buffer-full check counts the samples a push
+ * will complete.  Device memory it adds to a stream, made by the first such push: two input buffers of (N + 2 G + Q) *
+ * nchannels samples (4 bytes), one output buffer of Q * nchannels floats (Q = 4 Mi / nchannels frames), and tables of a
+ * few KB: 3 x 16 MB and at most 2 x 1.1 MB of history.
+ *   uwspr_blank_batch         a whole record: audio [nin][nchannels] interleaved (format UWSPR_AUDIO_F32 / _S16,
+ *                             1..UWSPR_PIPE_MAX_CHANNELS channels), blank 4 .. 1024, guard 0 .. 64 -> out [nin][nchannels]
+ *                             float; med [nblocks][nchannels] float (nblocks = ceil(nin / N)): the level of every
+ *                             COMPLETE block, 0 for a trailing partial one; nzero [nblocks][nchannels] int32: the
+ *                             outputs of that block set to zero.  med and nzero may be NULL.  where = UWSPR_HOST
+ *                             (complete on return) or UWSPR_DEVICE (asynchronous on the context's stream), as in
+ *                             uwspr_resample_batch.
+ *   uwspr_stream_blank_stats  per channel (at most cap of them): the samples output and the samples set to zero since
+ *                             open / reset, summed on the host from the per-block counts (waits for the copy
+ *                             stream); zeros when no blanker runs.  Returns the channel count. */
+#define UWSPR_BLANK_BLOCK 4096
+int uwspr_blank_batch(uwspr_ctx *ctx, const void *audio, long long nin, int nchannels, int format, int where, int blank,
+                      int guard, float *out, float *med, int *nzero);
+int uwspr_stream_blank_stats(uwspr_ctx *ctx, long long *samples, long long *zeroed, int cap);
 /* device memory for callers without a HIP runtime of their own (the block mirror's frame hand-over) */
 int uwspr_device_alloc(size_t bytes, void **ptr);
 void uwspr_device_free(void *ptr);
@@ -522,7 +579,11 @@ int uwspr_pipe_push_audio(uwspr_pipe *pipe, const void *audio, int nsamples, int
  * uwspr_resample_design supports, else UWSPR_ERR_ARG), latched by the first audio push; setting another value once the
  * audio stream runs is UWSPR_ERR_ARG.  The pieces then go through K11 and the front-end as described at
  * uwspr_resample_batch, the pipe makes room for the 12 kS/s samples a piece will produce, and the resampler's buffers
- * (see there) come on top of the figures above.  nframes counts frames at that rate; stream_pos / 375 stays seconds. */
+ * (see there) come on top of the figures above.  nframes counts frames at that rate; stream_pos / 375 stays seconds.
+ * Impulsive noise: "blank" and "blank_guard" are the pipe's own options as well (uwspr_pipe_set_option; 0 = off and 2 by
+ * default, ranges as at uwspr_blank_batch, else UWSPR_ERR_ARG), latched by the first audio push; another value once the
+ * audio stream runs is UWSPR_ERR_ARG.  The pieces then go through K12 first, as described at uwspr_blank_batch; the
+ * last "blank_guard" samples pushed are never output. */
 #define UWSPR_PIPE_MAX_CHANNELS 64
 int uwspr_pipe_push_audio_channels(uwspr_pipe *pipe, const void *audio, int nframes, int nchannels, int format);
 /* B frames already in device memory (frame b at frames + 2*stride*b floats, stride 0 = fl): searched as one
@@ -534,6 +595,9 @@ int uwspr_pipe_flush(uwspr_pipe *pipe);
  * in flight.  returns the count (>= 0) or a negative status. */
 int uwspr_pipe_collect(uwspr_pipe *pipe, uwspr_decode *out, int cap, int wait);
 int uwspr_pipe_get_stats(uwspr_pipe *pipe, uwspr_pipe_stats *st);
+/* uwspr_stream_blank_stats of the pipe's audio stream (the pipe's options "blank" / "blank_guard"): call it from the
+ * producer's thread */
+int uwspr_pipe_blank_stats(uwspr_pipe *pipe, long long *samples, long long *zeroed, int cap);
 /* uwspr_set_option on every lane's context (e.g. "fast_search").  Only while nothing is in flight (after
  * uwspr_pipe_flush / before the first batch): UWSPR_ERR_ARG otherwise, and for "sched", which the pipe chooses by its
  * lane count (uwspr_pipe_opts.sched_form).
