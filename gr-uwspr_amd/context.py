@@ -205,6 +205,44 @@ class Context:
         self._chk(f(self.h, C.c_void_p(audio.data_ptr()), fmt, nin, int(in0), nch, C.c_void_p(out.data_ptr()), nout,
                     int(m_first), plane))
 
+    def debug_frontend_carrier_launch(self, audio, in0, out, m_first, carriers, nch=1, plane=None, nout=None, nin=None):
+        """diagnostics: ONE launch of the carrier form of K0 (uwspr_debug_frontend_carrier_launch; what a stream's audio
+        push runs for any carriers but {1500 Hz} at 10 Hz) on torch CUDA tensors, in the context's "frontend" mode with its
+        "frontend_hbw".  audio: float32 or int16, nin frames [in0, in0 + nin) of nch interleaved channels; carriers: Hz;
+        out: float32, receives outputs [m_first, m_first + nout) of plane c * len(carriers) + k at pair plane_index *
+        plane.  The tensors must hold what the launch reads and writes: that is checked here."""
+        import torch
+        fmt = {torch.float32: N.AUDIO_F32, torch.int16: N.AUDIO_S16}.get(audio.dtype)
+        if fmt is None or not audio.is_cuda or not audio.is_contiguous():
+            raise TypeError("debug_frontend_carrier_launch: a contiguous float32 or int16 CUDA tensor, not %s" % audio.dtype)
+        if out.dtype != torch.float32 or not out.is_cuda or not out.is_contiguous():
+            raise TypeError("debug_frontend_carrier_launch: out is a contiguous float32 CUDA tensor, not %s" % out.dtype)
+        car = np.ascontiguousarray(carriers, np.int32).reshape(-1)
+        nch, NC = int(nch), int(car.size)
+        if nch < 1 or NC < 1:
+            raise ValueError("debug_frontend_carrier_launch: nch %d, %d carriers" % (nch, NC))
+        npl = nch * NC
+        if nin is None:
+            nin = audio.numel() // nch
+        if nout is None:
+            if plane is not None:
+                raise ValueError("debug_frontend_carrier_launch: plane without nout")
+            nout = out.numel() // (2 * npl)
+        if plane is None:
+            plane = nout
+        nin, nout, plane = int(nin), int(nout), int(plane)
+        if nin < 1 or nout < 1 or plane < nout or nin * nch > audio.numel() or 2 * ((npl - 1) * plane + nout) > out.numel():
+            raise ValueError("debug_frontend_carrier_launch: nin %d x nch %d / nout %d, plane %d x %d do not fit the tensors"
+                             % (nin, nch, nout, plane, npl))
+        f = self.L.uwspr_debug_frontend_carrier_launch
+        f.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_longlong, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                      C.c_int, C.c_longlong, C.c_longlong]
+        f.restype = C.c_int
+        if self._stream_ptr is None:
+            torch.cuda.current_stream(audio.device).synchronize()
+        self._chk(f(self.h, C.c_void_p(audio.data_ptr()), fmt, nin, int(in0), nch, NC, C.c_void_p(car.ctypes.data),
+                    C.c_void_p(out.data_ptr()), nout, int(m_first), plane))
+
     # -- resampler (K11) ----------------------------------------------------
     def resample(self, audio, rate, nout=None):
         """Audio at `rate` S/s -> 12 kS/s float32 (uwspr_resample_batch): a 1-D [n] or 2-D [n, C] numpy float32 or
@@ -934,18 +972,41 @@ def host_free(buf):
     N.lib().uwspr_host_free(C.c_void_p(buf._uwspr_ptr))
 
 
-def frontend_design(mode=FRONTEND_GRC, stage=0):
-    """uwspr_frontend_design: stage 0 -> (complex128 composite taps g, read-ahead D) of the K0 front-end
-    y[m] = sum_k g[k] x[32 m + D - k]; stages 1..3 (grc mode) -> the band-pass, low-pass and resampler designs."""
+def frontend_design(mode=FRONTEND_GRC, stage=0, centre=1500, half_bw=10):
+    """uwspr_frontend_design_at: stage 0 -> (complex128 composite taps g, read-ahead D) of the K0 front-end
+    y[m] = sum_k g[k] x[32 m + D - k]; stages 1..3 (grc mode) -> the band-pass, low-pass and resampler designs.
+    centre, half_bw: the flowgraph's Center_Frequency and Half_Bandwidth in integer Hz (options "carrier" and
+    "frontend_hbw"); away from a multiple of 375 Hz the rotator (frontend_rotator) follows the sum."""
     d = C.c_int32(0)
-    n = N.lib().uwspr_frontend_design(mode, stage, None, 0, C.byref(d))
+    centre, half_bw = int(centre), int(half_bw)
+    n = N.lib().uwspr_frontend_design_at(mode, centre, half_bw, stage, None, 0, C.byref(d))
     if n < 0:
-        raise N.UwsprError(n, "uwspr_frontend_design(mode=%d, stage=%d)" % (mode, stage))
+        raise N.UwsprError(n, "uwspr_frontend_design_at(mode=%d, centre=%d, half_bw=%d, stage=%d)" % (mode, centre, half_bw, stage))
     g = np.zeros(n * (2 if stage == 0 else 1), np.float64)
-    N.lib().uwspr_frontend_design(mode, stage, C.c_void_p(g.ctypes.data), n, C.byref(d))
+    N.lib().uwspr_frontend_design_at(mode, centre, half_bw, stage, C.c_void_p(g.ctypes.data), n, C.byref(d))
     if stage == 0:
         return g[0::2] + 1j * g[1::2], int(d.value)
     return g
+
+
+def frontend_rotator():
+    """uwspr_frontend_rotator: K0's rotator table -> float32 [375, 2], row i = (cos, -sin)(2 pi i / 375); output m of a
+    stream at carrier fc is multiplied by row ((fc mod 375) (m mod 375)) mod 375 unless 375 divides fc"""
+    out = np.zeros((375, 2), np.float32)
+    n = N.lib().uwspr_frontend_rotator(C.c_void_p(out.ctypes.data))
+    if n != 375:
+        raise N.UwsprError(n if n < 0 else -1, "uwspr_frontend_rotator")
+    return out
+
+
+def frontend_carrier_launch_counts():
+    """diagnostics: launches of K0's carrier form since the process started -> (with float32 input, with int16 input)"""
+    f = N.lib().uwspr_debug_frontend_carrier_counts
+    f.argtypes = [C.c_void_p]
+    f.restype = C.c_int
+    out = np.zeros(2, np.int64)
+    f(C.c_void_p(out.ctypes.data))
+    return int(out[0]), int(out[1])
 
 
 def resample_design(rate):
@@ -1186,8 +1247,9 @@ class Pipe:
     def __init__(self, fs=375, fl=45000, spb=256, maxdrift=0, maxfreqs=200, halfbandwidth=10, cf=1500,
                  threshold=10, device=0, hop=3375, batch_frames=256, max_per_frame=1, lanes=0,
                  host_threads=0, eager=False, sched=None, spare_after_us=0, passes=1, osd=0, osd_gap=None,
-                 block=0, audio_rate=None, blank=0, blank_guard=None):
+                 block=0, audio_rate=None, blank=0, blank_guard=None, carriers=None, frontend_hbw=None):
         self.L = N.lib()
+        self.carriers = [1500]
         self.h = C.c_void_p()
         self.fl = fl
         p = N.Params(fs, fl, spb, maxdrift, maxfreqs, halfbandwidth, cf, threshold)
@@ -1216,6 +1278,10 @@ class Pipe:
                 self.set_option("blank", blank)
             if blank_guard is not None:
                 self.set_option("blank_guard", blank_guard)
+            if carriers is not None:   # K0's centres in Hz: every pushed channel is heard at every one of them
+                self.set_carriers(carriers)
+            if frontend_hbw is not None:
+                self.set_option("frontend_hbw", frontend_hbw)
         except N.UwsprError:
             self.close()
             raise
@@ -1291,6 +1357,18 @@ class Pipe:
         """uwspr_pipe_set_option: an option of every lane's context; only while nothing is in flight"""
         self._chk(self.L.uwspr_pipe_set_option(self.h, name.encode(), int(value)))
 
+    def set_carriers(self, hz):
+        """uwspr_pipe_set_carriers: K0's centres in Hz (distinct integers, order kept), before the first audio push.  With
+        more than one, a record's "channel" field is the plane index: split_plane gives (channel, carrier)."""
+        car = np.ascontiguousarray([int(v) for v in hz], np.int32).reshape(-1)
+        self._chk(self.L.uwspr_pipe_set_carriers(self.h, C.c_void_p(car.ctypes.data), int(car.size)))
+        self.carriers = [int(v) for v in car]
+
+    def split_plane(self, channel_field):
+        """a record's "channel" field -> (audio channel, carrier in Hz): the field holds channel * n + k with n carriers"""
+        n = len(self.carriers)
+        return int(channel_field) // n, self.carriers[int(channel_field) % n]
+
     def blank_stats(self, channels=1):
         """uwspr_pipe_blank_stats: per channel, (samples output, samples set to zero) by the pipe's blanker -> two int64
         arrays [channels]; zeros when the pipe's "blank" is 0"""
@@ -1350,8 +1428,10 @@ def decode_wav(path, channels=None, **pipe_opts):
     "osd" (1: Fano timed out and ordered-statistics decoding gave the message, osd=1 or 2; else 0) and "block" (2, 3: Fano
     timed out and the soft symbols coherent over that many symbols decoded, block=2 or 3; else 0).
     channels="all": every channel of the file through one pipe, records in (take, channel, frame) order, each dict with
-    its "channel"."""
+    its "channel".  carriers=[Hz, ..]: every channel is heard at each of them (Pipe(carriers=..)), records in (take,
+    channel, carrier, frame) order, each dict with its "carrier" in Hz ("channel" stays the audio channel)."""
     x, rate = read_wav(path, channels, any_rate=True)
+    carriers = pipe_opts.get("carriers")
     pipe = Pipe(audio_rate=rate, **pipe_opts)
     try:
         piece = rate * 60
@@ -1369,7 +1449,10 @@ def decode_wav(path, channels=None, **pipe_opts):
              "freq": float(r["coarse"]["freq"]), "snr": float(r["coarse"]["snr"]),
              "text": unpack_message(r["message"])[1], "pass": int(r["pass"]), "osd": int(r["osd"]),
              "block": int(r["block"])}
+        ch, car = pipe.split_plane(r["channel"])
         if channels == "all":
-            d["channel"] = int(r["channel"])
+            d["channel"] = ch
+        if carriers is not None:
+            d["carrier"] = car
         out.append(d)
     return out

@@ -28,8 +28,13 @@
 // consecutive words.  LDS: 32 x (8 L + 1) samples + 32 J taps = 149 KB for the grc mode: one workgroup, 4 wavefronts
 // per SIMD.  1.2 GFLOP and 5.8 MB in per 2-minute frame (213 flop / B): FP32-FMA bound.
 #include <math.h>
+#include <string.h>
 
+#include <atomic>
 #include <complex>
+#include <map>
+#include <mutex>
+#include <tuple>
 #include <vector>
 
 #include "uwspr_internal.h"
@@ -65,6 +70,11 @@ __device__ __forceinline__ void k0_block(float (&ar)[K0_R], float (&ai)[K0_R], c
 __device__ __forceinline__ float k0_sample(float v) { return v; }
 __device__ __forceinline__ float k0_sample(int16_t v) { return (float)v * (1.0f / 32768); }
 
+// the rotator's product, one order (include/uwspr_hip.h; k8_cancel's product form): s * r with r = (c, d)
+__device__ __forceinline__ float2 k0_rotate(float2 s, float2 r) {
+  return make_float2(fmaf(s.x, r.x, -(s.y * r.y)), fmaf(s.x, r.y, s.y * r.x));
+}
+
 // taps: [32][J] float2, taps[p][jj] = g[32 (J - 1 - jj) + p] (zero beyond the filter); dcols = D / 32.
 // Origins: audio[b][0] is sample in0 of its record and out[b][0] is output m_first, i.e. out[b][i] = y[m_first + i]
 // reads audio[b][n - in0]; samples outside [in0, in0 + nin) count as zero.  The batch call passes 0 and 0, the
@@ -75,11 +85,23 @@ __device__ __forceinline__ float k0_sample(int16_t v) { return (float)v * (1.0f 
 // output block read the same input lines, so they are consecutive after xcd_swizzle and share an XCD's L2.  Only the
 // loader's address and the output's plane differ: channel b's outputs are bit for bit those of its one-channel stream.
 // (nch and plane are not read by the other forms, whose code is that of the one-record kernel.)
-template <typename T, bool MC>
+// CAR (the carrier form; MC addressing): NC carriers listen to every audio channel.  Workgroup (output block, plane
+// q = c NC + k) reads channel c as the MC form does, takes its taps from image k of taps[NC][32][J], and writes plane q
+// after carrier k's rotator: with f = fcm[k] = fc mod 375 != 0 the sum s of output m leaves as s * rot[(f (m mod 375))
+// mod 375] in k0_rotate's one order; with f == 0 the mixer is the identity at the decimated instants and s leaves as it
+// is (its bytes, not a product with (1, -0)).  The planes of one output block are consecutive after xcd_swizzle.
+// The form has the other forms' arguments (their kernels stay what they were, argument layout included): nch carries
+// nch | NC << 8, and the tables follow the tap images in one block -- taps[NC][32][J], rot[375] (float2), fcm[NC] (int).
+template <typename T, bool MC, bool CAR = false>
 __global__ __launch_bounds__(K0_WG) void k0_frontend(const T *__restrict__ audio, int nin, long long in0,
                                                      const float2 *__restrict__ taps, float2 *__restrict__ out,
                                                      int nout, long long m_first, int J, int dcols, int nch,
                                                      long long plane) {
+  static_assert(MC || !CAR, "the carrier form reads interleaved channels");
+  [[maybe_unused]] const int NC = CAR ? nch >> 8 : 1;
+  if constexpr (CAR) nch &= 255;
+  [[maybe_unused]] const float2 *rot = taps + (size_t)NC * K0_DEC * J;
+  [[maybe_unused]] const int *fcm = reinterpret_cast<const int *>(rot + 375);
   extern __shared__ __align__(16) float k0_lds[];
   const int L = k0_L(J), ROW = k0_row(J);
   float *xs = k0_lds;
@@ -87,7 +109,13 @@ __global__ __launch_bounds__(K0_WG) void k0_frontend(const T *__restrict__ audio
   const int tid = threadIdx.x;
   int b;
   unsigned blk;   // (unsigned, as blockIdx.x)
-  if constexpr (MC) {
+  [[maybe_unused]] int q = 0, kc = 0;   // carrier form: the plane and its carrier
+  if constexpr (CAR) {
+    const unsigned lb = xcd_swizzle(blockIdx.x, gridDim.x), np = (unsigned)(nch * NC);
+    blk = lb / np; q = (int)(lb - blk * np);
+    b = q / NC; kc = q - b * NC;
+    taps += (size_t)kc * K0_DEC * J;
+  } else if constexpr (MC) {
     const unsigned lb = xcd_swizzle(blockIdx.x, gridDim.x);
     blk = lb / (unsigned)nch; b = (int)(lb - blk * (unsigned)nch);
   } else {
@@ -152,7 +180,20 @@ __global__ __launch_bounds__(K0_WG) void k0_frontend(const T *__restrict__ audio
       re += q.x; im += q.y;
     }
     const int m = blk * K0_OUT + K0_R * l + i;
-    if (m < nout) out[MC ? (size_t)b * plane + m : (size_t)b * nout + m] = make_float2(re, im);
+    if constexpr (CAR) {
+      const int f = fcm[kc];
+      if (m < nout) {
+        float2 y = make_float2(re, im);
+        if (f != 0) {
+          const long long ma = m_first + m;
+          const int mr = (int)(ma % 375), mm = mr < 0 ? mr + 375 : mr;
+          y = k0_rotate(y, rot[(f * mm) % 375]);
+        }
+        out[(size_t)q * plane + m] = y;
+      }
+    } else {
+      if (m < nout) out[MC ? (size_t)b * plane + m : (size_t)b * nout + m] = make_float2(re, im);
+    }
   }
 }
 
@@ -239,33 +280,59 @@ static cplx octant(long k) {
   return cplx(cs[q], sn[q]);
 }
 
-// stage 0: the composite complex taps g (pairs) and the read-ahead D; stages 1..3 (grc mode): the three real designs
-int frontend_design(int mode, int stage, std::vector<double> &outv, int *delay) {
+// e^{+j 2 pi fc k / 12000} for an integer centre: fc k is reduced in integers first, and an angle that is a multiple of
+// pi/4 (every k at 1500 Hz) takes the exact octant values
+static cplx mixer(int fc, long k) {
+  const long r = ((((long)fc * (k % 12000)) % 12000) + 12000) % 12000;
+  if (r % 1500 == 0) return octant(r / 1500);
+  const double a = 2.0 * M_PI * (double)r / 12000.0;
+  return cplx(cos(a), sin(a));
+}
+
+bool frontend_carrier_ok(int mode, int fc, int hb) {
+  if (mode == UWSPR_FRONTEND_COMPACT) hb = 0;   // (the compact mode has no such variable)
+  else if (hb < 1 || hb > 150) return false;
+  return fc >= hb + 20 && fc <= 6000 - hb - 20;
+}
+
+// the rotator's table: rot[i] = e^{-j 2 pi i / 375} as binary32 pairs (cos, -sin), from the reduced index in binary64
+void frontend_rotator(float *out750) {
+  for (int i = 0; i < 375; i++) {
+    const double a = 2.0 * M_PI * (double)i / 375.0;
+    out750[2 * i] = (float)cos(a);
+    out750[2 * i + 1] = (float)(-sin(a));
+  }
+}
+
+// stage 0: the composite complex taps g (pairs) and the read-ahead D; stages 1..3 (grc mode): the three real designs.
+// fc, hb: the flowgraph's Center_Frequency and Half_Bandwidth (integer Hz; the compact mode has no hb)
+int frontend_design_at(int mode, int fc, int hb, int stage, std::vector<double> &outv, int *delay) {
   outv.clear();
   if (delay) *delay = 0;
+  if (mode != UWSPR_FRONTEND_COMPACT && mode != UWSPR_FRONTEND_GRC) return UWSPR_ERR_ARG;
+  if (!frontend_carrier_ok(mode, fc, hb)) return UWSPR_ERR_ARG;
   if (mode == UWSPR_FRONTEND_COMPACT) {
     if (stage != 0) return UWSPR_ERR_ARG;
-    // h[k] e^{-j pi (D - k) / 4}: Hamming-windowed sinc, cutoff 100 Hz, 1025 taps, unit DC gain, D = 512
+    // h[k] e^{-j 2 pi fc (D - k) / 12000}: Hamming-windowed sinc, cutoff 100 Hz, 1025 taps, unit DC gain, D = 512
     const int NT = 1025, D = K0_COMPACT_D;
     std::vector<double> h(NT);
-    const double fc = 100.0 / 12000.0;
+    const double fcut = 100.0 / 12000.0;
     double sum = 0.0;
     for (int k = 0; k < NT; k++) {
       const double t = (double)(k - D);
-      const double sinc = t == 0.0 ? 2.0 * fc : sin(2.0 * M_PI * fc * t) / (M_PI * t);
+      const double sinc = t == 0.0 ? 2.0 * fcut : sin(2.0 * M_PI * fcut * t) / (M_PI * t);
       h[k] = sinc * (0.54 - 0.46 * cos(2.0 * M_PI * (double)k / (double)(NT - 1)));
       sum += h[k];
     }
     for (int k = 0; k < NT; k++) {
-      const cplx g = (h[k] / sum) * std::conj(octant(D - k));
+      const cplx g = (h[k] / sum) * std::conj(mixer(fc, D - k));
       outv.push_back(g.real()); outv.push_back(g.imag());
     }
     if (delay) *delay = D;
     return UWSPR_OK;
   }
-  if (mode != UWSPR_FRONTEND_GRC) return UWSPR_ERR_ARG;
-  const std::vector<float> h1 = gr_firdes(1.0, 12000.0, 1500.0 - 10.0, 1500.0 + 10.0, 10.0, WIN_HAMMING, 6.76);
-  const std::vector<float> h2 = gr_firdes(1.0, 12000.0, -1.0, 1500.0 + 10.0, 10.0, WIN_HAMMING, 6.76);
+  const std::vector<float> h1 = gr_firdes(1.0, 12000.0, (double)fc - (double)hb, (double)fc + (double)hb, 10.0, WIN_HAMMING, 6.76);
+  const std::vector<float> h2 = gr_firdes(1.0, 12000.0, -1.0, (double)fc + (double)hb, 10.0, WIN_HAMMING, 6.76);
   const std::vector<float> h3 = gr_resampler_taps(1, 32);
   if (stage >= 1 && stage <= 3) {
     const std::vector<float> &h = stage == 1 ? h1 : stage == 2 ? h2 : h3;
@@ -277,21 +344,55 @@ int frontend_design(int mode, int stage, std::vector<double> &outv, int *delay) 
   for (size_t k = 0; k < h1.size(); k++) a[k] = cplx(h1[k], 0.0);
   // freq_xlating_fft_filter_ccc hands fft_filter_ccc gr_complex taps: the rotated taps are binary32 pairs
   for (size_t k = 0; k < h2.size(); k++) {
-    const cplx z = (double)h2[k] * octant((long)k);
+    const cplx z = (double)h2[k] * mixer(fc, (long)k);
     bq[k] = cplx((double)(float)z.real(), (double)(float)z.imag());
   }
   // the resampler filters BEHIND the mixer: its taps meet the input rotated, in exact arithmetic
-  for (size_t k = 0; k < h3.size(); k++) cq[k] = (double)h3[k] * octant((long)k);
+  for (size_t k = 0; k < h3.size(); k++) cq[k] = (double)h3[k] * mixer(fc, (long)k);
   const std::vector<cplx> g = conv(conv(a, bq), cq);
   for (const cplx &z : g) { outv.push_back(z.real()); outv.push_back(z.imag()); }
   return UWSPR_OK;
 }
 
+int frontend_design(int mode, int stage, std::vector<double> &outv, int *delay) {
+  return frontend_design_at(mode, UWSPR_CARRIER_DEFAULT, UWSPR_FRONTEND_HBW_DEFAULT, stage, outv, delay);
+}
+
 // the kernel's tap image: [32][J] float2, jj ascending = tap index descending
 int frontend_tap_image(int mode, std::vector<float> &img, int *J_out, int *dcols_out) {
+  return frontend_tap_image_at(mode, UWSPR_CARRIER_DEFAULT, UWSPR_FRONTEND_HBW_DEFAULT, img, J_out, dcols_out);
+}
+
+// (the images of the last designs are kept: a pipe with 64 carriers, or one opened again, designs each of them once)
+namespace {
+struct tap_image { std::vector<float> img; int J, dcols, rc; };
+std::mutex k0_img_mutex;
+std::map<std::tuple<int, int, int>, tap_image> k0_images;
+}  // namespace
+
+static int tap_image_build(int mode, int fc, int hb, std::vector<float> &img, int *J_out, int *dcols_out);
+
+int frontend_tap_image_at(int mode, int fc, int hb, std::vector<float> &img, int *J_out, int *dcols_out) {
+  if (mode == UWSPR_FRONTEND_COMPACT) hb = 0;   // (not read by that design)
+  const auto key = std::make_tuple(mode, fc, hb);
+  {
+    std::lock_guard<std::mutex> lk(k0_img_mutex);
+    const auto it = k0_images.find(key);
+    if (it != k0_images.end()) { img = it->second.img; *J_out = it->second.J; *dcols_out = it->second.dcols; return it->second.rc; }
+  }
+  const int rc = tap_image_build(mode, fc, hb, img, J_out, dcols_out);
+  if (rc == UWSPR_OK) {
+    std::lock_guard<std::mutex> lk(k0_img_mutex);
+    if (k0_images.size() >= 128) k0_images.clear();
+    k0_images[key] = tap_image{img, *J_out, *dcols_out, rc};
+  }
+  return rc;
+}
+
+static int tap_image_build(int mode, int fc, int hb, std::vector<float> &img, int *J_out, int *dcols_out) {
   std::vector<double> g;
   int D = 0;
-  const int rc = frontend_design(mode, 0, g, &D);
+  const int rc = frontend_design_at(mode, fc, hb, 0, g, &D);
   if (rc) return rc;
   const int NT = (int)g.size() / 2;
   int J = (NT + K0_DEC - 1) / K0_DEC;
@@ -313,7 +414,9 @@ int frontend_read_ahead(int mode) {
 int frontend_prepare() {
   // up to 160 KB of dynamic LDS (149 KB in the grc mode); int16 samples are widened before they reach LDS
   const void *k[] = {reinterpret_cast<const void *>(k0_frontend<float, false>), reinterpret_cast<const void *>(k0_frontend<int16_t, false>),
-                     reinterpret_cast<const void *>(k0_frontend<float, true>), reinterpret_cast<const void *>(k0_frontend<int16_t, true>)};
+                     reinterpret_cast<const void *>(k0_frontend<float, true>), reinterpret_cast<const void *>(k0_frontend<int16_t, true>),
+                     reinterpret_cast<const void *>(k0_frontend<float, true, true>),
+                     reinterpret_cast<const void *>(k0_frontend<int16_t, true, true>)};
   for (const void *f : k)
     if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return -1;
   return 0;
@@ -349,6 +452,41 @@ void launch_frontend_stream(hipStream_t s, const void *audio, bool s16, int nin,
   else
     hipLaunchKernelGGL((k0_frontend<float, false>), grid, dim3(K0_WG), k0_lds_bytes(J), s, (const float *)audio, nin, in0,
                        (const float2 *)taps, (float2 *)out, nout, m_first, J, dcols, 1, 0LL);
+}
+
+// the carrier form's device block for `carriers` (Hz) at half-bandwidth hb: taps[NC][32][J] float2, the rotator table
+// (375 float2), carrier k mod 375 (NC ints)
+int frontend_carrier_tables(int mode, const std::vector<int> &carriers, int hb, std::vector<float> &blk, int *J_out, int *dcols_out) {
+  blk.clear();
+  std::vector<float> img;
+  for (int fc : carriers) {
+    const int rc = frontend_tap_image_at(mode, fc, hb, img, J_out, dcols_out);
+    if (rc) return rc;
+    blk.insert(blk.end(), img.begin(), img.end());
+  }
+  const size_t at = blk.size();
+  blk.resize(at + 750 + carriers.size());
+  frontend_rotator(&blk[at]);
+  for (size_t k = 0; k < carriers.size(); k++) { const int f = carriers[k] % 375; memcpy(&blk[at + 750 + k], &f, sizeof(int)); }
+  return carriers.empty() ? UWSPR_ERR_ARG : UWSPR_OK;
+}
+
+// the carrier form: planes q = c NC + k (audio channel c, carrier k) of outputs m_first .. m_first + nout - 1, plane q at
+// out + 2 * q * plane floats; tables: frontend_carrier_tables' block on the device
+static std::atomic<long long> k0_carrier_launches[2];
+long long frontend_carrier_launch_count(int s16) { return k0_carrier_launches[s16 ? 1 : 0].load(); }
+
+void launch_frontend_carrier(hipStream_t s, const void *audio, bool s16, int nin, long long in0, const float *tables, int J,
+                             int dcols, float *out, int nout, long long m_first, int nch, int NC, long long plane) {
+  const int nblk = (nout + K0_OUT - 1) / K0_OUT;
+  const dim3 grid(nblk * nch * NC, 1);
+  k0_carrier_launches[s16 ? 1 : 0]++;
+  if (s16)
+    hipLaunchKernelGGL((k0_frontend<int16_t, true, true>), grid, dim3(K0_WG), k0_lds_bytes(J), s, (const int16_t *)audio, nin, in0,
+                       (const float2 *)tables, (float2 *)out, nout, m_first, J, dcols, nch | NC << 8, plane);
+  else
+    hipLaunchKernelGGL((k0_frontend<float, true, true>), grid, dim3(K0_WG), k0_lds_bytes(J), s, (const float *)audio, nin, in0,
+                       (const float2 *)tables, (float2 *)out, nout, m_first, J, dcols, nch | NC << 8, plane);
 }
 
 // int16 samples into a float stream buffer: the value K0's int16 loader computes (k0_sample)

@@ -102,6 +102,8 @@ struct uwspr_pipe {
   int block = 0;    // uwspr_pipe_set_option("block"): 2, 3 = K10's soft symbols of block lengths 2 .. block for those records
   int audio_rate = 12000;   // uwspr_pipe_set_option("audio_rate"): the rate of the pushed audio (12000: no resampler, else K11 ahead of K0)
   int blank = 0, blank_guard = 2;   // uwspr_pipe_set_option("blank" / "blank_guard"): K12 ahead of K11 / K0 (blank 0: off)
+  std::vector<int> carriers = std::vector<int>(1, UWSPR_CARRIER_DEFAULT);   // uwspr_pipe_set_carriers: K0's centres in Hz, in plane order
+  int frontend_hbw = UWSPR_FRONTEND_HBW_DEFAULT;                            // uwspr_pipe_set_option("frontend_hbw")
   char err[512];
   // Sticky status of the first RUNTIME failure (HIP, a lane's context), written by coordinators and the producer, read
   // by both without the lock.  Argument errors are not sticky: the call that made them returns UWSPR_ERR_ARG (with
@@ -638,7 +640,8 @@ static void release_lane(uwspr_pipe *q, pipe_lane &L) {   // a launch that faile
   q->cv_lane.notify_all();
 }
 
-// k frames of every channel: one batch per channel, channels 0..nch-1, each in place in its plane.  The view consumes
+// k frames of every plane (channel c, carrier k: plane c * ncar + k; one carrier: the channels): one batch per plane, in
+// plane order, each in place in its plane; the batch's `channel` is the plane index.  The view consumes
 // the frames of all planes; the lanes of channels 1.. wait for the same uploads (nothing is appended in between: the
 // producer thread is the only writer) and each lane's event joins the buffer's readers.
 static int launch_from_ring(uwspr_pipe *q, int k) {
@@ -646,7 +649,7 @@ static int launch_from_ring(uwspr_pipe *q, int k) {
   const float *frames = nullptr;
   long long pos = 0;
   int buf = 0;
-  for (int c = 0; c < r.nch; c++) {
+  for (int c = 0; c < r.npl; c++) {
     pipe_lane *L = take_lane(q);
     if (c == 0 && !r.view(k, L->stream, &frames, &pos, &buf)) {
       release_lane(q, *L);
@@ -760,13 +763,15 @@ extern "C" int uwspr_pipe_open(const uwspr_params *p, int device, const uwspr_pi
 // the device ring and the page-locked staging buffers.  Per channel plane: ceil(lanes / nch) + 3 takes of slack (at
 // most `lanes` batches are in flight, nch per take) + fl.  A ring nothing was pushed into yet takes the channel count
 // of the first push (a pipe's stream kind and channel count are latched by its first push).
-static int open_ingest(uwspr_pipe *q, int nch) {
+// With ncar carriers (audio pushes only) the planes are nch * ncar, and that product takes nch's place in the formula.
+static int open_ingest(uwspr_pipe *q, int nch, int ncar = 1) {
   stream_ring &r = q->ring;
-  if (r.is_open() && (r.nch == nch || r.kind != RING_EMPTY)) return UWSPR_OK;
+  if (r.is_open() && ((r.nch == nch && r.ncar == ncar) || r.kind != RING_EMPTY)) return UWSPR_OK;
   const bool staged = r.is_open();
-  const int takes = (q->o.lanes + nch - 1) / nch + 3;
-  if (!r.open(q->fl, q->o.hop, q->o.batch_frames, takes, nch))
-    return pfail(q, UWSPR_ERR_NOMEM, "stream ring (%d channel planes of %lld pairs, 2 buffers): %s", nch,
+  const int npl = nch * ncar;
+  const int takes = (q->o.lanes + npl - 1) / npl + 3;
+  if (!r.open(q->fl, q->o.hop, q->o.batch_frames, takes, nch, ncar))
+    return pfail(q, UWSPR_ERR_NOMEM, "stream ring (%d channel planes of %lld pairs, 2 buffers): %s", npl,
                  (long long)takes * q->o.batch_frames * q->o.hop + q->fl, hipGetErrorString(r.err));
   if (staged) return UWSPR_OK;
   for (int k = 0; k < uwspr_pipe::NSTAGE; k++) {
@@ -859,6 +864,15 @@ extern "C" int uwspr_pipe_push_audio_channels(uwspr_pipe *q, const void *audio, 
   const int mode = q->lanes[0].ctx->opt[UWSPR_OPT_FRONTEND];
   if (r.kind == RING_AUDIO && mode != r.au.mode)
     return parg(q, "uwspr_pipe_push_audio: option frontend changed to %d while the audio stream runs in mode %d", mode, r.au.mode);
+  // the carriers and "frontend_hbw": latched like the front-end mode, nchannels * carriers planes in all
+  const int ncar = (int)q->carriers.size(), hbw = q->frontend_hbw;
+  if ((long long)nchannels * ncar > UWSPR_PIPE_MAX_CHANNELS)
+    return parg(q, "uwspr_pipe_push_audio_channels: %d channels x %d carriers (at most %d planes)", nchannels, ncar, UWSPR_PIPE_MAX_CHANNELS);
+  for (int fc : q->carriers)
+    if (!frontend_carrier_ok(mode, fc, hbw))
+      return parg(q, "uwspr_pipe_push_audio: carrier %d Hz with half-bandwidth %d Hz (hb + 20 <= carrier <= 6000 - hb - 20)", fc, hbw);
+  if (r.kind == RING_AUDIO && (q->carriers != r.au.car || hbw != r.au.hbw))
+    return parg(q, "uwspr_pipe_push_audio: carriers / frontend_hbw changed while the audio stream runs (half-bandwidth %d Hz)", r.au.hbw);
   // option "audio_rate": latched like the front-end mode; any other rate than 12000 goes through K11 first
   const int rate = q->audio_rate;
   const bool rs_on = rate != 12000;
@@ -872,14 +886,14 @@ extern "C" int uwspr_pipe_push_audio_channels(uwspr_pipe *q, const void *audio, 
     return parg(q, "uwspr_pipe_push_audio: options blank / blank_guard changed to %d / %d while the audio stream runs with %d / %d",
                 blank, guard, r.bk.blank, r.bk.blank ? r.bk.guard : guard);
   (void)hipSetDevice(q->device);
-  if (const int rc = open_ingest(q, nchannels)) return rc;
+  if (const int rc = open_ingest(q, nchannels, ncar)) return rc;
   if (r.kind != RING_AUDIO && bk_on && !r.blank_latch(blank, guard, s16))
     return pfail(q, r.err == hipErrorOutOfMemory ? UWSPR_ERR_NOMEM : UWSPR_ERR_HIP, "blanker set-up (%d channels): %s", nchannels,
                  hipGetErrorString(r.err));
   if (r.kind != RING_AUDIO && rs_on && !r.resample_latch(rate, s16 && !bk_on))
     return pfail(q, r.err == hipErrorOutOfMemory ? UWSPR_ERR_NOMEM : UWSPR_ERR_HIP, "resampler set-up (%d S/s, %d channels): %s",
                  rate, nchannels, hipGetErrorString(r.err));
-  if (r.kind != RING_AUDIO && !r.audio_latch(mode, s16 && !rs_on && !bk_on))
+  if (r.kind != RING_AUDIO && !r.audio_latch(mode, s16 && !rs_on && !bk_on, &q->carriers, hbw))
     return pfail(q, r.err == hipErrorOutOfMemory ? UWSPR_ERR_NOMEM : UWSPR_ERR_HIP, "audio stream set-up (%d channels): %s",
                  nchannels, hipGetErrorString(r.err));
   const size_t es = (s16 ? 2 : 4) * (size_t)nchannels;   // bytes per frame
@@ -933,6 +947,22 @@ extern "C" int uwspr_pipe_submit_device(uwspr_pipe *q, const float *dev_frames, 
   return rc;
 }
 
+// K0's carriers: n distinct centres in Hz, in plane order (plane = channel * n + k).  Only before the first audio push;
+// nchannels * n <= UWSPR_PIPE_MAX_CHANNELS and the range against "frontend_hbw" are checked by the push that latches them.
+extern "C" int uwspr_pipe_set_carriers(uwspr_pipe *q, const int *hz, int n) {
+  if (!q) return UWSPR_ERR_ARG;
+  if (const int f = q->failed.load()) return f;
+  if (!hz || n < 1 || n > UWSPR_PIPE_MAX_CHANNELS) return parg(q, "uwspr_pipe_set_carriers: hz / n %d (1..%d)", n, UWSPR_PIPE_MAX_CHANNELS);
+  for (int i = 0; i < n; i++) {
+    if (hz[i] < 21 || hz[i] > 5979) return parg(q, "uwspr_pipe_set_carriers: carrier %d Hz (21 .. 5979)", hz[i]);
+    for (int j = 0; j < i; j++)
+      if (hz[j] == hz[i]) return parg(q, "uwspr_pipe_set_carriers: carrier %d Hz twice", hz[i]);
+  }
+  if (q->ring.kind == RING_AUDIO) return parg(q, "uwspr_pipe_set_carriers: the audio stream runs (carriers are latched by its first push)");
+  q->carriers.assign(hz, hz + n);
+  return UWSPR_OK;
+}
+
 // An option of every lane's context (uwspr_set_option).  Only while nothing is in flight -- the lanes read their
 // options when they launch -- and not "sched": the pipe picks the schedule form by its lane count (opts.sched_form).
 extern "C" int uwspr_pipe_set_option(uwspr_pipe *q, const char *name, int value) {
@@ -964,6 +994,14 @@ extern "C" int uwspr_pipe_set_option(uwspr_pipe *q, const char *name, int value)
       return parg(q, "uwspr_pipe_set_option: \"audio_rate\" = %d while the audio stream runs at %d S/s", value,
                   q->ring.rs.rate ? q->ring.rs.rate : 12000);
     q->audio_rate = value;
+    return UWSPR_OK;
+  }
+  if (!strcmp(name, "carrier")) return uwspr_pipe_set_carriers(q, &value, 1);
+  if (!strcmp(name, "frontend_hbw")) {   // the pipe's own: K0's half-bandwidth, latched by the first audio push
+    if (value < 1 || value > 150) return parg(q, "uwspr_pipe_set_option: \"frontend_hbw\" is 1 .. 150 Hz, not %d", value);
+    if (q->ring.kind == RING_AUDIO && value != q->ring.au.hbw)
+      return parg(q, "uwspr_pipe_set_option: \"frontend_hbw\" = %d while the audio stream runs with %d Hz", value, q->ring.au.hbw);
+    q->frontend_hbw = value;
     return UWSPR_OK;
   }
   if (!strcmp(name, "blank") || !strcmp(name, "blank_guard")) {   // the pipe's own: K12 ahead of K11 / K0, latched by the first push

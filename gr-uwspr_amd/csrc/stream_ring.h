@@ -18,6 +18,11 @@
 // channel.  The channels advance in lockstep, so the bookkeeping (base, have, pos, cur, the events) is shared:
 // reserve / view return plane 0 and channel c is at + 2 * c * plane floats; the tail move is one 2-D copy of all
 // planes.  The audio history is one interleaved [time][nch] buffer.
+//
+// Carriers (uwspr_pipe_set_carriers, option "carrier"): NC carriers listen to every audio channel, so the ring holds
+// npl = nch * ncar planes, plane c * ncar + k for channel c and carrier k.  nch stays the AUDIO channel count (the
+// interleave stride of the histories; what K11 and K12 see); npl is what the ring, reserve / view, the tail move and the
+// batches see.  With one carrier npl == nch.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -33,6 +38,14 @@ int frontend_prepare();
 int frontend_read_ahead(int mode);
 void launch_frontend_stream(hipStream_t s, const void *audio, bool s16, int nin, long long in0, const float *taps,
                             int J, int dcols, float *out, int nout, long long m_first, int nch, long long plane);
+// K0 at a centre fc and half-bandwidth hb, and its carrier form (the definition: include/uwspr_hip.h)
+bool frontend_carrier_ok(int mode, int fc, int hb);
+int frontend_tap_image_at(int mode, int fc, int hb, std::vector<float> &img, int *J, int *dcols);
+void frontend_rotator(float *out750);
+int frontend_carrier_tables(int mode, const std::vector<int> &carriers, int hb, std::vector<float> &blk, int *J, int *dcols);
+void launch_frontend_carrier(hipStream_t s, const void *audio, bool s16, int nin, long long in0, const float *tables, int J,
+                             int dcols, float *out, int nout, long long m_first, int nch, int NC, long long plane);
+long long frontend_carrier_launch_count(int s16);
 void launch_widen_s16(hipStream_t s, const int16_t *in, float *out, size_t n);
 
 // K11, the rational resampler ahead of K0 (k11_resample.hip; the definition: include/uwspr_hip.h)
@@ -59,7 +72,8 @@ struct stream_ring {
   int fl = 0, hop = 0, maxf = 0;
   float *buf[2] = {nullptr, nullptr};
   size_t cap = 0;                      // samples per buffer (per plane)
-  int nch = 1;                         // channel planes per buffer
+  int nch = 1;                         // audio channels
+  int ncar = 1, npl = 1;               // carriers per channel; planes per buffer (nch * ncar)
   size_t plane = 0;                    // pairs from one plane to the next (>= cap)
   int cur = 0;
   size_t base = 0, have = 0;           // unconsumed samples: buf[cur][base, base + have)
@@ -86,6 +100,11 @@ struct stream_ring {
     int s16 = 0;                       // the buffer holds int16 samples (every push so far was int16), else float
     int J = 0, dcols = 0, taps_mode = -1;
     float *d_taps = nullptr;           // [32][J] float2, the stream's own copy (a batch call may swap the context's)
+    // K0's centre(s) and half-bandwidth, latched with the mode.  Anything but {1500 Hz}, 10 Hz runs the carrier form:
+    // d_taps is then frontend_carrier_tables' block: [ncar][32][J] taps, the rotator table, the carriers mod 375
+    std::vector<int> car, taps_car;
+    int hbw = 0, taps_hbw = 0;
+    bool carrier_form = false;
     char *d_buf[2] = {nullptr, nullptr};
     size_t buf_bytes = 0;
     int cur = 0;
@@ -165,18 +184,19 @@ struct stream_ring {
     if (bk.h_nz) (void)hipHostFree(bk.h_nz);
     bk = blank_state();
     if (copy) { (void)hipStreamDestroy(copy); copy = nullptr; }
-    cap = 0; plane = 0; nch = 1; have = 0; base = 0; up_pending = false;
+    cap = 0; plane = 0; nch = 1; ncar = 1; npl = 1; have = 0; base = 0; up_pending = false;
   }
 
-  // takes_of_slack: how many full takes fit behind one another before the tail has to move; nplanes: channels
-  bool open(int fl_, int hop_, int max_frames, int takes_of_slack = 6, int nplanes = 1) {
+  // takes_of_slack: how many full takes fit behind one another before the tail has to move; nchannels audio channels
+  // with ncarriers carriers each: nchannels * ncarriers planes
+  bool open(int fl_, int hop_, int max_frames, int takes_of_slack = 6, int nchannels = 1, int ncarriers = 1) {
     close();
     fl = fl_; hop = hop_; maxf = max_frames;
     cap = (size_t)takes_of_slack * max_frames * hop + fl;
-    nch = nplanes;
-    plane = nch == 1 ? cap : (cap + 63) / 64 * 64;   // (planes start 512-byte aligned)
+    nch = nchannels; ncar = ncarriers; npl = nchannels * ncarriers;
+    plane = npl == 1 ? cap : (cap + 63) / 64 * 64;   // (planes start 512-byte aligned)
     for (int k = 0; k < 2; k++)
-      if ((err = hipMalloc((void **)&buf[k], plane * nch * 2 * sizeof(float))) != hipSuccess) { close(); return false; }
+      if ((err = hipMalloc((void **)&buf[k], plane * npl * 2 * sizeof(float))) != hipSuccess) { close(); return false; }
     if ((err = hipStreamCreateWithFlags(&copy, hipStreamNonBlocking)) != hipSuccess) { close(); return false; }
     if ((err = hipEventCreateWithFlags(&ev_up, hipEventDisableTiming)) != hipSuccess) { close(); return false; }
     cur = 0; base = 0; have = 0; pos = 0; up_pending = false; pin_next = 0;
@@ -207,10 +227,10 @@ struct stream_ring {
     for (hipEvent_t e : readers[other])
       if ((err = hipStreamWaitEvent(copy, e, 0)) != hipSuccess) return false;
     readers[other].clear();
-    if (have && nch == 1 && (err = hipMemcpyAsync(buf[other], buf[cur] + 2 * base, have * 2 * sizeof(float),
+    if (have && npl == 1 && (err = hipMemcpyAsync(buf[other], buf[cur] + 2 * base, have * 2 * sizeof(float),
                                                   hipMemcpyDeviceToDevice, copy)) != hipSuccess) return false;
-    if (have && nch > 1 && (err = hipMemcpy2DAsync(buf[other], plane * 2 * sizeof(float), buf[cur] + 2 * base,
-                                                   plane * 2 * sizeof(float), have * 2 * sizeof(float), (size_t)nch,
+    if (have && npl > 1 && (err = hipMemcpy2DAsync(buf[other], plane * 2 * sizeof(float), buf[cur] + 2 * base,
+                                                   plane * 2 * sizeof(float), have * 2 * sizeof(float), (size_t)npl,
                                                    hipMemcpyDeviceToDevice, copy)) != hipSuccess) return false;
     cur = other; base = 0;
     return true;
@@ -288,9 +308,19 @@ struct stream_ring {
     return m > au.m_next ? m - au.m_next : 0;
   }
 
-  // The first audio push after open / reset: taps of `mode`, buffers, a zero history.
-  bool audio_latch(int mode, bool s16) {
-    if (au.taps_mode != mode) {
+  static bool default_carriers(const std::vector<int> &car, int hbw) {
+    return car.size() == 1 && car[0] == UWSPR_CARRIER_DEFAULT && hbw == UWSPR_FRONTEND_HBW_DEFAULT;
+  }
+
+  // The first audio push after open / reset: taps of `mode`, buffers, a zero history.  car (ncar carriers, Hz) and hbw:
+  // K0's centres and half-bandwidth; null: the default set {1500}, 10.
+  bool audio_latch(int mode, bool s16, const std::vector<int> *car = nullptr, int hbw = UWSPR_FRONTEND_HBW_DEFAULT) {
+    const std::vector<int> dflt(1, UWSPR_CARRIER_DEFAULT);
+    const std::vector<int> &cs = car ? *car : dflt;
+    if ((int)cs.size() != ncar) { err = hipErrorInvalidValue; return false; }
+    if (!default_carriers(cs, hbw)) return carrier_latch(mode, s16, cs, hbw);
+    au.carrier_form = false; au.car = cs; au.hbw = hbw;
+    if (au.taps_mode != mode || !default_carriers(au.taps_car, au.taps_hbw)) {
       std::vector<float> img;
       int J = 0, dcols = 0;
       if (frontend_tap_image(mode, img, &J, &dcols) || frontend_prepare()) { err = hipErrorInvalidValue; return false; }
@@ -298,8 +328,29 @@ struct stream_ring {
       if (au.d_taps) { (void)hipFree(au.d_taps); au.d_taps = nullptr; }
       if ((err = hipMalloc((void **)&au.d_taps, img.size() * sizeof(float))) != hipSuccess) { au.d_taps = nullptr; return false; }
       if ((err = hipMemcpy(au.d_taps, img.data(), img.size() * sizeof(float), hipMemcpyHostToDevice)) != hipSuccess) return false;
-      au.taps_mode = mode; au.J = J; au.dcols = dcols;
+      au.taps_mode = mode; au.J = J; au.dcols = dcols; au.taps_car = cs; au.taps_hbw = hbw;
     }
+    return audio_latch_buffers(mode, s16);
+  }
+
+  // the carrier form's tables: one tap image per carrier, the rotator table, the carriers mod 375
+  bool carrier_latch(int mode, bool s16, const std::vector<int> &cs, int hbw) {
+    if (au.taps_mode != mode || au.taps_car != cs || au.taps_hbw != hbw) {
+      std::vector<float> all;
+      int J = 0, dcols = 0;
+      if (frontend_carrier_tables(mode, cs, hbw, all, &J, &dcols) || frontend_prepare()) { err = hipErrorInvalidValue; return false; }
+      if ((err = hipStreamSynchronize(copy)) != hipSuccess) return false;   // (launches with the old taps)
+      if (au.d_taps) { (void)hipFree(au.d_taps); au.d_taps = nullptr; }
+      au.taps_mode = -1;
+      if ((err = hipMalloc((void **)&au.d_taps, all.size() * sizeof(float))) != hipSuccess) { au.d_taps = nullptr; return false; }
+      if ((err = hipMemcpy(au.d_taps, all.data(), all.size() * sizeof(float), hipMemcpyHostToDevice)) != hipSuccess) return false;
+      au.taps_mode = mode; au.J = J; au.dcols = dcols; au.taps_car = cs; au.taps_hbw = hbw;
+    }
+    au.carrier_form = true; au.car = cs; au.hbw = hbw;
+    return audio_latch_buffers(mode, s16);
+  }
+
+  bool audio_latch_buffers(int mode, bool s16) {
     const size_t need = ((32 * (size_t)au.J + 32) * nch + audio_piece_frames() * nch) * sizeof(float);
     if (au.buf_bytes < need) {
       if ((err = hipStreamSynchronize(copy)) != hipSuccess) return false;
@@ -350,8 +401,12 @@ struct stream_ring {
         const int nout = (int)(m_end - au.m_next);
         float *dst = reserve((size_t)nout);
         if (!dst) return false;
-        launch_frontend_stream(copy, b, au.s16, (int)(au.hist + k), au.a0, au.d_taps, au.J, au.dcols, dst, nout, au.m_next,
-                               nch, (long long)plane);
+        if (au.carrier_form)
+          launch_frontend_carrier(copy, b, au.s16, (int)(au.hist + k), au.a0, au.d_taps, au.J, au.dcols, dst, nout, au.m_next,
+                                  nch, ncar, (long long)plane);
+        else
+          launch_frontend_stream(copy, b, au.s16, (int)(au.hist + k), au.a0, au.d_taps, au.J, au.dcols, dst, nout, au.m_next,
+                                 nch, (long long)plane);
         if ((err = hipGetLastError()) != hipSuccess) return false;
         if (!commit((size_t)nout)) return false;
         au.m_next = m_end;

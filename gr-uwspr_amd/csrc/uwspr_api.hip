@@ -107,6 +107,8 @@ static const struct { const char *name; int dflt, lo, hi; } kOptions[UWSPR_NOPT]
     {"audio_rate", 12000, 8000, 192000},   // uwspr_stream_push_audio: the rate of the pushed audio (12000: no resampler, else K11 ahead of K0)
     {"blank", 0, 0, 1024},          // uwspr_stream_push_audio: K12 ahead of K11 / K0, threshold in quarters of the block median (0: off; 4 .. 1024)
     {"blank_guard", 2, 0, 64},      // K12: samples zeroed either side of a flagged one
+    {"carrier", UWSPR_CARRIER_DEFAULT, 20, 5980},        // K0: the centre in Hz (the flowgraph's Center_Frequency); with frontend_hbw: hb + 20 .. 6000 - hb - 20
+    {"frontend_hbw", UWSPR_FRONTEND_HBW_DEFAULT, 1, 150},   // K0, grc mode: the half-bandwidth in Hz (the flowgraph's Half_Bandwidth)
 };
 
 static void refresh_options(uwspr_ctx *c) {
@@ -142,6 +144,14 @@ extern "C" int uwspr_set_option(uwspr_ctx *c, const char *name, int value) {
   }
   if (i == UWSPR_OPT_BLANK && value != 0 && value < 4)
     return fail(c, UWSPR_ERR_ARG, "option 'blank' = %d: 0 (off) or 4 .. 1024 quarters of the median", value);
+  if (i == UWSPR_OPT_CARRIER || i == UWSPR_OPT_FRONTEND_HBW || i == UWSPR_OPT_FRONTEND) {   // the three together
+    const int mode = i == UWSPR_OPT_FRONTEND ? value : c->opt[UWSPR_OPT_FRONTEND];
+    const int fc = i == UWSPR_OPT_CARRIER ? value : c->opt[UWSPR_OPT_CARRIER];
+    const int hb = i == UWSPR_OPT_FRONTEND_HBW ? value : c->opt[UWSPR_OPT_FRONTEND_HBW];
+    if (!frontend_carrier_ok(mode, fc, hb))
+      return fail(c, UWSPR_ERR_ARG, "option '%s' = %d: carrier %d Hz with half-bandwidth %d Hz (hb + 20 <= carrier <= 6000 - hb - 20)", name,
+                  value, fc, hb);
+  }
   c->opt[i] = value; c->opt_set[i] = true;
   refresh_options(c);
   return UWSPR_OK;
@@ -205,7 +215,7 @@ extern "C" int uwspr_ctx_create(const uwspr_params *p, int device, uwspr_ctx **o
   c->device = device;
   c->own_stream = c->stream = nullptr;
   c->d_window = c->d_twiddle = nullptr; c->d_off = nullptr; c->d_umap = nullptr; c->d_k3_tile = nullptr;
-  c->d_fe_taps = nullptr; c->fe_mode = -1; c->fe_J = 0; c->fe_dcols = 0; c->cap_audio = 0; c->d_audio = nullptr;
+  c->d_fe_taps = nullptr; c->fe_mode = -1; c->fe_fc = 0; c->fe_hb = 0; c->fe_J = 0; c->fe_dcols = 0; c->cap_audio = 0; c->d_audio = nullptr;
   c->cap_frames_bytes = 0; c->d_frames = nullptr; c->cap_B = 0;
   c->d_ps = c->d_psavg = c->d_smraw = c->d_smspec = c->d_noise = nullptr;
   c->d_cands = nullptr; c->d_npk = nullptr; c->d_work = nullptr; c->last_B = 0; c->num_cus = 256;
@@ -392,7 +402,7 @@ extern "C" void uwspr_ctx_destroy(uwspr_ctx *c) {
   blk_release(c);
   rs_release(c);
   bk_release(c);
-  void *bufs[] = {c->d_window, c->d_twiddle, c->d_k3_tile, c->d_off, c->d_umap, c->d_fe_taps, c->d_audio, c->d_frames, c->d_ps, c->d_psavg, c->d_smraw,
+  void *bufs[] = {c->d_window, c->d_twiddle, c->d_k3_tile, c->d_off, c->d_umap, c->d_fe_taps, c->d_dbg_taps, c->d_audio, c->d_frames, c->d_ps, c->d_psavg, c->d_smraw,
                   c->d_smspec, c->d_noise, c->d_cands, c->d_npk, c->d_work, c->d_syncgrid, c->d_hyps, c->d_grps, c->d_cent,
                   c->d_abi_hyps, c->d_p, c->d_sync, c->d_sym, c->d_state, c->d_dout, c->d_slab, c->d_tabs, c->d_counter, c->d_sched_stamps, c->d_pwin, c->d_ptab, c->d_need, c->d_stream_frames, c->d_tmpc, c->d_tmpn};
   for (void *b : bufs) if (b) (void)hipFree(b);
@@ -527,18 +537,25 @@ static int copy_out(uwspr_ctx *c, void *dst, const void *src, size_t bytes, int 
 }
 
 // -------------------------------------------------------------- front-end
-// the tap image of the context's `frontend` option on the device (built on first use and when the option changed)
+// the tap image of the context's `frontend`, `carrier` and `frontend_hbw` options on the device (built on first use and
+// when an option changed); away from the default centre and width also the carrier form's rotator table
+static bool frontend_default_set(const uwspr_ctx *c) {
+  return c->opt[UWSPR_OPT_CARRIER] == UWSPR_CARRIER_DEFAULT && c->opt[UWSPR_OPT_FRONTEND_HBW] == UWSPR_FRONTEND_HBW_DEFAULT;
+}
 static int frontend_taps(uwspr_ctx *c) {
-  if (c->d_fe_taps && c->fe_mode == c->opt[UWSPR_OPT_FRONTEND]) return UWSPR_OK;
+  const int fc = c->opt[UWSPR_OPT_CARRIER], hb = c->opt[UWSPR_OPT_FRONTEND_HBW];
+  if (c->d_fe_taps && c->fe_mode == c->opt[UWSPR_OPT_FRONTEND] && c->fe_fc == fc && c->fe_hb == hb) return UWSPR_OK;
   std::vector<float> img;
   int J = 0, dcols = 0;
-  if (frontend_tap_image(c->opt[UWSPR_OPT_FRONTEND], img, &J, &dcols)) return fail(c, UWSPR_ERR_ARG, "front-end mode %d", c->opt[UWSPR_OPT_FRONTEND]);
+  if (frontend_default_set(c) ? frontend_tap_image(c->opt[UWSPR_OPT_FRONTEND], img, &J, &dcols)
+                              : frontend_carrier_tables(c->opt[UWSPR_OPT_FRONTEND], std::vector<int>(1, fc), hb, img, &J, &dcols))
+    return fail(c, UWSPR_ERR_ARG, "front-end mode %d at %d Hz, half-bandwidth %d Hz", c->opt[UWSPR_OPT_FRONTEND], fc, hb);
   if (frontend_prepare()) return fail(c, UWSPR_ERR_HIP, "front-end kernel: %zu bytes of LDS refused", (size_t)160 * 1024);
   HIPCHK(c, hipStreamSynchronize(c->stream));          // (a launch with the other mode's taps may be in flight)
   if (c->d_fe_taps) { HIPCHK(c, hipFree(c->d_fe_taps)); c->d_fe_taps = nullptr; }
   HIPCHK(c, hipMalloc((void **)&c->d_fe_taps, img.size() * sizeof(float)));
   HIPCHK(c, hipMemcpy(c->d_fe_taps, img.data(), img.size() * sizeof(float), hipMemcpyHostToDevice));
-  c->fe_mode = c->opt[UWSPR_OPT_FRONTEND]; c->fe_J = J; c->fe_dcols = dcols;
+  c->fe_mode = c->opt[UWSPR_OPT_FRONTEND]; c->fe_J = J; c->fe_dcols = dcols; c->fe_fc = fc; c->fe_hb = hb;
   return UWSPR_OK;
 }
 
@@ -563,7 +580,14 @@ extern "C" int uwspr_frontend_batch(uwspr_ctx *c, const float *audio, int B, int
   } else if (where != UWSPR_DEVICE) {
     return fail(c, UWSPR_ERR_ARG, "where=%d", where);
   }
-  launch_frontend(c, da, B, nin, (float2 *)dout, nout);
+  if (frontend_default_set(c)) {
+    launch_frontend(c, da, B, nin, (float2 *)dout, nout);
+  } else {   // the carrier form, one record per launch (output m of a record is stream index m)
+    prof_scope ps(c, UWSPR_K_SPECTROGRAM, B);
+    for (int b = 0; b < B; b++)
+      launch_frontend_carrier(c->stream, da + (size_t)b * nin, false, nin, 0LL, c->d_fe_taps, c->fe_J, c->fe_dcols,
+                              dout + 2 * (size_t)b * nout, nout, 0LL, 1, 1, (long long)nout);
+  }
   HIPCHK(c, hipGetLastError());
   if (where == UWSPR_HOST) {
     HIPCHK(c, hipMemcpyAsync(frames_out, c->d_frames, (size_t)B * nout * 2 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
@@ -573,9 +597,19 @@ extern "C" int uwspr_frontend_batch(uwspr_ctx *c, const float *audio, int B, int
 }
 
 extern "C" int uwspr_frontend_design(int mode, int stage, double *taps, int cap, int *delay) {
+  return uwspr_frontend_design_at(mode, UWSPR_CARRIER_DEFAULT, UWSPR_FRONTEND_HBW_DEFAULT, stage, taps, cap, delay);
+}
+
+extern "C" int uwspr_frontend_rotator(float *out750) {
+  if (!out750) return UWSPR_ERR_ARG;
+  frontend_rotator(out750);
+  return 375;
+}
+
+extern "C" int uwspr_frontend_design_at(int mode, int centre_hz, int half_bw_hz, int stage, double *taps, int cap, int *delay) {
   std::vector<double> g;
   int d = 0;
-  const int rc = frontend_design(mode, stage, g, &d);
+  const int rc = frontend_design_at(mode, centre_hz, half_bw_hz, stage, g, &d);
   if (rc) return rc;
   if (delay) *delay = d;
   const int n = stage == 0 ? (int)g.size() / 2 : (int)g.size();     // complex pairs / real taps
@@ -1129,6 +1163,12 @@ extern "C" int uwspr_stream_push_audio(uwspr_ctx *c, const void *audio, int nsam
   if (nsamples > 0 && r.kind == RING_IQ) return fail(c, UWSPR_ERR_ARG, "uwspr_stream_push_audio on an (I,Q) stream (reset it first)");
   if (nsamples > 0 && r.kind == RING_AUDIO && mode != r.au.mode)
     return fail(c, UWSPR_ERR_ARG, "option frontend changed to %d while the audio stream runs in mode %d (reset it first)", mode, r.au.mode);
+  // options "carrier" / "frontend_hbw": latched like the front-end mode
+  const std::vector<int> car(1, c->opt[UWSPR_OPT_CARRIER]);
+  const int hbw = c->opt[UWSPR_OPT_FRONTEND_HBW];
+  if (nsamples > 0 && r.kind == RING_AUDIO && (car != r.au.car || hbw != r.au.hbw))
+    return fail(c, UWSPR_ERR_ARG, "options carrier / frontend_hbw changed to %d / %d while the audio stream runs with %d / %d (reset it first)",
+                car[0], hbw, r.au.car.empty() ? 0 : r.au.car[0], r.au.hbw);
   // option "audio_rate": latched like the front-end mode; any other rate than 12000 goes through K11 first
   const int rate = c->opt[UWSPR_OPT_AUDIO_RATE];
   const int running = r.kind == RING_AUDIO ? (r.rs.rate ? r.rs.rate : 12000) : 0;
@@ -1152,7 +1192,7 @@ extern "C" int uwspr_stream_push_audio(uwspr_ctx *c, const void *audio, int nsam
       return fail(c, r.err == hipErrorOutOfMemory ? UWSPR_ERR_NOMEM : UWSPR_ERR_HIP, "blanker set-up: %s", hipGetErrorString(r.err));
     if (r.kind != RING_AUDIO && rs_on && !r.resample_latch(rate, s16 && !bk_on))
       return fail(c, r.err == hipErrorOutOfMemory ? UWSPR_ERR_NOMEM : UWSPR_ERR_HIP, "resampler set-up (%d S/s): %s", rate, hipGetErrorString(r.err));
-    if (r.kind != RING_AUDIO && !r.audio_latch(mode, s16 && !rs_on && !bk_on))
+    if (r.kind != RING_AUDIO && !r.audio_latch(mode, s16 && !rs_on && !bk_on, &car, hbw))
       return fail(c, UWSPR_ERR_HIP, "audio stream set-up: %s", hipGetErrorString(r.err));
     bool ok;
     if (where == UWSPR_DEVICE) {   // produced by work on the context's stream
@@ -1406,6 +1446,50 @@ extern "C" int uwspr_debug_frontend_launch(uwspr_ctx *c, const void *audio_dev, 
   HIPCHK(c, hipGetLastError());
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return UWSPR_OK;
+}
+
+// diagnostics (not part of the ABI header): ONE launch of the carrier form of K0 (launch_frontend_carrier, what
+// stream_ring::push_audio calls for any set of carriers but {1500 Hz}, 10 Hz) on device memory, in the context's `frontend`
+// mode and with its `frontend_hbw`, on the context's stream, waited for.  audio_dev holds nin frames [in0, in0 + nin) of
+// nch interleaved channels; carriers[NC] in Hz (nch * NC <= UWSPR_PIPE_MAX_CHANNELS); out_dev receives outputs
+// [m_first, m_first + nout) of plane q = c * NC + k at out_dev + 2 * q * plane floats (plane >= nout pairs).
+extern "C" int uwspr_debug_frontend_carrier_launch(uwspr_ctx *c, const void *audio_dev, int format, int nin, long long in0, int nch,
+                                                   int NC, const int *carriers, float *out_dev, int nout, long long m_first,
+                                                   long long plane) {
+  int rc = ready(c);
+  if (rc) return rc;
+  const long long lim = 1LL << 46;
+  if (!audio_dev || !out_dev || !carriers || nin < 1 || nout < 1 || nch < 1 || NC < 1 || (long long)nch * NC > UWSPR_PIPE_MAX_CHANNELS ||
+      (format != UWSPR_AUDIO_F32 && format != UWSPR_AUDIO_S16) || plane < nout || in0 < -lim || in0 > lim || m_first < -lim || m_first > lim)
+    return fail(c, UWSPR_ERR_ARG, "uwspr_debug_frontend_carrier_launch: audio/out/carriers/format %d/nin %d/in0 %lld/nout %d/m_first %lld/nch %d/NC %d/plane %lld",
+                format, nin, in0, nout, m_first, nch, NC, plane);
+  const int mode = c->opt[UWSPR_OPT_FRONTEND], hb = c->opt[UWSPR_OPT_FRONTEND_HBW];
+  const std::vector<int> car(carriers, carriers + NC);
+  for (int fc : car)
+    if (!frontend_carrier_ok(mode, fc, hb)) return fail(c, UWSPR_ERR_ARG, "uwspr_debug_frontend_carrier_launch: carrier %d Hz, half-bandwidth %d Hz", fc, hb);
+  if (!c->d_dbg_taps || c->dbg_mode != mode || c->dbg_hb != hb || c->dbg_car != car) {
+    std::vector<float> all;
+    int J = 0, dcols = 0;
+    if (frontend_carrier_tables(mode, car, hb, all, &J, &dcols)) return fail(c, UWSPR_ERR_ARG, "front-end mode %d, %d carriers", mode, NC);
+    if (frontend_prepare()) return fail(c, UWSPR_ERR_HIP, "front-end kernel: %zu bytes of LDS refused", (size_t)160 * 1024);
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (c->d_dbg_taps) { HIPCHK(c, hipFree(c->d_dbg_taps)); c->d_dbg_taps = nullptr; }
+    HIPCHK(c, hipMalloc((void **)&c->d_dbg_taps, all.size() * sizeof(float)));
+    HIPCHK(c, hipMemcpy(c->d_dbg_taps, all.data(), all.size() * sizeof(float), hipMemcpyHostToDevice));
+    c->dbg_mode = mode; c->dbg_hb = hb; c->dbg_car = car; c->dbg_J = J; c->dbg_dcols = dcols;
+  }
+  launch_frontend_carrier(c->stream, audio_dev, format == UWSPR_AUDIO_S16, nin, in0, c->d_dbg_taps, c->dbg_J, c->dbg_dcols, out_dev,
+                          nout, m_first, nch, NC, plane);
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return UWSPR_OK;
+}
+
+// launches of K0's carrier form since the process started: out[0] float32 input, out[1] int16 input
+extern "C" int uwspr_debug_frontend_carrier_counts(long long *out) {
+  if (!out) return UWSPR_ERR_ARG;
+  out[0] = frontend_carrier_launch_count(0); out[1] = frontend_carrier_launch_count(1);
+  return 2;
 }
 
 // diagnostics (not part of the ABI header): ONE launch of K11 (launch_resample, what uwspr_resample_batch and a stream's

@@ -30,6 +30,8 @@ enum {
   UWSPR_OPT_AUDIO_RATE,         // rate of the audio uwspr_stream_push_audio takes (default 12000: no resampler; else K11 ahead of K0)
   UWSPR_OPT_BLANK,              // uwspr_stream_push_audio: K12's threshold in quarters of the block median (default 0: no blanker)
   UWSPR_OPT_BLANK_GUARD,        // K12's guard G: samples zeroed either side of a flagged one (default 2)
+  UWSPR_OPT_CARRIER,            // K0's centre in Hz (default 1500), the flowgraph's Center_Frequency
+  UWSPR_OPT_FRONTEND_HBW,       // K0's half-bandwidth in Hz (default 10; grc mode), the flowgraph's Half_Bandwidth
   UWSPR_NOPT
 };
 
@@ -196,6 +198,12 @@ struct uwspr_ctx {
   uint16_t *d_umap;    // [n_ifr][cell_hyps]: hypothesis -> distinct sequence
   float *d_fe_taps;    // [32][fe_J][2] complex front-end taps by phase (K0), built on first use for mode fe_mode
   int fe_mode, fe_J, fe_dcols;
+  int fe_fc, fe_hb;    // the centre and half-bandwidth d_fe_taps was designed for
+                       // (away from 1500 Hz, 10 Hz: frontend_carrier_tables' block, the rotator table behind the taps)
+  // uwspr_debug_frontend_carrier_launch's tables, kept between calls with the same carriers: [NC][32][J] taps, rotator, fc mod 375
+  std::vector<int> dbg_car;
+  int dbg_mode = -1, dbg_hb = 0, dbg_J = 0, dbg_dcols = 0;
+  float *d_dbg_taps = nullptr;
   size_t cap_audio; float *d_audio;   // staging when the audio is host memory
 
   // batch scratch (grown on demand, never shrunk)
@@ -308,6 +316,8 @@ int blockdemod_run(uwspr_ctx *c, const float *src, size_t stride, const uwspr_bl
 // ---- launchers (each enqueues on ctx->stream) ------------------------------
 int frontend_design(int mode, int stage, std::vector<double> &out, int *delay);
 int frontend_tap_image(int mode, std::vector<float> &img, int *J, int *dcols);
+// the same at centre fc and half-bandwidth hb (integer Hz; frontend_carrier_ok says which are allowed)
+int frontend_design_at(int mode, int fc, int hb, int stage, std::vector<double> &out, int *delay);
 // firdes::low_pass(1, fs, cutoff, tw, WIN_HAMMING) as GNU Radio 3.7 designs it (binary32 taps; k0_frontend.hip)
 std::vector<float> lowpass_hamming(double fs, double cutoff, double tw);
 int frontend_prepare();

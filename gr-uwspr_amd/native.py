@@ -264,7 +264,7 @@ class Prof(C.Structure):
 ABI_SYMBOLS = [
     "uwspr_ctx_create", "uwspr_ctx_destroy", "uwspr_last_error", "uwspr_status_string",
     "uwspr_get_info", "uwspr_set_stream", "uwspr_synchronize", "uwspr_frontend_batch",
-    "uwspr_frontend_design", "uwspr_resample_design", "uwspr_resample_batch", "uwspr_blank_batch", "uwspr_stream_blank_stats", "uwspr_pipe_blank_stats", "uwspr_set_frame_stride", "uwspr_stream_open", "uwspr_stream_push", "uwspr_stream_push_audio", "uwspr_stream_wait_uploads",
+    "uwspr_frontend_design", "uwspr_frontend_design_at", "uwspr_frontend_rotator", "uwspr_resample_design", "uwspr_resample_batch", "uwspr_blank_batch", "uwspr_stream_blank_stats", "uwspr_pipe_blank_stats", "uwspr_set_frame_stride", "uwspr_stream_open", "uwspr_stream_push", "uwspr_stream_push_audio", "uwspr_stream_wait_uploads",
     "uwspr_stream_take_view", "uwspr_stream_take", "uwspr_stream_reset",
     "uwspr_device_alloc", "uwspr_device_free", "uwspr_host_alloc", "uwspr_host_free", "uwspr_fdr_batch",
     "uwspr_fdr_read_spectrum", "uwspr_fdr_keep_syncgrid", "uwspr_fdr_read_syncgrid",
@@ -277,7 +277,7 @@ ABI_SYMBOLS = [
     "uwspr_dist_unique_id", "uwspr_dist_init", "uwspr_dist_gather", "uwspr_dist_finalize",
     "uwspr_pipe_open", "uwspr_pipe_close", "uwspr_pipe_last_error", "uwspr_pipe_acquire", "uwspr_pipe_commit",
     "uwspr_pipe_push", "uwspr_pipe_push_audio", "uwspr_pipe_push_audio_channels", "uwspr_pipe_submit_device", "uwspr_pipe_flush", "uwspr_pipe_collect", "uwspr_pipe_get_stats",
-    "uwspr_pipe_inject_failure", "uwspr_pipe_set_option",
+    "uwspr_pipe_inject_failure", "uwspr_pipe_set_option", "uwspr_pipe_set_carriers",
 ]
 
 _lib = None
@@ -318,6 +318,8 @@ def lib():
     L.uwspr_synchronize.argtypes = [vp]
     L.uwspr_frontend_batch.argtypes = [vp, vp, ip, ip, ip, vp]
     L.uwspr_frontend_design.argtypes = [ip, ip, vp, ip, vp]
+    L.uwspr_frontend_design_at.argtypes = [ip, ip, ip, ip, vp, ip, vp]
+    L.uwspr_frontend_rotator.argtypes = [vp]
     L.uwspr_resample_design.argtypes = [ip, vp, ip, vp, vp, vp, vp]
     L.uwspr_resample_batch.argtypes = [vp, vp, C.c_longlong, ip, ip, ip, ip, vp, C.c_longlong]
     L.uwspr_blank_batch.argtypes = [vp, vp, C.c_longlong, ip, ip, ip, ip, ip, vp, vp, vp]
@@ -399,5 +401,6 @@ def lib():
     L.uwspr_pipe_get_stats.argtypes = [vp, C.POINTER(PipeStats)]
     L.uwspr_pipe_inject_failure.argtypes = [vp, C.c_longlong, ip]
     L.uwspr_pipe_set_option.argtypes = [vp, C.c_char_p, ip]
+    L.uwspr_pipe_set_carriers.argtypes = [vp, vp, ip]
     _lib = L
     return L

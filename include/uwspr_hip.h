@@ -180,8 +180,35 @@ int uwspr_synchronize(uwspr_ctx *ctx);
  * stage by stage in binary64.  audio [B][nin] (zero outside the record), frames_out [B][fl] (I,Q) pairs.
  * uwspr_frontend_design: stage 0 = the composite complex taps g (cap counts (re, im) pairs) and *delay = D of
  * y[m] = sum_k g[k] x[32 m + D - k]; stages 1, 2, 3 (grc mode) = the band-pass, low-pass and resampler designs
- * (real taps).  Returns the tap count (taps may be NULL), < 0 on a bad mode / stage. */
+ * (real taps).  Returns the tap count (taps may be NULL), < 0 on a bad mode / stage.
+ *
+ * Another carrier.  The flowgraph's two variables are options of the context: "carrier" (Center_Frequency, integer Hz,
+ * default 1500) and "frontend_hbw" (Half_Bandwidth, Hz, default 10).  The grc mode designs
+ *   h1 = band_pass(1, 12000, fc - hb, fc + hb, 10, HAMMING),
+ *   h2 = low_pass(1, 12000, fc + hb, 10, HAMMING) rotated by e^{+j 2 pi fc k / 12000} and rounded to binary32 pairs,
+ *   h3 = the resampler's Kaiser design rotated in exact arithmetic,      g = h1 * rot(h2) * rot(h3)
+ * (6831 taps whatever fc and hb are: the tap counts follow the 10 Hz transition width); the compact mode mixes the same
+ * 1025-tap low-pass by -fc and has no hb.  fc k is reduced mod 12000 in integers before any cos / sin, and a multiple of
+ * pi/4 takes the exact octant values, so (1500, 10) gives the taps it always gave, byte for byte.
+ * Allowed: 1 <= hb <= 150 (the / 32 resampler passes 0.4 x 375 Hz) and hb + 20 <= fc <= 6000 - hb - 20 (the compact
+ * mode: 20 <= fc <= 5980); anything else is UWSPR_ERR_ARG.
+ * The rotator.  At the decimated instants the chain's mixer is e^{-j 2 pi fc m / 375}: the identity exactly when 375
+ * divides fc (1500 needs none), otherwise one of 375 values.  uwspr_frontend_rotator returns the table K0 uses,
+ *   rot[i] = ((float)cos(2 pi i / 375), (float)(-sin(2 pi i / 375))),  i = 0 .. 374, computed in binary64,
+ * and output m of a stream (m its 64-bit stream index) is, with s the sum K0 forms at any carrier (16 chains of fused
+ * multiply-adds, added in wavefront order) and (c, d) = rot[((fc mod 375) (m mod 375)) mod 375],
+ *   y.re = fmaf(s.re, c, -(s.im d)),   y.im = fmaf(s.re, d, s.im c)      -- this one order;
+ * when fc mod 375 == 0 no product is made and y is s's bytes, NaN and inf included.
+ * Both options are latched by a stream's first audio push like "frontend" (a change while it runs is UWSPR_ERR_ARG and
+ * leaves the stream as it was); uwspr_frontend_batch reads them at every call.  With (1500, 10) nothing new runs or is
+ * allocated.  Not built: transmit (K7) stays at 1500 Hz, carriers are integer Hz, and uwspr_params.cf (the SLM Doppler
+ * scale) stays the caller's: one per context or pipe, to be set to the carrier when there is one carrier.
+ * uwspr_frontend_design_at: uwspr_frontend_design at (centre_hz, half_bw_hz). */
 enum { UWSPR_FRONTEND_GRC = 0, UWSPR_FRONTEND_COMPACT = 1 };
+#define UWSPR_CARRIER_DEFAULT 1500
+#define UWSPR_FRONTEND_HBW_DEFAULT 10
+int uwspr_frontend_design_at(int mode, int centre_hz, int half_bw_hz, int stage, double *taps, int cap, int *delay);
+int uwspr_frontend_rotator(float *out750);
 int uwspr_frontend_batch(uwspr_ctx *ctx, const float *audio, int B, int nin, int where,
                          float *frames_out);
 int uwspr_frontend_design(int mode, int stage, double *taps, int cap, int *delay);
@@ -537,7 +564,8 @@ typedef struct uwspr_decode {
   int32_t idt;            /* the jiggered try that decoded (-1: none) */
   int8_t message[7];
   uint8_t block;          /* 2, 3: Fano timed out on every gated try and the soft symbols of that block length decoded (option "block"); 0 otherwise */
-  int16_t channel;        /* the audio channel of a multichannel pipe (uwspr_pipe_push_audio_channels); 0 otherwise */
+  int16_t channel;        /* the audio channel of a multichannel pipe (uwspr_pipe_push_audio_channels); 0 otherwise.  With n > 1
+                             carriers (uwspr_pipe_set_carriers): the plane index channel * n + carrier index */
   uint8_t pass;           /* 1: found by the second pass (option "passes" = 2), in the frame with its decoded signals taken out; 0 otherwise */
   uint8_t osd;            /* 1: Fano timed out on every gated try and ordered-statistics decoding gave the message (option "osd"); 0 otherwise */
 } uwspr_decode;
@@ -583,9 +611,25 @@ int uwspr_pipe_push_audio(uwspr_pipe *pipe, const void *audio, int nsamples, int
  * Impulsive noise: "blank" and "blank_guard" are the pipe's own options as well (uwspr_pipe_set_option; 0 = off and 2 by
  * default, ranges as at uwspr_blank_batch, else UWSPR_ERR_ARG), latched by the first audio push; another value once the
  * audio stream runs is UWSPR_ERR_ARG.  The pieces then go through K12 first, as described at uwspr_blank_batch; the
- * last "blank_guard" samples pushed are never output. */
+ * last "blank_guard" samples pushed are never output.
+ * Several carriers (FDMA, or one source that is not at 1500 Hz): uwspr_pipe_set_carriers(pipe, hz, n) gives K0's
+ * centres in Hz, n >= 1 distinct integers whose order is kept; "frontend_hbw" (uwspr_pipe_set_option, 1 .. 150, default
+ * 10) is the pipe's own half-bandwidth, and "carrier" = hz is uwspr_pipe_set_carriers(pipe, &hz, 1).  Legal only before
+ * the first audio push (afterwards UWSPR_ERR_ARG); that push latches them with the channel count and checks
+ * nchannels * n <= UWSPR_PIPE_MAX_CHANNELS and hb + 20 <= hz <= 6000 - hb - 20 (UWSPR_ERR_ARG, nothing latched).  Every
+ * audio channel c is then heard at every carrier k: plane c * n + k is a stream of its own, K0's carrier form (see
+ * uwspr_frontend_design_at: taps at hz[k], then the rotator) fills it from the same audio, and whatever is said above of
+ * "every channel" holds of every plane: a take launches one batch per plane in plane order, records come in (take,
+ * plane, frame) order, and per plane frame and stream_pos count as a one-carrier, one-channel pipe's.  With n > 1 a
+ * record's `channel` field holds the PLANE index c * n + k (uwspr_decode has no free byte and the ABI version stays);
+ * with n == 1 it is the channel.  K11 and K12 see the nchannels audio channels only.  With {1500}, 10 nothing new runs.
+ * Memory: nchannels * n takes nchannels' place in the ring's formula above (the audio buffers keep nchannels), plus
+ * n x 55 KB of tap images (32 J pairs of 8 bytes) and 3 KB of rotator table.
+ * uwspr_params.cf (the straight-line model's Doppler scale) stays the caller's, one per pipe, as the reference's FDR
+ * block has it: with one carrier set cf to it; with several, cf's scale serves them all (no per-carrier tables). */
 #define UWSPR_PIPE_MAX_CHANNELS 64
 int uwspr_pipe_push_audio_channels(uwspr_pipe *pipe, const void *audio, int nframes, int nchannels, int format);
+int uwspr_pipe_set_carriers(uwspr_pipe *pipe, const int *hz, int n);
 /* B frames already in device memory (frame b at frames + 2*stride*b floats, stride 0 = fl): searched as one
  * batch.  The memory must stay valid until the batch's results have been collected. */
 int uwspr_pipe_submit_device(uwspr_pipe *pipe, const float *dev_frames, int B, int stride);
