@@ -37,6 +37,7 @@ constexpr int K12_PER = K12_N / K12_WG;            // patterns per lane (16)
 constexpr int K12_GMAX = 64;
 constexpr int K12_ROUNDS = (K12_N + 2 * K12_GMAX + K12_WG - 1) / K12_WG;   // staged samples per lane in k12_apply (17)
 static_assert(K12_N == 4096 && K12_PER == 16, "k12_level holds 16 patterns per lane");
+static_assert(K12_GMAX == stage::BLANK_GMAX, "stream_stage.h sizes the stream's history by the largest guard");
 
 __device__ __forceinline__ float k12_sample(float v) { return v; }
 __device__ __forceinline__ float k12_sample(int16_t v) { return (float)v * (1.0f / 32768); }
@@ -187,17 +188,12 @@ hipError_t launch_blank_level(hipStream_t s, const void *audio, bool s16, long l
   return hipGetLastError();
 }
 
-// blocks the outputs [y_first, y_first + nout) touch
-long long blank_blocks_of(long long y_first, long long nout) {
-  return nout > 0 ? (y_first + nout - 1) / K12_N - y_first / K12_N + 1 : 0;
-}
-
-// outputs [y_first, y_first + nout) of every channel -> out[nout][nch], their zero counts -> nz[blank_blocks_of()][nch]
+// outputs [y_first, y_first + nout) of every channel -> out[nout][nch], their zero counts -> nz[stage::blank_blocks_of()][nch]
 hipError_t launch_blank_apply(hipStream_t s, const void *audio, bool s16, long long nin, long long in0, int nch, const float *lev,
                               long long nlev, long long blk0, int blank, int guard, float *out, long long nout, long long y_first,
                               int *nz) {
   if (nout <= 0) return hipSuccess;
-  const long long nblk = blank_blocks_of(y_first, nout);
+  const long long nblk = stage::blank_blocks_of(y_first, nout);
   if (nblk * nch > 0x7fffffffLL || guard < 0 || guard > K12_GMAX) return hipErrorInvalidValue;
   const dim3 grid((unsigned)(nblk * nch));
   k12_launches[s16 ? 3 : 2]++;

@@ -846,7 +846,7 @@ extern "C" int uwspr_pipe_push(uwspr_pipe *q, const float *iq, int nsamples) {
 }
 
 // Audio through the same page-locked staging (its bytes: batch_frames * hop (I,Q) pairs per buffer), then K0 on the
-// copy stream into the ring (stream_ring::push_audio); batches are launched from the ring as uwspr_pipe_commit does,
+// copy stream into the ring (stream_ring::chain_push); batches are launched from the ring as uwspr_pipe_commit does,
 // one per channel.  One channel is the same call with nchannels = 1.
 extern "C" int uwspr_pipe_push_audio_channels(uwspr_pipe *q, const void *audio, int nframes, int nchannels, int format) {
   if (!q || (nframes > 0 && !audio) || nframes < 0) return UWSPR_ERR_ARG;
@@ -861,64 +861,46 @@ extern "C" int uwspr_pipe_push_audio_channels(uwspr_pipe *q, const void *audio, 
   if (r.kind == RING_AUDIO && nchannels != r.nch)
     return parg(q, "uwspr_pipe_push_audio_channels: %d channels into a stream of %d", nchannels, r.nch);
   const bool s16 = format == UWSPR_AUDIO_S16;
-  const int mode = q->lanes[0].ctx->opt[UWSPR_OPT_FRONTEND];
-  if (r.kind == RING_AUDIO && mode != r.au.mode)
-    return parg(q, "uwspr_pipe_push_audio: option frontend changed to %d while the audio stream runs in mode %d", mode, r.au.mode);
-  // the carriers and "frontend_hbw": latched like the front-end mode, nchannels * carriers planes in all
-  const int ncar = (int)q->carriers.size(), hbw = q->frontend_hbw;
+  // the front-end mode, the carriers and "frontend_hbw" (nchannels * carriers planes in all), "audio_rate", "blank" /
+  // "blank_guard": latched by the stream's first push
+  const audio_chain_cfg cfg = {q->lanes[0].ctx->opt[UWSPR_OPT_FRONTEND], q->carriers, q->frontend_hbw, q->audio_rate, q->blank, q->blank_guard};
+  const chain_part changed = r.chain_mismatch(cfg);
+  char why[160];
+  if (changed == CHAIN_FRONTEND) return parg(q, "uwspr_pipe_push_audio: %s", chain_refusal(changed, cfg, r.chain_latched(), why));
+  const int ncar = (int)cfg.carriers.size();
   if ((long long)nchannels * ncar > UWSPR_PIPE_MAX_CHANNELS)
     return parg(q, "uwspr_pipe_push_audio_channels: %d channels x %d carriers (at most %d planes)", nchannels, ncar, UWSPR_PIPE_MAX_CHANNELS);
-  for (int fc : q->carriers)
-    if (!frontend_carrier_ok(mode, fc, hbw))
-      return parg(q, "uwspr_pipe_push_audio: carrier %d Hz with half-bandwidth %d Hz (hb + 20 <= carrier <= 6000 - hb - 20)", fc, hbw);
-  if (r.kind == RING_AUDIO && (q->carriers != r.au.car || hbw != r.au.hbw))
-    return parg(q, "uwspr_pipe_push_audio: carriers / frontend_hbw changed while the audio stream runs (half-bandwidth %d Hz)", r.au.hbw);
-  // option "audio_rate": latched like the front-end mode; any other rate than 12000 goes through K11 first
-  const int rate = q->audio_rate;
-  const bool rs_on = rate != 12000;
-  const int running = r.kind == RING_AUDIO ? (r.rs.rate ? r.rs.rate : 12000) : 0;
-  if (running && rate != running)
-    return parg(q, "uwspr_pipe_push_audio: option audio_rate changed to %d while the audio stream runs at %d S/s", rate, running);
-  // options "blank" / "blank_guard": latched in the same way; "blank" != 0 puts K12 ahead of both
-  const int blank = q->blank, guard = q->blank_guard;
-  const bool bk_on = blank != 0;
-  if (r.kind == RING_AUDIO && (blank != r.bk.blank || (bk_on && guard != r.bk.guard)))
-    return parg(q, "uwspr_pipe_push_audio: options blank / blank_guard changed to %d / %d while the audio stream runs with %d / %d",
-                blank, guard, r.bk.blank, r.bk.blank ? r.bk.guard : guard);
+  for (int fc : cfg.carriers)
+    if (!frontend_carrier_ok(cfg.mode, fc, cfg.hbw))
+      return parg(q, "uwspr_pipe_push_audio: carrier %d Hz with half-bandwidth %d Hz (hb + 20 <= carrier <= 6000 - hb - 20)", fc, cfg.hbw);
+  if (changed) return parg(q, "uwspr_pipe_push_audio: %s", chain_refusal(changed, cfg, r.chain_latched(), why));
   (void)hipSetDevice(q->device);
   if (const int rc = open_ingest(q, nchannels, ncar)) return rc;
-  if (r.kind != RING_AUDIO && bk_on && !r.blank_latch(blank, guard, s16))
-    return pfail(q, r.err == hipErrorOutOfMemory ? UWSPR_ERR_NOMEM : UWSPR_ERR_HIP, "blanker set-up (%d channels): %s", nchannels,
-                 hipGetErrorString(r.err));
-  if (r.kind != RING_AUDIO && rs_on && !r.resample_latch(rate, s16 && !bk_on))
-    return pfail(q, r.err == hipErrorOutOfMemory ? UWSPR_ERR_NOMEM : UWSPR_ERR_HIP, "resampler set-up (%d S/s, %d channels): %s",
-                 rate, nchannels, hipGetErrorString(r.err));
-  if (r.kind != RING_AUDIO && !r.audio_latch(mode, s16 && !rs_on && !bk_on, &q->carriers, hbw))
-    return pfail(q, r.err == hipErrorOutOfMemory ? UWSPR_ERR_NOMEM : UWSPR_ERR_HIP, "audio stream set-up (%d channels): %s",
-                 nchannels, hipGetErrorString(r.err));
+  if (const chain_part f = r.chain_latch(cfg, s16))
+    return pfail(q, r.err == hipErrorOutOfMemory ? UWSPR_ERR_NOMEM : UWSPR_ERR_HIP, "%s set-up (%d S/s, %d channels): %s", chain_part_name(f),
+                 cfg.rate, nchannels, hipGetErrorString(r.err));
   const size_t es = (s16 ? 2 : 4) * (size_t)nchannels;   // bytes per frame
   size_t piece = q->stage_samples * 2 * sizeof(float) / es;
-  // several channels: whole K0 workgroups per piece (32 * 512 frames), so a launch has no ragged last output block
+  // several channels straight into K0: whole K0 workgroups per piece (32 * 512 frames), so a launch has no ragged last
+  // output block
   constexpr size_t kBlockFrames = 32 * 512;
-  if (!rs_on && !bk_on && nchannels > 1 && piece >= kBlockFrames) piece = piece / kBlockFrames * kBlockFrames;
+  if (cfg.rate == 12000 && !cfg.blank && nchannels > 1 && piece >= kBlockFrames) piece = piece / kBlockFrames * kBlockFrames;
   // a rate below 12000 makes more 12 kS/s samples than it is given: a piece yields no more of them than a 12 kS/s piece
-  if (rs_on && r.rs.pl.L > r.rs.pl.M) piece = piece * (size_t)r.rs.pl.M / (size_t)r.rs.pl.L;
+  int L = 1, M = 1;
+  r.chain_ratio(&L, &M);
+  if (L > M) piece = piece * (size_t)M / (size_t)L;
   if (piece < 1) piece = 1;
   for (size_t off = 0; off < (size_t)nframes;) {
     const size_t n = (size_t)nframes - off < piece ? (size_t)nframes - off : piece;
     const int s = q->stage_next;
     if (q->stage_busy[s]) { PHIP(q, hipEventSynchronize(q->stage_ev[s])); q->stage_busy[s] = false; }
     memcpy(q->h_stage[s], (const char *)audio + off * es, n * es);
-    // (the samples the blanker will complete, the 12 kS/s samples those make)
-    const size_t nout = (size_t)r.audio_outputs((size_t)r.resample_outputs((size_t)r.blank_outputs(n, blank, guard), rate), mode);
+    const size_t nout = (size_t)r.chain_outputs(n, cfg);
     while (r.have + nout > r.cap && r.ready() > 0) {
       const int rc = launch_from_ring(q, r.ready() < q->o.batch_frames ? r.ready() : q->o.batch_frames);
       if (rc) return rc;
     }
-    if (!(bk_on   ? r.push_blanked(q->h_stage[s], n, s16, false, rs_on)
-          : rs_on ? r.push_resampled(q->h_stage[s], n, s16, false)
-                  : r.push_audio(q->h_stage[s], n, s16, false)))
-      return pfail(q, UWSPR_ERR_HIP, "audio stream: %s", hipGetErrorString(r.err));
+    if (!r.chain_push(q->h_stage[s], n, s16, false)) return pfail(q, UWSPR_ERR_HIP, "audio stream: %s", hipGetErrorString(r.err));
     PHIP(q, hipEventRecord(q->stage_ev[s], r.copy));
     q->stage_busy[s] = true;
     q->stage_next = (s + 1) % uwspr_pipe::NSTAGE;
@@ -990,17 +972,16 @@ extern "C" int uwspr_pipe_set_option(uwspr_pipe *q, const char *name, int value)
   if (!strcmp(name, "audio_rate")) {   // the pipe's own: the rate of the audio its pushes carry, latched by the first push
     resample_plan pl;
     if (resample_design(value, pl)) return parg(q, "uwspr_pipe_set_option: \"audio_rate\" = %d is not a supported rate", value);
-    if (q->ring.kind == RING_AUDIO && value != (q->ring.rs.rate ? q->ring.rs.rate : 12000))
-      return parg(q, "uwspr_pipe_set_option: \"audio_rate\" = %d while the audio stream runs at %d S/s", value,
-                  q->ring.rs.rate ? q->ring.rs.rate : 12000);
+    if (const int running = q->ring.chain_running_rate(); running && value != running)
+      return parg(q, "uwspr_pipe_set_option: \"audio_rate\" = %d while the audio stream runs at %d S/s", value, running);
     q->audio_rate = value;
     return UWSPR_OK;
   }
   if (!strcmp(name, "carrier")) return uwspr_pipe_set_carriers(q, &value, 1);
   if (!strcmp(name, "frontend_hbw")) {   // the pipe's own: K0's half-bandwidth, latched by the first audio push
     if (value < 1 || value > 150) return parg(q, "uwspr_pipe_set_option: \"frontend_hbw\" is 1 .. 150 Hz, not %d", value);
-    if (q->ring.kind == RING_AUDIO && value != q->ring.au.hbw)
-      return parg(q, "uwspr_pipe_set_option: \"frontend_hbw\" = %d while the audio stream runs with %d Hz", value, q->ring.au.hbw);
+    if (const audio_chain_cfg has = q->ring.chain_latched(); has.rate && value != has.hbw)
+      return parg(q, "uwspr_pipe_set_option: \"frontend_hbw\" = %d while the audio stream runs with %d Hz", value, has.hbw);
     q->frontend_hbw = value;
     return UWSPR_OK;
   }
@@ -1008,9 +989,11 @@ extern "C" int uwspr_pipe_set_option(uwspr_pipe *q, const char *name, int value)
     const bool g = name[5] != 0;
     if (g ? (value < 0 || value > 64) : (value != 0 && (value < 4 || value > 1024)))
       return parg(q, g ? "uwspr_pipe_set_option: \"blank_guard\" is 0 .. 64, not %d" : "uwspr_pipe_set_option: \"blank\" is 0 or 4 .. 1024, not %d", value);
-    if (q->ring.kind == RING_AUDIO && (g ? (q->ring.bk.blank && value != q->ring.bk.guard) : value != q->ring.bk.blank))
+    audio_chain_cfg has = q->ring.chain_latched(), now = has;   // (what the running stream has, but for this option)
+    (g ? now.guard : now.blank) = value;
+    if (q->ring.chain_mismatch(now))
       return parg(q, "uwspr_pipe_set_option: \"%s\" = %d while the audio stream runs with blank %d, guard %d", name, value,
-                  q->ring.bk.blank, q->ring.bk.guard);
+                  has.blank, has.guard);
     (g ? q->blank_guard : q->blank) = value;
     return UWSPR_OK;
   }

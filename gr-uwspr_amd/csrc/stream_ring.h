@@ -23,12 +23,23 @@
 // npl = nch * ncar planes, plane c * ncar + k for channel c and carrier k.  nch stays the AUDIO channel count (the
 // interleave stride of the histories; what K11 and K12 see); npl is what the ring, reserve / view, the tail move and the
 // batches see.  With one carrier npl == nch.
+//
+// Audio (chain_push): real samples go through a chain of stages on the copy stream into the ring -- K12, the blanker
+// (option "blank" != 0), K11, the resampler (option "audio_rate" != 12000), and K0, the front-end, always.  What the
+// chain is made of is latched by the first audio push after open / reset (chain_latch) and a stage hands its outputs
+// to the next as a device source.  Every stage keeps its input in a staged_input: two device buffers, the current one
+// holding [history | new frames], the history being the inputs the stage's next output still reads.  Which output a
+// piece completes, from where the history is kept and how large the buffers are is stream_stage.h's arithmetic.
+// Formats: a staged input stays int16 while every push is; a float push widens its history once (s / 32768, exact) and
+// from then on int16 pushes are widened on arrival, so formats may mix and every output sees the same sample values.
 #pragma once
 
 #include <hip/hip_runtime.h>
 #include <string.h>
 
 #include <vector>
+
+#include "stream_stage.h"
 
 namespace uwspr {
 
@@ -64,9 +75,35 @@ hipError_t launch_blank_level(hipStream_t s, const void *audio, bool s16, long l
 hipError_t launch_blank_apply(hipStream_t s, const void *audio, bool s16, long long nin, long long in0, int nch, const float *lev,
                               long long nlev, long long blk0, int blank, int guard, float *out, long long nout, long long y_first,
                               int *nz);
-long long blank_blocks_of(long long y_first, long long nout);
+static_assert(stage::BLANK_N == UWSPR_BLANK_BLOCK, "stream_stage.h restates the block length");
 
 enum { RING_EMPTY = 0, RING_IQ = 1, RING_AUDIO = 2 };   // what the stream is, decided by its first push
+
+// What an audio stream's chain is made of: the options its first push latches.
+struct audio_chain_cfg {
+  int mode;                            // K0's tap mode (option "frontend")
+  std::vector<int> carriers;           // K0's centres in Hz, in plane order
+  int hbw;                             // K0's half-bandwidth
+  int rate;                            // of the pushed audio; any other than 12000 puts K11 ahead of K0
+  int blank, guard;                    // blank != 0 puts K12 ahead of both
+};
+// the part of a chain a refused change or a failed set-up belongs to
+enum chain_part { CHAIN_OK = 0, CHAIN_FRONTEND, CHAIN_CARRIERS, CHAIN_RATE, CHAIN_BLANK };
+
+// n elements a stage owns, on the device or page-locked on the host.  alloc() frees what was held first and holds
+// nothing after a failure.
+template <typename T, bool HOST = false>
+struct owned {
+  T *p = nullptr;
+  size_t n = 0;
+  void release() { if (p) (void)(HOST ? hipHostFree(p) : hipFree(p)); p = nullptr; n = 0; }
+  hipError_t alloc(size_t count) {
+    release();
+    const hipError_t e = HOST ? hipHostMalloc((void **)&p, count * sizeof(T), hipHostMallocDefault) : hipMalloc((void **)&p, count * sizeof(T));
+    if (e == hipSuccess) n = count; else p = nullptr;
+    return e;
+  }
+};
 
 struct stream_ring {
   int fl = 0, hop = 0, maxf = 0;
@@ -88,73 +125,93 @@ struct stream_ring {
   hipEvent_t pin_ev[2] = {nullptr, nullptr};
   bool pin_busy[2] = {false, false};
   int pin_next = 0;
-  bool last_direct = false;            // the last append DMAs straight from the caller's (page-locked) buffer
+  bool last_direct = false;            // the last append / push DMAs straight from the caller's (page-locked) buffer
   hipError_t err = hipSuccess;
   int kind = RING_EMPTY;
-  // Audio streams (push_audio): 12 kS/s real samples (frames of nch interleaved samples) go through K0 into the
-  // ring.  Output m of the stream is y[m] = sum_k g[k] x[32 m + D - k] (audio index 32 m = stream index m) and is
-  // produced as soon as x[32 m + D] has been pushed.  The device buffer holds [history | new frames]: the history is
-  // the audio from index 32 (m_next + dcols - J) on, at most 32 J frames, zero before the stream's first sample.
+
+  // A stage's input: frames of nch samples, int16 while every push so far was (s16), else float.  d[cur] holds
+  // [history | new frames] from input h.i_base on; the other buffer takes int16 arrivals on their way to a float
+  // history, and the tail when the history's origin moves.  Everything runs on the ring's copy stream.
+  struct staged_input {
+    owned<char> d[2];
+    int cur = 0, s16 = 0;
+    stage::history h;
+    size_t frame_bytes(const stream_ring &r) const { return (s16 ? 2 : 4) * (size_t)r.nch; }
+    bool ensure(stream_ring &r, size_t bytes) { return r.ensure(d[0], bytes) && r.ensure(d[1], bytes); }
+    void release() { d[0].release(); d[1].release(); }
+    // a stream's first frames: format and history (the caller fills or zeroes it)
+    void start(bool s16_, long long i_base, size_t hist) { s16 = s16_; h.i_base = i_base; h.hist = hist; }
+    // before the first float frames: an int16 history becomes float
+    bool widen_history(stream_ring &r) {
+      if (!s16) return true;
+      launch_widen_s16(r.copy, (const int16_t *)d[cur].p, (float *)d[cur ^ 1].p, h.hist * (size_t)r.nch);
+      cur ^= 1; s16 = 0;
+      return (r.err = hipGetLastError()) == hipSuccess;
+    }
+    // k frames from src (see upload) behind the history; returns the buffer the stage's kernels read (h.hist + k frames
+    // from input h.i_base on), null on failure
+    char *take(stream_ring &r, const void *src, size_t k, bool s16_in, bool on_device, hipEvent_t src_ready) {
+      const size_t C = (size_t)r.nch;
+      char *b = d[cur].p, *at = b + h.hist * frame_bytes(r);
+      if (s16_in && !s16) {   // (the other buffer is free until keep(), which comes after on the same stream)
+        if (!r.upload(d[cur ^ 1].p, src, k * 2 * C, on_device, src_ready)) return nullptr;
+        launch_widen_s16(r.copy, (const int16_t *)d[cur ^ 1].p, (float *)at, k * C);
+        if ((r.err = hipGetLastError()) != hipSuccess) return nullptr;
+      } else if (!r.upload(at, src, k * frame_bytes(r), on_device, src_ready)) {
+        return nullptr;
+      }
+      return b;
+    }
+    // after the launches on the k frames take() brought: inputs from `from` on are the new history
+    bool keep(stream_ring &r, size_t k, long long from) {
+      const size_t es = frame_bytes(r);
+      const stage::history::tail t = h.advance(k, from);
+      if (!t.moves) return true;
+      if (t.len && (r.err = hipMemcpyAsync(d[cur ^ 1].p, d[cur].p + t.off * es, t.len * es, hipMemcpyDeviceToDevice, r.copy)) != hipSuccess)
+        return false;
+      cur ^= 1;
+      return true;
+    }
+  };
+
+  // K0: 12 kS/s frames into the ring, one plane per channel and carrier
   struct audio_state {
     int mode = -1;                     // latched by the first push after open / reset
-    int s16 = 0;                       // the buffer holds int16 samples (every push so far was int16), else float
     int J = 0, dcols = 0, taps_mode = -1;
-    float *d_taps = nullptr;           // [32][J] float2, the stream's own copy (a batch call may swap the context's)
-    // K0's centre(s) and half-bandwidth, latched with the mode.  Anything but {1500 Hz}, 10 Hz runs the carrier form:
-    // d_taps is then frontend_carrier_tables' block: [ncar][32][J] taps, the rotator table, the carriers mod 375
-    std::vector<int> car, taps_car;
+    // [32][J] float2, the stream's own copy (a batch call may swap the context's).  Anything but {1500 Hz}, 10 Hz runs
+    // the carrier form: then frontend_carrier_tables' block -- [ncar][32][J] taps, the rotator table, the carriers mod 375
+    owned<float> taps;
+    std::vector<int> car, taps_car;    // K0's centre(s) and half-bandwidth, latched with the mode
     int hbw = 0, taps_hbw = 0;
     bool carrier_form = false;
-    char *d_buf[2] = {nullptr, nullptr};
-    size_t buf_bytes = 0;
-    int cur = 0;
-    long long a0 = 0;                  // audio index of d_buf[cur][0]
-    size_t hist = 0;                   // frames held in d_buf[cur]: audio [a0, a0 + hist)
+    staged_input in;                   // audio indices; zero before the stream's first sample
     long long m_next = 0;              // stream index of the next output
   } au;
-  // Audio at another rate (option "audio_rate" != 12000): the pushed frames go through K11 into a device buffer of
-  // 12 kS/s float frames, which push_audio takes as a device source on the same stream.  Output j of the resampler is
-  // complete as soon as input floor((j M + D) / L) has been pushed; the device buffer holds [history | new frames], the
-  // history being the inputs from floor((j_next M + D) / L) - (T - 1) on (at most T - 1 frames, zero before the first).
-  // Counters restart at 0 with every open / reset: K0 sees output j as 12 kS/s sample 32 pos + j.
+  // K11: frames at another rate into 12 kS/s float frames for K0.  Counters restart at 0 with every open / reset: K0 sees
+  // output j as 12 kS/s sample 32 pos + j.
   struct resample_state {
-    int rate = 0;                      // latched by the first audio push after open / reset (0: none yet; 12000: no resampler)
+    int rate = 0;                      // latched by the first audio push after open / reset (0: no resampler)
     int taps_rate = 0, TP = 0;
     resample_plan pl;                  // of taps_rate
-    float *d_taps = nullptr;           // [L][TP]
-    int s16 = 0;                       // the input buffer holds int16 frames (every push so far was int16)
-    char *d_in[2] = {nullptr, nullptr};
-    size_t in_bytes = 0;
-    int cur = 0;
-    long long i_base = 0;              // input index of d_in[cur][0]
-    size_t hist = 0;                   // frames held: inputs [i_base, i_base + hist)
+    owned<float> taps;                 // [L][TP]
+    staged_input in;
     long long n_in = 0, j_next = 0;    // inputs pushed, next output
-    float *d_out = nullptr;            // [out_frames][nch]
-    size_t out_frames = 0;
+    owned<float> out;                  // [audio_piece_frames()][nch]
   } rs;
-  // Impulsive noise (option "blank" != 0): the pushed frames go through K12 into a device buffer of float frames at the
-  // same rate, which push_resampled or push_audio takes as a device source on the same stream.  Output i is complete as
-  // soon as input i + G has been pushed.  The device buffer holds [history | new frames]: the history is whatever is
-  // not yet output plus its guard (inputs from y_next - G on) and the incomplete block (from (n_in div N) N on), at
-  // most N + 2 G frames.  The level table holds the last three complete blocks ahead of the ones a push completes.
-  // The per-block zero counts go to the host through a page-locked queue and are summed there (blank_drain).
+  // K12: frames with their impulses zeroed, as float frames at the same rate for K11 or K0.  The level table holds the
+  // last three complete blocks ahead of the ones a push completes; the per-block zero counts go to the host through a
+  // page-locked queue and are summed there (blank_drain).
   struct blank_state {
     int blank = 0, guard = 0;          // latched by the first audio push after open / reset (blank 0: no blanker)
-    int s16 = 0;                       // the input buffer holds int16 frames (every push so far was int16)
-    char *d_in[2] = {nullptr, nullptr};
-    size_t in_bytes = 0;
-    int cur = 0;
-    long long i_base = 0;              // input index of d_in[cur][0]
-    size_t hist = 0;                   // frames held: inputs [i_base, i_base + hist)
+    staged_input in;
     long long n_in = 0, y_next = 0;    // inputs pushed, next output
-    float *d_out = nullptr;            // [out_frames][nch]
-    size_t out_frames = 0;
-    float *d_lev[2] = {nullptr, nullptr};   // [lev_rows][nch]: the levels of blocks lev0 .. blk_done - 1
-    size_t lev_rows = 0;
+    owned<float> out;                  // [audio_piece_frames()][nch]
+    owned<float> lev[2];               // [blank_lev_rows][nch]: the levels of blocks lev0 .. blk_done - 1
     int lcur = 0;
     long long lev0 = 0, blk_done = 0;  // first block of the table, complete blocks so far
-    int *d_nz = nullptr, *h_nz = nullptr;   // zero counts [..][nch] of the launches since the last drain, device and page-locked host
-    size_t nz_cap = 0, nz_used = 0;    // in ints (multiples of nch)
+    owned<int> nz;                     // zero counts [..][nch] of the launches since the last drain
+    owned<int, true> h_nz;             // their page-locked copy
+    size_t nz_used = 0;                // in ints (multiples of nch)
     std::vector<long long> zeroed;     // per channel, drained so far
     bool stale = false;                // a reset left counts in flight: drained and dropped by the next latch
   } bk;
@@ -171,17 +228,11 @@ struct stream_ring {
     if (pin) { (void)hipHostFree(pin); pin = nullptr; }
     for (int k = 0; k < 2; k++) if (pin_ev[k]) { (void)hipEventDestroy(pin_ev[k]); pin_ev[k] = nullptr; }
     if (ev_up) { (void)hipEventDestroy(ev_up); ev_up = nullptr; }
-    for (int k = 0; k < 2; k++) if (au.d_buf[k]) { (void)hipFree(au.d_buf[k]); au.d_buf[k] = nullptr; }
-    if (au.d_taps) { (void)hipFree(au.d_taps); au.d_taps = nullptr; }
+    au.in.release(); au.taps.release();
     au = audio_state();
-    for (int k = 0; k < 2; k++) if (rs.d_in[k]) (void)hipFree(rs.d_in[k]);
-    if (rs.d_out) (void)hipFree(rs.d_out);
-    if (rs.d_taps) (void)hipFree(rs.d_taps);
+    rs.in.release(); rs.taps.release(); rs.out.release();
     rs = resample_state();
-    for (int k = 0; k < 2; k++) { if (bk.d_in[k]) (void)hipFree(bk.d_in[k]); if (bk.d_lev[k]) (void)hipFree(bk.d_lev[k]); }
-    if (bk.d_out) (void)hipFree(bk.d_out);
-    if (bk.d_nz) (void)hipFree(bk.d_nz);
-    if (bk.h_nz) (void)hipHostFree(bk.h_nz);
+    bk.in.release(); bk.out.release(); bk.lev[0].release(); bk.lev[1].release(); bk.nz.release(); bk.h_nz.release();
     bk = blank_state();
     if (copy) { (void)hipStreamDestroy(copy); copy = nullptr; }
     cap = 0; plane = 0; nch = 1; ncar = 1; npl = 1; have = 0; base = 0; up_pending = false;
@@ -294,143 +345,96 @@ struct stream_ring {
     return commit(n);
   }
 
-  // ---- audio streams
-  // stream index one past the last output that audio [.., a_end) completes (floor division: a_end may be < D)
-  static long long audio_complete(long long a_end, int dcols) {
-    const long long t = a_end - 1 - 32LL * dcols;
-    return (t >= 0 ? t / 32 : -((-t + 31) / 32)) + 1;
+  // ---- the audio chain's memory
+  // a stage's buffer of `count` elements in place of the one it holds (launches on the copy stream may still read that)
+  template <typename O>
+  bool renew(O &o, size_t count) {
+    if ((err = hipStreamSynchronize(copy)) != hipSuccess) return false;
+    return (err = o.alloc(count)) == hipSuccess;
   }
-  // outputs a push of n samples would add, for a stream in front-end mode `mode`
+  template <typename O>
+  bool ensure(O &o, size_t count) { return o.n >= count || renew(o, count); }
+
+  // ---- K0
+  // outputs a push of n 12 kS/s samples would add, for a stream in front-end mode `mode`
   long long audio_outputs(size_t n, int mode) const {
     const int dcols = frontend_read_ahead(mode) / 32;
-    const long long a_end = au.mode >= 0 ? au.a0 + (long long)au.hist : 32LL * au.m_next;
-    const long long m = audio_complete(a_end + (long long)n, dcols);
-    return m > au.m_next ? m - au.m_next : 0;
+    const long long a_end = au.mode >= 0 ? au.in.h.i_base + (long long)au.in.h.hist : 32LL * au.m_next;
+    return stage::added(stage::audio_complete(a_end + (long long)n, dcols), au.m_next);
   }
 
   static bool default_carriers(const std::vector<int> &car, int hbw) {
     return car.size() == 1 && car[0] == UWSPR_CARRIER_DEFAULT && hbw == UWSPR_FRONTEND_HBW_DEFAULT;
   }
 
-  // The first audio push after open / reset: taps of `mode`, buffers, a zero history.  car (ncar carriers, Hz) and hbw:
-  // K0's centres and half-bandwidth; null: the default set {1500}, 10.
-  bool audio_latch(int mode, bool s16, const std::vector<int> *car = nullptr, int hbw = UWSPR_FRONTEND_HBW_DEFAULT) {
-    const std::vector<int> dflt(1, UWSPR_CARRIER_DEFAULT);
-    const std::vector<int> &cs = car ? *car : dflt;
+  // The first audio push after open / reset: taps of `mode` at the centres cs (ncar carriers, Hz) and half-bandwidth hbw
+  // -- the default set {1500}, 10 as one tap image, anything else as the carrier form's tables --, buffers, a zero history.
+  bool audio_latch(int mode, bool s16, const std::vector<int> &cs, int hbw) {
     if ((int)cs.size() != ncar) { err = hipErrorInvalidValue; return false; }
-    if (!default_carriers(cs, hbw)) return carrier_latch(mode, s16, cs, hbw);
-    au.carrier_form = false; au.car = cs; au.hbw = hbw;
-    if (au.taps_mode != mode || !default_carriers(au.taps_car, au.taps_hbw)) {
+    const bool form = !default_carriers(cs, hbw);
+    if (au.taps_mode != mode || au.taps_car != cs || au.taps_hbw != hbw) {
       std::vector<float> img;
       int J = 0, dcols = 0;
-      if (frontend_tap_image(mode, img, &J, &dcols) || frontend_prepare()) { err = hipErrorInvalidValue; return false; }
-      if ((err = hipStreamSynchronize(copy)) != hipSuccess) return false;   // (launches with the old taps)
-      if (au.d_taps) { (void)hipFree(au.d_taps); au.d_taps = nullptr; }
-      if ((err = hipMalloc((void **)&au.d_taps, img.size() * sizeof(float))) != hipSuccess) { au.d_taps = nullptr; return false; }
-      if ((err = hipMemcpy(au.d_taps, img.data(), img.size() * sizeof(float), hipMemcpyHostToDevice)) != hipSuccess) return false;
+      if ((form ? frontend_carrier_tables(mode, cs, hbw, img, &J, &dcols) : frontend_tap_image(mode, img, &J, &dcols)) ||
+          frontend_prepare()) { err = hipErrorInvalidValue; return false; }
+      au.taps_mode = -1;   // (no taps are resident until the new ones have arrived)
+      if (!renew(au.taps, img.size())) return false;
+      if ((err = hipMemcpy(au.taps.p, img.data(), img.size() * sizeof(float), hipMemcpyHostToDevice)) != hipSuccess) return false;
       au.taps_mode = mode; au.J = J; au.dcols = dcols; au.taps_car = cs; au.taps_hbw = hbw;
     }
-    return audio_latch_buffers(mode, s16);
-  }
-
-  // the carrier form's tables: one tap image per carrier, the rotator table, the carriers mod 375
-  bool carrier_latch(int mode, bool s16, const std::vector<int> &cs, int hbw) {
-    if (au.taps_mode != mode || au.taps_car != cs || au.taps_hbw != hbw) {
-      std::vector<float> all;
-      int J = 0, dcols = 0;
-      if (frontend_carrier_tables(mode, cs, hbw, all, &J, &dcols) || frontend_prepare()) { err = hipErrorInvalidValue; return false; }
-      if ((err = hipStreamSynchronize(copy)) != hipSuccess) return false;   // (launches with the old taps)
-      if (au.d_taps) { (void)hipFree(au.d_taps); au.d_taps = nullptr; }
-      au.taps_mode = -1;
-      if ((err = hipMalloc((void **)&au.d_taps, all.size() * sizeof(float))) != hipSuccess) { au.d_taps = nullptr; return false; }
-      if ((err = hipMemcpy(au.d_taps, all.data(), all.size() * sizeof(float), hipMemcpyHostToDevice)) != hipSuccess) return false;
-      au.taps_mode = mode; au.J = J; au.dcols = dcols; au.taps_car = cs; au.taps_hbw = hbw;
-    }
-    au.carrier_form = true; au.car = cs; au.hbw = hbw;
-    return audio_latch_buffers(mode, s16);
-  }
-
-  bool audio_latch_buffers(int mode, bool s16) {
-    const size_t need = ((32 * (size_t)au.J + 32) * nch + audio_piece_frames() * nch) * sizeof(float);
-    if (au.buf_bytes < need) {
-      if ((err = hipStreamSynchronize(copy)) != hipSuccess) return false;
-      for (int k = 0; k < 2; k++) {
-        if (au.d_buf[k]) { (void)hipFree(au.d_buf[k]); au.d_buf[k] = nullptr; }
-        if ((err = hipMalloc((void **)&au.d_buf[k], need)) != hipSuccess) { au.d_buf[k] = nullptr; au.buf_bytes = 0; return false; }
-      }
-      au.buf_bytes = need;
-    }
-    au.mode = mode; au.s16 = s16;
-    au.a0 = 32 * (au.m_next + au.dcols - au.J);
-    au.hist = (size_t)(32LL * au.m_next - au.a0);
-    if ((err = hipMemsetAsync(au.d_buf[au.cur], 0, au.hist * nch * (s16 ? 2 : 4), copy)) != hipSuccess) return false;
+    au.carrier_form = form; au.car = cs; au.hbw = hbw;
+    if (!au.in.ensure(*this, stage::audio_need(au.J, audio_piece_frames(), (size_t)nch) * sizeof(float))) return false;
+    au.mode = mode;
+    const long long a0 = stage::audio_keep(au.m_next, au.J, au.dcols);
+    au.in.start(s16, a0, (size_t)(32LL * au.m_next - a0));
+    if ((err = hipMemsetAsync(au.in.d[au.in.cur].p, 0, au.in.h.hist * au.in.frame_bytes(*this), copy)) != hipSuccess) return false;
     kind = RING_AUDIO;
     return true;
   }
 
-  // n audio frames of nch samples (int16 when s16, else float) from src (see upload): upload behind the history, K0
-  // for the outputs that became complete straight into the ring (one plane per channel), keep the new tail as
-  // history.  The caller has latched the stream and checked room() against audio_outputs(n).  An int16 stream stays int16 while every push is; a float push
-  // widens its history once (s / 32768, exact) and from then on int16 pushes are widened on arrival, so formats may
-  // mix and every output sees the same sample values.
-  bool push_audio(const void *src, size_t n, bool s16_in, bool on_device, hipEvent_t src_ready = nullptr) {
-    last_direct = false;
-    const size_t C = (size_t)nch;
-    if (n && au.s16 && !s16_in) {
-      launch_widen_s16(copy, (const int16_t *)au.d_buf[au.cur], (float *)au.d_buf[au.cur ^ 1], au.hist * C);
-      if ((err = hipGetLastError()) != hipSuccess) return false;
-      au.cur ^= 1; au.s16 = 0;
-    }
-    const bool widen = s16_in && !au.s16;   // int16 samples into a float buffer
-    const size_t es = (au.s16 ? 2 : 4) * C, es_in = (s16_in ? 2 : 4) * C;   // bytes per frame
-    const size_t piece = audio_piece_frames();
+  // A push through one stage: n frames of nch samples (int16 when s16_in, else float) from src (see upload), cut into
+  // pieces of at most `piece` frames.  Each piece goes behind the stage's history; stage(b, k, &from) launches on the
+  // buffer b for the outputs the k new frames complete, hands them on, and says from which input on the history stays.
+  template <typename F>
+  bool staged_push(staged_input &in, size_t piece, const void *src, size_t n, bool s16_in, bool on_device, hipEvent_t src_ready,
+                   F stage) {
+    if (n && !s16_in && !in.widen_history(*this)) return false;
+    const size_t es_in = (s16_in ? 2 : 4) * (size_t)nch;   // bytes per frame
     for (size_t off = 0; off < n;) {
       const size_t k = n - off < piece ? n - off : piece;
-      char *b = au.d_buf[au.cur];
-      if (widen) {   // (the other buffer is free until the tail copy below, which comes after on the same stream)
-        char *tmp = au.d_buf[au.cur ^ 1];
-        if (!upload(tmp, (const char *)src + off * es_in, k * es_in, on_device, src_ready)) return false;
-        launch_widen_s16(copy, (const int16_t *)tmp, (float *)(b + au.hist * es), k * C);
-        if ((err = hipGetLastError()) != hipSuccess) return false;
-      } else if (!upload(b + au.hist * es, (const char *)src + off * es_in, k * es_in, on_device, src_ready)) {
-        return false;
-      }
-      const long long a_end = au.a0 + (long long)(au.hist + k);
-      const long long m_end = audio_complete(a_end, au.dcols);
+      char *b = in.take(*this, (const char *)src + off * es_in, k, s16_in, on_device, src_ready);
+      long long from = 0;
+      if (!b || !stage(b, k, &from) || !in.keep(*this, k, from)) return false;
+      off += k;
+    }
+    return true;
+  }
+
+  // 12 kS/s frames: K0 for the outputs that became complete, straight into the ring.  (The caller has checked room()
+  // against chain_outputs().)
+  bool push_audio(const void *src, size_t n, bool s16_in, bool on_device, hipEvent_t src_ready) {
+    return staged_push(au.in, audio_piece_frames(), src, n, s16_in, on_device, src_ready, [this](char *b, size_t k, long long *from) {
+      const int held = (int)(au.in.h.hist + k);
+      const long long a0 = au.in.h.i_base, m_end = stage::audio_complete(a0 + held, au.dcols);
       if (m_end > au.m_next) {
         const int nout = (int)(m_end - au.m_next);
         float *dst = reserve((size_t)nout);
         if (!dst) return false;
         if (au.carrier_form)
-          launch_frontend_carrier(copy, b, au.s16, (int)(au.hist + k), au.a0, au.d_taps, au.J, au.dcols, dst, nout, au.m_next,
-                                  nch, ncar, (long long)plane);
+          launch_frontend_carrier(copy, b, au.in.s16, held, a0, au.taps.p, au.J, au.dcols, dst, nout, au.m_next, nch, ncar,
+                                  (long long)plane);
         else
-          launch_frontend_stream(copy, b, au.s16, (int)(au.hist + k), au.a0, au.d_taps, au.J, au.dcols, dst, nout, au.m_next,
-                                 nch, (long long)plane);
+          launch_frontend_stream(copy, b, au.in.s16, held, a0, au.taps.p, au.J, au.dcols, dst, nout, au.m_next, nch, (long long)plane);
         if ((err = hipGetLastError()) != hipSuccess) return false;
         if (!commit((size_t)nout)) return false;
         au.m_next = m_end;
       }
-      const long long a0n = 32 * (au.m_next + au.dcols - au.J);
-      au.hist = (size_t)(a_end - a0n);
-      if (a0n != au.a0) {   // the tail to the front of the other buffer
-        if ((err = hipMemcpyAsync(au.d_buf[au.cur ^ 1], b + (size_t)(a0n - au.a0) * es, au.hist * es,
-                                  hipMemcpyDeviceToDevice, copy)) != hipSuccess) return false;
-        au.cur ^= 1; au.a0 = a0n;
-      }
-      off += k;
-    }
-    if (n && (err = hipEventRecord(ev_up, copy)) != hipSuccess) return false;
-    if (n) up_pending = true;
-    return true;
+      *from = stage::audio_keep(au.m_next, au.J, au.dcols);
+      return true;
+    });
   }
 
-  // ---- audio at another rate (K11 ahead of K0)
-  // one past the last resampler output that n_in pushed inputs complete
-  static long long resample_complete(long long n_in, const resample_plan &pl) {
-    const long long t = n_in * pl.L - 1 - pl.D;
-    return t >= 0 ? t / pl.M + 1 : 0;
-  }
+  // ---- K11
   // 12 kS/s samples a push of n frames at `rate` would add (rate: the latched one, or the one the push would latch);
   // -1: the rate is not supported
   long long resample_outputs(size_t n, int rate) const {
@@ -439,19 +443,12 @@ struct stream_ring {
     const resample_plan *pl = &rs.pl;
     if (rs.taps_rate != rate) { if (resample_design(rate, tmp)) return -1; pl = &tmp; }
     const bool running = rs.rate == rate;
-    const long long j = resample_complete((running ? rs.n_in : 0) + (long long)n, *pl);
-    const long long jn = running ? rs.j_next : 0;
-    return j > jn ? j - jn : 0;
+    return stage::added(stage::resample_complete((running ? rs.n_in : 0) + (long long)n, pl->L, pl->M, pl->D), running ? rs.j_next : 0);
   }
-  // most input frames per K11 launch: its outputs fit d_out (audio_piece_frames() frames, one K0 piece) whatever L / M is
-  size_t resample_piece_frames() const {
-    const size_t outp = audio_piece_frames();
-    const size_t by_out = (size_t)((long long)(outp - 2) * rs.pl.M / rs.pl.L);
-    return by_out < outp ? by_out : outp;
-  }
+  size_t resample_piece_frames() const { return stage::resample_piece_frames(audio_piece_frames(), rs.pl.L, rs.pl.M); }
 
-  // The first audio push after open / reset at a rate other than 12000: taps and buffers of `rate`, zero history,
-  // counters at 0.  (The caller latches K0's side with audio_latch(mode, false): the resampler delivers float frames.)
+  // The first audio push after open / reset at a rate other than 12000: taps and buffers of `rate`, an empty history
+  // (inputs before 0 read as zero in the kernel), counters at 0.
   bool resample_latch(int rate, bool s16) {
     if (rs.taps_rate != rate) {
       resample_plan pl;
@@ -459,128 +456,57 @@ struct stream_ring {
       int TP = 0;
       if (resample_design(rate, pl)) { err = hipErrorInvalidValue; return false; }
       resample_tap_image(pl, img, &TP);
-      if ((err = hipStreamSynchronize(copy)) != hipSuccess) return false;   // (launches with the old taps)
-      if (rs.d_taps) { (void)hipFree(rs.d_taps); rs.d_taps = nullptr; rs.taps_rate = 0; }
-      if ((err = hipMalloc((void **)&rs.d_taps, img.size() * sizeof(float))) != hipSuccess) { rs.d_taps = nullptr; return false; }
-      if ((err = hipMemcpy(rs.d_taps, img.data(), img.size() * sizeof(float), hipMemcpyHostToDevice)) != hipSuccess) return false;
+      rs.taps_rate = 0;
+      if (!renew(rs.taps, img.size())) return false;
+      if ((err = hipMemcpy(rs.taps.p, img.data(), img.size() * sizeof(float), hipMemcpyHostToDevice)) != hipSuccess) return false;
       rs.taps_rate = rate; rs.pl = pl; rs.TP = TP;
     }
-    const size_t C = (size_t)nch, outp = audio_piece_frames();
-    const size_t need = ((size_t)rs.pl.T + resample_piece_frames()) * C * sizeof(float);
-    if (rs.in_bytes < need || rs.out_frames < outp) {
-      if ((err = hipStreamSynchronize(copy)) != hipSuccess) return false;
-      for (int k = 0; k < 2; k++) {
-        if (rs.d_in[k]) { (void)hipFree(rs.d_in[k]); rs.d_in[k] = nullptr; }
-        rs.in_bytes = 0;
-        if ((err = hipMalloc((void **)&rs.d_in[k], need)) != hipSuccess) { rs.d_in[k] = nullptr; return false; }
-      }
-      rs.in_bytes = need;
-      if (rs.d_out) { (void)hipFree(rs.d_out); rs.d_out = nullptr; }
-      rs.out_frames = 0;
-      if ((err = hipMalloc((void **)&rs.d_out, outp * C * sizeof(float))) != hipSuccess) { rs.d_out = nullptr; return false; }
-      rs.out_frames = outp;
-    }
-    rs.rate = rate; rs.s16 = s16;
-    rs.i_base = 0; rs.hist = 0; rs.n_in = 0; rs.j_next = 0;   // (inputs before 0 read as zero in the kernel)
+    const size_t C = (size_t)nch;
+    if (!rs.in.ensure(*this, stage::resample_in_need(rs.pl.T, resample_piece_frames(), C) * sizeof(float)) ||
+        !ensure(rs.out, stage::resample_out_need(audio_piece_frames(), C))) return false;
+    rs.rate = rate; rs.n_in = 0; rs.j_next = 0;
+    rs.in.start(s16, 0, 0);
     return true;
   }
 
-  // n frames of nch samples at the latched rate: behind the resampler's history, K11 for the outputs that became
-  // complete, those into push_audio as a device source on the copy stream.  Formats mix as in push_audio.  The caller
-  // has latched both sides and checked room() against audio_outputs(resample_outputs(n)).
-  bool push_resampled(const void *src, size_t n, bool s16_in, bool on_device, hipEvent_t src_ready = nullptr) {
-    const size_t C = (size_t)nch;
-    bool direct = false;
-    if (n && rs.s16 && !s16_in) {
-      launch_widen_s16(copy, (const int16_t *)rs.d_in[rs.cur], (float *)rs.d_in[rs.cur ^ 1], rs.hist * C);
-      if ((err = hipGetLastError()) != hipSuccess) return false;
-      rs.cur ^= 1; rs.s16 = 0;
-    }
-    const bool widen = s16_in && !rs.s16;
-    const size_t es = (rs.s16 ? 2 : 4) * C, es_in = (s16_in ? 2 : 4) * C;
-    const size_t piece = resample_piece_frames();
-    for (size_t off = 0; off < n;) {
-      const size_t k = n - off < piece ? n - off : piece;
-      char *b = rs.d_in[rs.cur];
-      last_direct = false;
-      if (widen) {
-        char *tmp = rs.d_in[rs.cur ^ 1];
-        if (!upload(tmp, (const char *)src + off * es_in, k * es_in, on_device, src_ready)) return false;
-        launch_widen_s16(copy, (const int16_t *)tmp, (float *)(b + rs.hist * es), k * C);
-        if ((err = hipGetLastError()) != hipSuccess) return false;
-      } else if (!upload(b + rs.hist * es, (const char *)src + off * es_in, k * es_in, on_device, src_ready)) {
-        return false;
-      }
-      direct = direct || last_direct;
+  // frames at the latched rate: K11 for the outputs that became complete, those on to K0
+  bool push_resampled(const void *src, size_t n, bool s16_in, bool on_device, hipEvent_t src_ready) {
+    return staged_push(rs.in, resample_piece_frames(), src, n, s16_in, on_device, src_ready, [this](char *b, size_t k, long long *from) {
+      const resample_plan &pl = rs.pl;
       rs.n_in += (long long)k;
-      const long long j_end = resample_complete(rs.n_in, rs.pl);
+      const long long j_end = stage::resample_complete(rs.n_in, pl.L, pl.M, pl.D);
       if (j_end > rs.j_next) {
         const long long nout = j_end - rs.j_next;
-        if ((size_t)nout > rs.out_frames) { err = hipErrorInvalidValue; return false; }
-        if ((err = launch_resample(copy, b, rs.s16 != 0, (long long)(rs.hist + k), rs.i_base, nch, rs.d_taps, rs.pl, rs.TP,
-                                   rs.d_out, nout, rs.j_next)) != hipSuccess) return false;
+        if ((size_t)nout * (size_t)nch > rs.out.n) { err = hipErrorInvalidValue; return false; }
+        if ((err = launch_resample(copy, b, rs.in.s16 != 0, (long long)(rs.in.h.hist + k), rs.in.h.i_base, nch, rs.taps.p, pl, rs.TP,
+                                   rs.out.p, nout, rs.j_next)) != hipSuccess) return false;
         rs.j_next = j_end;
-        if (!push_audio(rs.d_out, (size_t)nout, false, true, nullptr)) return false;
+        if (!push_audio(rs.out.p, (size_t)nout, false, true, nullptr)) return false;
       }
-      // keep the inputs the next output's window starts at
-      long long keep = (rs.j_next * rs.pl.M + rs.pl.D) / rs.pl.L - (rs.pl.T - 1);
-      if (keep > rs.n_in) keep = rs.n_in;
-      if (keep < rs.i_base) keep = rs.i_base;
-      const size_t nh = (size_t)(rs.n_in - keep);
-      if (keep != rs.i_base) {   // the tail to the front of the other buffer
-        if (nh && (err = hipMemcpyAsync(rs.d_in[rs.cur ^ 1], b + (size_t)(keep - rs.i_base) * es, nh * es,
-                                        hipMemcpyDeviceToDevice, copy)) != hipSuccess) return false;
-        rs.cur ^= 1; rs.i_base = keep;
-      }
-      rs.hist = nh;
-      off += k;
-    }
-    last_direct = direct;
-    if (n && (err = hipEventRecord(ev_up, copy)) != hipSuccess) return false;
-    if (n) up_pending = true;
-    return true;
+      *from = stage::resample_keep(rs.j_next, pl.L, pl.M, pl.T, pl.D);
+      return true;
+    });
   }
 
-  // ---- impulsive noise (K12 ahead of K11 and K0)
-  static constexpr long long BLANK_N = UWSPR_BLANK_BLOCK;
+  // ---- K12
   // samples a push of n frames would complete, for the blanker that runs or the one the push would latch (blank 0: n)
   long long blank_outputs(size_t n, int blank, int guard) const {
     if (!blank) return (long long)n;
     const bool running = bk.blank != 0;
-    const long long y = (running ? bk.n_in : 0) + (long long)n - guard, yn = running ? bk.y_next : 0;
-    return y > yn ? y - yn : 0;
+    return stage::added(stage::blank_complete((running ? bk.n_in : 0) + (long long)n, guard), running ? bk.y_next : 0);
   }
-  size_t blank_piece_frames() const { return audio_piece_frames(); }
 
-  // The first audio push after open / reset with "blank" != 0: buffers, an empty history, counters at 0.  (The caller
-  // latches the stages behind with float input: the blanker delivers float frames.)
+  // The first audio push after open / reset with "blank" != 0: buffers, an empty history, counters at 0.
   bool blank_latch(int blank, int guard, bool s16) {
-    const size_t C = (size_t)nch, piece = blank_piece_frames();
-    const size_t need = ((size_t)BLANK_N + 2 * 64 + piece) * C * sizeof(float);
-    const size_t rows = piece / (size_t)BLANK_N + 6, nzc = (piece / (size_t)BLANK_N + 2) * C * 64;
+    const size_t C = (size_t)nch, piece = audio_piece_frames();
     if (bk.stale && (err = hipStreamSynchronize(copy)) != hipSuccess) return false;   // (counts of the stream before the reset)
     bk.stale = false;
-    if (bk.in_bytes < need || bk.out_frames < piece || bk.lev_rows < rows || bk.nz_cap < nzc) {
-      if ((err = hipStreamSynchronize(copy)) != hipSuccess) return false;
-      for (int k = 0; k < 2; k++) {
-        if (bk.d_in[k]) { (void)hipFree(bk.d_in[k]); bk.d_in[k] = nullptr; }
-        if (bk.d_lev[k]) { (void)hipFree(bk.d_lev[k]); bk.d_lev[k] = nullptr; }
-      }
-      if (bk.d_out) { (void)hipFree(bk.d_out); bk.d_out = nullptr; }
-      if (bk.d_nz) { (void)hipFree(bk.d_nz); bk.d_nz = nullptr; }
-      if (bk.h_nz) { (void)hipHostFree(bk.h_nz); bk.h_nz = nullptr; }
-      bk.in_bytes = 0; bk.out_frames = 0; bk.lev_rows = 0; bk.nz_cap = 0;
-      for (int k = 0; k < 2; k++) {
-        if ((err = hipMalloc((void **)&bk.d_in[k], need)) != hipSuccess) { bk.d_in[k] = nullptr; return false; }
-        if ((err = hipMalloc((void **)&bk.d_lev[k], rows * C * sizeof(float))) != hipSuccess) { bk.d_lev[k] = nullptr; return false; }
-      }
-      if ((err = hipMalloc((void **)&bk.d_out, piece * C * sizeof(float))) != hipSuccess) { bk.d_out = nullptr; return false; }
-      if ((err = hipMalloc((void **)&bk.d_nz, nzc * sizeof(int))) != hipSuccess) { bk.d_nz = nullptr; return false; }
-      if ((err = hipHostMalloc((void **)&bk.h_nz, nzc * sizeof(int), hipHostMallocDefault)) != hipSuccess) { bk.h_nz = nullptr; return false; }
-      bk.in_bytes = need; bk.out_frames = piece; bk.lev_rows = rows; bk.nz_cap = nzc;
-    }
-    bk.blank = blank; bk.guard = guard; bk.s16 = s16;
-    bk.i_base = 0; bk.hist = 0; bk.n_in = 0; bk.y_next = 0; bk.lev0 = 0; bk.blk_done = 0; bk.nz_used = 0;
+    if (!bk.in.ensure(*this, stage::blank_in_need(piece, C) * sizeof(float)) || !ensure(bk.out, piece * C) ||
+        !ensure(bk.lev[0], stage::blank_lev_rows(piece) * C) || !ensure(bk.lev[1], stage::blank_lev_rows(piece) * C) ||
+        !ensure(bk.nz, stage::blank_nz_cap(piece, C)) || !ensure(bk.h_nz, stage::blank_nz_cap(piece, C))) return false;
+    bk.blank = blank; bk.guard = guard;
+    bk.n_in = 0; bk.y_next = 0; bk.lev0 = 0; bk.blk_done = 0; bk.nz_used = 0;
+    bk.in.start(s16, 0, 0);
     bk.zeroed.assign(C, 0);
     return true;
   }
@@ -589,85 +515,98 @@ struct stream_ring {
   bool blank_drain() {
     if (!bk.nz_used) return true;
     if ((err = hipStreamSynchronize(copy)) != hipSuccess) return false;
-    for (size_t i = 0; i < bk.nz_used; i++) bk.zeroed[i % (size_t)nch] += bk.h_nz[i];
+    for (size_t i = 0; i < bk.nz_used; i++) bk.zeroed[i % (size_t)nch] += bk.h_nz.p[i];
     bk.nz_used = 0;
     return true;
   }
-
-  // n frames of nch samples: behind the blanker's history, k12_level for the blocks the push completes, k12_apply for
-  // the outputs it completes, those into push_resampled (rs_on) or push_audio as a device source on the copy stream.
-  // Formats mix as in push_audio.  The caller has latched every stage and checked room() against what the outputs make.
-  bool push_blanked(const void *src, size_t n, bool s16_in, bool on_device, bool rs_on, hipEvent_t src_ready = nullptr) {
-    const size_t C = (size_t)nch;
-    const long long G = bk.guard;
-    bool direct = false;
-    if (n && bk.s16 && !s16_in) {
-      launch_widen_s16(copy, (const int16_t *)bk.d_in[bk.cur], (float *)bk.d_in[bk.cur ^ 1], bk.hist * C);
-      if ((err = hipGetLastError()) != hipSuccess) return false;
-      bk.cur ^= 1; bk.s16 = 0;
+  // per-channel totals since open / reset: outputs made and outputs zeroed (both 0 without a blanker)
+  bool blank_stats(long long *samples, long long *zeroed, int cap) {
+    if (bk.blank && !blank_drain()) return false;
+    for (int k = 0; k < nch && k < cap; k++) {
+      samples[k] = bk.blank ? bk.y_next : 0;
+      zeroed[k] = bk.blank ? bk.zeroed[(size_t)k] : 0;
     }
-    const bool widen = s16_in && !bk.s16;
-    const size_t es = (bk.s16 ? 2 : 4) * C, es_in = (s16_in ? 2 : 4) * C;
-    const size_t piece = blank_piece_frames();
-    for (size_t off = 0; off < n;) {
-      const size_t k = n - off < piece ? n - off : piece;
-      char *b = bk.d_in[bk.cur];
-      last_direct = false;
-      if (widen) {
-        char *tmp = bk.d_in[bk.cur ^ 1];
-        if (!upload(tmp, (const char *)src + off * es_in, k * es_in, on_device, src_ready)) return false;
-        launch_widen_s16(copy, (const int16_t *)tmp, (float *)(b + bk.hist * es), k * C);
-        if ((err = hipGetLastError()) != hipSuccess) return false;
-      } else if (!upload(b + bk.hist * es, (const char *)src + off * es_in, k * es_in, on_device, src_ready)) {
-        return false;
-      }
-      direct = direct || last_direct;
+    return true;
+  }
+
+  // frames at the pushed rate: k12_level for the blocks that became complete, k12_apply for the outputs, those on to
+  // K11 or K0
+  bool push_blanked(const void *src, size_t n, bool s16_in, bool on_device, hipEvent_t src_ready) {
+    return staged_push(bk.in, audio_piece_frames(), src, n, s16_in, on_device, src_ready, [this](char *b, size_t k, long long *from) {
+      const size_t C = (size_t)nch;
+      const long long held = (long long)(bk.in.h.hist + k), in0 = bk.in.h.i_base;
       bk.n_in += (long long)k;
-      const long long held = (long long)(bk.hist + k);
-      // the blocks this piece completes
-      const long long done = bk.n_in / BLANK_N;
+      const long long done = stage::blank_blocks_done(bk.n_in);
       if (done > bk.blk_done) {
-        if ((size_t)(done - bk.lev0) > bk.lev_rows) { err = hipErrorInvalidValue; return false; }
-        if ((err = launch_blank_level(copy, b, bk.s16 != 0, held, bk.i_base, nch, bk.d_lev[bk.lcur] + (size_t)(bk.blk_done - bk.lev0) * C,
+        if ((size_t)(done - bk.lev0) * C > bk.lev[bk.lcur].n) { err = hipErrorInvalidValue; return false; }
+        if ((err = launch_blank_level(copy, b, bk.in.s16 != 0, held, in0, nch, bk.lev[bk.lcur].p + (size_t)(bk.blk_done - bk.lev0) * C,
                                       done - bk.blk_done, bk.blk_done)) != hipSuccess) return false;
         bk.blk_done = done;
       }
-      // the outputs it completes
-      const long long y_end = bk.n_in - G;
+      const long long y_end = stage::blank_complete(bk.n_in, bk.guard);
       if (y_end > bk.y_next) {
         const long long nout = y_end - bk.y_next;
-        const size_t nzn = (size_t)blank_blocks_of(bk.y_next, nout) * C;
-        if ((size_t)nout > bk.out_frames || nzn > bk.nz_cap) { err = hipErrorInvalidValue; return false; }
-        if (bk.nz_used + nzn > bk.nz_cap && !blank_drain()) return false;
-        if ((err = launch_blank_apply(copy, b, bk.s16 != 0, held, bk.i_base, nch, bk.d_lev[bk.lcur], bk.blk_done - bk.lev0, bk.lev0,
-                                      bk.blank, bk.guard, bk.d_out, nout, bk.y_next, bk.d_nz + bk.nz_used)) != hipSuccess) return false;
-        if ((err = hipMemcpyAsync(bk.h_nz + bk.nz_used, bk.d_nz + bk.nz_used, nzn * sizeof(int), hipMemcpyDeviceToHost, copy)) != hipSuccess)
+        const size_t nzn = (size_t)stage::blank_blocks_of(bk.y_next, nout) * C;
+        if ((size_t)nout * C > bk.out.n || nzn > bk.nz.n) { err = hipErrorInvalidValue; return false; }
+        if (bk.nz_used + nzn > bk.nz.n && !blank_drain()) return false;
+        if ((err = launch_blank_apply(copy, b, bk.in.s16 != 0, held, in0, nch, bk.lev[bk.lcur].p, bk.blk_done - bk.lev0, bk.lev0, bk.blank,
+                                      bk.guard, bk.out.p, nout, bk.y_next, bk.nz.p + bk.nz_used)) != hipSuccess) return false;
+        if ((err = hipMemcpyAsync(bk.h_nz.p + bk.nz_used, bk.nz.p + bk.nz_used, nzn * sizeof(int), hipMemcpyDeviceToHost, copy)) != hipSuccess)
           return false;
         bk.nz_used += nzn;
         bk.y_next = y_end;
-        if (!(rs_on ? push_resampled(bk.d_out, (size_t)nout, false, true, nullptr) : push_audio(bk.d_out, (size_t)nout, false, true, nullptr)))
+        if (!(rs.rate ? push_resampled(bk.out.p, (size_t)nout, false, true, nullptr) : push_audio(bk.out.p, (size_t)nout, false, true, nullptr)))
           return false;
       }
-      // the level table keeps the last three complete blocks
-      const long long lev0n = bk.blk_done > 3 ? bk.blk_done - 3 : 0;
+      const long long lev0n = stage::blank_lev_first(bk.blk_done);
       if (lev0n != bk.lev0) {
-        if ((err = hipMemcpyAsync(bk.d_lev[bk.lcur ^ 1], bk.d_lev[bk.lcur] + (size_t)(lev0n - bk.lev0) * C,
+        if ((err = hipMemcpyAsync(bk.lev[bk.lcur ^ 1].p, bk.lev[bk.lcur].p + (size_t)(lev0n - bk.lev0) * C,
                                   (size_t)(bk.blk_done - lev0n) * C * sizeof(float), hipMemcpyDeviceToDevice, copy)) != hipSuccess) return false;
         bk.lcur ^= 1; bk.lev0 = lev0n;
       }
-      // keep what is not yet output with its guard, and the incomplete block
-      long long keep = bk.y_next - G < bk.blk_done * BLANK_N ? bk.y_next - G : bk.blk_done * BLANK_N;
-      if (keep < bk.i_base) keep = bk.i_base;
-      const size_t nh = (size_t)(bk.n_in - keep);
-      if (keep != bk.i_base) {   // the tail to the front of the other buffer
-        if (nh && (err = hipMemcpyAsync(bk.d_in[bk.cur ^ 1], b + (size_t)(keep - bk.i_base) * es, nh * es,
-                                        hipMemcpyDeviceToDevice, copy)) != hipSuccess) return false;
-        bk.cur ^= 1; bk.i_base = keep;
-      }
-      bk.hist = nh;
-      off += k;
-    }
-    last_direct = direct;
+      *from = stage::blank_keep(bk.y_next, bk.guard, bk.blk_done);
+      return true;
+    });
+  }
+
+  // ---- the chain: what the two doors (uwspr_stream_push_audio, uwspr_pipe_push_audio_channels) see of all this
+  // the rate an audio stream runs at (0: no audio stream runs)
+  int chain_running_rate() const { return kind != RING_AUDIO ? 0 : rs.rate ? rs.rate : 12000; }
+  // what the running audio stream has latched (rate 0: none runs)
+  audio_chain_cfg chain_latched() const { return {au.mode, au.car, au.hbw, chain_running_rate(), bk.blank, bk.guard}; }
+  // the first setting of c that differs from what the running audio stream has latched ("blank_guard" counts with a
+  // blanker only); CHAIN_OK: none, or no audio stream runs
+  chain_part chain_mismatch(const audio_chain_cfg &c) const {
+    if (kind != RING_AUDIO) return CHAIN_OK;
+    if (c.mode != au.mode) return CHAIN_FRONTEND;
+    if (c.carriers != au.car || c.hbw != au.hbw) return CHAIN_CARRIERS;
+    if (c.rate != chain_running_rate()) return CHAIN_RATE;
+    if (c.blank != bk.blank || (c.blank && c.guard != bk.guard)) return CHAIN_BLANK;
+    return CHAIN_OK;
+  }
+  // the resampler's ratio L / M = 12000 / rate (1 / 1 without one)
+  void chain_ratio(int *L, int *M) const { *L = rs.rate ? rs.pl.L : 1; *M = rs.rate ? rs.pl.M : 1; }
+  // ring samples a push of n frames would add, for the running chain or the one c would latch; -1: c.rate is not supported
+  long long chain_outputs(size_t n, const audio_chain_cfg &c) const {
+    const long long n12 = resample_outputs((size_t)blank_outputs(n, c.blank, c.guard), c.rate);
+    return n12 < 0 ? -1 : audio_outputs((size_t)n12, c.mode);
+  }
+  // Before the first audio push after open / reset (nothing to do while a stream runs): every stage of c, the first
+  // taking the pushed format and the ones behind it float frames.  Returns the stage that failed (err says why).
+  chain_part chain_latch(const audio_chain_cfg &c, bool s16) {
+    if (kind == RING_AUDIO) return CHAIN_OK;
+    const bool bk_on = c.blank != 0, rs_on = c.rate != 12000;
+    if (bk_on && !blank_latch(c.blank, c.guard, s16)) return CHAIN_BLANK;
+    if (rs_on && !resample_latch(c.rate, s16 && !bk_on)) return CHAIN_RATE;
+    if (!audio_latch(c.mode, s16 && !rs_on && !bk_on, c.carriers, c.hbw)) return CHAIN_FRONTEND;
+    return CHAIN_OK;
+  }
+  // n frames of nch samples into the latched chain's first stage.  The caller has checked room() against chain_outputs(n).
+  bool chain_push(const void *src, size_t n, bool s16, bool on_device, hipEvent_t src_ready = nullptr) {
+    last_direct = false;
+    if (!(bk.blank ? push_blanked(src, n, s16, on_device, src_ready)
+          : rs.rate ? push_resampled(src, n, s16, on_device, src_ready)
+                    : push_audio(src, n, s16, on_device, src_ready))) return false;
     if (n && (err = hipEventRecord(ev_up, copy)) != hipSuccess) return false;
     if (n) up_pending = true;
     return true;

@@ -663,12 +663,7 @@ extern "C" int uwspr_blank_batch(uwspr_ctx *c, const void *audio, long long nin,
 int uwspr::ring_blank_stats(stream_ring &r, long long *samples, long long *zeroed, int cap) {
   if (cap < 0 || (cap > 0 && (!samples || !zeroed))) return UWSPR_ERR_ARG;
   const int C = r.is_open() ? r.nch : 1;
-  if (r.bk.blank && !r.blank_drain()) return UWSPR_ERR_HIP;
-  for (int k = 0; k < C && k < cap; k++) {
-    samples[k] = r.bk.blank ? r.bk.y_next : 0;
-    zeroed[k] = r.bk.blank ? r.bk.zeroed[(size_t)k] : 0;
-  }
-  return C;
+  return r.blank_stats(samples, zeroed, cap) ? C : UWSPR_ERR_HIP;
 }
 
 extern "C" int uwspr_stream_blank_stats(uwspr_ctx *c, long long *samples, long long *zeroed, int cap) {
@@ -1149,7 +1144,25 @@ extern "C" int uwspr_stream_push(uwspr_ctx *c, const float *iq, int nsamples, in
   return UWSPR_OK;
 }
 
-// 12 kS/s audio -> K0 on the ring's copy stream -> the ring (stream_ring::push_audio)
+// what a push or an option is refused for while the audio stream runs with `have` (both doors word it the same)
+const char *uwspr::chain_refusal(chain_part part, const audio_chain_cfg &want, const audio_chain_cfg &have, char (&buf)[160]) {
+  if (part == CHAIN_FRONTEND)
+    snprintf(buf, sizeof(buf), "option frontend changed to %d while the audio stream runs in mode %d", want.mode, have.mode);
+  else if (part == CHAIN_CARRIERS)
+    snprintf(buf, sizeof(buf), "carrier / frontend_hbw changed to %d Hz / %d Hz while the audio stream runs with %d Hz / %d Hz",
+             want.carriers.empty() ? 0 : want.carriers[0], want.hbw, have.carriers.empty() ? 0 : have.carriers[0], have.hbw);
+  else if (part == CHAIN_RATE)
+    snprintf(buf, sizeof(buf), "option audio_rate changed to %d while the audio stream runs at %d S/s", want.rate, have.rate);
+  else
+    snprintf(buf, sizeof(buf), "options blank / blank_guard changed to %d / %d while the audio stream runs with %d / %d", want.blank,
+             want.guard, have.blank, have.blank ? have.guard : want.guard);
+  return buf;
+}
+const char *uwspr::chain_part_name(chain_part part) {
+  return part == CHAIN_BLANK ? "blanker" : part == CHAIN_RATE ? "resampler" : "audio stream";
+}
+
+// audio -> the stages the options name, on the ring's copy stream -> the ring (stream_ring::chain_push)
 extern "C" int uwspr_stream_push_audio(uwspr_ctx *c, const void *audio, int nsamples, int format, int where, int *nready) {
   int rc = ready(c);
   if (rc) return rc;
@@ -1159,51 +1172,28 @@ extern "C" int uwspr_stream_push_audio(uwspr_ctx *c, const void *audio, int nsam
   if (format != UWSPR_AUDIO_F32 && format != UWSPR_AUDIO_S16) return fail(c, UWSPR_ERR_ARG, "audio format %d", format);
   if (where != UWSPR_HOST && where != UWSPR_DEVICE && where != UWSPR_HOST_ASYNC) return fail(c, UWSPR_ERR_ARG, "where=%d", where);
   if (c->p.fs != 375) return fail(c, UWSPR_ERR_UNSUPPORTED, "front-end is 12000 -> 375 S/s (fs=%d)", c->p.fs);
-  const int mode = c->opt[UWSPR_OPT_FRONTEND];
   if (nsamples > 0 && r.kind == RING_IQ) return fail(c, UWSPR_ERR_ARG, "uwspr_stream_push_audio on an (I,Q) stream (reset it first)");
-  if (nsamples > 0 && r.kind == RING_AUDIO && mode != r.au.mode)
-    return fail(c, UWSPR_ERR_ARG, "option frontend changed to %d while the audio stream runs in mode %d (reset it first)", mode, r.au.mode);
-  // options "carrier" / "frontend_hbw": latched like the front-end mode
-  const std::vector<int> car(1, c->opt[UWSPR_OPT_CARRIER]);
-  const int hbw = c->opt[UWSPR_OPT_FRONTEND_HBW];
-  if (nsamples > 0 && r.kind == RING_AUDIO && (car != r.au.car || hbw != r.au.hbw))
-    return fail(c, UWSPR_ERR_ARG, "options carrier / frontend_hbw changed to %d / %d while the audio stream runs with %d / %d (reset it first)",
-                car[0], hbw, r.au.car.empty() ? 0 : r.au.car[0], r.au.hbw);
-  // option "audio_rate": latched like the front-end mode; any other rate than 12000 goes through K11 first
-  const int rate = c->opt[UWSPR_OPT_AUDIO_RATE];
-  const int running = r.kind == RING_AUDIO ? (r.rs.rate ? r.rs.rate : 12000) : 0;
-  if (nsamples > 0 && running && rate != running)
-    return fail(c, UWSPR_ERR_ARG, "option audio_rate changed to %d while the audio stream runs at %d S/s (reset it first)", rate, running);
-  // options "blank" / "blank_guard": latched in the same way; "blank" != 0 puts K12 ahead of both
-  const int blank = c->opt[UWSPR_OPT_BLANK], guard = c->opt[UWSPR_OPT_BLANK_GUARD];
-  const bool bk_on = blank != 0;
-  if (nsamples > 0 && r.kind == RING_AUDIO && (blank != r.bk.blank || (bk_on && guard != r.bk.guard)))
-    return fail(c, UWSPR_ERR_ARG, "options blank / blank_guard changed to %d / %d while the audio stream runs with %d / %d (reset it first)",
-                blank, guard, r.bk.blank, r.bk.blank ? r.bk.guard : guard);
-  const long long n12 = r.resample_outputs((size_t)r.blank_outputs((size_t)nsamples, blank, guard), rate);
-  if (n12 < 0) return fail(c, UWSPR_ERR_ARG, "option audio_rate = %d: not a supported rate", rate);
-  const bool rs_on = rate != 12000;
-  const long long nout = r.audio_outputs((size_t)n12, mode);
+  // options "frontend", "carrier" / "frontend_hbw", "audio_rate", "blank" / "blank_guard": latched by the stream's first push
+  const audio_chain_cfg cfg = {c->opt[UWSPR_OPT_FRONTEND], std::vector<int>(1, c->opt[UWSPR_OPT_CARRIER]), c->opt[UWSPR_OPT_FRONTEND_HBW],
+                               c->opt[UWSPR_OPT_AUDIO_RATE], c->opt[UWSPR_OPT_BLANK], c->opt[UWSPR_OPT_BLANK_GUARD]};
+  char why[160];
+  if (const chain_part d = nsamples > 0 ? r.chain_mismatch(cfg) : CHAIN_OK)
+    return fail(c, UWSPR_ERR_ARG, "%s (reset it first)", chain_refusal(d, cfg, r.chain_latched(), why));
+  const long long nout = r.chain_outputs((size_t)nsamples, cfg);
+  if (nout < 0) return fail(c, UWSPR_ERR_ARG, "option audio_rate = %d: not a supported rate", cfg.rate);
   if (r.have + (size_t)nout > r.cap)
     return fail(c, UWSPR_ERR_ARG, "stream buffer full (%zu + %lld > %zu samples): take frames first", r.have, nout, r.cap);
   if (nsamples > 0) {
     const bool s16 = format == UWSPR_AUDIO_S16;
-    if (r.kind != RING_AUDIO && bk_on && !r.blank_latch(blank, guard, s16))
-      return fail(c, r.err == hipErrorOutOfMemory ? UWSPR_ERR_NOMEM : UWSPR_ERR_HIP, "blanker set-up: %s", hipGetErrorString(r.err));
-    if (r.kind != RING_AUDIO && rs_on && !r.resample_latch(rate, s16 && !bk_on))
-      return fail(c, r.err == hipErrorOutOfMemory ? UWSPR_ERR_NOMEM : UWSPR_ERR_HIP, "resampler set-up (%d S/s): %s", rate, hipGetErrorString(r.err));
-    if (r.kind != RING_AUDIO && !r.audio_latch(mode, s16 && !rs_on && !bk_on, &car, hbw))
-      return fail(c, UWSPR_ERR_HIP, "audio stream set-up: %s", hipGetErrorString(r.err));
+    if (const chain_part f = r.chain_latch(cfg, s16))
+      return fail(c, r.err == hipErrorOutOfMemory ? UWSPR_ERR_NOMEM : UWSPR_ERR_HIP, "%s set-up (%d S/s): %s", chain_part_name(f), cfg.rate,
+                  hipGetErrorString(r.err));
     bool ok;
     if (where == UWSPR_DEVICE) {   // produced by work on the context's stream
       HIPCHK(c, hipEventRecord(c->ring_ev, c->stream));
-      ok = bk_on   ? r.push_blanked(audio, (size_t)nsamples, s16, true, rs_on, c->ring_ev)
-           : rs_on ? r.push_resampled(audio, (size_t)nsamples, s16, true, c->ring_ev)
-                   : r.push_audio(audio, (size_t)nsamples, s16, true, c->ring_ev);
+      ok = r.chain_push(audio, (size_t)nsamples, s16, true, c->ring_ev);
     } else {
-      ok = bk_on   ? r.push_blanked(audio, (size_t)nsamples, s16, false, rs_on)
-           : rs_on ? r.push_resampled(audio, (size_t)nsamples, s16, false)
-                   : r.push_audio(audio, (size_t)nsamples, s16, false);
+      ok = r.chain_push(audio, (size_t)nsamples, s16, false);
       if (ok && where == UWSPR_HOST && r.last_direct) ok = r.wait_uploads();   // as uwspr_stream_push
     }
     if (!ok) return fail(c, UWSPR_ERR_HIP, "audio stream: %s", hipGetErrorString(r.err));

@@ -337,6 +337,8 @@ int bk_debug_launch(uwspr_ctx *c, const void *audio_dev, int s16, long long nin,
                     long long nout, long long y_first, int *nz_dev);
 long long blank_launch_count(int which);
 int ring_blank_stats(stream_ring &r, long long *samples, long long *zeroed, int cap);   // uwspr_api.hip
+const char *chain_refusal(chain_part part, const audio_chain_cfg &want, const audio_chain_cfg &have, char (&buf)[160]);   // uwspr_api.hip
+const char *chain_part_name(chain_part part);
 void launch_frontend(uwspr_ctx *c, const float *audio, int B, int nin, float2 *out, int nout);
 void launch_spectrogram(uwspr_ctx *c, const float *frames, int B);
 void launch_spectrum(uwspr_ctx *c, int B);
