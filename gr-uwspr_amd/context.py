@@ -989,6 +989,21 @@ def frontend_design(mode=FRONTEND_GRC, stage=0, centre=1500, half_bw=10):
     return g
 
 
+def tx_taps():
+    """diagnostics: K7's filter (uwspr_debug_tx_taps; host only, no device) -> (g complex128 [3179], the composite of
+    c2ToWaveFile.grc's chain designed in binary64; image float32 [32, 104, 2], the (Re g, -Im g) tap image the render
+    kernel reads: image[p, i] is tap p + 32 i, +0 behind the last one)"""
+    f = N.lib().uwspr_debug_tx_taps
+    f.argtypes = [C.c_void_p, C.c_void_p]
+    f.restype = C.c_int
+    g = np.zeros((3179, 2), np.float64)
+    image = np.full((32, 104, 2), np.nan, np.float32)
+    n = f(C.c_void_p(g.ctypes.data), C.c_void_p(image.ctypes.data))
+    if n != 3179:
+        raise N.UwsprError(n if n < 0 else -1, "uwspr_debug_tx_taps: %d taps, this binding holds 3179" % n)
+    return g[:, 0] + 1j * g[:, 1], image
+
+
 def frontend_rotator():
     """uwspr_frontend_rotator: K0's rotator table -> float32 [375, 2], row i = (cos, -sin)(2 pi i / 375); output m of a
     stream at carrier fc is multiplied by row ((fc mod 375) (m mod 375)) mod 375 unless 375 divides fc"""

@@ -179,12 +179,13 @@ __device__ __forceinline__ uint4 philox4x32_10(uint4 c, uint2 k) {
 __device__ __forceinline__ float tx_gauss(unsigned long long seed, int ch, long long n) {
   const uint4 r = philox4x32_10(make_uint4((uint32_t)n, (uint32_t)((unsigned long long)n >> 32), (uint32_t)ch, 0u),
                                 make_uint2((uint32_t)seed, (uint32_t)(seed >> 32)));
-  const float u1 = ((float)(r.x >> 8) + 0.5f) * (1.0f / 16777216.0f);   // (0, 1)
+  // (0, 1]: from 2^23 on the + 0.5f rounds to even, so 2^24 - 1 gives u1 = 1 and a sample of exactly 0 (finite)
+  const float u1 = ((float)(r.x >> 8) + 0.5f) * (1.0f / 16777216.0f);
   const float u2 = (float)(r.y >> 8) * (1.0f / 16777216.0f);            // [0, 1)
   return sqrtf(-2.0f * logf(u1)) * cospif(2.0f * u2);
 }
 
-__device__ __forceinline__ int16_t tx_s16(float v) {   // round(32767 x), saturated
+__device__ __forceinline__ int16_t tx_s16(float v) {   // fl32(32767 x) clamped to [-32768, 32767], then to nearest, halves to even
   const float q = fminf(fmaxf(32767.0f * v, -32768.0f), 32767.0f);
   return (int16_t)(int)rintf(q);
 }
@@ -350,6 +351,17 @@ static std::vector<std::complex<double>> tx_composite() {
   return g;
 }
 
+// the taps as the kernel reads them: phase p = n mod 32 holds (Re g, -Im g)[p + 32 i] at [p][i], +0 behind the last tap
+static std::vector<float2> tx_tap_image(const std::vector<std::complex<double>> &g) {
+  std::vector<float2> img((size_t)K7_DEC * K7_T, make_float2(0.0f, 0.0f));
+  for (int p = 0; p < K7_DEC; p++)
+    for (int i = 0; i < K7_T; i++) {
+      const int q = p + K7_DEC * i;
+      if (q < (int)g.size()) img[(size_t)p * K7_T + i] = make_float2((float)g[q].real(), (float)-g[q].imag());
+    }
+  return img;
+}
+
 static int tx_begin(uwspr_ctx *c) {
   if (!c) return UWSPR_ERR_ARG;
   if (!c->own_stream) return tx_fail(c, UWSPR_ERR_NODEVICE, "context has no device (creation failed: %s)", c->err);
@@ -359,12 +371,7 @@ static int tx_begin(uwspr_ctx *c) {
   if (!c->tx->d_taps) {
     const std::vector<std::complex<double>> g = tx_composite();
     if ((int)g.size() != K7_NT) return tx_fail(c, UWSPR_ERR_HIP, "transmit taps: %zu, expected %d", g.size(), K7_NT);
-    std::vector<float2> img((size_t)K7_DEC * K7_T, make_float2(0.0f, 0.0f));
-    for (int p = 0; p < K7_DEC; p++)
-      for (int i = 0; i < K7_T; i++) {
-        const int q = p + K7_DEC * i;
-        if (q < K7_NT) img[(size_t)p * K7_T + i] = make_float2((float)g[q].real(), (float)-g[q].imag());
-      }
+    const std::vector<float2> img = tx_tap_image(g);
     if (hipFuncSetAttribute(reinterpret_cast<const void *>(k7_render<false, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)k7_lds_bytes()) != hipSuccess ||
         hipFuncSetAttribute(reinterpret_cast<const void *>(k7_render<true, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)k7_lds_bytes()) != hipSuccess ||
         hipFuncSetAttribute(reinterpret_cast<const void *>(k7_render<false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)k7_lds_bytes()) != hipSuccess ||
@@ -683,6 +690,20 @@ static int tx_render(uwspr_ctx *c, const uwspr_tx_signal *sig, const uwspr_tx_mo
     }
   }
   return UWSPR_OK;
+}
+
+// Test door (not part of the ABI, like uwspr_debug_frontend_launch): the binary64 composite g [3179][2] (re, im) and the
+// tap image [32][104][2] as tx_begin uploads it.  Host only: no context, no device.  Either pointer may be null.
+extern "C" int uwspr_debug_tx_taps(double *g, float *image) {
+  const std::vector<std::complex<double>> t = tx_composite();
+  if ((int)t.size() != K7_NT) return UWSPR_ERR_ARG;
+  if (g)
+    for (int q = 0; q < K7_NT; q++) { g[2 * q] = t[q].real(); g[2 * q + 1] = t[q].imag(); }
+  if (image) {
+    const std::vector<float2> img = tx_tap_image(t);
+    memcpy(image, img.data(), img.size() * sizeof(float2));
+  }
+  return K7_NT;
 }
 
 extern "C" int uwspr_tx_baseband(uwspr_ctx *c, const uwspr_tx_signal *sig, int nsig, int channel, long long t0, int n,

@@ -800,7 +800,7 @@ int uwspr_tx_baseband(uwspr_ctx *ctx, const uwspr_tx_signal *sig, int nsig, int 
  * composite of c2ToWaveFile.grc's chain (zero-stuff x32, low_pass(1, 12000, 200, 10, HAMMING), low_pass(1, 12000, 2500,
  * 100, HAMMING) at 1500 Hz, real part): a tone at f Hz of uwspr_tx_baseband's output comes out at 1500 + f Hz, a unit
  * baseband as a tone of amplitude ~1/32.  format UWSPR_AUDIO_F32, or UWSPR_AUDIO_S16
- * = round(32767 x) saturated.  Renders of consecutive pieces concatenate to the bytes of one render; host and device
+ * = the binary32 product 32767 x clamped to [-32768, 32767] and rounded to nearest, halves to even.  Renders of consecutive pieces concatenate to the bytes of one render; host and device
  * output are the same bytes.  chan [C], 1 <= C <= UWSPR_PIPE_MAX_CHANNELS, t0 >= 0; every signal's channel < C.  Bad
  * arguments fail the call with UWSPR_ERR_ARG before any device use.  where: UWSPR_HOST (complete on return) or
  * UWSPR_DEVICE (asynchronous on the context's stream). */
