@@ -747,12 +747,17 @@ class Context:
     def tx_baseband(self, signals, n=45000, t0=0, channel=0, out=None):
         """375 S/s baseband samples [t0, t0 + n) of one channel's signals (tx_signals), as c2_read returns a .c2 file:
         numpy [n, 2] float32, or written into `out` (a torch CUDA float32 tensor of n pairs).  A signal with a "motion"
-        (tx_motions) sends the call through uwspr_tx_baseband_moving."""
+        (tx_motions) sends the call through uwspr_tx_baseband_moving, one with a "carrier" (tx_carriers: Hz; here it
+        only scales a motion's Doppler, the baseband is not rotated) through uwspr_tx_baseband_at."""
         signals = list(signals)
-        sig, mot = tx_signals(signals), tx_motions(signals)
+        sig, mot, car = tx_signals(signals), tx_motions(signals), tx_carriers(signals)
         sp = C.c_void_p(C.addressof(sig)) if len(sig) else None
-        call = self.L.uwspr_tx_baseband if mot is None else \
-            (lambda h, *a: self.L.uwspr_tx_baseband_moving(h, a[0], C.c_void_p(C.addressof(mot)), *a[1:]))
+        if car is not None:
+            mp = None if mot is None else C.c_void_p(C.addressof(mot))
+            call = lambda h, *a: self.L.uwspr_tx_baseband_at(h, a[0], mp, C.c_void_p(car.ctypes.data), *a[1:])  # noqa: E731
+        else:
+            call = self.L.uwspr_tx_baseband if mot is None else \
+                (lambda h, *a: self.L.uwspr_tx_baseband_moving(h, a[0], C.c_void_p(C.addressof(mot)), *a[1:]))
         if out is not None and _is_torch(out):
             import torch
             if not (out.is_cuda and out.is_contiguous() and out.dtype == torch.float32 and out.numel() >= 2 * n):
@@ -776,11 +781,17 @@ class Context:
         (a 1-D float32 / int16 numpy array or torch tensor, or None) and background_gain are one value for every channel
         or a list of one per channel.  A background is moved to where the output is made: to out's device for device
         output (once per call: keep it there for repeated renders), to host memory for host output.  A signal with a
-        "motion" (tx_motions) sends the call through uwspr_tx_render_moving."""
+        "motion" (tx_motions) sends the call through uwspr_tx_render_moving; one with a "carrier" (tx_carriers: integer
+        Hz, 170 .. the option "tx_cutoff" - 250; the others stay at 1500) through uwspr_tx_render_at: the transmission is
+        centred on carrier + f0 Hz, and a channel may carry several carriers at once."""
         signals = list(signals)
-        sig, mot = tx_signals(signals), tx_motions(signals)
-        call = self.L.uwspr_tx_render if mot is None else \
-            (lambda h, *a: self.L.uwspr_tx_render_moving(h, a[0], C.c_void_p(C.addressof(mot)), *a[1:]))
+        sig, mot, car = tx_signals(signals), tx_motions(signals), tx_carriers(signals)
+        if car is not None:
+            mp = None if mot is None else C.c_void_p(C.addressof(mot))
+            call = lambda h, *a: self.L.uwspr_tx_render_at(h, a[0], mp, C.c_void_p(car.ctypes.data), *a[1:])  # noqa: E731
+        else:
+            call = self.L.uwspr_tx_render if mot is None else \
+                (lambda h, *a: self.L.uwspr_tx_render_moving(h, a[0], C.c_void_p(C.addressof(mot)), *a[1:]))
         dev_out = out is not None and _is_torch(out)
         if dev_out and not out.is_cuda:
             raise TypeError("tx_render: out must be a CUDA tensor (or None for a numpy result)")
@@ -1004,6 +1015,31 @@ def tx_taps():
     return g[:, 0] + 1j * g[:, 1], image
 
 
+def tx_design(carrier=1500, cutoff=2500):
+    """uwspr_tx_design_at (host only, no device): K7's filter at `carrier` Hz with the second low-pass cut off at `cutoff`
+    Hz -> (g complex128 [3179], image float32 [32, 104, 2]) as tx_taps returns them; (1500, 2500) is tx_taps' bytes.
+    ValueError outside 170 <= carrier <= cutoff - 250, 500 <= cutoff <= 5900."""
+    g = np.zeros((3179, 2), np.float64)
+    image = np.full((32, 104, 2), np.nan, np.float32)
+    n = N.lib().uwspr_tx_design_at(int(carrier), int(cutoff), C.c_void_p(g.ctypes.data), C.c_void_p(image.ctypes.data))
+    if n == -6:   # UWSPR_ERR_ARG
+        raise ValueError("tx_design: carrier %d Hz with cut-off %d Hz (170 <= carrier <= cutoff - 250, 500 <= cutoff <= 5900)"
+                         % (int(carrier), int(cutoff)))
+    if n != 3179:
+        raise N.UwsprError(n if n < 0 else -1, "uwspr_tx_design_at: %d taps, this binding holds 3179" % n)
+    return g[:, 0] + 1j * g[:, 1], image
+
+
+def tx_carrier_launch_counts():
+    """diagnostics: launches of K7's carrier form since the process started -> (float32 output, int16 output)"""
+    f = N.lib().uwspr_debug_tx_carrier_counts
+    f.argtypes = [C.c_void_p]
+    f.restype = C.c_int
+    out = np.zeros(2, np.int64)
+    f(C.c_void_p(out.ctypes.data))
+    return int(out[0]), int(out[1])
+
+
 def frontend_rotator():
     """uwspr_frontend_rotator: K0's rotator table -> float32 [375, 2], row i = (cos, -sin)(2 pi i / 375); output m of a
     stream at carrier fc is multiplied by row ((fc mod 375) (m mod 375)) mod 375 unless 375 divides fc"""
@@ -1135,7 +1171,7 @@ def block_items(items):
 def tx_signals(signals):
     """A list of transmissions -> the uwspr_tx_signal array.  Each is a dict: "text" (or "message": 7 bytes, or
     "symbols": 162), "channel" (0), "start" (baseband sample of the first symbol, 375), "f0" (Hz, 0), "drift" (Hz over the
-    transmission, 0), "phase0" (rad, 0), "gain" (1), and optionally "motion" (tx_motions)."""
+    transmission, 0), "phase0" (rad, 0), "gain" (1), and optionally "motion" (tx_motions) and "carrier" (tx_carriers)."""
     signals = list(signals)
     arr = (N.TxSignal * max(len(signals), 1))()
     for i, s in enumerate(signals):
@@ -1149,6 +1185,21 @@ def tx_signals(signals):
         arr[i].f0_hz, arr[i].drift_hz = float(s.get("f0", 0.0)), float(s.get("drift", 0.0))
         arr[i].phase0, arr[i].gain = float(s.get("phase0", 0.0)), float(s.get("gain", 1.0))
     return arr if signals else (N.TxSignal * 0)()
+
+
+def tx_carriers(signals):
+    """The carrier array (int32, Hz) of a list of transmissions (tx_signals' dicts), or None when none has a "carrier":
+    the calls then go the way they always went.  A signal without the key stays at 1500 Hz."""
+    signals = list(signals)
+    if not any("carrier" in s for s in signals):
+        return None
+    out = np.empty(len(signals), np.int32)
+    for i, s in enumerate(signals):
+        fc = s.get("carrier", 1500)
+        if int(fc) != fc:
+            raise ValueError("carrier: integer Hz, not %r" % (fc,))
+        out[i] = int(fc)
+    return out
 
 
 _TX_MODELS = {"static": N.TX_STATIC, "doppler": N.TX_DOPPLER, "delay": N.TX_DELAY}
@@ -1221,7 +1272,8 @@ def encode_wav(path, schedule, channels=1, snr_db=None, seed=0, gain=1.0, second
     """c2ToWaveFile from text: a 16-bit 12 kS/s WAV of `channels` channels carrying the schedule's transmissions.
     schedule: (text, channel, start_s, f0) entries; start_s is the start of the entry's 2-minute slot (its first symbol
     is 1 s later, as in a .c2 file) and f0 the offset in Hz (the transmission is centred on 1500 + f0 Hz).  An entry may
-    also be a tx_signals dict (a moving source: its "motion"), its gain `gain` unless it names one.  snr_db: AWGN per channel (seed + channel) for that SNR in 2500 Hz, None = none.  The file is rendered
+    also be a tx_signals dict (a moving source: its "motion"; another carrier: its "carrier" in Hz, the transmission then
+    centred on carrier + f0 -- what decode_wav(carriers=[...]) listens to), its gain `gain` unless it names one.  snr_db: AWGN per channel (seed + channel) for that SNR in 2500 Hz, None = none.  The file is rendered
     in pieces of piece_s seconds and lasts `seconds` (default: until the last slot's frame is complete)."""
     import wave
     sig, slots = [], []

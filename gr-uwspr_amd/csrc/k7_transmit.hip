@@ -30,13 +30,25 @@
 // kernels, so static renders run the code they ran before.  R(t_first) is evaluated once per signal ON THE DEVICE
 // (k7_motion_prep), with the hypot the samples use: a zero-velocity trajectory has D = 0 exactly, so k' = k and the
 // phase are the static ones bit for bit.
+//
+// Another carrier, and several at once (<CARRIER = true>; include/uwspr_hip.h states it to the bit).  With n = q + 32 j
+// the mixer at fc factors into e^{-j 2 pi fc q / 12000}, which goes into the taps (g_fc: as many taps whatever fc is),
+// and e^{-j 2 pi fc j / 375}, a rotator on baseband sample j with 375 values -- K0's table, and the identity when 375
+// divides fc.  A channel's signals are grouped by carrier; the workgroup loops over its channel's groups in ascending
+// Hz: render the group's 616 samples (rotated by the lane that makes them), stage that carrier's tap image, run the same
+// FIR loop, and store the chain to the output staging (first group) or add it there (one binary32 add per later group).
+// A chain starts at +0 and never becomes -0, so a group whose signals are all silent adds +0 and changes no byte:
+// the host may drop signals outside a call's window, and pieces still concatenate.  The four <CARRIER = false>
+// instances are the kernels they were; with every carrier at 1500 Hz and the cut-off at 2500 Hz they are what runs.
 #include <math.h>
 #include <stdarg.h>
 #include <stdio.h>
 #include <string.h>
 
 #include <algorithm>
+#include <atomic>
 #include <complex>
+#include <map>
 #include <vector>
 
 #include "uwspr_internal.h"
@@ -73,9 +85,11 @@ struct tx_dsig {
   double wd;            // 2 pi drift / ((N - 1) 375) (rad per sample^2)
   double ph[K7_NSYM];   // phase at the first sample of each symbol, phase0 included
   uint8_t sym[K7_NSYM];
-  uint8_t _pad[6];
+  uint16_t fc;          // the signal's carrier in Hz: a motion's Doppler phase is -2 pi fc D(t) (carved out of the padding)
+  uint8_t _pad[4];
 };
 static_assert(sizeof(tx_dsig) % 8 == 0, "tx_dsig is 8-byte aligned in arrays");
+static_assert(sizeof(tx_dsig) == 16 + 8 * (2 + K7_NSYM) + K7_NSYM + 6, "tx_dsig keeps its size: the carrier lives in the padding");
 
 // A signal's motion as the kernels read it, beside its tx_dsig (same index).  r0 and rref are filled in on the device.
 struct tx_dmot {
@@ -87,7 +101,7 @@ struct tx_dmot {
   int flags;
 };
 static_assert(sizeof(tx_dmot) % 8 == 0, "tx_dmot is 8-byte aligned in arrays");
-constexpr double K7_C = 1500.0, K7_FC = 1500.0;   // sound speed (slm.cc), the chain's carrier
+constexpr double K7_C = 1500.0;   // sound speed (slm.cc)
 
 struct tx_dchan {
   float sigma, bg_gain;
@@ -98,6 +112,19 @@ struct tx_dchan {
   int sig0, nsig;       // the channel's signals: sigs[sig0 .. sig0 + nsig) (sorted by channel, index order kept)
   int _pad;
 };
+
+// The carrier form's tables, one device block in place of the 1500 Hz tap image (so that the kernel's arguments are the
+// other forms'): rot[375] (float2, uwspr_frontend_rotator's table), goff[K7_GOFF] (int: channel c's groups are
+// grps[goff[c] .. goff[c + 1]), ascending carrier), grps[goff[C]], then the call's tap images [NG][32][K7_T] (float2).
+struct tx_dgrp {
+  int fcm;              // carrier mod 375 (0: no rotator)
+  int img;              // the carrier's tap image in the block
+  int sig0, nsig;       // the group's signals: sigs[sig0 .. sig0 + nsig) (sorted by (channel, carrier), index order kept)
+};
+constexpr int K7_NROT = 375;
+constexpr int K7_GOFF = UWSPR_PIPE_MAX_CHANNELS + 2;   // C + 1 offsets, padded to keep what follows 16-byte aligned
+constexpr int K7_MAX_CARRIERS = 64;                    // distinct carriers in one call
+static_assert((K7_NROT * sizeof(float2) + K7_GOFF * sizeof(int)) % 16 == 0 && sizeof(tx_dgrp) == 16, "the block's parts stay aligned");
 
 // ---------------------------------------------------------------- device side
 __device__ __forceinline__ void tx_add(const tx_dsig &s, long long j, float &re, float &im) {
@@ -131,7 +158,7 @@ __device__ __forceinline__ void tx_add_moving(const tx_dsig &s, const tx_dmot &m
   const double r = kp - 256.0 * (double)q;
   const double th = s.ph[q] + r * (K7_TWO_PI * ((double)s.sym[q] - 1.5) / 256.0 + s.wf) +
                     s.wd * (r * ((double)(256 * q) - 0.5 * (K7_NTX - 1)) + 0.5 * r * (r - 1.0)) -
-                    (K7_TWO_PI * K7_FC) * d;
+                    (K7_TWO_PI * (double)s.fc) * d;
   const float g = (m.flags & UWSPR_TX_SPREADING) ? (float)((double)s.gain * (m.r0 / R)) : s.gain;
   double sn, cs;
   sincos(th, &sn, &cs);
@@ -206,30 +233,16 @@ __device__ __forceinline__ void k7_block(float (&acc)[K7_R], const float2 (&A)[8
   }
 }
 
-// Workgroup b renders audio [32 mb, 32 mb + 16384) of channel b mod C, mb = nb0 + 512 (b div C), and writes the
-// samples that fall in [t0, t0 + nframes) to out[(n - t0) C + ch].
-template <bool S16, bool MOVING>
-__global__ __launch_bounds__(K7_WG) void k7_render(const tx_dsig *__restrict__ sigs, const tx_dmot *__restrict__ mots, int nsig,
-                                                   const tx_dchan *__restrict__ chans, int C,
-                                                   const float2 *__restrict__ taps, long long t0, long long nframes,
-                                                   long long nb0, void *__restrict__ out) {
-  extern __shared__ __align__(16) float k7_lds[];
-  float2 *xs = reinterpret_cast<float2 *>(k7_lds);          // [8][K7_G]
-  float2 *tp = xs + K7_NX;                                  // [32][K7_T]
-  float *ys = reinterpret_cast<float *>(tp + K7_DEC * K7_T); // [32][K7_YP]
-  const int ch = (int)(blockIdx.x % (unsigned)C);
-  const long long mb = nb0 + (long long)(blockIdx.x / (unsigned)C) * K7_M;
-  const int tid = threadIdx.x;
-  const tx_dchan cz = chans[ch];
-  const tx_dmot *mz = nullptr;
-  if constexpr (MOVING) mz = mots + cz.sig0;
-  for (int col = tid; col < K7_NX; col += K7_WG)
-    xs[(col & 7) * K7_G + (col >> 3)] = tx_baseband_at<MOVING>(sigs + cz.sig0, mz, cz.nsig, ch, mb - K7_T + col);
-  for (int i = tid; i < K7_DEC * K7_T; i += K7_WG) tp[i] = taps[i];
-  __syncthreads();
+// the rotator's product in K0's one order (k0_rotate): x * r with r = (c, d)
+__device__ __forceinline__ float2 k7_rotate(float2 x, float2 r) {
+  return make_float2(fmaf(x.x, r.x, -(x.y * r.y)), fmaf(x.x, r.y, x.y * r.x));
+}
 
-  // lane l, phase p: steps m = mb + 8 l + r.  Tap block t (taps 8t .. 8t+7) reads columns 8 (l + 12 - t) .. +15,
-  // i.e. groups l + 12 - t (A) and l + 13 - t (B); the next block's B is this block's A.
+// The FIR of one staged window and tap image: lane l, phase p: steps m = mb + 8 l + r.  Tap block t (taps 8t .. 8t+7)
+// reads columns 8 (l + 12 - t) .. +15, i.e. groups l + 12 - t (A) and l + 13 - t (B); the next block's B is this
+// block's A.  ADD: the chain is added to what ys holds (a later carrier group), one binary32 add.
+template <bool ADD>
+__device__ __forceinline__ void k7_fir(const float2 *xs, const float2 *tp, float *ys, int tid) {
   const int w = tid >> 6, l = tid & 63;
   for (int h = 0; h < 2; h++) {
     const int p = 2 * w + h;
@@ -250,7 +263,91 @@ __global__ __launch_bounds__(K7_WG) void k7_render(const tx_dsig *__restrict__ s
       k7_block(acc, A, B, g + 8 * t + 8);
     }
 #pragma unroll
-    for (int r = 0; r < K7_R; r++) ys[p * K7_YP + 8 * l + r] = acc[r];
+    for (int r = 0; r < K7_R; r++) {
+      if constexpr (ADD) ys[p * K7_YP + 8 * l + r] = ys[p * K7_YP + 8 * l + r] + acc[r];
+      else ys[p * K7_YP + 8 * l + r] = acc[r];
+    }
+  }
+}
+
+// Workgroup b renders audio [32 mb, 32 mb + 16384) of channel b mod C, mb = nb0 + 512 (b div C), and writes the
+// samples that fall in [t0, t0 + nframes) to out[(n - t0) C + ch].
+// CARRIER: `taps` is the carrier form's block (tx_dgrp above) and the workgroup walks its channel's carrier groups.  Between
+// two groups every wavefront must be done reading the window and the taps before they are staged again (the barrier at
+// the loop's head); a thread adds into the ys words it stored itself, so ys needs none until the epilogue.
+template <bool S16, bool MOVING, bool CARRIER = false>
+__global__ __launch_bounds__(K7_WG) void k7_render(const tx_dsig *__restrict__ sigs, const tx_dmot *__restrict__ mots, int nsig,
+                                                   const tx_dchan *__restrict__ chans, int C,
+                                                   const float2 *__restrict__ taps, long long t0, long long nframes,
+                                                   long long nb0, void *__restrict__ out) {
+  extern __shared__ __align__(16) float k7_lds[];
+  float2 *xs = reinterpret_cast<float2 *>(k7_lds);          // [8][K7_G]
+  float2 *tp = xs + K7_NX;                                  // [32][K7_T]
+  float *ys = reinterpret_cast<float *>(tp + K7_DEC * K7_T); // [32][K7_YP]
+  const int ch = (int)(blockIdx.x % (unsigned)C);
+  const long long mb = nb0 + (long long)(blockIdx.x / (unsigned)C) * K7_M;
+  const int tid = threadIdx.x;
+  const tx_dchan cz = chans[ch];
+  if constexpr (CARRIER) {
+    const float2 *rot = taps;
+    const int *goff = reinterpret_cast<const int *>(rot + K7_NROT);
+    const tx_dgrp *grps = reinterpret_cast<const tx_dgrp *>(goff + K7_GOFF);
+    const float2 *images = reinterpret_cast<const float2 *>(grps + goff[C]);
+    const int g0 = goff[ch], g1 = goff[ch + 1];              // (the same for the whole workgroup: the barriers below are uniform)
+    if (g0 == g1)                                            // no signal: the +0 a chain over silence gives
+      for (int e = tid; e < K7_DEC * K7_YP; e += K7_WG) ys[e] = 0.0f;
+    for (int g = g0; g < g1; g++) {
+      if (g > g0) __syncthreads();
+      const tx_dgrp gr = grps[g];
+      const tx_dmot *mz = nullptr;
+      if constexpr (MOVING) mz = mots + gr.sig0;
+      for (int col = tid; col < K7_NX; col += K7_WG) {
+        const long long j = mb - K7_T + col;
+        float2 x = tx_baseband_at<MOVING>(sigs + gr.sig0, mz, gr.nsig, ch, j);
+        if (gr.fcm) {
+          int jm = (int)(j % K7_NROT);
+          if (jm < 0) jm += K7_NROT;                         // j mod 375 in 0 .. 374 for negative j as well
+          x = k7_rotate(x, rot[(gr.fcm * jm) % K7_NROT]);
+        }
+        xs[(col & 7) * K7_G + (col >> 3)] = x;
+      }
+      const float2 *img = images + (size_t)gr.img * (K7_DEC * K7_T);
+      for (int i = tid; i < K7_DEC * K7_T; i += K7_WG) tp[i] = img[i];
+      __syncthreads();
+      if (g == g0) k7_fir<false>(xs, tp, ys, tid);
+      else k7_fir<true>(xs, tp, ys, tid);
+    }
+  } else {
+    const tx_dmot *mz = nullptr;
+    if constexpr (MOVING) mz = mots + cz.sig0;
+    for (int col = tid; col < K7_NX; col += K7_WG)
+      xs[(col & 7) * K7_G + (col >> 3)] = tx_baseband_at<MOVING>(sigs + cz.sig0, mz, cz.nsig, ch, mb - K7_T + col);
+    for (int i = tid; i < K7_DEC * K7_T; i += K7_WG) tp[i] = taps[i];
+    __syncthreads();
+
+    // (k7_fir<false>'s loop, kept in the kernel's own text: these four instances are the code they were)
+    const int w = tid >> 6, l = tid & 63;
+    for (int h = 0; h < 2; h++) {
+      const int p = 2 * w + h;
+      const float2 *g = tp + p * K7_T;
+      float acc[K7_R];
+#pragma unroll
+      for (int r = 0; r < K7_R; r++) acc[r] = 0.0f;
+      float2 A[8], B[8];
+#pragma unroll
+      for (int v = 0; v < 8; v++) { B[v] = xs[v * K7_G + l + 13]; A[v] = xs[v * K7_G + l + 12]; }
+      k7_block(acc, A, B, g);
+      for (int t = 1; t < K7_T / 8; t += 2) {    // two blocks per trip: the window's halves swap roles, no copies
+#pragma unroll
+        for (int v = 0; v < 8; v++) B[v] = xs[v * K7_G + l + 12 - t];
+        k7_block(acc, B, A, g + 8 * t);
+#pragma unroll
+        for (int v = 0; v < 8; v++) A[v] = xs[v * K7_G + l + 11 - t];
+        k7_block(acc, A, B, g + 8 * t + 8);
+      }
+#pragma unroll
+      for (int r = 0; r < K7_R; r++) ys[p * K7_YP + 8 * l + r] = acc[r];
+    }
   }
   __syncthreads();
 
@@ -291,12 +388,16 @@ struct tx_state {
   tx_dchan *d_chan = nullptr;
   void *d_out = nullptr; size_t cap_out = 0;    // host-output staging (bytes)
   void *d_bg = nullptr; size_t cap_bg = 0;      // host backgrounds staged (bytes)
+  // the carrier form (nothing here is made until it first runs)
+  void *d_car = nullptr; size_t cap_car = 0;    // the call's block: rotator, group table, tap images (tx_dgrp)
+  bool car_ready = false;                       // the carrier instances were given their LDS
+  std::map<std::pair<int, int>, std::vector<float2>> images;   // (carrier, cut-off) -> tap image
 };
 
 void tx_release(uwspr_ctx *c) {
   if (!c || !c->tx) return;
   tx_state *t = c->tx;
-  void *bufs[] = {t->d_taps, t->d_sig, t->d_mot, t->d_chan, t->d_out, t->d_bg};
+  void *bufs[] = {t->d_taps, t->d_sig, t->d_mot, t->d_chan, t->d_out, t->d_bg, t->d_car};
   for (void *b : bufs) if (b) (void)hipFree(b);
   delete t;
   c->tx = nullptr;
@@ -336,18 +437,32 @@ static std::complex<double> tx_octant(long k) {   // e^{+j k pi / 4}, exact octa
   return std::complex<double>(cs[q], sn[q]);
 }
 
-// g[q] = e^{-j pi q/4} sum_k h2r[k] h1[q - k], h2r = the rotated taps as freq_xlating_fir_filter holds them (binary32
-// pairs); designed in binary64
-static std::vector<std::complex<double>> tx_composite() {
-  const std::vector<float> h1 = lowpass_hamming(12000.0, 200.0, 10.0);     // 2891 taps
-  const std::vector<float> h2 = lowpass_hamming(12000.0, 2500.0, 100.0);   // 289 taps
+// e^{+j 2 pi fc k / 12000} for an integer carrier and k >= 0: fc k is reduced mod 12000 in integers first, and an angle
+// that is a multiple of pi/4 (every k at 1500 Hz) takes the exact octant values
+static std::complex<double> tx_mixer(int fc, long k) {
+  const long r = ((long)(fc % 12000) * (k % 12000)) % 12000;
+  if (r % 1500 == 0) return tx_octant(r / 1500);
+  const double a = K7_TWO_PI * (double)r / 12000.0;
+  return std::complex<double>(cos(a), sin(a));
+}
+
+static bool tx_carrier_ok(int fc, int cutoff) {
+  return cutoff >= 500 && cutoff <= 5900 && fc >= 170 && fc <= cutoff - 250;
+}
+
+// g_fc[q] = e^{-j 2 pi fc q / 12000} sum_k h2r[k] h1[q - k], h2r[k] = h2[k] e^{+j 2 pi fc k / 12000} = the rotated taps
+// as freq_xlating_fir_filter holds them (binary32 pairs), h2 = low_pass(1, 12000, cutoff, 100); designed in binary64.
+// (1500, 2500): the mixer is tx_octant at every k, the composite it always was.
+static std::vector<std::complex<double>> tx_composite(int fc = UWSPR_CARRIER_DEFAULT, int cutoff = UWSPR_TX_CUTOFF_DEFAULT) {
+  const std::vector<float> h1 = lowpass_hamming(12000.0, 200.0, 10.0);             // 2891 taps
+  const std::vector<float> h2 = lowpass_hamming(12000.0, (double)cutoff, 100.0);   // 289 taps
   std::vector<std::complex<double>> g(h1.size() + h2.size() - 1, std::complex<double>(0, 0));
   for (size_t k = 0; k < h2.size(); k++) {
-    const std::complex<double> z = (double)h2[k] * tx_octant((long)k);
+    const std::complex<double> z = (double)h2[k] * tx_mixer(fc, (long)k);
     const std::complex<double> zr((double)(float)z.real(), (double)(float)z.imag());
     for (size_t i = 0; i < h1.size(); i++) g[k + i] += zr * (double)h1[i];
   }
-  for (size_t q = 0; q < g.size(); q++) g[q] *= std::conj(tx_octant((long)q));
+  for (size_t q = 0; q < g.size(); q++) g[q] *= std::conj(tx_mixer(fc, (long)q));
   return g;
 }
 
@@ -458,12 +573,26 @@ static int tx_motion_check(uwspr_ctx *c, int i, const uwspr_tx_motion &m, long l
 
 // check the records (channel < C when C > 0; motions, when given) and build the device form of those that pass
 // keep(s, lo, hi) ([start + lo, start + hi): where the signal may be non-zero)
+// car: a carrier per signal in Hz, or null (1500 for all).  Every entry is checked against the context's "tx_cutoff",
+// the signals the window drops included; *other (when given) tells whether some signal's carrier is not 1500 Hz.
 template <typename Keep>
-static int tx_prepare(uwspr_ctx *c, const uwspr_tx_signal *sig, const uwspr_tx_motion *mot, int nsig, int C, Keep keep,
-                      std::vector<tx_dsig> &out, std::vector<tx_dmot> *mout) {
+static int tx_prepare(uwspr_ctx *c, const uwspr_tx_signal *sig, const uwspr_tx_motion *mot, const int32_t *car, int nsig, int C,
+                      Keep keep, std::vector<tx_dsig> &out, std::vector<tx_dmot> *mout, bool *other = nullptr) {
   if (nsig < 0 || (nsig > 0 && !sig)) return tx_fail(c, UWSPR_ERR_ARG, "uwspr_tx: signals %p, nsig %d", (const void *)sig, nsig);
   out.clear();
   if (mout) mout->clear();
+  if (other) *other = false;
+  const int cutoff = c->opt[UWSPR_OPT_TX_CUTOFF];
+  std::vector<int> distinct;
+  for (int i = 0; i < nsig; i++) {
+    const int fc = car ? car[i] : UWSPR_CARRIER_DEFAULT;
+    if (!tx_carrier_ok(fc, cutoff))
+      return tx_fail(c, UWSPR_ERR_ARG, "uwspr_tx: signal %d carrier %d Hz (170 .. tx_cutoff - 250 = %d)", i, fc, cutoff - 250);
+    if (fc != UWSPR_CARRIER_DEFAULT && other) *other = true;
+    if (std::find(distinct.begin(), distinct.end(), fc) == distinct.end()) distinct.push_back(fc);
+  }
+  if ((int)distinct.size() > K7_MAX_CARRIERS)
+    return tx_fail(c, UWSPR_ERR_ARG, "uwspr_tx: %zu distinct carriers (<= %d)", distinct.size(), K7_MAX_CARRIERS);
   for (int i = 0; i < nsig; i++) {
     const uwspr_tx_signal &s = sig[i];
     for (int k = 0; k < K7_NSYM; k++)
@@ -491,7 +620,8 @@ static int tx_prepare(uwspr_ctx *c, const uwspr_tx_signal *sig, const uwspr_tx_m
     tx_dsig d;
     memset(&d, 0, sizeof(d));
     d.start = s.start; d.channel = s.channel; d.gain = s.gain;
-    d.wf = K7_TWO_PI * s.f0_hz / K7_FS;
+    d.fc = (uint16_t)(car ? car[i] : UWSPR_CARRIER_DEFAULT);
+    d.wf =K7_TWO_PI * s.f0_hz / K7_FS;
     d.wd = K7_TWO_PI * s.drift_hz / ((double)(K7_NTX - 1) * K7_FS);
     double ph = s.phase0;
     for (int q = 0; q < K7_NSYM; q++) {
@@ -532,18 +662,77 @@ static int tx_upload_motions(uwspr_ctx *c, const std::vector<tx_dmot> &m) {
   return UWSPR_OK;
 }
 
+static std::atomic<long long> k7_carrier_launches[2];   // launches of the carrier form since the process started (f32, s16)
+
+// The carrier form's block (tx_dgrp) for signals sorted by (channel, carrier): the rotator table, the groups of every
+// channel, and one tap image per distinct carrier of the call (designed once per (carrier, cut-off) and context).  The
+// first use also gives the four carrier instances their LDS.
+static int tx_carrier_block(uwspr_ctx *c, const std::vector<tx_dsig> &v, int C, int cutoff, std::vector<char> &block) {
+  tx_state *t = c->tx;
+  if (!t->car_ready) {
+    if (hipFuncSetAttribute(reinterpret_cast<const void *>(k7_render<false, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)k7_lds_bytes()) != hipSuccess ||
+        hipFuncSetAttribute(reinterpret_cast<const void *>(k7_render<true, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)k7_lds_bytes()) != hipSuccess ||
+        hipFuncSetAttribute(reinterpret_cast<const void *>(k7_render<false, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)k7_lds_bytes()) != hipSuccess ||
+        hipFuncSetAttribute(reinterpret_cast<const void *>(k7_render<true, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)k7_lds_bytes()) != hipSuccess)
+      return tx_fail(c, UWSPR_ERR_HIP, "transmit kernel (carrier form): %zu bytes of LDS refused", k7_lds_bytes());
+    t->car_ready = true;
+  }
+  std::vector<int> fcs;                       // the call's distinct carriers, ascending: image index = position
+  for (const tx_dsig &s : v) fcs.push_back((int)s.fc);
+  std::sort(fcs.begin(), fcs.end());
+  fcs.erase(std::unique(fcs.begin(), fcs.end()), fcs.end());
+  if ((int)fcs.size() > K7_MAX_CARRIERS) return tx_fail(c, UWSPR_ERR_ARG, "uwspr_tx: %zu distinct carriers (<= %d)", fcs.size(), K7_MAX_CARRIERS);
+  std::vector<int> goff(K7_GOFF, 0);
+  std::vector<tx_dgrp> grps;
+  size_t i = 0;
+  for (int ch = 0; ch < C; ch++) {
+    goff[ch] = (int)grps.size();
+    while (i < v.size() && v[i].channel == ch) {
+      size_t e = i;
+      while (e < v.size() && v[e].channel == ch && v[e].fc == v[i].fc) e++;
+      tx_dgrp g;
+      g.fcm = (int)v[i].fc % K7_NROT;
+      g.img = (int)(std::lower_bound(fcs.begin(), fcs.end(), (int)v[i].fc) - fcs.begin());
+      g.sig0 = (int)i; g.nsig = (int)(e - i);
+      grps.push_back(g);
+      i = e;
+    }
+  }
+  for (int ch = C; ch < K7_GOFF; ch++) goff[ch] = (int)grps.size();
+  if (i != v.size()) return tx_fail(c, UWSPR_ERR_HIP, "uwspr_tx: carrier groups cover %zu of %zu signals", i, v.size());
+  const size_t img_bytes = (size_t)K7_DEC * K7_T * sizeof(float2);
+  const size_t at_goff = K7_NROT * sizeof(float2), at_grps = at_goff + K7_GOFF * sizeof(int);
+  const size_t at_img = at_grps + grps.size() * sizeof(tx_dgrp);
+  block.assign(at_img + fcs.size() * img_bytes, 0);
+  frontend_rotator(reinterpret_cast<float *>(block.data()));
+  memcpy(block.data() + at_goff, goff.data(), K7_GOFF * sizeof(int));
+  if (!grps.empty()) memcpy(block.data() + at_grps, grps.data(), grps.size() * sizeof(tx_dgrp));
+  for (size_t k = 0; k < fcs.size(); k++) {
+    const std::pair<int, int> key(fcs[k], cutoff);
+    auto it = t->images.find(key);
+    if (it == t->images.end()) {
+      if (t->images.size() >= 1024) t->images.clear();   // (a sweep over carriers does not grow the cache without bound)
+      const std::vector<std::complex<double>> g = tx_composite(fcs[k], cutoff);
+      if ((int)g.size() != K7_NT) return tx_fail(c, UWSPR_ERR_HIP, "transmit taps at %d Hz, cut-off %d Hz: %zu, expected %d", fcs[k], cutoff, g.size(), K7_NT);
+      it = t->images.emplace(key, tx_tap_image(g)).first;
+    }
+    memcpy(block.data() + at_img + k * img_bytes, it->second.data(), img_bytes);
+  }
+  return UWSPR_OK;
+}
+
 }  // namespace uwspr
 
 using namespace uwspr;
 
-static int tx_baseband(uwspr_ctx *c, const uwspr_tx_signal *sig, const uwspr_tx_motion *mot, int nsig, int channel,
-                       long long t0, int n, float *iq, int where) {
+static int tx_baseband(uwspr_ctx *c, const uwspr_tx_signal *sig, const uwspr_tx_motion *mot, const int32_t *car, int nsig,
+                       int channel, long long t0, int n, float *iq, int where) {
   if (!c) return UWSPR_ERR_ARG;
   if (n < 0 || (n > 0 && !iq) || channel < 0 || (where != UWSPR_HOST && where != UWSPR_DEVICE))
     return tx_fail(c, UWSPR_ERR_ARG, "uwspr_tx_baseband: n %d, iq %p, channel %d, where %d", n, (void *)iq, channel, where);
   std::vector<tx_dsig> v;
   std::vector<tx_dmot> mv;
-  int rc = tx_prepare(c, sig, mot, nsig, 0, [&](const uwspr_tx_signal &s, long long lo, long long hi) {
+  int rc = tx_prepare(c, sig, mot, car, nsig, 0, [&](const uwspr_tx_signal &s, long long lo, long long hi) {
     return s.channel == channel && s.start + lo < t0 + n && s.start + hi > t0;
   }, v, mot ? &mv : nullptr);
   if (rc) return rc;
@@ -575,7 +764,7 @@ static int tx_baseband(uwspr_ctx *c, const uwspr_tx_signal *sig, const uwspr_tx_
   return UWSPR_OK;
 }
 
-static int tx_render(uwspr_ctx *c, const uwspr_tx_signal *sig, const uwspr_tx_motion *mot, int nsig,
+static int tx_render(uwspr_ctx *c, const uwspr_tx_signal *sig, const uwspr_tx_motion *mot, const int32_t *car, int nsig,
                      const uwspr_tx_channel *chan, int C, long long t0, long long nframes, int format, void *out, int where) {
   if (!c) return UWSPR_ERR_ARG;
   if (C < 1 || C > UWSPR_PIPE_MAX_CHANNELS || !chan || t0 < 0 || nframes < 0 || (nframes > 0 && !out) ||
@@ -594,11 +783,15 @@ static int tx_render(uwspr_ctx *c, const uwspr_tx_signal *sig, const uwspr_tx_mo
   // unless delayed (the others add exact zeros)
   std::vector<tx_dsig> v;
   std::vector<tx_dmot> mv;
-  int rc = tx_prepare(c, sig, mot, nsig, C, [&](const uwspr_tx_signal &s, long long lo, long long hi) {
+  bool other = false;
+  int rc = tx_prepare(c, sig, mot, car, nsig, C, [&](const uwspr_tx_signal &s, long long lo, long long hi) {
     return K7_DEC * (s.start + lo) < t0 + nframes && K7_DEC * (s.start + hi - 1) + K7_NT - 1 >= t0;
-  }, v, mot ? &mv : nullptr);
+  }, v, mot ? &mv : nullptr, &other);
   if (rc) return rc;
   if (nframes == 0) return UWSPR_OK;
+  // the carrier form: asked for by a carrier, by the cut-off or by "tx_form"; otherwise the 1500 Hz kernels, as ever
+  const int cutoff = c->opt[UWSPR_OPT_TX_CUTOFF];
+  const bool carrier = other || cutoff != UWSPR_TX_CUTOFF_DEFAULT || c->opt[UWSPR_OPT_TX_FORM] != 0;
   const size_t esz = format == UWSPR_AUDIO_S16 ? 2 : 4;
   if ((rc = tx_device_ready(c))) return rc;
   if (where == UWSPR_DEVICE) {   // device pointers must be device memory: a host pointer would fault the kernel
@@ -611,18 +804,21 @@ static int tx_render(uwspr_ctx *c, const uwspr_tx_signal *sig, const uwspr_tx_mo
                        chan[k].background, (long long)chan[k].background_len);
   }
   // the kernel walks only its channel's signals: sorted by channel, ascending index within one (the order they add up in)
-  // (a motion moves with its signal)
+  // (a motion moves with its signal); the carrier form: by (channel, carrier), index order kept inside a group
   const bool moving = tx_any_moving(mv);
+  const auto before = [carrier](const tx_dsig &a, const tx_dsig &b) {
+    return a.channel != b.channel ? a.channel < b.channel : (carrier && a.fc < b.fc);
+  };
   if (moving) {
     std::vector<int> ix(v.size());
     for (size_t i = 0; i < ix.size(); i++) ix[i] = (int)i;
-    std::stable_sort(ix.begin(), ix.end(), [&](int a, int b) { return v[a].channel < v[b].channel; });
+    std::stable_sort(ix.begin(), ix.end(), [&](int a, int b) { return before(v[a], v[b]); });
     std::vector<tx_dsig> vs(v.size());
     std::vector<tx_dmot> ms(v.size());
     for (size_t i = 0; i < ix.size(); i++) { vs[i] = v[ix[i]]; ms[i] = mv[ix[i]]; }
     v.swap(vs); mv.swap(ms);
   } else {
-    std::stable_sort(v.begin(), v.end(), [](const tx_dsig &a, const tx_dsig &b) { return a.channel < b.channel; });
+    std::stable_sort(v.begin(), v.end(), before);
   }
   if ((rc = tx_begin(c))) return rc;
   tx_state *t = c->tx;
@@ -657,6 +853,12 @@ static int tx_render(uwspr_ctx *c, const uwspr_tx_signal *sig, const uwspr_tx_mo
   }
   if (!t->d_chan) TXCHK(c, hipMalloc((void **)&t->d_chan, UWSPR_PIPE_MAX_CHANNELS * sizeof(tx_dchan)));
   TXCHK(c, hipMemcpyAsync(t->d_chan, dc.data(), C * sizeof(tx_dchan), hipMemcpyHostToDevice, c->stream));
+  std::vector<char> block;
+  if (carrier) {
+    if ((rc = tx_carrier_block(c, v, C, cutoff, block))) return rc;
+    if ((rc = tx_grow(c, &t->d_car, &t->cap_car, block.size()))) return rc;
+    TXCHK(c, hipMemcpyAsync(t->d_car, block.data(), block.size(), hipMemcpyHostToDevice, c->stream));
+  }
   TXCHK(c, hipStreamSynchronize(c->stream));   // (the records above live on this call's stack)
 
   // device output: one launch; host output: pieces of at most 2^24 samples through a staging buffer (the render of any
@@ -671,7 +873,22 @@ static int tx_render(uwspr_ctx *c, const uwspr_tx_signal *sig, const uwspr_tx_mo
     void *dst = where == UWSPR_HOST ? t->d_out : (void *)((char *)out + (size_t)k * C * esz);
     const dim3 grid((unsigned)(nblk * C));
     const tx_dmot *dm = moving ? t->d_mot : nullptr;
-    if (format == UWSPR_AUDIO_S16 && moving)
+    if (carrier) {
+      const float2 *blk = static_cast<const float2 *>(t->d_car);
+      if (format == UWSPR_AUDIO_S16 && moving)
+        hipLaunchKernelGGL((k7_render<true, true, true>), grid, dim3(K7_WG), k7_lds_bytes(), c->stream, t->d_sig, dm, (int)v.size(),
+                           t->d_chan, C, blk, a, len, nb0, dst);
+      else if (format == UWSPR_AUDIO_S16)
+        hipLaunchKernelGGL((k7_render<true, false, true>), grid, dim3(K7_WG), k7_lds_bytes(), c->stream, t->d_sig, dm, (int)v.size(),
+                           t->d_chan, C, blk, a, len, nb0, dst);
+      else if (moving)
+        hipLaunchKernelGGL((k7_render<false, true, true>), grid, dim3(K7_WG), k7_lds_bytes(), c->stream, t->d_sig, dm, (int)v.size(),
+                           t->d_chan, C, blk, a, len, nb0, dst);
+      else
+        hipLaunchKernelGGL((k7_render<false, false, true>), grid, dim3(K7_WG), k7_lds_bytes(), c->stream, t->d_sig, dm, (int)v.size(),
+                           t->d_chan, C, blk, a, len, nb0, dst);
+      k7_carrier_launches[format == UWSPR_AUDIO_S16 ? 1 : 0]++;
+    } else if (format == UWSPR_AUDIO_S16 && moving)
       hipLaunchKernelGGL((k7_render<true, true>), grid, dim3(K7_WG), k7_lds_bytes(), c->stream, t->d_sig, dm, (int)v.size(),
                          t->d_chan, C, t->d_taps, a, len, nb0, dst);
     else if (format == UWSPR_AUDIO_S16)
@@ -708,21 +925,53 @@ extern "C" int uwspr_debug_tx_taps(double *g, float *image) {
 
 extern "C" int uwspr_tx_baseband(uwspr_ctx *c, const uwspr_tx_signal *sig, int nsig, int channel, long long t0, int n,
                                  float *iq, int where) {
-  return tx_baseband(c, sig, nullptr, nsig, channel, t0, n, iq, where);
+  return tx_baseband(c, sig, nullptr, nullptr, nsig, channel, t0, n, iq, where);
 }
 
 extern "C" int uwspr_tx_baseband_moving(uwspr_ctx *c, const uwspr_tx_signal *sig, const uwspr_tx_motion *motion, int nsig,
                                         int channel, long long t0, int n, float *iq, int where) {
-  return tx_baseband(c, sig, motion, nsig, channel, t0, n, iq, where);
+  return tx_baseband(c, sig, motion, nullptr, nsig, channel, t0, n, iq, where);
 }
 
 extern "C" int uwspr_tx_render(uwspr_ctx *c, const uwspr_tx_signal *sig, int nsig, const uwspr_tx_channel *chan, int C,
                                long long t0, long long nframes, int format, void *out, int where) {
-  return tx_render(c, sig, nullptr, nsig, chan, C, t0, nframes, format, out, where);
+  return tx_render(c, sig, nullptr, nullptr, nsig, chan, C, t0, nframes, format, out, where);
 }
 
 extern "C" int uwspr_tx_render_moving(uwspr_ctx *c, const uwspr_tx_signal *sig, const uwspr_tx_motion *motion, int nsig,
                                       const uwspr_tx_channel *chan, int C, long long t0, long long nframes, int format,
                                       void *out, int where) {
-  return tx_render(c, sig, motion, nsig, chan, C, t0, nframes, format, out, where);
+  return tx_render(c, sig, motion, nullptr, nsig, chan, C, t0, nframes, format, out, where);
+}
+
+extern "C" int uwspr_tx_baseband_at(uwspr_ctx *c, const uwspr_tx_signal *sig, const uwspr_tx_motion *motion,
+                                    const int32_t *carrier_hz, int nsig, int channel, long long t0, int n, float *iq, int where) {
+  return tx_baseband(c, sig, motion, carrier_hz, nsig, channel, t0, n, iq, where);
+}
+
+extern "C" int uwspr_tx_render_at(uwspr_ctx *c, const uwspr_tx_signal *sig, const uwspr_tx_motion *motion, const int32_t *carrier_hz,
+                                  int nsig, const uwspr_tx_channel *chan, int C, long long t0, long long nframes, int format,
+                                  void *out, int where) {
+  return tx_render(c, sig, motion, carrier_hz, nsig, chan, C, t0, nframes, format, out, where);
+}
+
+extern "C" int uwspr_tx_design_at(int carrier_hz, int cutoff_hz, double *g, float *image) {
+  if (!tx_carrier_ok(carrier_hz, cutoff_hz)) return UWSPR_ERR_ARG;
+  const std::vector<std::complex<double>> t = tx_composite(carrier_hz, cutoff_hz);
+  if ((int)t.size() != K7_NT) return UWSPR_ERR_ARG;   // (the callers' buffers hold 3179)
+  if (g)
+    for (size_t q = 0; q < t.size(); q++) { g[2 * q] = t[q].real(); g[2 * q + 1] = t[q].imag(); }
+  if (image) {
+    const std::vector<float2> img = tx_tap_image(t);
+    memcpy(image, img.data(), img.size() * sizeof(float2));
+  }
+  return (int)t.size();
+}
+
+// Test door (not part of the ABI): launches of K7's carrier form since the process started: out[0] float32 output,
+// out[1] int16 output
+extern "C" int uwspr_debug_tx_carrier_counts(long long *out) {
+  if (!out) return UWSPR_ERR_ARG;
+  out[0] = k7_carrier_launches[0].load(); out[1] = k7_carrier_launches[1].load();
+  return 2;
 }

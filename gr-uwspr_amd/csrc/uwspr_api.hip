@@ -109,6 +109,8 @@ static const struct { const char *name; int dflt, lo, hi; } kOptions[UWSPR_NOPT]
     {"blank_guard", 2, 0, 64},      // K12: samples zeroed either side of a flagged one
     {"carrier", UWSPR_CARRIER_DEFAULT, 20, 5980},        // K0: the centre in Hz (the flowgraph's Center_Frequency); with frontend_hbw: hb + 20 .. 6000 - hb - 20
     {"frontend_hbw", UWSPR_FRONTEND_HBW_DEFAULT, 1, 150},   // K0, grc mode: the half-bandwidth in Hz (the flowgraph's Half_Bandwidth)
+    {"tx_cutoff", UWSPR_TX_CUTOFF_DEFAULT, 500, 5900},   // K7: the cut-off of the chain's second low-pass in Hz; a signal's carrier: 170 .. tx_cutoff - 250
+    {"tx_form", 0, 0, 1},           // K7: 0 the carrier form where a carrier != 1500 or tx_cutoff != 2500 asks for it, 1 always (the same bytes)
 };
 
 static void refresh_options(uwspr_ctx *c) {

@@ -32,6 +32,8 @@ enum {
   UWSPR_OPT_BLANK_GUARD,        // K12's guard G: samples zeroed either side of a flagged one (default 2)
   UWSPR_OPT_CARRIER,            // K0's centre in Hz (default 1500), the flowgraph's Center_Frequency
   UWSPR_OPT_FRONTEND_HBW,       // K0's half-bandwidth in Hz (default 10; grc mode), the flowgraph's Half_Bandwidth
+  UWSPR_OPT_TX_CUTOFF,          // K7: cut-off of the transmit chain's second low-pass in Hz (default 2500)
+  UWSPR_OPT_TX_FORM,            // K7: 0 (default) the carrier form only where a carrier or the cut-off asks for it, 1 always
   UWSPR_NOPT
 };
 

@@ -273,7 +273,8 @@ ABI_SYMBOLS = [
     "uwspr_fano_decode", "uwspr_fano_encode", "uwspr_decode_candidate", "uwspr_host_threads", "uwspr_host_set_ranks", "uwspr_decode_batch", "uwspr_unpack_message",
     "uwspr_c2_read",
     "uwspr_wspr_pack", "uwspr_nhash", "uwspr_wspr_symbols", "uwspr_c2_write", "uwspr_tx_baseband", "uwspr_tx_render",
-    "uwspr_tx_baseband_moving", "uwspr_tx_render_moving", "uwspr_subtract_batch", "uwspr_osd_batch", "uwspr_blockdemod_batch",
+    "uwspr_tx_baseband_moving", "uwspr_tx_render_moving", "uwspr_tx_baseband_at", "uwspr_tx_render_at", "uwspr_tx_design_at",
+    "uwspr_subtract_batch", "uwspr_osd_batch", "uwspr_blockdemod_batch",
     "uwspr_dist_unique_id", "uwspr_dist_init", "uwspr_dist_gather", "uwspr_dist_finalize",
     "uwspr_pipe_open", "uwspr_pipe_close", "uwspr_pipe_last_error", "uwspr_pipe_acquire", "uwspr_pipe_commit",
     "uwspr_pipe_push", "uwspr_pipe_push_audio", "uwspr_pipe_push_audio_channels", "uwspr_pipe_submit_device", "uwspr_pipe_flush", "uwspr_pipe_collect", "uwspr_pipe_get_stats",
@@ -378,6 +379,9 @@ def lib():
     L.uwspr_tx_render.argtypes = [vp, vp, ip, vp, ip, C.c_longlong, C.c_longlong, ip, vp, ip]
     L.uwspr_tx_baseband_moving.argtypes = [vp, vp, vp, ip, ip, C.c_longlong, ip, vp, ip]
     L.uwspr_tx_render_moving.argtypes = [vp, vp, vp, ip, vp, ip, C.c_longlong, C.c_longlong, ip, vp, ip]
+    L.uwspr_tx_baseband_at.argtypes = [vp, vp, vp, vp, ip, ip, C.c_longlong, ip, vp, ip]
+    L.uwspr_tx_render_at.argtypes = [vp, vp, vp, vp, ip, vp, ip, C.c_longlong, C.c_longlong, ip, vp, ip]
+    L.uwspr_tx_design_at.argtypes = [ip, ip, vp, vp]
     L.uwspr_subtract_batch.argtypes = [vp, vp, ip, ip, vp, ip, ip, vp, vp]
     L.uwspr_osd_batch.argtypes = [vp, vp, ip, ip, ip, vp]
     L.uwspr_blockdemod_batch.argtypes = [vp, vp, ip, ip, vp, ip, vp]

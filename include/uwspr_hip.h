@@ -48,7 +48,9 @@ extern "C" {
                                     audio at other rates: uwspr_resample_design, uwspr_resample_batch, the option
                                     "audio_rate" of contexts and pipes;
                                     impulsive noise: uwspr_blank_batch, uwspr_stream_blank_stats, uwspr_pipe_blank_stats,
-                                    the options "blank" and "blank_guard" of contexts and pipes */
+                                    the options "blank" and "blank_guard" of contexts and pipes;
+                                    transmit at any carrier: uwspr_tx_render_at, uwspr_tx_baseband_at, uwspr_tx_design_at,
+                                    the options "tx_cutoff" and "tx_form" */
 
 typedef enum {
   UWSPR_OK = 0,
@@ -201,7 +203,7 @@ int uwspr_synchronize(uwspr_ctx *ctx);
  * when fc mod 375 == 0 no product is made and y is s's bytes, NaN and inf included.
  * Both options are latched by a stream's first audio push like "frontend" (a change while it runs is UWSPR_ERR_ARG and
  * leaves the stream as it was); uwspr_frontend_batch reads them at every call.  With (1500, 10) nothing new runs or is
- * allocated.  Not built: transmit (K7) stays at 1500 Hz, carriers are integer Hz, and uwspr_params.cf (the SLM Doppler
+ * allocated.  The transmitter follows ("Transmit at another carrier" below).  Not built: carriers are integer Hz, and uwspr_params.cf (the SLM Doppler
  * scale) stays the caller's: one per context or pipe, to be set to the carrier when there is one carrier.
  * uwspr_frontend_design_at: uwspr_frontend_design at (centre_hz, half_bw_hz). */
 enum { UWSPR_FRONTEND_GRC = 0, UWSPR_FRONTEND_COMPACT = 1 };
@@ -808,8 +810,8 @@ int uwspr_tx_render(uwspr_ctx *ctx, const uwspr_tx_signal *sig, int nsig, const 
                     long long t0, long long nframes, int format, void *out, int where);
 
 /* A moving source: the straight-line model (SLM) of the receiver's nonlinear search (lib/slm.cc).  The hydrophone is
- * at the origin and the source at q(t) = (v1 t + p1, v2 t + p2) metres, R(t) = |q(t)|, c = 1500 m/s, fc = 1500 Hz (the
- * chain's carrier).  Baseband index start + k of a transmission has trajectory time t = t_first + k / 375 s.  With
+ * at the origin and the source at q(t) = (v1 t + p1, v2 t + p2) metres, R(t) = |q(t)|, c = 1500 m/s, fc = the signal's
+ * carrier (1500 Hz unless uwspr_tx_render_at / uwspr_tx_baseband_at name another: each signal's Doppler phase uses its own).  Baseband index start + k of a transmission has trajectory time t = t_first + k / 375 s.  With
  * theta the static phase above (uwspr_tx_baseband's orientation, gain e^{+j theta}) and D(t) = (R(t) - R(t_first)) / c,
  * or R(t) / c with UWSPR_TX_ABSOLUTE:
  *   UWSPR_TX_STATIC   the signal as uwspr_tx_baseband makes it (the motion is ignored);
@@ -845,6 +847,49 @@ int uwspr_tx_baseband_moving(uwspr_ctx *ctx, const uwspr_tx_signal *sig, const u
 int uwspr_tx_render_moving(uwspr_ctx *ctx, const uwspr_tx_signal *sig, const uwspr_tx_motion *motion, int nsig,
                            const uwspr_tx_channel *chan, int C, long long t0, long long nframes, int format, void *out,
                            int where);
+
+/* Transmit at another carrier, and at several at once (K7's carrier form; the transpose of K0's).  carrier_hz is NULL
+ * (1500 Hz for every signal) or has nsig entries, integer Hz; motion is NULL or has nsig entries.  The option "tx_cutoff"
+ * (integer Hz, default 2500, 500 .. 5900) is the cut-off of the flowgraph's second low-pass.  Allowed carriers:
+ * 170 <= fc <= tx_cutoff - 250 (the rotated filter is a band-pass around -fc that must pass the baseband at 0 Hz: with
+ * |f0| <= 150 Hz and the 100 Hz transition centred on the cut-off the signal stays fc + 250 below it); anything else, in
+ * any entry -- one whose signal the window drops included --, or more than 64 distinct carriers in one call, is
+ * UWSPR_ERR_ARG before any launch.
+ * The flowgraph's chain is zero-stuff x32, h1 = low_pass(1, 12000, 200, 10), freq_xlating_fir_filter holding
+ * h2 = low_pass(1, 12000, tx_cutoff, 100) rotated to fc, the mixer at fc, the real part.  With audio index n = q + 32 j
+ * the mixer factors, e^{-j 2 pi fc n / 12000} = e^{-j 2 pi fc q / 12000} e^{-j 2 pi fc j / 375}: the first factor goes
+ * into the taps, the second is a rotator on baseband sample j with 375 values, the identity when 375 divides fc.
+ * Taps (uwspr_tx_design_at: g [3179] (re, im) pairs in binary64, image [32][104] (Re g, -Im g) binary32 pairs, tap p + 32 i
+ * at [p][i], +0 behind the last; either may be NULL; host only; returns 3179, or UWSPR_ERR_ARG outside the ranges above):
+ *   g_fc[q] = e^{-j 2 pi fc q / 12000} sum_k h2r[k] h1[q - k],
+ *   h2r[k]  = h2[k] e^{+j 2 pi fc k / 12000} rounded to binary32 pairs as freq_xlating_fir_filter holds them,
+ * designed in binary64; fc k and fc q are reduced mod 12000 in integers before any cos / sin, and a multiple of pi/4 takes
+ * the exact octant values, so (1500, 2500) gives the tap image it always gave, byte for byte.  3179 taps whatever fc and
+ * the cut-off are (2891 + 289 - 1: the transition widths alone set the counts).
+ * Channel c's audio sample n:
+ *   1. the channel's kept signals are grouped by carrier, the distinct carriers ascending in Hz: f_1 < ... < f_G;
+ *   2. x_f[j] = the sum of group f's signals in ascending signal index, as the .c2 file holds the baseband (the
+ *      conjugate of uwspr_tx_baseband's), formed exactly as the 1500 Hz render forms its one sum;
+ *   3. the rotator: if 375 divides f, xr_f is x_f's bytes; otherwise, with (c, d) = rot[((f mod 375)(j mod 375)) mod 375],
+ *      j mod 375 in 0 .. 374 for negative j as well and rot the table of uwspr_frontend_rotator,
+ *        xr.re = fmaf(x.re, c, -(x.im d)),   xr.im = fmaf(x.re, d, x.im c)      -- K0's one order;
+ *   4. chain_f[n] = the 1500 Hz render's one chain of 208 fused multiply-adds from +0 (tap index ascending, real before
+ *      imaginary) over g_f's image and xr_f;
+ *   5. a = chain_{f_1}[n], then a = fl32(a + chain_{f_g}[n]) for g = 2 .. G;
+ *   6. noise, background and quantiser as in uwspr_tx_render.
+ * A chain starts at +0 and cannot become -0, so a group whose signals are all silent adds +0 and changes no byte: renders
+ * of any pieces concatenate to the bytes of one render also where a carrier's signals begin or end partway.
+ * The carrier form runs when some signal's carrier is not 1500, or "tx_cutoff" is not 2500, or the option "tx_form" is 1
+ * (0, the default: only then); with everything at the defaults the 1500 Hz kernels run, nothing new is allocated and every
+ * byte is what it was; "tx_form" = 1 gives those same bytes through the carrier form.  The four calls above are these with
+ * carrier_hz NULL.  uwspr_tx_baseband_at's output is not rotated: there the carrier only scales a motion's Doppler. */
+#define UWSPR_TX_CUTOFF_DEFAULT 2500
+int uwspr_tx_render_at(uwspr_ctx *ctx, const uwspr_tx_signal *sig, const uwspr_tx_motion *motion, const int32_t *carrier_hz,
+                       int nsig, const uwspr_tx_channel *chan, int C, long long t0, long long nframes, int format, void *out,
+                       int where);
+int uwspr_tx_baseband_at(uwspr_ctx *ctx, const uwspr_tx_signal *sig, const uwspr_tx_motion *motion, const int32_t *carrier_hz,
+                         int nsig, int channel, long long t0, int n, float *iq, int where);
+int uwspr_tx_design_at(int carrier_hz, int cutoff_hz, double *g, float *image);
 
 /* ---- known-symbol subtraction (K8, k8_subtract.hip) --------------------------------------------------------------- */
 /* A decoded transmission is rebuilt from its 162 channel symbols, fitted to the samples and taken out of them, so that a
