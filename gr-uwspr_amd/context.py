@@ -724,6 +724,34 @@ class Context:
                                          C.c_void_p(res.ctypes.data) if len(a) else None))
         return res
 
+    # -- list search (K13: uwspr_deep_set_list, uwspr_deep_batch) -------------
+    def deep_set_list(self, known):
+        """The list of expected messages: WSPR texts (packed with wspr_pack) or an [M, 7] int8 array of packed messages;
+        empty clears it.  Distinct 50-bit messages, at most native.DEEP_MAX (include/uwspr_hip.h states the rules)."""
+        m = deep_list(known)
+        self._chk(self.L.uwspr_deep_set_list(self.h, C.c_void_p(m.ctypes.data) if len(m) else None, len(m)))
+
+    def deep(self, symbols):
+        """Soft-symbol vectors as uwspr_demod_out.symbols[idt] holds them -- [n, 162] uint8, a numpy array or a torch CUDA
+        tensor (read in place) -- scored against every codeword of the list.  -> a DEEP_RESULT_DTYPE array: best (index
+        in the list), sbest, snext per vector (include/uwspr_hip.h states the definition)."""
+        R = N.DEEP_RESULT_DTYPE
+        if _is_torch(symbols):
+            import torch
+            assert symbols.is_cuda and symbols.is_contiguous() and symbols.dtype == torch.uint8
+            n = symbols.numel() // N.NSYM
+            out = torch.zeros(max(n, 1) * R.itemsize, dtype=torch.uint8, device=symbols.device)
+            if self._stream_ptr is None:
+                torch.cuda.current_stream(symbols.device).synchronize()
+            self._chk(self.L.uwspr_deep_batch(self.h, C.c_void_p(symbols.data_ptr()), n, N.DEVICE, C.c_void_p(out.data_ptr())))
+            self.synchronize()
+            return out.cpu().numpy()[:n * R.itemsize].view(R).copy()
+        a = np.ascontiguousarray(symbols, dtype=np.uint8).reshape(-1, N.NSYM)
+        res = np.zeros(len(a), R)
+        self._chk(self.L.uwspr_deep_batch(self.h, C.c_void_p(a.ctypes.data) if len(a) else None, len(a), N.HOST,
+                                          C.c_void_p(res.ctypes.data) if len(a) else None))
+        return res
+
     # -- block demodulation (K10: uwspr_blockdemod_batch) ---------------------
     def blockdemod(self, frames, items):
         """Soft symbols coherent over 1, 2 and 3 symbols.  items: a BLOCK_ITEM_DTYPE array, or dicts with "frame", "shift",
@@ -1115,6 +1143,18 @@ def wspr_pack(text):
     return m
 
 
+def deep_list(known):
+    """texts (wspr_pack) or packed messages -> a contiguous [M, 7] int8 array (M = 0: an empty list)"""
+    if known is None or len(known) == 0:
+        return np.zeros((0, 7), np.int8)
+    if isinstance(known, np.ndarray):
+        if known.dtype != np.int8 or known.ndim != 2 or known.shape[1] != 7:
+            raise TypeError("a list of messages: texts or an [M, 7] int8 array, not %s %s" % (known.dtype, known.shape))
+        return np.ascontiguousarray(known)
+    return np.ascontiguousarray(np.stack([wspr_pack(t) if isinstance(t, str) else
+                                          np.ascontiguousarray(t, dtype=np.int8).reshape(7) for t in known]))
+
+
 def nhash(key, initval=146):
     """lookup3 hashlittle() of a byte string (the type 3 callsign hash is nhash(call) & 32767)"""
     k = key.encode() if isinstance(key, str) else bytes(key)
@@ -1314,7 +1354,8 @@ class Pipe:
     def __init__(self, fs=375, fl=45000, spb=256, maxdrift=0, maxfreqs=200, halfbandwidth=10, cf=1500,
                  threshold=10, device=0, hop=3375, batch_frames=256, max_per_frame=1, lanes=0,
                  host_threads=0, eager=False, sched=None, spare_after_us=0, passes=1, osd=0, osd_gap=None,
-                 block=0, audio_rate=None, blank=0, blank_guard=None, carriers=None, frontend_hbw=None):
+                 block=0, audio_rate=None, blank=0, blank_guard=None, carriers=None, frontend_hbw=None, known=None,
+                 deep_min=None, deep_gap=None):
         self.L = N.lib()
         self.carriers = [1500]
         self.h = C.c_void_p()
@@ -1349,6 +1390,12 @@ class Pipe:
                 self.set_carriers(carriers)
             if frontend_hbw is not None:
                 self.set_option("frontend_hbw", frontend_hbw)
+            if known is not None and len(known):   # the list of expected messages: K13 on what Fano timed out on (records with osd = 2)
+                self.set_list(known)
+            if deep_min is not None:
+                self.set_option("deep_min", deep_min)
+            if deep_gap is not None:
+                self.set_option("deep_gap", deep_gap)
         except N.UwsprError:
             self.close()
             raise
@@ -1424,6 +1471,12 @@ class Pipe:
         """uwspr_pipe_set_option: an option of every lane's context; only while nothing is in flight"""
         self._chk(self.L.uwspr_pipe_set_option(self.h, name.encode(), int(value)))
 
+    def set_list(self, known):
+        """uwspr_pipe_set_list: the list of expected messages (texts or an [M, 7] int8 array; empty: the stage is off);
+        only while nothing is in flight"""
+        m = deep_list(known)
+        self._chk(self.L.uwspr_pipe_set_list(self.h, C.c_void_p(m.ctypes.data) if len(m) else None, len(m)))
+
     def set_carriers(self, hz):
         """uwspr_pipe_set_carriers: K0's centres in Hz (distinct integers, order kept), before the first audio push.  With
         more than one, a record's "channel" field is the plane index: split_plane gives (channel, carrier)."""
@@ -1493,7 +1546,8 @@ def decode_wav(path, channels=None, **pipe_opts):
     Pipe's push_audio -> one dict per decoded record, in frame order: frame, t (stream_pos / 375 s), the coarse freq
     and snr, the unpacked text, "pass" (1: found by the second pass of passes=2, under a decoded signal; else 0) and
     "osd" (1: Fano timed out and ordered-statistics decoding gave the message, osd=1 or 2; else 0) and "block" (2, 3: Fano
-    timed out and the soft symbols coherent over that many symbols decoded, block=2 or 3; else 0).
+    timed out and the soft symbols coherent over that many symbols decoded, block=2 or 3; else 0) and "deep" (1: Fano timed
+    out and the list search gave the message, known=[texts or packed messages]; else 0).
     channels="all": every channel of the file through one pipe, records in (take, channel, frame) order, each dict with
     its "channel".  carriers=[Hz, ..]: every channel is heard at each of them (Pipe(carriers=..)), records in (take,
     channel, carrier, frame) order, each dict with its "carrier" in Hz ("channel" stays the audio channel)."""
@@ -1514,8 +1568,8 @@ def decode_wav(path, channels=None, **pipe_opts):
             continue
         d = {"frame": int(r["frame"]), "t": int(r["stream_pos"]) / 375.0,
              "freq": float(r["coarse"]["freq"]), "snr": float(r["coarse"]["snr"]),
-             "text": unpack_message(r["message"])[1], "pass": int(r["pass"]), "osd": int(r["osd"]),
-             "block": int(r["block"])}
+             "text": unpack_message(r["message"])[1], "pass": int(r["pass"]), "osd": int(r["osd"] == 1),
+             "block": int(r["block"]), "deep": int(r["osd"] == 2)}
         ch, car = pipe.split_plane(r["channel"])
         if channels == "all":
             d["channel"] = ch

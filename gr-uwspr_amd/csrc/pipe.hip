@@ -72,6 +72,10 @@ struct pipe_lane {
   std::vector<int> osd_rec, osd_idt;         // item -> record, try
   std::vector<unsigned long long> osd_off;   // item -> byte offset of its symbols in d_out
   std::vector<uwspr_osd_result> osd_res;
+  // list search (uwspr_pipe_set_list): the same records, one K13 item each (osdf = 2: decoded by it)
+  std::vector<int> deep_rec, deep_idt;
+  std::vector<unsigned long long> deep_off;
+  std::vector<uwspr_deep_result> deep_res;
   // block demodulation (option "block"): the same records, one K10 item each
   std::vector<uint8_t> blkf;                 // [B*per] 2, 3: decoded from the soft symbols of that block length
   std::vector<int> blk_rec, blk_idt;         // item -> record, try
@@ -99,6 +103,11 @@ struct uwspr_pipe {
   int device = 0, fl = 0, maxfreqs = 0, per = 1;
   int passes = 1;   // uwspr_pipe_set_option("passes"): 2 = subtract what decoded and search the residual again
   int osd = 0, osd_gap = UWSPR_OSD_GAP_DEFAULT;   // uwspr_pipe_set_option("osd" / "osd_gap"): K9 on what Fano timed out on
+  // uwspr_pipe_set_list / uwspr_pipe_set_option("deep_min" / "deep_gap"): K13 on those records against the list; one device
+  // table for all lanes (made and freed by set_list, read-only in between), the list's bytes on the host
+  int deep_M = 0, deep_min = UWSPR_DEEP_MIN_DEFAULT, deep_gap = UWSPR_DEEP_GAP_DEFAULT;
+  int8_t *d_deep_tab = nullptr;
+  std::vector<int8_t> deep_msgs;
   int block = 0;    // uwspr_pipe_set_option("block"): 2, 3 = K10's soft symbols of block lengths 2 .. block for those records
   int audio_rate = 12000;   // uwspr_pipe_set_option("audio_rate"): the rate of the pushed audio (12000: no resampler, else K11 ahead of K0)
   int blank = 0, blank_guard = 2;   // uwspr_pipe_set_option("blank" / "blank_guard"): K12 ahead of K11 / K0 (blank 0: off)
@@ -175,6 +184,7 @@ static int parg(uwspr_pipe *q, const char *fmt, ...) {
 // waits for the lane's event, runs Fano on what the GPU produced, resumes what try 0 did not decode.  Leaves L.dec /
 // L.idt / L.msg for the B * per records of L.h_out.
 static int osd_tail(uwspr_pipe *q, pipe_lane &L, int nrec, tail_acc &ta);
+static int deep_tail(uwspr_pipe *q, pipe_lane &L, int nrec, tail_acc &ta);
 static int block_tail(uwspr_pipe *q, pipe_lane &L, const float *frames, int nrec, tail_acc &ta);
 
 static int host_tail(uwspr_pipe *q, pipe_lane &L, const float *frames, int B, bool first, tail_acc &ta) {
@@ -268,11 +278,13 @@ static int host_tail(uwspr_pipe *q, pipe_lane &L, const float *frames, int B, bo
   memset(L.blkf.data(), 0, (size_t)nrec);
   if (q->block > 0)
     if (const int rc = block_tail(q, L, frames, nrec, ta)) return rc;
+  if (q->deep_M > 0)
+    if (const int rc = deep_tail(q, L, nrec, ta)) return rc;
   if (q->osd > 0) return osd_tail(q, L, nrec, ta);
   return UWSPR_OK;
 }
 
-// The item rule of the options "block" and "osd": record i is an item when it was worth a try, no try decoded and at least
+// The item rule of the options "block" and "osd" and of the list search: record i is an item when it was worth a try, no try decoded and at least
 // one try passed the gates of cc:470; its try is the gated one with the largest jig_sync, the first one on ties (-1: no item).
 static int fallback_try(const uwspr_pipe *q, const pipe_lane &L, int i) {
   const float minsync2 = 0.12f, minrms = (float)(52.0 * (50 / 64.0));   // the gates of decode_try (host_tail.cpp)
@@ -314,6 +326,39 @@ static int osd_tail(uwspr_pipe *q, pipe_lane &L, int nrec, tail_acc &ta) {
     const int i = L.osd_rec[k];
     L.dec[i] = 1; L.idt[i] = L.osd_idt[k]; L.osdf[i] = 1;
     memcpy(&L.msg[7 * (size_t)i], r.message, 7);
+  }
+  ta.resume_s += now_s() - t0;
+  return UWSPR_OK;
+}
+
+// The list search (uwspr_pipe_set_list).  The items are osd_tail's (fallback_try), their symbols read in place likewise; K13
+// scores each against the pipe's table.  An item with sbest >= deep_min and (M == 1 or sbest - snext >= deep_gap) makes its
+// record a decoded one with the list's bytes (no unpacking: the list is the user's word).  Its time counts as resume time.
+static int deep_tail(uwspr_pipe *q, pipe_lane &L, int nrec, tail_acc &ta) {
+  L.deep_rec.clear(); L.deep_idt.clear(); L.deep_off.clear();
+  for (int i = 0; i < nrec; i++) {
+    const int pick = fallback_try(q, L, i);
+    if (pick < 0) continue;
+    L.deep_rec.push_back(i); L.deep_idt.push_back(pick);
+    L.deep_off.push_back((unsigned long long)((const char *)&L.d_out[i].symbols[pick][0] - (const char *)L.d_out));
+  }
+  const int n = (int)L.deep_rec.size();
+  if (n == 0) return UWSPR_OK;
+  const double t0 = now_s();
+  uwspr_deep_result *d_res = nullptr;
+  const int rc = deep_run(L.ctx, q->d_deep_tab, q->deep_M, (const uint8_t *)L.d_out, L.deep_off.data(), n, nullptr, &d_res);
+  if (rc) return pfail(q, rc, "list search: %s", uwspr_last_error(L.ctx));
+  L.deep_res.resize((size_t)n);
+  PHIP(q, hipMemcpyAsync(L.deep_res.data(), d_res, (size_t)n * sizeof(uwspr_deep_result), hipMemcpyDeviceToHost, L.stream));
+  PHIP(q, hipEventRecord(L.ev_done, L.stream));
+  PHIP(q, hipEventSynchronize(L.ev_done));
+  for (int k = 0; k < n; k++) {
+    const uwspr_deep_result &r = L.deep_res[k];
+    if (r.best < 0 || r.best >= q->deep_M || r.sbest < q->deep_min) continue;
+    if (q->deep_M > 1 && (long long)r.sbest - (long long)r.snext < (long long)q->deep_gap) continue;
+    const int i = L.deep_rec[k];
+    L.dec[i] = 1; L.idt[i] = L.deep_idt[k]; L.osdf[i] = 2;
+    memcpy(&L.msg[7 * (size_t)i], &q->deep_msgs[7 * (size_t)r.best], 7);
   }
   ta.resume_s += now_s() - t0;
   return UWSPR_OK;
@@ -687,6 +732,7 @@ extern "C" void uwspr_pipe_close(uwspr_pipe *q) {
     if (L.ev_done) (void)hipEventDestroy(L.ev_done);
     if (L.ctx) uwspr_ctx_destroy(L.ctx);
   }
+  if (q->d_deep_tab) (void)hipFree(q->d_deep_tab);
   q->ring.close();
   for (int k = 0; k < uwspr_pipe::NSTAGE; k++) {
     if (q->h_stage[k]) (void)hipHostFree(q->h_stage[k]);
@@ -969,6 +1015,15 @@ extern "C" int uwspr_pipe_set_option(uwspr_pipe *q, const char *name, int value)
     (gap ? q->osd_gap : q->osd) = value;
     return UWSPR_OK;
   }
+  if (!strcmp(name, "deep_min") || !strcmp(name, "deep_gap")) {   // the pipe's own: the list search's acceptance thresholds
+    const bool gap = name[5] == 'g';
+    if (value < 0) return parg(q, "uwspr_pipe_set_option: \"%s\" is >= 0, not %d", name, value);
+    std::lock_guard<std::mutex> lk(q->m);
+    for (auto &L : q->lanes)
+      if (L.busy) { snprintf(q->err, sizeof(q->err), "uwspr_pipe_set_option(%s): batches in flight (flush first)", name); return UWSPR_ERR_ARG; }
+    (gap ? q->deep_gap : q->deep_min) = value;
+    return UWSPR_OK;
+  }
   if (!strcmp(name, "audio_rate")) {   // the pipe's own: the rate of the audio its pushes carry, latched by the first push
     resample_plan pl;
     if (resample_design(value, pl)) return parg(q, "uwspr_pipe_set_option: \"audio_rate\" = %d is not a supported rate", value);
@@ -1018,6 +1073,39 @@ extern "C" int uwspr_pipe_set_option(uwspr_pipe *q, const char *name, int value)
       return UWSPR_ERR_ARG;
     }
   }
+  return UWSPR_OK;
+}
+
+// The list of expected messages: checked, its table built on the host and uploaded before anything of the pipe changes;
+// one table for all lanes (the lanes' contexts live on the pipe's device and only read it).
+extern "C" int uwspr_pipe_set_list(uwspr_pipe *q, const int8_t *messages7, int M) {
+  if (!q) return UWSPR_ERR_ARG;
+  if (M != 0) {
+    char why[160];
+    if (deep_check_list(messages7, M, why, sizeof(why))) return parg(q, "uwspr_pipe_set_list: %s", why);
+  }
+  if (const int f = q->failed.load()) return f;
+  int8_t *d_new = nullptr;
+  if (M > 0) {
+    std::vector<int8_t> tab;
+    if (deep_build_table(messages7, M, tab)) return parg(q, "uwspr_pipe_set_list: symbols of a message");
+    (void)hipSetDevice(q->device);
+    if (hipMalloc((void **)&d_new, tab.size()) != hipSuccess) { (void)hipGetLastError(); return pfail(q, UWSPR_ERR_NOMEM, "uwspr_pipe_set_list: %zu bytes for the table", tab.size()); }
+    const hipError_t e = hipMemcpy(d_new, tab.data(), tab.size(), hipMemcpyHostToDevice);
+    if (e != hipSuccess) { (void)hipFree(d_new); return pfail(q, UWSPR_ERR_HIP, "uwspr_pipe_set_list: upload of the table: %s", hipGetErrorString(e)); }
+  }
+  std::lock_guard<std::mutex> lk(q->m);
+  for (auto &L : q->lanes)
+    if (L.busy) {
+      if (d_new) (void)hipFree(d_new);
+      snprintf(q->err, sizeof(q->err), "uwspr_pipe_set_list: batches in flight (flush first)");
+      return UWSPR_ERR_ARG;
+    }
+  if (q->d_deep_tab) (void)hipFree(q->d_deep_tab);   // (nothing in flight: no lane reads it)
+  q->d_deep_tab = d_new;
+  q->deep_M = M;
+  if (M > 0) q->deep_msgs.assign(messages7, messages7 + 7 * (size_t)M);
+  else std::vector<int8_t>().swap(q->deep_msgs);
   return UWSPR_OK;
 }
 

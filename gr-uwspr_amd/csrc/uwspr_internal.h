@@ -180,6 +180,8 @@ struct rs_state;
 void rs_release(uwspr_ctx *c);   // k11_resample.hip: frees what uwspr_resample_batch made
 struct bk_state;
 void bk_release(uwspr_ctx *c);   // k12_blank.hip: frees what uwspr_blank_batch made
+struct deep_state;
+void deep_release(uwspr_ctx *c); // k13_deep.hip: frees what uwspr_deep_set_list / uwspr_deep_batch made
 
 }  // namespace uwspr
 
@@ -284,6 +286,8 @@ struct uwspr_ctx {
   uwspr::rs_state *rs;
   // blanker (k12_blank.hip): the batch call's staging and tables, made by the first use
   uwspr::bk_state *bk;
+  // list search (k13_deep.hip): the list's table and call scratch, made by uwspr_deep_set_list / the first use
+  uwspr::deep_state *deep;
 
   int prof_mask;
   std::vector<uwspr::ev_pair> prof_events;
@@ -306,6 +310,16 @@ int subtract_run(uwspr_ctx *c, const float *src, size_t stride, int nslots, cons
 // handed back through *res_out.  order 0..2 (the caller checks it).
 int osd_run(uwspr_ctx *c, const uint8_t *base, const unsigned long long *off, int n, int order, uwspr_osd_result *res,
             uwspr_osd_result **res_out);
+
+// K13 (k13_deep.hip): n > 0 items on the context's stream against a table of M messages in the kernel's operand layout
+// (d_tab: device memory made from deep_build_table; null = the list of uwspr_deep_set_list), item i = the 162 interleaved
+// soft symbols at base + off[i] (off: host array, null = 162 i; base: device memory); results to res (device memory), or
+// with res null to a buffer of the context handed back through *res_out.  deep_check_list: null when the list keeps the
+// rules at uwspr_deep_set_list, else what is wrong (written into msg).
+int deep_run(uwspr_ctx *c, const int8_t *d_tab, int M, const uint8_t *base, const unsigned long long *off, int n,
+             uwspr_deep_result *res, uwspr_deep_result **res_out);
+const char *deep_check_list(const int8_t *messages7, int M, char *msg, size_t cap);
+int deep_build_table(const int8_t *messages7, int M, std::vector<int8_t> &tab);
 
 // K10 (k10_blockdemod.hip): nitems > 0 items (host records that passed blockdemod_check against the frames of src: sorted by
 // frame, frames in [0, nframes), finite f / drift, bounded shift) on the context's stream; src: device frames, frame b at

@@ -26,7 +26,7 @@ LIBPATH = os.path.join(LIBDIR, "libuwspr_hip_exp_%s.so" % _EXTRA_TAG if _EXTRA e
 HOSTLIB = os.path.join(LIBDIR, "libuwspr_blocks.so")
 
 SOURCES = ["uwspr_api.hip", "k0_frontend.hip", "k1_spectrogram.hip", "k2_spectrum.hip", "k3_coarse.hip",
-           "k4_tonecorr.hip", "k4_grid.hip", "k4_pair.hip", "k4_jig.hip", "k5_fold_schedule.hip", "k6_sched.hip", "k7_transmit.hip", "k8_subtract.hip", "k9_osd.hip", "k10_blockdemod.hip", "k11_resample.hip", "k12_blank.hip", "pipe.hip", "dist.hip", "host_tail.cpp"]
+           "k4_tonecorr.hip", "k4_grid.hip", "k4_pair.hip", "k4_jig.hip", "k5_fold_schedule.hip", "k6_sched.hip", "k7_transmit.hip", "k8_subtract.hip", "k9_osd.hip", "k10_blockdemod.hip", "k11_resample.hip", "k12_blank.hip", "k13_deep.hip", "pipe.hip", "dist.hip", "host_tail.cpp"]
 HIPFLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off",
             "-fno-slp-vectorize", "-fhip-fp32-correctly-rounded-divide-sqrt", "-fPIC", "-Wall", "-Wno-unused-function"]
 
@@ -216,6 +216,9 @@ assert OSD_RESULT_DTYPE.itemsize == 20
 BLOCK_ITEM_DTYPE = np.dtype([("frame", "<i4"), ("shift", "<i4"), ("f_hz", "<f4"), ("drift_hz", "<f4")])
 assert BLOCK_ITEM_DTYPE.itemsize == 16
 OSD_GAP_DEFAULT = 485   # UWSPR_OSD_GAP_DEFAULT
+DEEP_RESULT_DTYPE = np.dtype([("best", "<i4"), ("sbest", "<i4"), ("snext", "<i4"), ("reserved", "<i4")])
+assert DEEP_RESULT_DTYPE.itemsize == 16
+DEEP_MAX, DEEP_MIN_DEFAULT, DEEP_GAP_DEFAULT = 65536, 4373, 1145   # UWSPR_DEEP_MAX, UWSPR_DEEP_MIN_DEFAULT, UWSPR_DEEP_GAP_DEFAULT
 PIPE_MAX_CHANNELS = 64
 
 
@@ -274,11 +277,11 @@ ABI_SYMBOLS = [
     "uwspr_c2_read",
     "uwspr_wspr_pack", "uwspr_nhash", "uwspr_wspr_symbols", "uwspr_c2_write", "uwspr_tx_baseband", "uwspr_tx_render",
     "uwspr_tx_baseband_moving", "uwspr_tx_render_moving", "uwspr_tx_baseband_at", "uwspr_tx_render_at", "uwspr_tx_design_at",
-    "uwspr_subtract_batch", "uwspr_osd_batch", "uwspr_blockdemod_batch",
+    "uwspr_subtract_batch", "uwspr_osd_batch", "uwspr_blockdemod_batch", "uwspr_deep_set_list", "uwspr_deep_batch",
     "uwspr_dist_unique_id", "uwspr_dist_init", "uwspr_dist_gather", "uwspr_dist_finalize",
     "uwspr_pipe_open", "uwspr_pipe_close", "uwspr_pipe_last_error", "uwspr_pipe_acquire", "uwspr_pipe_commit",
     "uwspr_pipe_push", "uwspr_pipe_push_audio", "uwspr_pipe_push_audio_channels", "uwspr_pipe_submit_device", "uwspr_pipe_flush", "uwspr_pipe_collect", "uwspr_pipe_get_stats",
-    "uwspr_pipe_inject_failure", "uwspr_pipe_set_option", "uwspr_pipe_set_carriers",
+    "uwspr_pipe_inject_failure", "uwspr_pipe_set_option", "uwspr_pipe_set_carriers", "uwspr_pipe_set_list",
 ]
 
 _lib = None
@@ -385,6 +388,8 @@ def lib():
     L.uwspr_subtract_batch.argtypes = [vp, vp, ip, ip, vp, ip, ip, vp, vp]
     L.uwspr_osd_batch.argtypes = [vp, vp, ip, ip, ip, vp]
     L.uwspr_blockdemod_batch.argtypes = [vp, vp, ip, ip, vp, ip, vp]
+    L.uwspr_deep_set_list.argtypes = [vp, vp, ip]
+    L.uwspr_deep_batch.argtypes = [vp, vp, ip, ip, vp]
     L.uwspr_dist_unique_id.argtypes = [vp]
     L.uwspr_dist_init.argtypes = [vp, ip, ip, vp]
     L.uwspr_dist_gather.argtypes = [vp, vp, C.c_size_t, vp, ip, ip]
@@ -406,5 +411,6 @@ def lib():
     L.uwspr_pipe_inject_failure.argtypes = [vp, C.c_longlong, ip]
     L.uwspr_pipe_set_option.argtypes = [vp, C.c_char_p, ip]
     L.uwspr_pipe_set_carriers.argtypes = [vp, vp, ip]
+    L.uwspr_pipe_set_list.argtypes = [vp, vp, ip]
     _lib = L
     return L

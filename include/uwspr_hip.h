@@ -50,7 +50,9 @@ extern "C" {
                                     impulsive noise: uwspr_blank_batch, uwspr_stream_blank_stats, uwspr_pipe_blank_stats,
                                     the options "blank" and "blank_guard" of contexts and pipes;
                                     transmit at any carrier: uwspr_tx_render_at, uwspr_tx_baseband_at, uwspr_tx_design_at,
-                                    the options "tx_cutoff" and "tx_form" */
+                                    the options "tx_cutoff" and "tx_form";
+                                    list search: uwspr_deep_result, uwspr_deep_set_list, uwspr_deep_batch,
+                                    uwspr_pipe_set_list, the pipe options "deep_min" and "deep_gap", uwspr_decode.osd = 2 */
 
 typedef enum {
   UWSPR_OK = 0,
@@ -569,7 +571,8 @@ typedef struct uwspr_decode {
   int16_t channel;        /* the audio channel of a multichannel pipe (uwspr_pipe_push_audio_channels); 0 otherwise.  With n > 1
                              carriers (uwspr_pipe_set_carriers): the plane index channel * n + carrier index */
   uint8_t pass;           /* 1: found by the second pass (option "passes" = 2), in the frame with its decoded signals taken out; 0 otherwise */
-  uint8_t osd;            /* 1: Fano timed out on every gated try and ordered-statistics decoding gave the message (option "osd"); 0 otherwise */
+  uint8_t osd;            /* 1: ordered-statistics decoding, 2: list search -- Fano timed out on every gated try and K9 (option "osd") or
+                             K13 (uwspr_pipe_set_list) gave the message; 0 otherwise */
 } uwspr_decode;
 typedef struct uwspr_pipe_stats {
   int64_t frames, batches, candidates, decoded, resumed;   /* resumed: records whose other tries were produced */
@@ -677,8 +680,24 @@ int uwspr_pipe_blank_stats(uwspr_pipe *pipe, long long *samples, long long *zero
  * whose bytes uwspr_unpack_message accepts turns the record into a decoded one: decoded = 1, idt = that try, message set,
  * block = n.  It is an ordinary decoded record from there on (counted, subtracted by "passes" = 2, no item of "osd").
  * These calls count in fano_calls / fano_timeouts, their time in resume_s.  With "block" = 0 every byte and statistic is
- * what it is without the option. */
+ * what it is without the option.
+ * "deep_min" and "deep_gap" (both >= 0; defaults UWSPR_DEEP_MIN_DEFAULT and UWSPR_DEEP_GAP_DEFAULT) are the pipe's own: the
+ * acceptance thresholds of the list search, see uwspr_pipe_set_list. */
 int uwspr_pipe_set_option(uwspr_pipe *pipe, const char *name, int value);
+/* The list of expected messages (the rules of uwspr_deep_set_list below; host memory, copied): with a list set, K13
+ * (uwspr_deep_batch below) runs on the batch's lane behind its host tail, resumed tries included, after "block" and before
+ * "osd" -- and behind the second pass's host tail with "passes" = 2 -- on the records those two take: one item per record
+ * with worth_a_try that decoded on no try and has a gated try (cc:470), the gated try with the largest jig_sync (the first
+ * one on ties), its symbols read where they lie in the lane's device records.  An item with sbest >= "deep_min" and (M == 1
+ * or sbest - snext >= "deep_gap") turns the record into a decoded one: decoded = 1, idt = that try, message = the list's
+ * bytes of `best`, osd = 2.  uwspr_unpack_message is not asked: the list is the user's word.  It is an ordinary decoded
+ * record from there on (counted in the stats' decoded, subtracted by "passes" = 2, no item of "osd").  Its time counts in
+ * resume_s.  Only while nothing is in flight (UWSPR_ERR_ARG otherwise, as for uwspr_pipe_set_option); a list that breaks
+ * the rules is UWSPR_ERR_ARG and the list in force stays.  M = 0 turns the stage off and frees the table: every byte and
+ * statistic is then what it is without a list, and nothing of K13 runs or is allocated.
+ * Device memory: ONE table per pipe, read by every lane, 192 bytes per message rounded up to 16 messages (M = 65536:
+ * 12.6 MB), plus per lane that ran it 16 bytes per item and message chunk (at most 1024 chunks per 16 items). */
+int uwspr_pipe_set_list(uwspr_pipe *pipe, const int8_t *messages7 /*[M][7]*/, int M);
 /* Error behaviour.  An argument error (too many samples, a bad B or stride) fails THAT call with UWSPR_ERR_ARG and
  * its message; the pipe goes on.  A runtime failure (HIP, a lane's context) is sticky: the batch it hit emits
  * nothing, records of the batches before it stay collectable, every later call -- and uwspr_pipe_collect once
@@ -1000,6 +1019,37 @@ typedef struct uwspr_block_item {
 } uwspr_block_item;
 int uwspr_blockdemod_batch(uwspr_ctx *ctx, const float *frames, int B, int where, const uwspr_block_item *items, int nitems,
                            uint8_t *symbols /*[nitems][3][162]*/);
+
+/* ---- list search (K13, k13_deep.hip) --------------------------------------------------------------------------------- */
+/* Maximum-likelihood decoding over a list of expected messages (a deployment's callsign / locator / power texts): the 162
+ * soft symbols of a try scored against every codeword of the list.  The reference has no counterpart (WSJT's "deep search"
+ * against its callsign database); all integers, so host, device and the test's restatement (tests/deep_exact.py) give the
+ * same bytes.
+ * The list: M messages of 7 bytes each, as uwspr_wspr_pack makes them; 1 <= M <= UWSPR_DEEP_MAX, the low 6 bits of byte 6
+ * zero, no two messages equal.  Anything else is UWSPR_ERR_ARG and nothing is changed.
+ * The code bits: c[m][p] = uwspr_wspr_symbols(message m)[p] >> 1, p = 0..161 -- the positions in the interleaved order in
+ * which uwspr_demod_out.symbols[idt] holds a vector; nothing in this stage de-interleaves.
+ * The score of a vector s[0..161] of bytes:
+ *     S[m] = sum_p (2 c[m][p] - 1) ((int)s[p] - 128)
+ * 162 int32 terms, |S| <= 20736; the order of summation does not matter.
+ * The result per vector: best = the m with the largest S, the smallest m on ties; sbest = S[best]; snext = the largest
+ * S[m] over m != best (it may equal sbest; INT32_MIN when M = 1); reserved = 0.
+ * Accepted (the pipe's rule, not this call's) means sbest >= deep_min and (M == 1 or sbest - snext >= deep_gap).
+ * UWSPR_DEEP_MIN_DEFAULT, UWSPR_DEEP_GAP_DEFAULT: profiles/deep.txt says where the numbers come from (margins, not bounds).
+ * uwspr_deep_set_list: messages7 [M][7] in HOST memory; the table (+-1 bytes, K padded from 162 to 192 with zeros, 192
+ * bytes per message rounded up to 16 messages: 12.6 MB at M = 65536) is built on the host and uploaded once; it replaces
+ * the list before.  M = 0 clears the list and frees the table.  The list is checked before anything else, device included.
+ * uwspr_deep_batch: symbols [n][162], res [n]: host memory (UWSPR_HOST, complete on return) or device memory
+ * (UWSPR_DEVICE, asynchronous on the context's stream; both must lie inside device allocations of the context's device,
+ * else UWSPR_ERR_ARG before any launch).  With no list set UWSPR_ERR_ARG; n = 0 is fine. */
+#define UWSPR_DEEP_MAX 65536
+#define UWSPR_DEEP_MIN_DEFAULT 4373
+#define UWSPR_DEEP_GAP_DEFAULT 1145
+typedef struct uwspr_deep_result {
+  int32_t best, sbest, snext, reserved;
+} uwspr_deep_result;
+int uwspr_deep_set_list(uwspr_ctx *ctx, const int8_t *messages7 /*[M][7]*/, int M);
+int uwspr_deep_batch(uwspr_ctx *ctx, const uint8_t *symbols /*[n][162]*/, int n, int where, uwspr_deep_result *res);
 
 #ifdef __cplusplus
 }
