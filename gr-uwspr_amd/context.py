@@ -752,6 +752,35 @@ class Context:
                                           C.c_void_p(res.ctypes.data) if len(a) else None))
         return res
 
+    # -- call search (K14: uwspr_calls_set, uwspr_calls_batch) -----------------
+    def calls_set(self, calls, grids=None, powers=None):
+        """The call set: callsigns of type-1 messages (1 to native.CALLS_MAX, distinct; empty clears it), any locator and
+        power unless restricted: grids = 2-character fields ("FN") and / or 4-character locators ("FN42"), powers = a subset
+        of native.P19 in dBm (include/uwspr_hip.h states the rules)."""
+        arr, A, bm, pm = calls_args(calls, grids, powers)
+        self._chk(self.L.uwspr_calls_set(self.h, arr, A, C.c_void_p(bm.ctypes.data) if bm is not None else None, pm))
+
+    def calls(self, symbols):
+        """Soft-symbol vectors as at Context.deep -- [n, 162] uint8, a numpy array or a torch CUDA tensor (read in place) --
+        scored against every allowed (callsign, locator, power) of the call set.  -> a CALL_RESULT_DTYPE array: best (the
+        hypothesis index h), call (index), ngrid, dbm, sbest, snext per vector (include/uwspr_hip.h states the definition)."""
+        R = N.CALL_RESULT_DTYPE
+        if _is_torch(symbols):
+            import torch
+            assert symbols.is_cuda and symbols.is_contiguous() and symbols.dtype == torch.uint8
+            n = symbols.numel() // N.NSYM
+            out = torch.zeros(max(n, 1) * R.itemsize, dtype=torch.uint8, device=symbols.device)
+            if self._stream_ptr is None:
+                torch.cuda.current_stream(symbols.device).synchronize()
+            self._chk(self.L.uwspr_calls_batch(self.h, C.c_void_p(symbols.data_ptr()), n, N.DEVICE, C.c_void_p(out.data_ptr())))
+            self.synchronize()
+            return out.cpu().numpy()[:n * R.itemsize].view(R).copy()
+        a = np.ascontiguousarray(symbols, dtype=np.uint8).reshape(-1, N.NSYM)
+        res = np.zeros(len(a), R)
+        self._chk(self.L.uwspr_calls_batch(self.h, C.c_void_p(a.ctypes.data) if len(a) else None, len(a), N.HOST,
+                                           C.c_void_p(res.ctypes.data) if len(a) else None))
+        return res
+
     # -- block demodulation (K10: uwspr_blockdemod_batch) ---------------------
     def blockdemod(self, frames, items):
         """Soft symbols coherent over 1, 2 and 3 symbols.  items: a BLOCK_ITEM_DTYPE array, or dicts with "frame", "shift",
@@ -1155,6 +1184,62 @@ def deep_list(known):
                                           np.ascontiguousarray(t, dtype=np.int8).reshape(7) for t in known]))
 
 
+def grid_ngrid(grid4):
+    """a 4-character locator -> ngrid, the number uwspr_wspr_pack gives it (0 .. 32399)"""
+    g = str(grid4).upper()
+    if len(g) != 4 or not ("A" <= g[0] <= "R" and "A" <= g[1] <= "R" and g[2].isdigit() and g[3].isdigit()):
+        raise ValueError("a locator is two letters A..R and two digits, not %r" % (grid4,))
+    return 180 * (179 - 10 * (ord(g[0]) - 65) - (ord(g[2]) - 48)) + 10 * (ord(g[1]) - 65) + (ord(g[3]) - 48)
+
+
+def grids_bitmap(grids):
+    """2-character fields ("FN": its 100 locators) and / or 4-character locators -> the [4050] uint8 bitmap over ngrid (bit g:
+    byte g >> 3, bit g & 7); None: None (every locator)"""
+    if grids is None:
+        return None
+    bm = np.zeros(N.CALL_NGRID // 8, np.uint8)
+    for s in ([grids] if isinstance(grids, str) else grids):
+        s = str(s)
+        if len(s) not in (2, 4):
+            raise ValueError("a field (\"FN\") or a locator (\"FN42\"), not %r" % (s,))
+        for c in ([s] if len(s) == 4 else ["%s%d%d" % (s, i, j) for i in range(10) for j in range(10)]):
+            g = grid_ngrid(c)
+            bm[g >> 3] |= 1 << (g & 7)
+    return bm
+
+
+def powers_mask(powers):
+    """a subset of native.P19 (dBm) -> the power mask; None: 0 (every power)"""
+    if powers is None:
+        return 0
+    pm = 0
+    for p in powers:
+        if int(p) != p or int(p) not in N.P19:
+            raise N.UwsprError(-6, "call set: %r dBm is not one of the 19 type-1 powers %s" % (p, list(N.P19)))
+        pm |= 1 << N.P19.index(int(p))
+    if pm == 0:
+        raise N.UwsprError(-6, "call set: the set is empty: no power is allowed")
+    return pm
+
+
+def calls_args(calls, grids, powers):
+    """-> (char *[A], A, bitmap or None, power mask) for uwspr_calls_set / uwspr_pipe_set_calls"""
+    calls = [] if calls is None else ([calls] if isinstance(calls, str) else list(calls))
+    arr = (C.c_char_p * max(len(calls), 1))(*[str(c).encode("ascii", "replace") for c in calls])
+    return arr, len(calls), grids_bitmap(grids), powers_mask(powers)
+
+
+def call_message(call, grid4, dbm):
+    """message(h): the 7 bytes of "CALL GRID4 dBm" composed from its parts (uwspr_call_message) -- what wspr_pack gives
+    for that text"""
+    m = np.zeros(7, np.int8)
+    rc = N.lib().uwspr_call_message(str(call).encode("ascii", "replace"), grid4 if isinstance(grid4, (int, np.integer)) else grid_ngrid(grid4),
+                                    int(dbm), C.c_void_p(m.ctypes.data))
+    if rc:
+        raise N.UwsprError(rc, "call_message: %r %r %r is not a type-1 message" % (call, grid4, dbm))
+    return m
+
+
 def nhash(key, initval=146):
     """lookup3 hashlittle() of a byte string (the type 3 callsign hash is nhash(call) & 32767)"""
     k = key.encode() if isinstance(key, str) else bytes(key)
@@ -1355,7 +1440,7 @@ class Pipe:
                  threshold=10, device=0, hop=3375, batch_frames=256, max_per_frame=1, lanes=0,
                  host_threads=0, eager=False, sched=None, spare_after_us=0, passes=1, osd=0, osd_gap=None,
                  block=0, audio_rate=None, blank=0, blank_guard=None, carriers=None, frontend_hbw=None, known=None,
-                 deep_min=None, deep_gap=None):
+                 deep_min=None, deep_gap=None, calls=None, call_grids=None, call_powers=None, call_min=None, call_gap=None):
         self.L = N.lib()
         self.carriers = [1500]
         self.h = C.c_void_p()
@@ -1396,6 +1481,12 @@ class Pipe:
                 self.set_option("deep_min", deep_min)
             if deep_gap is not None:
                 self.set_option("deep_gap", deep_gap)
+            if calls is not None and len(calls):   # the call set: K14 on what Fano timed out on and the list left (records with osd = 3)
+                self.set_calls(calls, call_grids, call_powers)
+            if call_min is not None:
+                self.set_option("call_min", call_min)
+            if call_gap is not None:
+                self.set_option("call_gap", call_gap)
         except N.UwsprError:
             self.close()
             raise
@@ -1477,6 +1568,12 @@ class Pipe:
         m = deep_list(known)
         self._chk(self.L.uwspr_pipe_set_list(self.h, C.c_void_p(m.ctypes.data) if len(m) else None, len(m)))
 
+    def set_calls(self, calls, grids=None, powers=None):
+        """uwspr_pipe_set_calls: the call set (callsigns, grids and powers as at Context.calls_set; no callsign: the stage
+        is off); only while nothing is in flight"""
+        arr, A, bm, pm = calls_args(calls, grids, powers)
+        self._chk(self.L.uwspr_pipe_set_calls(self.h, arr, A, C.c_void_p(bm.ctypes.data) if bm is not None else None, pm))
+
     def set_carriers(self, hz):
         """uwspr_pipe_set_carriers: K0's centres in Hz (distinct integers, order kept), before the first audio push.  With
         more than one, a record's "channel" field is the plane index: split_plane gives (channel, carrier)."""
@@ -1540,6 +1637,15 @@ def read_wav(path, channels=None, any_rate=False):
     return np.ascontiguousarray(x, dtype=np.int16), rate
 
 
+def record_dict(r):
+    """a decoded pipe record -> decode_wav's dict without its "channel" and "carrier" (the record's osd byte split into
+    "osd", "deep" and "call")"""
+    return {"frame": int(r["frame"]), "t": int(r["stream_pos"]) / 375.0,
+            "freq": float(r["coarse"]["freq"]), "snr": float(r["coarse"]["snr"]),
+            "text": unpack_message(r["message"])[1], "pass": int(r["pass"]), "osd": int(r["osd"] == 1),
+            "block": int(r["block"]), "deep": int(r["osd"] == 2), "call": int(r["osd"] == 3)}
+
+
 def decode_wav(path, channels=None, **pipe_opts):
     """Decode a recording (12 kS/s, or any rate read_wav(any_rate=True) returns: the pipe's audio_rate is set from the
     file) as the receiver flowgraph does (examples/AudioSourceDecode.grc): the file through a
@@ -1547,7 +1653,8 @@ def decode_wav(path, channels=None, **pipe_opts):
     and snr, the unpacked text, "pass" (1: found by the second pass of passes=2, under a decoded signal; else 0) and
     "osd" (1: Fano timed out and ordered-statistics decoding gave the message, osd=1 or 2; else 0) and "block" (2, 3: Fano
     timed out and the soft symbols coherent over that many symbols decoded, block=2 or 3; else 0) and "deep" (1: Fano timed
-    out and the list search gave the message, known=[texts or packed messages]; else 0).
+    out and the list search gave the message, known=[texts or packed messages]; else 0) and "call" (1: Fano timed out and
+    the call search gave the message, calls=[callsigns]; else 0).
     channels="all": every channel of the file through one pipe, records in (take, channel, frame) order, each dict with
     its "channel".  carriers=[Hz, ..]: every channel is heard at each of them (Pipe(carriers=..)), records in (take,
     channel, carrier, frame) order, each dict with its "carrier" in Hz ("channel" stays the audio channel)."""
@@ -1566,10 +1673,7 @@ def decode_wav(path, channels=None, **pipe_opts):
     for r in recs:
         if not r["decoded"]:
             continue
-        d = {"frame": int(r["frame"]), "t": int(r["stream_pos"]) / 375.0,
-             "freq": float(r["coarse"]["freq"]), "snr": float(r["coarse"]["snr"]),
-             "text": unpack_message(r["message"])[1], "pass": int(r["pass"]), "osd": int(r["osd"] == 1),
-             "block": int(r["block"]), "deep": int(r["osd"] == 2)}
+        d = record_dict(r)
         ch, car = pipe.split_plane(r["channel"])
         if channels == "all":
             d["channel"] = ch

@@ -76,6 +76,10 @@ struct pipe_lane {
   std::vector<int> deep_rec, deep_idt;
   std::vector<unsigned long long> deep_off;
   std::vector<uwspr_deep_result> deep_res;
+  // call search (uwspr_pipe_set_calls): the records the list search left, one K14 item each (osdf = 3: decoded by it)
+  std::vector<int> call_rec, call_idt;
+  std::vector<unsigned long long> call_off;
+  std::vector<uwspr_call_result> call_res;
   // block demodulation (option "block"): the same records, one K10 item each
   std::vector<uint8_t> blkf;                 // [B*per] 2, 3: decoded from the soft symbols of that block length
   std::vector<int> blk_rec, blk_idt;         // item -> record, try
@@ -108,6 +112,10 @@ struct uwspr_pipe {
   int deep_M = 0, deep_min = UWSPR_DEEP_MIN_DEFAULT, deep_gap = UWSPR_DEEP_GAP_DEFAULT;
   int8_t *d_deep_tab = nullptr;
   std::vector<int8_t> deep_msgs;
+  // uwspr_pipe_set_calls / uwspr_pipe_set_option("call_min" / "call_gap"): K14 on those records against the call set; one
+  // device set for all lanes (made and freed by set_calls, read-only in between)
+  calls_set *call_set = nullptr;
+  int call_min = UWSPR_CALL_MIN_DEFAULT, call_gap = UWSPR_CALL_GAP_DEFAULT;
   int block = 0;    // uwspr_pipe_set_option("block"): 2, 3 = K10's soft symbols of block lengths 2 .. block for those records
   int audio_rate = 12000;   // uwspr_pipe_set_option("audio_rate"): the rate of the pushed audio (12000: no resampler, else K11 ahead of K0)
   int blank = 0, blank_guard = 2;   // uwspr_pipe_set_option("blank" / "blank_guard"): K12 ahead of K11 / K0 (blank 0: off)
@@ -185,6 +193,7 @@ static int parg(uwspr_pipe *q, const char *fmt, ...) {
 // L.idt / L.msg for the B * per records of L.h_out.
 static int osd_tail(uwspr_pipe *q, pipe_lane &L, int nrec, tail_acc &ta);
 static int deep_tail(uwspr_pipe *q, pipe_lane &L, int nrec, tail_acc &ta);
+static int calls_tail(uwspr_pipe *q, pipe_lane &L, int nrec, tail_acc &ta);
 static int block_tail(uwspr_pipe *q, pipe_lane &L, const float *frames, int nrec, tail_acc &ta);
 
 static int host_tail(uwspr_pipe *q, pipe_lane &L, const float *frames, int B, bool first, tail_acc &ta) {
@@ -280,11 +289,13 @@ static int host_tail(uwspr_pipe *q, pipe_lane &L, const float *frames, int B, bo
     if (const int rc = block_tail(q, L, frames, nrec, ta)) return rc;
   if (q->deep_M > 0)
     if (const int rc = deep_tail(q, L, nrec, ta)) return rc;
+  if (q->call_set)
+    if (const int rc = calls_tail(q, L, nrec, ta)) return rc;
   if (q->osd > 0) return osd_tail(q, L, nrec, ta);
   return UWSPR_OK;
 }
 
-// The item rule of the options "block" and "osd" and of the list search: record i is an item when it was worth a try, no try decoded and at least
+// The item rule of the options "block" and "osd", of the list search and of the call search: record i is an item when it was worth a try, no try decoded and at least
 // one try passed the gates of cc:470; its try is the gated one with the largest jig_sync, the first one on ties (-1: no item).
 static int fallback_try(const uwspr_pipe *q, const pipe_lane &L, int i) {
   const float minsync2 = 0.12f, minrms = (float)(52.0 * (50 / 64.0));   // the gates of decode_try (host_tail.cpp)
@@ -359,6 +370,41 @@ static int deep_tail(uwspr_pipe *q, pipe_lane &L, int nrec, tail_acc &ta) {
     const int i = L.deep_rec[k];
     L.dec[i] = 1; L.idt[i] = L.deep_idt[k]; L.osdf[i] = 2;
     memcpy(&L.msg[7 * (size_t)i], &q->deep_msgs[7 * (size_t)r.best], 7);
+  }
+  ta.resume_s += now_s() - t0;
+  return UWSPR_OK;
+}
+
+// The call search (uwspr_pipe_set_calls), behind the list search: the items are again fallback_try's (a record the list
+// search decoded is none any more), their symbols read in place; K14 scores each against the pipe's call set.  An item with
+// sbest >= call_min and (one allowed hypothesis or sbest - snext >= call_gap) makes its record a decoded one with
+// message(best) (no unpacking: the message is valid by construction).  Its time counts as resume time.
+static int calls_tail(uwspr_pipe *q, pipe_lane &L, int nrec, tail_acc &ta) {
+  L.call_rec.clear(); L.call_idt.clear(); L.call_off.clear();
+  for (int i = 0; i < nrec; i++) {
+    const int pick = fallback_try(q, L, i);
+    if (pick < 0) continue;
+    L.call_rec.push_back(i); L.call_idt.push_back(pick);
+    L.call_off.push_back((unsigned long long)((const char *)&L.d_out[i].symbols[pick][0] - (const char *)L.d_out));
+  }
+  const int n = (int)L.call_rec.size();
+  if (n == 0) return UWSPR_OK;
+  const double t0 = now_s();
+  uwspr_call_result *d_res = nullptr;
+  const int rc = calls_run(L.ctx, q->call_set, (const uint8_t *)L.d_out, L.call_off.data(), n, nullptr, &d_res);
+  if (rc) return pfail(q, rc, "call search: %s", uwspr_last_error(L.ctx));
+  L.call_res.resize((size_t)n);
+  PHIP(q, hipMemcpyAsync(L.call_res.data(), d_res, (size_t)n * sizeof(uwspr_call_result), hipMemcpyDeviceToHost, L.stream));
+  PHIP(q, hipEventRecord(L.ev_done, L.stream));
+  PHIP(q, hipEventSynchronize(L.ev_done));
+  const long long nhyp = calls_count(q->call_set);
+  for (int k = 0; k < n; k++) {
+    const uwspr_call_result &r = L.call_res[k];
+    if (r.best < 0 || r.best >= UWSPR_CALLS_MAX * UWSPR_CALL_NGRID * UWSPR_CALL_NPOW || r.sbest < q->call_min) continue;
+    if (nhyp > 1 && (long long)r.sbest - (long long)r.snext < (long long)q->call_gap) continue;
+    const int i = L.call_rec[k];
+    L.dec[i] = 1; L.idt[i] = L.call_idt[k]; L.osdf[i] = 3;
+    calls_message(q->call_set, r.best, &L.msg[7 * (size_t)i]);
   }
   ta.resume_s += now_s() - t0;
   return UWSPR_OK;
@@ -733,6 +779,7 @@ extern "C" void uwspr_pipe_close(uwspr_pipe *q) {
     if (L.ctx) uwspr_ctx_destroy(L.ctx);
   }
   if (q->d_deep_tab) (void)hipFree(q->d_deep_tab);
+  calls_free_set(q->call_set);
   q->ring.close();
   for (int k = 0; k < uwspr_pipe::NSTAGE; k++) {
     if (q->h_stage[k]) (void)hipHostFree(q->h_stage[k]);
@@ -1024,6 +1071,15 @@ extern "C" int uwspr_pipe_set_option(uwspr_pipe *q, const char *name, int value)
     (gap ? q->deep_gap : q->deep_min) = value;
     return UWSPR_OK;
   }
+  if (!strcmp(name, "call_min") || !strcmp(name, "call_gap")) {   // the pipe's own: the call search's acceptance thresholds
+    const bool gap = name[5] == 'g';
+    if (value < 0) return parg(q, "uwspr_pipe_set_option: \"%s\" is >= 0, not %d", name, value);
+    std::lock_guard<std::mutex> lk(q->m);
+    for (auto &L : q->lanes)
+      if (L.busy) { snprintf(q->err, sizeof(q->err), "uwspr_pipe_set_option(%s): batches in flight (flush first)", name); return UWSPR_ERR_ARG; }
+    (gap ? q->call_gap : q->call_min) = value;
+    return UWSPR_OK;
+  }
   if (!strcmp(name, "audio_rate")) {   // the pipe's own: the rate of the audio its pushes carry, latched by the first push
     resample_plan pl;
     if (resample_design(value, pl)) return parg(q, "uwspr_pipe_set_option: \"audio_rate\" = %d is not a supported rate", value);
@@ -1106,6 +1162,32 @@ extern "C" int uwspr_pipe_set_list(uwspr_pipe *q, const int8_t *messages7, int M
   q->deep_M = M;
   if (M > 0) q->deep_msgs.assign(messages7, messages7 + 7 * (size_t)M);
   else std::vector<int8_t>().swap(q->deep_msgs);
+  return UWSPR_OK;
+}
+
+// The call set: checked, built on the host and uploaded before anything of the pipe changes; one set for all lanes (the
+// lanes' contexts live on the pipe's device and only read it).
+extern "C" int uwspr_pipe_set_calls(uwspr_pipe *q, const char *const *calls, int A, const uint8_t *grid_bitmap, uint32_t power_mask) {
+  if (!q) return UWSPR_ERR_ARG;
+  char why[200];
+  if (A != 0 && calls_check(calls, A, grid_bitmap, power_mask, nullptr, why, sizeof(why))) return parg(q, "uwspr_pipe_set_calls: %s", why);
+  if (const int f = q->failed.load()) return f;
+  calls_set *fresh = nullptr;
+  if (A > 0) {
+    (void)hipSetDevice(q->device);
+    int rc = UWSPR_OK;
+    fresh = calls_build(calls, A, grid_bitmap, power_mask, &rc, why, sizeof(why));
+    if (!fresh) return rc == UWSPR_ERR_ARG ? parg(q, "uwspr_pipe_set_calls: %s", why) : pfail(q, rc, "uwspr_pipe_set_calls: %s", why);
+  }
+  std::lock_guard<std::mutex> lk(q->m);
+  for (auto &L : q->lanes)
+    if (L.busy) {
+      calls_free_set(fresh);
+      snprintf(q->err, sizeof(q->err), "uwspr_pipe_set_calls: batches in flight (flush first)");
+      return UWSPR_ERR_ARG;
+    }
+  calls_free_set(q->call_set);   // (nothing in flight: no lane reads it)
+  q->call_set = fresh;
   return UWSPR_OK;
 }
 

@@ -182,6 +182,9 @@ struct bk_state;
 void bk_release(uwspr_ctx *c);   // k12_blank.hip: frees what uwspr_blank_batch made
 struct deep_state;
 void deep_release(uwspr_ctx *c); // k13_deep.hip: frees what uwspr_deep_set_list / uwspr_deep_batch made
+struct calls_state;
+struct calls_set;
+void calls_release(uwspr_ctx *c); // k14_calls.hip: frees what uwspr_calls_set / uwspr_calls_batch made
 
 }  // namespace uwspr
 
@@ -288,6 +291,8 @@ struct uwspr_ctx {
   uwspr::bk_state *bk;
   // list search (k13_deep.hip): the list's table and call scratch, made by uwspr_deep_set_list / the first use
   uwspr::deep_state *deep;
+  // call search (k14_calls.hip): the call set and call scratch, made by uwspr_calls_set / the first use
+  uwspr::calls_state *calls;
 
   int prof_mask;
   std::vector<uwspr::ev_pair> prof_events;
@@ -320,6 +325,20 @@ int deep_run(uwspr_ctx *c, const int8_t *d_tab, int M, const uint8_t *base, cons
              uwspr_deep_result *res, uwspr_deep_result **res_out);
 const char *deep_check_list(const int8_t *messages7, int M, char *msg, size_t cap);
 int deep_build_table(const int8_t *messages7, int M, std::vector<int8_t> &tab);
+
+// K14 (k14_calls.hip): a call set is checked (calls_check: null when it keeps the rules at uwspr_calls_set, else what is
+// wrong, no device asked) and built into memory of the current device (calls_build: null with *status and msg on failure;
+// read-only from then on, freed by calls_free_set).  calls_run: n > 0 items on the context's stream against a set (null =
+// the set of uwspr_calls_set), items and results as at deep_run.  calls_message: message(h) of a set; calls_count: its
+// number of allowed hypotheses.
+const char *calls_check(const char *const *calls, int A, const uint8_t *grid_bitmap, uint32_t power_mask, int32_t *n1_out,
+                        char *msg, size_t cap);
+calls_set *calls_build(const char *const *calls, int A, const uint8_t *grid_bitmap, uint32_t power_mask, int *status, char *msg, size_t cap);
+void calls_free_set(calls_set *s);
+int calls_run(uwspr_ctx *c, const calls_set *set, const uint8_t *base, const unsigned long long *off, int n,
+              uwspr_call_result *res, uwspr_call_result **res_out);
+void calls_message(const calls_set *s, int h, int8_t *message7);
+long long calls_count(const calls_set *s);
 
 // K10 (k10_blockdemod.hip): nitems > 0 items (host records that passed blockdemod_check against the frames of src: sorted by
 // frame, frames in [0, nframes), finite f / drift, bounded shift) on the context's stream; src: device frames, frame b at

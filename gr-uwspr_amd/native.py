@@ -26,7 +26,7 @@ LIBPATH = os.path.join(LIBDIR, "libuwspr_hip_exp_%s.so" % _EXTRA_TAG if _EXTRA e
 HOSTLIB = os.path.join(LIBDIR, "libuwspr_blocks.so")
 
 SOURCES = ["uwspr_api.hip", "k0_frontend.hip", "k1_spectrogram.hip", "k2_spectrum.hip", "k3_coarse.hip",
-           "k4_tonecorr.hip", "k4_grid.hip", "k4_pair.hip", "k4_jig.hip", "k5_fold_schedule.hip", "k6_sched.hip", "k7_transmit.hip", "k8_subtract.hip", "k9_osd.hip", "k10_blockdemod.hip", "k11_resample.hip", "k12_blank.hip", "k13_deep.hip", "pipe.hip", "dist.hip", "host_tail.cpp"]
+           "k4_tonecorr.hip", "k4_grid.hip", "k4_pair.hip", "k4_jig.hip", "k5_fold_schedule.hip", "k6_sched.hip", "k7_transmit.hip", "k8_subtract.hip", "k9_osd.hip", "k10_blockdemod.hip", "k11_resample.hip", "k12_blank.hip", "k13_deep.hip", "k14_calls.hip", "pipe.hip", "dist.hip", "host_tail.cpp"]
 HIPFLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off",
             "-fno-slp-vectorize", "-fhip-fp32-correctly-rounded-divide-sqrt", "-fPIC", "-Wall", "-Wno-unused-function"]
 
@@ -219,6 +219,12 @@ OSD_GAP_DEFAULT = 485   # UWSPR_OSD_GAP_DEFAULT
 DEEP_RESULT_DTYPE = np.dtype([("best", "<i4"), ("sbest", "<i4"), ("snext", "<i4"), ("reserved", "<i4")])
 assert DEEP_RESULT_DTYPE.itemsize == 16
 DEEP_MAX, DEEP_MIN_DEFAULT, DEEP_GAP_DEFAULT = 65536, 4373, 1145   # UWSPR_DEEP_MAX, UWSPR_DEEP_MIN_DEFAULT, UWSPR_DEEP_GAP_DEFAULT
+CALL_RESULT_DTYPE = np.dtype([("best", "<i4"), ("call", "<i4"), ("ngrid", "<i4"), ("dbm", "<i4"), ("sbest", "<i4"), ("snext", "<i4"),
+                              ("reserved", "<i4", (2,))])
+assert CALL_RESULT_DTYPE.itemsize == 32
+CALLS_MAX, CALL_NGRID = 64, 32400   # UWSPR_CALLS_MAX, UWSPR_CALL_NGRID
+P19 = (0, 3, 7, 10, 13, 17, 20, 23, 27, 30, 33, 37, 40, 43, 47, 50, 53, 57, 60)   # the type-1 powers in dBm (UWSPR_CALL_NPOW of them)
+CALL_MIN_DEFAULT, CALL_GAP_DEFAULT = 5370, 725   # UWSPR_CALL_MIN_DEFAULT, UWSPR_CALL_GAP_DEFAULT
 PIPE_MAX_CHANNELS = 64
 
 
@@ -278,10 +284,11 @@ ABI_SYMBOLS = [
     "uwspr_wspr_pack", "uwspr_nhash", "uwspr_wspr_symbols", "uwspr_c2_write", "uwspr_tx_baseband", "uwspr_tx_render",
     "uwspr_tx_baseband_moving", "uwspr_tx_render_moving", "uwspr_tx_baseband_at", "uwspr_tx_render_at", "uwspr_tx_design_at",
     "uwspr_subtract_batch", "uwspr_osd_batch", "uwspr_blockdemod_batch", "uwspr_deep_set_list", "uwspr_deep_batch",
+    "uwspr_calls_set", "uwspr_calls_batch", "uwspr_call_message",
     "uwspr_dist_unique_id", "uwspr_dist_init", "uwspr_dist_gather", "uwspr_dist_finalize",
     "uwspr_pipe_open", "uwspr_pipe_close", "uwspr_pipe_last_error", "uwspr_pipe_acquire", "uwspr_pipe_commit",
     "uwspr_pipe_push", "uwspr_pipe_push_audio", "uwspr_pipe_push_audio_channels", "uwspr_pipe_submit_device", "uwspr_pipe_flush", "uwspr_pipe_collect", "uwspr_pipe_get_stats",
-    "uwspr_pipe_inject_failure", "uwspr_pipe_set_option", "uwspr_pipe_set_carriers", "uwspr_pipe_set_list",
+    "uwspr_pipe_inject_failure", "uwspr_pipe_set_option", "uwspr_pipe_set_carriers", "uwspr_pipe_set_list", "uwspr_pipe_set_calls",
 ]
 
 _lib = None
@@ -390,6 +397,9 @@ def lib():
     L.uwspr_blockdemod_batch.argtypes = [vp, vp, ip, ip, vp, ip, vp]
     L.uwspr_deep_set_list.argtypes = [vp, vp, ip]
     L.uwspr_deep_batch.argtypes = [vp, vp, ip, ip, vp]
+    L.uwspr_calls_set.argtypes = [vp, vp, ip, vp, C.c_uint32]
+    L.uwspr_calls_batch.argtypes = [vp, vp, ip, ip, vp]
+    L.uwspr_call_message.argtypes = [C.c_char_p, ip, ip, vp]
     L.uwspr_dist_unique_id.argtypes = [vp]
     L.uwspr_dist_init.argtypes = [vp, ip, ip, vp]
     L.uwspr_dist_gather.argtypes = [vp, vp, C.c_size_t, vp, ip, ip]
@@ -412,5 +422,6 @@ def lib():
     L.uwspr_pipe_set_option.argtypes = [vp, C.c_char_p, ip]
     L.uwspr_pipe_set_carriers.argtypes = [vp, vp, ip]
     L.uwspr_pipe_set_list.argtypes = [vp, vp, ip]
+    L.uwspr_pipe_set_calls.argtypes = [vp, vp, ip, vp, C.c_uint32]
     _lib = L
     return L

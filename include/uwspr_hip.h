@@ -52,7 +52,10 @@ extern "C" {
                                     transmit at any carrier: uwspr_tx_render_at, uwspr_tx_baseband_at, uwspr_tx_design_at,
                                     the options "tx_cutoff" and "tx_form";
                                     list search: uwspr_deep_result, uwspr_deep_set_list, uwspr_deep_batch,
-                                    uwspr_pipe_set_list, the pipe options "deep_min" and "deep_gap", uwspr_decode.osd = 2 */
+                                    uwspr_pipe_set_list, the pipe options "deep_min" and "deep_gap", uwspr_decode.osd = 2;
+                                    call search (only entry points and a value of uwspr_decode.osd are added, so the
+                                    version stays what it is): uwspr_call_result, uwspr_calls_set, uwspr_calls_batch, uwspr_call_message,
+                                    uwspr_pipe_set_calls, the pipe options "call_min" and "call_gap", uwspr_decode.osd = 3 */
 
 typedef enum {
   UWSPR_OK = 0,
@@ -571,8 +574,8 @@ typedef struct uwspr_decode {
   int16_t channel;        /* the audio channel of a multichannel pipe (uwspr_pipe_push_audio_channels); 0 otherwise.  With n > 1
                              carriers (uwspr_pipe_set_carriers): the plane index channel * n + carrier index */
   uint8_t pass;           /* 1: found by the second pass (option "passes" = 2), in the frame with its decoded signals taken out; 0 otherwise */
-  uint8_t osd;            /* 1: ordered-statistics decoding, 2: list search -- Fano timed out on every gated try and K9 (option "osd") or
-                             K13 (uwspr_pipe_set_list) gave the message; 0 otherwise */
+  uint8_t osd;            /* 1: ordered-statistics decoding, 2: list search, 3: call search -- Fano timed out on every gated try and K9
+                             (option "osd"), K13 (uwspr_pipe_set_list) or K14 (uwspr_pipe_set_calls) gave the message; 0 otherwise */
 } uwspr_decode;
 typedef struct uwspr_pipe_stats {
   int64_t frames, batches, candidates, decoded, resumed;   /* resumed: records whose other tries were produced */
@@ -682,7 +685,8 @@ int uwspr_pipe_blank_stats(uwspr_pipe *pipe, long long *samples, long long *zero
  * These calls count in fano_calls / fano_timeouts, their time in resume_s.  With "block" = 0 every byte and statistic is
  * what it is without the option.
  * "deep_min" and "deep_gap" (both >= 0; defaults UWSPR_DEEP_MIN_DEFAULT and UWSPR_DEEP_GAP_DEFAULT) are the pipe's own: the
- * acceptance thresholds of the list search, see uwspr_pipe_set_list. */
+ * acceptance thresholds of the list search, see uwspr_pipe_set_list.  "call_min" and "call_gap" (both >= 0; defaults
+ * UWSPR_CALL_MIN_DEFAULT and UWSPR_CALL_GAP_DEFAULT) likewise: those of the call search, see uwspr_pipe_set_calls. */
 int uwspr_pipe_set_option(uwspr_pipe *pipe, const char *name, int value);
 /* The list of expected messages (the rules of uwspr_deep_set_list below; host memory, copied): with a list set, K13
  * (uwspr_deep_batch below) runs on the batch's lane behind its host tail, resumed tries included, after "block" and before
@@ -698,6 +702,21 @@ int uwspr_pipe_set_option(uwspr_pipe *pipe, const char *name, int value);
  * Device memory: ONE table per pipe, read by every lane, 192 bytes per message rounded up to 16 messages (M = 65536:
  * 12.6 MB), plus per lane that ran it 16 bytes per item and message chunk (at most 1024 chunks per 16 items). */
 int uwspr_pipe_set_list(uwspr_pipe *pipe, const int8_t *messages7 /*[M][7]*/, int M);
+/* The call set (the rules and arguments of uwspr_calls_set below; host memory, copied): with a set, K14 (uwspr_calls_batch
+ * below) runs on the batch's lane behind its host tail after "block" and the list search -- a given list is the more
+ * specific knowledge and goes first -- and before "osd", also behind the second pass's host tail with "passes" = 2, on the
+ * records those stages take (the item rule at uwspr_pipe_set_list; a record the list search decoded is no item any more),
+ * its symbols read where they lie in the lane's device records.  An item with sbest >= "call_min" and (a single allowed
+ * hypothesis or sbest - snext >= "call_gap") turns the record into a decoded one: decoded = 1, idt = that try, message =
+ * message(best), osd = 3.  uwspr_unpack_message is not asked: the message is valid by construction.  It is an ordinary
+ * decoded record from there on (counted in the stats' decoded, subtracted by "passes" = 2, no item of "osd").  Its time
+ * counts in resume_s.  Only while nothing is in flight (UWSPR_ERR_ARG otherwise); a set that breaks the rules is
+ * UWSPR_ERR_ARG and the set in force stays.  A = 0 turns the stage off and frees the set: every byte and statistic is then
+ * what it is without one, and nothing of K14 runs or is allocated.
+ * Device memory: ONE set per pipe, read by every lane (the 6.2 MB locator table, 3648 bytes per callsign, the bitmap), plus
+ * per lane that ran it 12 bytes per item and workgroup of its row (about 2048 workgroups per 16 items). */
+int uwspr_pipe_set_calls(uwspr_pipe *pipe, const char *const *calls, int A, const uint8_t *grid_bitmap /*[4050] or NULL*/,
+                         uint32_t power_mask);
 /* Error behaviour.  An argument error (too many samples, a bad B or stride) fails THAT call with UWSPR_ERR_ARG and
  * its message; the pipe goes on.  A runtime failure (HIP, a lane's context) is sticky: the batch it hit emits
  * nothing, records of the batches before it stay collectable, every later call -- and uwspr_pipe_collect once
@@ -1050,6 +1069,58 @@ typedef struct uwspr_deep_result {
 } uwspr_deep_result;
 int uwspr_deep_set_list(uwspr_ctx *ctx, const int8_t *messages7 /*[M][7]*/, int M);
 int uwspr_deep_batch(uwspr_ctx *ctx, const uint8_t *symbols /*[n][162]*/, int n, int where, uwspr_deep_result *res);
+
+/* ---- call search (K14, k14_calls.hip) -------------------------------------------------------------------------------- */
+/* Maximum-likelihood decoding over every type-1 message "CALL GRID4 dBm" of known callsigns: the callsign is known, the
+ * locator and the power are free (a glider or drifter that moves, a beacon that carries its telemetry in locator and
+ * power).  The list search needs the whole text; this needs the callsign only.  The reference has no counterpart (WSJT's
+ * deep search expands a callsign database by locator); all integers, so host, device and the test's restatement
+ * (tests/call_exact.py) give the same bytes.
+ * A call set:
+ *   - A callsigns, 1 <= A <= UWSPR_CALLS_MAX: texts that uwspr_wspr_pack accepts as the callsign of a type-1 message (3 to 6
+ *     letters and digits; no compound "PFX/CALL", no hashed "<CALL>"), distinct after packing (lower case is upper case);
+ *   - a locator bitmap over ngrid = 0 .. UWSPR_CALL_NGRID - 1 (ngrid as uwspr_wspr_pack numbers a 4-character locator:
+ *     180 (179 - 10 (c0 - 'A') - (c2 - '0')) + 10 (c1 - 'A') + (c3 - '0')), bit g = byte g >> 3, bit g & 7, 4050 bytes;
+ *     NULL allows every locator;
+ *   - a power mask over the UWSPR_CALL_NPOW = 19 type-1 powers P19 = 0, 3, 7, 10, 13, 17, .., 53, 57, 60 dBm, bit d = P19[d];
+ *     0 allows all; a bit beyond the 19 is an error.
+ * At least one hypothesis must be allowed.  Anything else is UWSPR_ERR_ARG, checked before any device is asked for, and
+ * nothing is changed.
+ * A hypothesis is h = (a UWSPR_CALL_NGRID + g) 19 + d -- a the index of the callsign, g its ngrid, d the index into P19 --
+ * and message(h) the 7 bytes uwspr_wspr_pack("CALL GRID4 dBm") gives; uwspr_call_message composes them from (call, ngrid,
+ * dBm) (UWSPR_ERR_ARG for a bad callsign, ngrid outside 0 .. 32399 or a power not in P19).
+ * The code bits and the score are the list search's: c[h][p] = uwspr_wspr_symbols(message(h))[p] >> 1 and
+ *     S[h] = sum_p (2 c[h][p] - 1) ((int)s[p] - 128),
+ * so a list that holds message(h) gives the same S through uwspr_deep_batch.  Nothing is tabulated per hypothesis: a type-1
+ * message is n1 (28 bits, the callsign) and n2 = 128 ngrid + dBm + 64, the three occupy disjoint bits of the 50, and the
+ * code is linear (uwspr_fano_encode starts from the zero state, the interleaver is a permutation, the code bit is
+ * sym >> 1), so c[call, g, d] = c[call only] XOR c[ngrid = g only] XOR c[dBm + 64 only]: one table of 32400 locator
+ * codewords for every callsign and power (6.2 MB, built on the host once per set), and a 162-entry sign per (callsign, power).
+ * The result per vector: best = the allowed h with the largest S, the smallest h on ties; call, ngrid, dbm = its parts (dbm
+ * in dBm, not the index); sbest = S[best]; snext = the largest S over the other allowed h (it may equal sbest; INT32_MIN
+ * with a single allowed hypothesis); reserved = 0.
+ * Accepted (the pipe's rule, not this call's) means sbest >= call_min and (one allowed hypothesis or sbest - snext >=
+ * call_gap).  UWSPR_CALL_MIN_DEFAULT, UWSPR_CALL_GAP_DEFAULT: profiles/calls.txt says where the numbers come from (margins,
+ * not bounds).  They are not the list search's: a set is 615 600 hypotheses per callsign, and the other locators and
+ * powers of the transmitted callsign are correlated with the transmitted message.
+ * uwspr_calls_set: calls [A] texts and grid_bitmap in HOST memory; it replaces the set before.  A = 0 clears the set and
+ * frees its memory.
+ * uwspr_calls_batch: symbols [n][162], res [n]: host memory (UWSPR_HOST, complete on return) or device memory
+ * (UWSPR_DEVICE, asynchronous on the context's stream; both must lie inside device allocations of the context's device,
+ * else UWSPR_ERR_ARG before any launch).  With no set UWSPR_ERR_ARG; n = 0 is fine. */
+#define UWSPR_CALLS_MAX 64
+#define UWSPR_CALL_NGRID 32400
+#define UWSPR_CALL_NPOW 19
+#define UWSPR_CALL_MIN_DEFAULT 5370
+#define UWSPR_CALL_GAP_DEFAULT 725
+typedef struct uwspr_call_result {
+  int32_t best, call, ngrid, dbm, sbest, snext;
+  int32_t reserved[2];
+} uwspr_call_result;
+int uwspr_calls_set(uwspr_ctx *ctx, const char *const *calls, int A, const uint8_t *grid_bitmap /*[4050] or NULL*/,
+                    uint32_t power_mask);
+int uwspr_calls_batch(uwspr_ctx *ctx, const uint8_t *symbols /*[n][162]*/, int n, int where, uwspr_call_result *res);
+int uwspr_call_message(const char *call, int ngrid, int dbm, int8_t *message7);
 
 #ifdef __cplusplus
 }
