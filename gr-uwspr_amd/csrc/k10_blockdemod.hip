@@ -1,7 +1,7 @@
 // K10 -- block demodulation: soft symbols from complex tone correlations summed coherently over 1, 2 and 3 neighbouring
 // symbols (uwspr_blockdemod_batch; the pipe's option "block").  The reference has no counterpart (its soft symbols are
 // per-symbol magnitudes, sync_and_demodulate_impl.cc:240-254): the definition is this project's, in include/uwspr_hip.h,
-// and tests/test_gpu_blockdemod.py restates it in binary64.  Binary32 with fused multiply-adds; every phase in binary64.
+// and tests/blockdemod_exact.py restates it in binary64.  Binary32 with fused multiply-adds; every phase in binary64.
 //
 // One workgroup of three wavefronts per item (frame, shift, f, drift).  Lane i < 162 owns symbol i: it walks the symbol's
 // 256 samples once, for all four tones.  The samples come through LDS in chunks of 16 per symbol -- the loads are 128-byte
@@ -45,6 +45,8 @@ __device__ __forceinline__ void k10_mac(float2 &acc, float2 a, float2 b) {
 }
 __device__ __forceinline__ float k10_abs(float2 a) { return sqrtf(fmaf(a.x, a.x, a.y * a.y)); }
 __device__ __forceinline__ float k10_abs2(float2 a, float2 b) { return k10_abs(make_float2(a.x + b.x, a.y + b.y)); }
+// the larger of two P, a NaN if either is one (fmaxf would return the other operand): the block's soft values are then NaN
+__device__ __forceinline__ float k10_max(float a, float b) { return (a >= b || a != a) ? a : b; }
 
 // out [item][3][162]
 __global__ __launch_bounds__(K10_WG) void k10_blockdemod(const float2 *__restrict__ frames, size_t stride, int np,
@@ -102,8 +104,8 @@ __global__ __launch_bounds__(K10_WG) void k10_blockdemod(const float2 *__restric
     const float2 a0 = z[p0][i0], a1 = z[p0 + 2][i0];
     const float2 b0 = k10_mul(z[p1][i0 + 1], r1[i0]), b1 = k10_mul(z[p1 + 2][i0 + 1], r1[i0]);
     const float P00 = k10_abs2(a0, b0), P01 = k10_abs2(a0, b1), P10 = k10_abs2(a1, b0), P11 = k10_abs2(a1, b1);
-    soft[1][i0] = fmaxf(P10, P11) - fmaxf(P00, P01);
-    soft[1][i0 + 1] = fmaxf(P01, P11) - fmaxf(P00, P10);
+    soft[1][i0] = k10_max(P10, P11) - k10_max(P00, P01);
+    soft[1][i0 + 1] = k10_max(P01, P11) - k10_max(P00, P10);
   }
   if (tid < K10_NSYM / 3) {   // n = 3: block tid covers symbols i0 .. i0 + 2
     const int i0 = 3 * tid, p0 = pr3_bit(i0), p1 = pr3_bit(i0 + 1), p2 = pr3_bit(i0 + 2);
@@ -119,7 +121,7 @@ __global__ __launch_bounds__(K10_WG) void k10_blockdemod(const float2 *__restric
       const int d0 = d & 1, d1 = (d >> 1) & 1, d2 = d >> 2;
       const float2 s = make_float2(a[d0].x + b[d1].x, a[d0].y + b[d1].y);
       const float P = k10_abs2(s, c[d2]);
-      m[0][d0] = fmaxf(m[0][d0], P); m[1][d1] = fmaxf(m[1][d1], P); m[2][d2] = fmaxf(m[2][d2], P);
+      m[0][d0] = k10_max(m[0][d0], P); m[1][d1] = k10_max(m[1][d1], P); m[2][d2] = k10_max(m[2][d2], P);
     }
 #pragma unroll
     for (int q = 0; q < 3; q++) soft[2][i0 + q] = m[q][1] - m[q][0];

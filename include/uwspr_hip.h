@@ -1020,7 +1020,9 @@ int uwspr_osd_batch(uwspr_ctx *ctx, const uint8_t *symbols /*[n][162]*/, int n, 
  *   - Block length n in {1, 2, 3}: block b covers the symbols i0 = n b .. i0 + n - 1 (162, 81, 54 blocks).  For every data
  *     sequence d in {0,1}^n,
  *         P(d) = | sum_{m < n} z_{i0+m}[pr3[i0+m] + 2 d_m] e^{-j psi_m} |,   psi_m = sum_{q < m} theta_{i0+q}.
- *   - soft[i0+m] = max_{d: d_m = 1} P(d) - max_{d: d_m = 0} P(d).  With n = 1 this is mode 2's p[pr3 + 2] - p[pr3].
+ *   - soft[i0+m] = max_{d: d_m = 1} P(d) - max_{d: d_m = 0} P(d).  With n = 1 this is mode 2's p[pr3 + 2] - p[pr3].  If any
+ *     P(d) of a block is NaN, soft of every symbol of that block is NaN -- the maxima propagate NaN -- so fac is NaN and
+ *     all 162 bytes of that block length are 128, whatever n.
  *   - Normalisation as in mode 2 (cc:240-254): fsum and f2sum the mean and the mean square of the 162 values, fac =
  *     sqrt(f2sum - fsum^2), v = 50 soft / fac clipped to [-128, 127], byte = (uint8)(v + 128).  When fac is not a positive
  *     finite number every byte is 128.

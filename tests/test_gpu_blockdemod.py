@@ -1,18 +1,19 @@
 """K10 (uwspr_blockdemod_batch) against a binary64 numpy restatement of the definition in include/uwspr_hip.h: complex tone
 correlations per symbol, the per-symbol carrier rotation theta_i = 2 pi f_i 256 / 375 + pi, blocks of 1, 2 and 3 symbols,
-the maxima over their data sequences, mode 2's normalisation.  block_restate is written from the header's text, not from
-the kernel, and is what tests/golden/make_block_pipe_seeds.py picks the pipe test's seeds with.
+the maxima over their data sequences, mode 2's normalisation.  block_restate (tests/blockdemod_exact.py, importable from
+here as before) is written from the header's text, not from the kernel, and is what tests/golden/make_block_pipe_seeds.py
+picks the pipe test's seeds with.  The edges of the definition are in tests/test_gpu_blockdemod_edges.py.
 
 Frames: three of tests/test_gpu_osd_pipe.py's text_frame model at -24 dB and one noise-free frame of the same model.
 Tolerance: every byte within 1 of the restatement's and at most 1 % of a call's bytes different at all -- a 256-term
 binary32 sum is off by <= 1.5e-5 relative at worst (typically 1e-6), which after 50 / fac puts v within ~1e-3 of its exact
 value, so a byte flips with probability <= ~2e-3; an error in the definition changes tens of per cent."""
 import ctypes as C
-import itertools
 
 import numpy as np
 import pytest
 
+from blockdemod_exact import block_restate, clean_frame, frame_offset, slm_at_zero  # noqa: F401 (the pipe test and the seed script import them from here)
 from test_gpu_osd_pipe import text_frame
 
 TEXT, SNR_DB = "K1ABC FN42 37", -24.0
@@ -21,65 +22,6 @@ CLEAN_SEED = 14
 DF = 375.0 / 256.0
 NSYM, NP, HOP = 162, 45000, 3375
 LAST = 45000 - 41472 + 300    # a shift with which the last symbols run off the end
-
-
-def frame_offset(seed):
-    """the frequency offset text_frame draws for `seed` (its generator's first draw)"""
-    return np.random.Generator(np.random.Philox(0x05D7E87 + seed)).uniform(-6.0, 6.0)
-
-
-def clean_frame(G, text, seed, off=None, drift=0.0):
-    """text_frame's signal without its noise (off: another frequency offset than the seed's; drift: the item model's
-    (drift / 2)(i - 81) / 81 per symbol on top of it)"""
-    sym = G.wspr_symbols(text).astype(np.float64)
-    off = frame_offset(seed) if off is None else off
-    fi = off + (drift / 2.0) * (np.arange(NSYM) - 81.0) / 81.0
-    phase = 2.0 * np.pi * np.cumsum(np.repeat((sym - 1.5) * DF + fi, 256)) / 375.0
-    sig = np.zeros((NP, 2), np.float64)
-    sig[375:375 + NSYM * 256, 0] = np.cos(phase)
-    sig[375:375 + NSYM * 256, 1] = np.sin(phase)
-    return sig.astype(np.float32)
-
-
-def block_restate(frame, shift, f, drift, pr3):
-    """include/uwspr_hip.h, "block demodulation", in binary64 -> [3, 162] uint8 (block lengths 1, 2, 3)"""
-    x = frame[:, 0].astype(np.float64) + 1j * frame[:, 1].astype(np.float64)
-    i = np.arange(NSYM)
-    k = np.arange(256)
-    n = int(shift) + 256 * i[:, None] + k[None, :]
-    ok = (n > 0) & (n < NP)
-    xs = np.where(ok, x[np.clip(n, 0, len(x) - 1)], 0.0)
-    fi = float(np.float32(f)) + (float(np.float32(drift)) / 2.0) * (i - 81) / 81.0
-    z = np.empty((NSYM, 4), np.complex128)
-    for j in range(4):
-        z[:, j] = (xs * np.exp(-2j * np.pi * (fi[:, None] + (j - 1.5) * DF) * k[None, :] / 375.0)).sum(axis=1)
-    theta = 2.0 * np.pi * fi * 256.0 / 375.0 + np.pi
-    out = np.full((3, NSYM), 128, np.uint8)
-    for nb in (1, 2, 3):
-        soft = np.zeros(NSYM)
-        for b in range(NSYM // nb):
-            i0 = nb * b
-            psi = np.concatenate([[0.0], np.cumsum(theta[i0:i0 + nb - 1])])
-            P = {d: abs(sum(z[i0 + m, int(pr3[i0 + m]) + 2 * d[m]] * np.exp(-1j * psi[m]) for m in range(nb)))
-                 for d in itertools.product((0, 1), repeat=nb)}
-            for m in range(nb):
-                soft[i0 + m] = max(p for d, p in P.items() if d[m] == 1) - max(p for d, p in P.items() if d[m] == 0)
-        fsum, f2sum = soft.mean(), (soft * soft).mean()
-        with np.errstate(invalid="ignore"):
-            fac = np.sqrt(f2sum - fsum * fsum)
-        if np.isfinite(fac) and fac > 0:
-            out[nb - 1] = np.trunc(np.clip(50.0 * soft / fac, -128.0, 127.0) + 128.0).astype(np.uint8)
-    return out
-
-
-def slm_at_zero(c, cf=1500.0):
-    """slmFrequencyDrift (lib/slm.cc:36-73) at t = 0 for a NONLINEAR candidate record, as the fine search adds it to f0"""
-    v1, v2, q1, q2 = float(c["V1"]), float(c["V2"]), float(c["p1"]), float(c["p2"])
-    den = np.sqrt(q1 * q1 + q2 * q2)
-    if den == 0:
-        return np.float32(0.0)
-    sign = 1.0 if (q1 * v1 + q2 * v2) > 0 else -1.0
-    return np.float32(-sign * abs(v1 * q1 + v2 * q2) / den * cf / 1500.0)
 
 
 @pytest.fixture(scope="module")
@@ -109,16 +51,6 @@ def _close(got, want, what):
     print("%s: %d of %d bytes differ (%.3f %%), largest difference %d" % (what, int((d > 0).sum()), d.size, 100.0 * (d > 0).mean(), int(d.max())))
     assert d.max() <= 1, what
     assert (d > 0).mean() <= 0.01, what
-
-
-def test_restatement_needs_no_gpu(G, data):
-    """the restatement alone, on the noise-free frame: every vector carries the transmitted bits and decodes"""
-    sym = G.wspr_symbols(TEXT)
-    for nb in range(3):
-        v = data["want"][4][nb]
-        assert np.array_equal(v >= 128, (sym >> 1).astype(bool)), nb
-        rc, msg = G.fano_decode(G.deinterleave(v))[:2]
-        assert rc == 0 and G.unpack_message(msg[:7].astype(np.int8)) == (0, TEXT)
 
 
 @pytest.mark.gpu

@@ -2,7 +2,7 @@
 """K10 (block demodulation) on the GPU:
   * the time of one uwspr_blockdemod_batch launch of 1, 64 and 512 items (HIP events around the launch:
     uwspr_debug_blockdemod_time), items spread over 8 frames of tests/test_gpu_osd_pipe.py's text_frame model;
-  * the distance of the 512-item call to the binary64 restatement (tests/test_gpu_blockdemod.py: block_restate), on its
+  * the distance of the 512-item call to the binary64 restatement (tests/blockdemod_exact.py: block_restate), on its
     first --check items (default: all): the share of bytes that differ and the largest difference;
   * pipe frames/s with block = 3 against block = 0 on the same stream of frames nothing decodes on (synth frames at -34 dB).
 Each GPU step runs in a child process of its own under a time limit; a step that fails ends the probe.
@@ -32,7 +32,7 @@ def _items(n, offs):
 def step_kernel(a):
     import torch
     import gr_uwspr_amd as G
-    from test_gpu_blockdemod import block_restate, frame_offset
+    from blockdemod_exact import block_restate, frame_offset
     from test_gpu_osd_pipe import text_frame
     seeds = list(range(100, 108))
     frames = np.stack([text_frame(G, "K1ABC FN42 37", s, -28.0) for s in seeds])
