@@ -17,6 +17,6 @@ from .context import (Context, FrameView, Pipe, host_threads, host_set_ranks, de
                       read_wav, decode_wav, wspr_pack, nhash, wspr_symbols, write_c2, tx_signals, tx_sigma, encode_wav,
                       tx_motions, slm_trajectories, slm_drift, sub_items, block_items, resample_design, resample_launch_counts, frontend_rotator, frontend_carrier_launch_counts,
                       supported_rate, blank_launch_counts, BLANK_BLOCK, tx_taps, tx_design,
-                      tx_carriers, tx_carrier_launch_counts, call_message, grids_bitmap, grid_ngrid, powers_mask)
+                      tx_carriers, tx_carrier_launch_counts, tx_fades, tx_impulses, tx_fade_design, tx_medium_launch_counts, call_message, grids_bitmap, grid_ngrid, powers_mask)
 from . import synth  # noqa: F401
 from .sweep import sweep_grid, sweep_grid_uniform  # noqa: F401

@@ -805,11 +805,16 @@ class Context:
         """375 S/s baseband samples [t0, t0 + n) of one channel's signals (tx_signals), as c2_read returns a .c2 file:
         numpy [n, 2] float32, or written into `out` (a torch CUDA float32 tensor of n pairs).  A signal with a "motion"
         (tx_motions) sends the call through uwspr_tx_baseband_moving, one with a "carrier" (tx_carriers: Hz; here it
-        only scales a motion's Doppler, the baseband is not rotated) through uwspr_tx_baseband_at."""
+        only scales a motion's Doppler, the baseband is not rotated) through uwspr_tx_baseband_at, one with a "fading"
+        (tx_fades) through uwspr_tx_baseband_medium."""
         signals = list(signals)
-        sig, mot, car = tx_signals(signals), tx_motions(signals), tx_carriers(signals)
+        sig, mot, car, fad = tx_signals(signals), tx_motions(signals), tx_carriers(signals), tx_fades(signals)
         sp = C.c_void_p(C.addressof(sig)) if len(sig) else None
-        if car is not None:
+        if fad is not None:
+            mp = None if mot is None else C.c_void_p(C.addressof(mot))
+            cp = None if car is None else C.c_void_p(car.ctypes.data)
+            call = lambda h, *a: self.L.uwspr_tx_baseband_medium(h, a[0], mp, cp, C.c_void_p(C.addressof(fad)), *a[1:])  # noqa: E731
+        elif car is not None:
             mp = None if mot is None else C.c_void_p(C.addressof(mot))
             call = lambda h, *a: self.L.uwspr_tx_baseband_at(h, a[0], mp, C.c_void_p(car.ctypes.data), *a[1:])  # noqa: E731
         else:
@@ -831,7 +836,7 @@ class Context:
         return iq
 
     def tx_render(self, signals, nframes, t0=0, channels=1, sigma=0.0, seed=0, background=None, background_gain=1.0,
-                  format="f32", out=None):
+                  format="f32", out=None, impulses=None):
         """12 kS/s audio frames [t0, t0 + nframes) of a `channels`-channel recording (uwspr_tx_render) -> numpy
         [nframes, channels] float32 / int16 (format "f32" / "s16"), or written into `out`, a torch CUDA tensor of that
         shape and dtype (what stream_push_audio / a pipe takes, with no PCIe crossing).  sigma, seed, background
@@ -840,10 +845,20 @@ class Context:
         output (once per call: keep it there for repeated renders), to host memory for host output.  A signal with a
         "motion" (tx_motions) sends the call through uwspr_tx_render_moving; one with a "carrier" (tx_carriers: integer
         Hz, 170 .. the option "tx_cutoff" - 250; the others stay at 1500) through uwspr_tx_render_at: the transmission is
-        centred on carrier + f0 Hz, and a channel may carry several carriers at once."""
+        centred on carrier + f0 Hz, and a channel may carry several carriers at once.  A signal with a "fading"
+        (tx_fades), or impulses -- a dict {"rate": events per sample, "sigma", "seed": 0, "length": 1} or a list of one
+        (or None) per channel: Bernoulli-Gaussian bursts between the AWGN and the background -- send the call through
+        uwspr_tx_render_medium."""
         signals = list(signals)
-        sig, mot, car = tx_signals(signals), tx_motions(signals), tx_carriers(signals)
-        if car is not None:
+        sig, mot, car, fad = tx_signals(signals), tx_motions(signals), tx_carriers(signals), tx_fades(signals)
+        imp = tx_impulses(impulses, int(channels))
+        if fad is not None or imp is not None:
+            mp = None if mot is None else C.c_void_p(C.addressof(mot))
+            cp = None if car is None else C.c_void_p(car.ctypes.data)
+            fp = None if fad is None else C.c_void_p(C.addressof(fad))
+            ip_ = None if imp is None else C.c_void_p(C.addressof(imp))
+            call = lambda h, *a: self.L.uwspr_tx_render_medium(h, a[0], mp, cp, fp, a[1], a[2], ip_, *a[3:])  # noqa: E731
+        elif car is not None:
             mp = None if mot is None else C.c_void_p(C.addressof(mot))
             call = lambda h, *a: self.L.uwspr_tx_render_at(h, a[0], mp, C.c_void_p(car.ctypes.data), *a[1:])  # noqa: E731
         else:
@@ -1097,6 +1112,31 @@ def tx_carrier_launch_counts():
     return int(out[0]), int(out[1])
 
 
+def tx_medium_launch_counts():
+    """diagnostics: launches of K7's medium form since the process started -> (float32 output, int16 output, baseband)"""
+    f = N.lib().uwspr_debug_tx_medium_counts
+    f.argtypes = [C.c_void_p]
+    f.restype = C.c_int
+    out = np.zeros(3, np.int64)
+    f(C.c_void_p(out.ctypes.data))
+    return int(out[0]), int(out[1]), int(out[2])
+
+
+def tx_fade_design(fade):
+    """uwspr_tx_fade_design (host only, no device): a "fading" dict (tx_fades) -> (a0, a1, omega float64 [M] in rad per
+    baseband sample, phi float64 [M]): the gain is h(k) = a0 + a1 sum_m exp(j (omega_m k + phi_m)), k counted from the
+    transmission's first sample.  ValueError outside the ranges include/uwspr_hip.h gives."""
+    arr = tx_fades([{"fading": fade}])
+    a = np.zeros(2, np.float64)
+    om = np.zeros(N.TX_FADE_MAX_PATHS, np.float64)
+    ph = np.zeros(N.TX_FADE_MAX_PATHS, np.float64)
+    m = N.lib().uwspr_tx_fade_design(C.c_void_p(C.addressof(arr)), C.c_void_p(a.ctypes.data), C.c_void_p(om.ctypes.data),
+                                     C.c_void_p(ph.ctypes.data))
+    if m < 1:
+        raise ValueError("tx_fade_design: %r (spread 0 .. 20 Hz, |shift| <= 20 Hz, k 0 .. 1e6, paths 1 .. 32)" % (fade,))
+    return float(a[0]), float(a[1]), om[:m].copy(), ph[:m].copy()
+
+
 def frontend_rotator():
     """uwspr_frontend_rotator: K0's rotator table -> float32 [375, 2], row i = (cos, -sin)(2 pi i / 375); output m of a
     stream at carrier fc is multiplied by row ((fc mod 375) (m mod 375)) mod 375 unless 375 divides fc"""
@@ -1327,6 +1367,51 @@ def tx_carriers(signals):
     return out
 
 
+def tx_fades(signals):
+    """The uwspr_tx_fade array of a list of transmissions (tx_signals' dicts), or None when none has a "fading".  A fading
+    is a dict: "spread" (Hz: the Doppler spread, two sigma of a Gaussian Doppler spectrum, 0 .. 20), "shift" (Hz, the
+    scattered part's mean Doppler, 0), "k" (the Rician K factor, fixed : scattered power, 0 = Rayleigh), "seed" (0) and
+    "paths" (the sinusoids summed, 16; 1 with k = 0 is a pure Doppler shift).  A signal without one does not fade
+    (paths = 0).  include/uwspr_hip.h states the model."""
+    signals = list(signals)
+    if not any(s.get("fading") is not None for s in signals):
+        return None
+    arr = (N.TxFade * len(signals))()
+    for i, s in enumerate(signals):
+        f = s.get("fading")
+        if f is None:
+            continue
+        unknown = set(f) - {"spread", "shift", "k", "seed", "paths"}
+        if unknown:
+            raise ValueError("fading: unknown keys %s" % sorted(unknown))
+        arr[i].spread_hz, arr[i].shift_hz, arr[i].k_factor = float(f["spread"]), float(f.get("shift", 0.0)), float(f.get("k", 0.0))
+        arr[i].seed, arr[i].paths = int(f.get("seed", 0)) & (2 ** 64 - 1), int(f.get("paths", 16))
+    return arr
+
+
+def tx_impulses(impulses, channels):
+    """The uwspr_tx_impulse array of tx_render's `impulses` (None; one dict for every channel; or a list of one dict or
+    None per channel), or None when there are none.  Keys: "rate", "sigma", "seed" (0), "length" (1)."""
+    if impulses is None:
+        return None
+    per = list(impulses) if isinstance(impulses, (list, tuple)) else [impulses] * channels
+    if len(per) != channels:
+        raise ValueError("impulses: %d entries for %d channels" % (len(per), channels))
+    if all(z is None for z in per):
+        return None
+    arr = (N.TxImpulse * max(channels, 1))()
+    for k, z in enumerate(per):
+        arr[k].length = 1
+        if z is None:
+            continue
+        unknown = set(z) - {"rate", "sigma", "seed", "length"}
+        if unknown:
+            raise ValueError("impulses: unknown keys %s" % sorted(unknown))
+        arr[k].rate, arr[k].sigma = float(z["rate"]), float(z["sigma"])
+        arr[k].seed, arr[k].length = int(z.get("seed", 0)) & (2 ** 64 - 1), int(z.get("length", 1))
+    return arr
+
+
 _TX_MODELS = {"static": N.TX_STATIC, "doppler": N.TX_DOPPLER, "delay": N.TX_DELAY}
 
 
@@ -1393,13 +1478,14 @@ def tx_sigma(snr_db, gain=1.0):
     return float(np.sqrt(0.5 * a * a * (AUDIO_RATE / 2.0) / 2500.0 * 10.0 ** (-float(snr_db) / 10.0)))
 
 
-def encode_wav(path, schedule, channels=1, snr_db=None, seed=0, gain=1.0, seconds=None, piece_s=60, ctx=None):
+def encode_wav(path, schedule, channels=1, snr_db=None, seed=0, gain=1.0, seconds=None, piece_s=60, ctx=None, impulses=None):
     """c2ToWaveFile from text: a 16-bit 12 kS/s WAV of `channels` channels carrying the schedule's transmissions.
     schedule: (text, channel, start_s, f0) entries; start_s is the start of the entry's 2-minute slot (its first symbol
     is 1 s later, as in a .c2 file) and f0 the offset in Hz (the transmission is centred on 1500 + f0 Hz).  An entry may
     also be a tx_signals dict (a moving source: its "motion"; another carrier: its "carrier" in Hz, the transmission then
     centred on carrier + f0 -- what decode_wav(carriers=[...]) listens to), its gain `gain` unless it names one.  snr_db: AWGN per channel (seed + channel) for that SNR in 2500 Hz, None = none.  The file is rendered
-    in pieces of piece_s seconds and lasts `seconds` (default: until the last slot's frame is complete)."""
+    in pieces of piece_s seconds and lasts `seconds` (default: until the last slot's frame is complete).  A dict entry may
+    carry a "fading" (tx_fades); impulses: tx_render's (impulsive noise per channel)."""
     import wave
     sig, slots = [], []
     for e in schedule:
@@ -1424,7 +1510,7 @@ def encode_wav(path, schedule, channels=1, snr_db=None, seed=0, gain=1.0, second
             step = int(piece_s * AUDIO_RATE)
             for k in range(0, n, step):
                 x = ctx.tx_render(sig, min(step, n - k), t0=k, channels=channels, sigma=sigma,
-                                  seed=[int(seed) + c for c in range(int(channels))], format="s16")
+                                  seed=[int(seed) + c for c in range(int(channels))], format="s16", impulses=impulses)
                 w.writeframes(x.astype("<i2").tobytes())
     finally:
         if own:

@@ -40,6 +40,12 @@
 // A chain starts at +0 and never becomes -0, so a group whose signals are all silent adds +0 and changes no byte:
 // the host may drop signals outside a call's window, and pieces still concatenate.  The four <CARRIER = false>
 // instances are the kernels they were; with every carrier at 1500 Hz and the cut-off at 2500 Hz they are what runs.
+//
+// A medium between source and hydrophone (<MEDIUM = true>, on the carrier form only; include/uwspr_hip.h states it to the
+// bit).  A faded signal's sample is multiplied by h(k) = a0 + a1 sum_m e^{j (w_m k + phi_m)}, k = j - start: up to 32 more
+// binary64 sincos per baseband sample, in the staging loop -- the FIR reads what it always read.  A channel's impulses
+// (Bernoulli-Gaussian bursts, Philox blocks of their own) are added in the epilogue between the AWGN and the background.
+// Calls in which nothing fades and no channel has impulses run the kernels they ran before.
 #include <math.h>
 #include <stdarg.h>
 #include <stdio.h>
@@ -126,6 +132,28 @@ constexpr int K7_GOFF = UWSPR_PIPE_MAX_CHANNELS + 2;   // C + 1 offsets, padded 
 constexpr int K7_MAX_CARRIERS = 64;                    // distinct carriers in one call
 static_assert((K7_NROT * sizeof(float2) + K7_GOFF * sizeof(int)) % 16 == 0 && sizeof(tx_dgrp) == 16, "the block's parts stay aligned");
 
+// A signal's fade as the kernels read it, beside its tx_dsig (same index): uwspr_tx_fade_design's output.  paths = 0: the
+// signal does not fade.
+constexpr int K7_FADE_MAX = 32;
+struct tx_dfade {
+  double a0, a1;
+  int paths;
+  int _pad;
+  double om[K7_FADE_MAX];   // rad per baseband sample
+  double ph[K7_FADE_MAX];
+};
+static_assert(sizeof(tx_dfade) == 24 + 16 * K7_FADE_MAX, "tx_dfade is 8-byte aligned in arrays");
+
+// A channel's impulses as the kernels read them, beside its tx_dchan (same index).  thr = 0: none.
+struct tx_dimp {
+  unsigned long long seed;
+  uint32_t thr;         // index e is an event when word x of its block is below thr
+  float sigma;
+  int length;
+  int _pad;
+};
+static_assert(sizeof(tx_dimp) == 24, "tx_dimp is 8-byte aligned in arrays");
+
 // ---------------------------------------------------------------- device side
 __device__ __forceinline__ void tx_add(const tx_dsig &s, long long j, float &re, float &im) {
   const long long k = j - s.start;
@@ -164,6 +192,71 @@ __device__ __forceinline__ void tx_add_moving(const tx_dsig &s, const tx_dmot &m
   sincos(th, &sn, &cs);
   re += g * (float)cs;
   im -= g * (float)sn;
+}
+
+// The medium form's tx_add / tx_add_moving: theta, the gain and the support are theirs, expression for expression (with
+// D = 0 the Doppler term is not subtracted at all, as tx_add has it); a signal with f.paths = 0 ends as they end, a faded
+// one is turned by h(k), k = j - start, in binary64 before the one rounding to binary32.
+template <bool MOVING>
+__device__ __forceinline__ void tx_add_medium(const tx_dsig &s, const tx_dmot *m, const tx_dfade &f, long long j,
+                                              float &re, float &im) {
+  const long long k = j - s.start;
+  bool moves = false;
+  if constexpr (MOVING) moves = m->model != UWSPR_TX_STATIC;
+  int q;
+  double r, th;
+  float g = s.gain;
+  if (moves) {
+    if (k < m->lo || k >= m->hi) return;
+    const double t = m->t_first + (double)k / K7_FS;
+    const double R = hypot(m->v1 * t + m->p1, m->v2 * t + m->p2);
+    const double d = (R - m->rref) / K7_C;
+    double kp = (double)k;
+    if (m->model == UWSPR_TX_DELAY) {
+      kp -= K7_FS * d;
+      if (!(kp >= 0.0 && kp < (double)K7_NTX)) return;
+    }
+    q = (int)floor(kp * (1.0 / 256.0));
+    r = kp - 256.0 * (double)q;
+    th = s.ph[q] + r * (K7_TWO_PI * ((double)s.sym[q] - 1.5) / 256.0 + s.wf) +
+         s.wd * (r * ((double)(256 * q) - 0.5 * (K7_NTX - 1)) + 0.5 * r * (r - 1.0)) -
+         (K7_TWO_PI * (double)s.fc) * d;
+    if (m->flags & UWSPR_TX_SPREADING) g = (float)((double)s.gain * (m->r0 / R));
+  } else {
+    if (k < 0 || k >= K7_NTX) return;
+    q = (int)(k >> 8);
+    r = (double)(int)(k & 255);
+    th = s.ph[q] + r * (K7_TWO_PI * ((double)s.sym[q] - 1.5) / 256.0 + s.wf) +
+         s.wd * (r * ((double)(256 * q) - 0.5 * (K7_NTX - 1)) + 0.5 * r * (r - 1.0));
+  }
+  double sn, cs;
+  sincos(th, &sn, &cs);
+  if (f.paths > 0) {
+    const double kd = (double)k;
+    double sr = 0.0, si = 0.0;
+    for (int p = 0; p < f.paths; p++) {       // m ascending, one binary64 add each
+      double sp, cp;
+      sincos(f.om[p] * kd + f.ph[p], &sp, &cp);
+      sr += cp;
+      si += sp;
+    }
+    const double hr = f.a0 + f.a1 * sr, hi = f.a1 * si;
+    const double yr = cs * hr - sn * hi, yi = cs * hi + sn * hr;
+    re += g * (float)yr;
+    im -= g * (float)yi;
+  } else {
+    re += g * (float)cs;
+    im -= g * (float)sn;
+  }
+}
+
+template <bool MOVING>
+__device__ __forceinline__ float2 tx_baseband_medium(const tx_dsig *__restrict__ sigs, const tx_dmot *__restrict__ mots,
+                                                     const tx_dfade *__restrict__ fades, int nsig, int ch, long long j) {
+  float re = 0.0f, im = 0.0f;
+  for (int s = 0; s < nsig; s++)
+    if (sigs[s].channel == ch) tx_add_medium<MOVING>(sigs[s], MOVING ? mots + s : nullptr, fades[s], j, re, im);
+  return make_float2(re, im);
 }
 
 // baseband sample j of a channel in the file's orientation (I + jQ = gain e^{-j theta}: what wsprsim writes and
@@ -210,6 +303,27 @@ __device__ __forceinline__ float tx_gauss(unsigned long long seed, int ch, long 
   const float u1 = ((float)(r.x >> 8) + 0.5f) * (1.0f / 16777216.0f);
   const float u2 = (float)(r.y >> 8) * (1.0f / 16777216.0f);            // [0, 1)
   return sqrtf(-2.0f * logf(u1)) * cospif(2.0f * u2);
+}
+
+// tx_gauss's Box-Muller on words x, y of a block that the caller drew
+__device__ __forceinline__ float tx_gauss_of(uint4 r) {
+  const float u1 = ((float)(r.x >> 8) + 0.5f) * (1.0f / 16777216.0f);
+  const float u2 = (float)(r.y >> 8) * (1.0f / 16777216.0f);
+  return sqrtf(-2.0f * logf(u1)) * cospif(2.0f * u2);
+}
+
+// What channel ch's impulses add to audio sample n, v being the sample after its AWGN: the events e = n - d >= 0,
+// d ascending, one binary32 add each.  Event test: counter (e, ch, 1); burst sample d: counter (e, ch, 2 + d).
+__device__ __forceinline__ float tx_impulses(const tx_dimp &z, int ch, long long n, float v) {
+  const uint2 key = make_uint2((uint32_t)z.seed, (uint32_t)(z.seed >> 32));
+  for (int d = 0; d < z.length; d++) {
+    const long long e = n - d;
+    if (e < 0) break;
+    const uint32_t lo = (uint32_t)e, hi = (uint32_t)((unsigned long long)e >> 32);
+    if (philox4x32_10(make_uint4(lo, hi, (uint32_t)ch, 1u), key).x < z.thr)
+      v += z.sigma * tx_gauss_of(philox4x32_10(make_uint4(lo, hi, (uint32_t)ch, 2u + (uint32_t)d), key));
+  }
+  return v;
 }
 
 __device__ __forceinline__ int16_t tx_s16(float v) {   // fl32(32767 x) clamped to [-32768, 32767], then to nearest, halves to even
@@ -275,11 +389,14 @@ __device__ __forceinline__ void k7_fir(const float2 *xs, const float2 *tp, float
 // CARRIER: `taps` is the carrier form's block (tx_dgrp above) and the workgroup walks its channel's carrier groups.  Between
 // two groups every wavefront must be done reading the window and the taps before they are staged again (the barrier at
 // the loop's head); a thread adds into the ys words it stored itself, so ys needs none until the epilogue.
-template <bool S16, bool MOVING, bool CARRIER = false>
+// MEDIUM (with CARRIER): fades[s] belongs to sigs[s], imps[ch] to chans[ch]; the other instances never read either.
+template <bool S16, bool MOVING, bool CARRIER = false, bool MEDIUM = false>
 __global__ __launch_bounds__(K7_WG) void k7_render(const tx_dsig *__restrict__ sigs, const tx_dmot *__restrict__ mots, int nsig,
                                                    const tx_dchan *__restrict__ chans, int C,
                                                    const float2 *__restrict__ taps, long long t0, long long nframes,
-                                                   long long nb0, void *__restrict__ out) {
+                                                   long long nb0, void *__restrict__ out,
+                                                   const tx_dfade *__restrict__ fades, const tx_dimp *__restrict__ imps) {
+  static_assert(CARRIER || !MEDIUM, "the medium form is built on the carrier form");
   extern __shared__ __align__(16) float k7_lds[];
   float2 *xs = reinterpret_cast<float2 *>(k7_lds);          // [8][K7_G]
   float2 *tp = xs + K7_NX;                                  // [32][K7_T]
@@ -303,7 +420,9 @@ __global__ __launch_bounds__(K7_WG) void k7_render(const tx_dsig *__restrict__ s
       if constexpr (MOVING) mz = mots + gr.sig0;
       for (int col = tid; col < K7_NX; col += K7_WG) {
         const long long j = mb - K7_T + col;
-        float2 x = tx_baseband_at<MOVING>(sigs + gr.sig0, mz, gr.nsig, ch, j);
+        float2 x;
+        if constexpr (MEDIUM) x = tx_baseband_medium<MOVING>(sigs + gr.sig0, mz, fades + gr.sig0, gr.nsig, ch, j);
+        else x = tx_baseband_at<MOVING>(sigs + gr.sig0, mz, gr.nsig, ch, j);
         if (gr.fcm) {
           int jm = (int)(j % K7_NROT);
           if (jm < 0) jm += K7_NROT;                         // j mod 375 in 0 .. 374 for negative j as well
@@ -351,12 +470,17 @@ __global__ __launch_bounds__(K7_WG) void k7_render(const tx_dsig *__restrict__ s
   }
   __syncthreads();
 
+  tx_dimp iz;
+  if constexpr (MEDIUM) iz = imps[ch];
   const long long n0 = (long long)K7_DEC * mb;
   for (int e = tid; e < K7_OUT; e += K7_WG) {
     const long long n = n0 + e;
     if (n < t0 || n - t0 >= nframes) continue;
     float v = ys[(e & 31) * K7_YP + (e >> 5)];
     if (cz.sigma > 0.0f) v += cz.sigma * tx_gauss(cz.seed, ch, n);
+    if constexpr (MEDIUM) {
+      if (iz.thr) v = tx_impulses(iz, ch, n, v);
+    }
     if (cz.bg) {
       const long long i = n % cz.bg_len;
       const float b = cz.bg_s16 ? (float)static_cast<const int16_t *>(cz.bg)[i] * (1.0f / 32768)
@@ -371,11 +495,13 @@ __global__ __launch_bounds__(K7_WG) void k7_render(const tx_dsig *__restrict__ s
 
 // baseband samples [t0, t0 + n) of one channel, as uwspr_c2_read returns a .c2 file (Q negated against the file:
 // gain e^{+j theta})
-template <bool MOVING>
+template <bool MOVING, bool MEDIUM = false>
 __global__ void k7_baseband(const tx_dsig *__restrict__ sigs, const tx_dmot *__restrict__ mots, int nsig, int ch,
-                            long long t0, int n, float2 *__restrict__ out) {
+                            long long t0, int n, float2 *__restrict__ out, const tx_dfade *__restrict__ fades) {
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
-    const float2 x = tx_baseband_at<MOVING>(sigs, mots, nsig, ch, t0 + i);
+    float2 x;
+    if constexpr (MEDIUM) x = tx_baseband_medium<MOVING>(sigs, mots, fades, nsig, ch, t0 + i);
+    else x = tx_baseband_at<MOVING>(sigs, mots, nsig, ch, t0 + i);
     out[i] = make_float2(x.x, -x.y);
   }
 }
@@ -392,12 +518,16 @@ struct tx_state {
   void *d_car = nullptr; size_t cap_car = 0;    // the call's block: rotator, group table, tap images (tx_dgrp)
   bool car_ready = false;                       // the carrier instances were given their LDS
   std::map<std::pair<int, int>, std::vector<float2>> images;   // (carrier, cut-off) -> tap image
+  // the medium form (nothing here is made until it first runs)
+  tx_dfade *d_fade = nullptr; size_t cap_fade = 0;
+  tx_dimp *d_imp = nullptr;
+  bool med_ready = false;                       // the medium instances were given their LDS
 };
 
 void tx_release(uwspr_ctx *c) {
   if (!c || !c->tx) return;
   tx_state *t = c->tx;
-  void *bufs[] = {t->d_taps, t->d_sig, t->d_mot, t->d_chan, t->d_out, t->d_bg, t->d_car};
+  void *bufs[] = {t->d_taps, t->d_sig, t->d_mot, t->d_chan, t->d_out, t->d_bg, t->d_car, t->d_fade, t->d_imp};
   for (void *b : bufs) if (b) (void)hipFree(b);
   delete t;
   c->tx = nullptr;
@@ -571,16 +701,59 @@ static int tx_motion_check(uwspr_ctx *c, int i, const uwspr_tx_motion &m, long l
   return UWSPR_OK;
 }
 
+// philox4x32_10 on the host (the fade design's draws)
+static void tx_philox_host(const uint32_t ctr[4], uint64_t seed, uint32_t out[4]) {
+  uint32_t c0 = ctr[0], c1 = ctr[1], c2 = ctr[2], c3 = ctr[3], k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
+  for (int i = 0; i < 10; i++) {
+    const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
+    const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
+    c1 = (uint32_t)p1; c3 = (uint32_t)p0; c0 = n0; c2 = n2;
+    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+  }
+  out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
+}
+
+static bool tx_fade_ok(const uwspr_tx_fade &f) {
+  return f.paths >= 1 && f.paths <= K7_FADE_MAX && tx_finite(f.spread_hz) && f.spread_hz >= 0.0 && f.spread_hz <= 20.0 &&
+         tx_finite(f.shift_hz) && fabs(f.shift_hz) <= 20.0 && tx_finite(f.k_factor) && f.k_factor >= 0.0 && f.k_factor <= 1e6;
+}
+
+// uwspr_tx_fade_design (include/uwspr_hip.h): binary64 throughout, each line one expression of the header's
+static int tx_fade_design(const uwspr_tx_fade &f, double a[2], double *omega, double *phi) {
+  if (!tx_fade_ok(f)) return UWSPR_ERR_ARG;
+  const int M = f.paths;
+  if (a) {
+    a[0] = sqrt(f.k_factor / (f.k_factor + 1.0));
+    a[1] = sqrt(1.0 / ((f.k_factor + 1.0) * (double)M));
+  }
+  for (int m = 0; m < M; m++) {
+    const uint32_t ctr[4] = {(uint32_t)m, 0u, 0x46414445u, 0u};
+    uint32_t w[4];
+    tx_philox_host(ctr, f.seed, w);
+    const double u1 = ((double)(w[0] >> 8) + 0.5) / 16777216.0;
+    const double u2 = (double)(w[1] >> 8) / 16777216.0;
+    const double u3 = (double)(w[2] >> 8) / 16777216.0;
+    const double nu = f.shift_hz + ((f.spread_hz / 2.0) * sqrt(-2.0 * log(u1))) * cos(K7_TWO_PI * u2);
+    if (omega) omega[m] = K7_TWO_PI * nu / K7_FS;
+    if (phi) phi[m] = K7_TWO_PI * u3;
+  }
+  return M;
+}
+
 // check the records (channel < C when C > 0; motions, when given) and build the device form of those that pass
 // keep(s, lo, hi) ([start + lo, start + hi): where the signal may be non-zero)
 // car: a carrier per signal in Hz, or null (1500 for all).  Every entry is checked against the context's "tx_cutoff",
 // the signals the window drops included; *other (when given) tells whether some signal's carrier is not 1500 Hz.
+// fade: a fade per signal, or null; checked like the carriers, designed for the kept signals into *fout (one per kept
+// signal, paths = 0 where the signal does not fade).
 template <typename Keep>
 static int tx_prepare(uwspr_ctx *c, const uwspr_tx_signal *sig, const uwspr_tx_motion *mot, const int32_t *car, int nsig, int C,
-                      Keep keep, std::vector<tx_dsig> &out, std::vector<tx_dmot> *mout, bool *other = nullptr) {
+                      Keep keep, std::vector<tx_dsig> &out, std::vector<tx_dmot> *mout, bool *other = nullptr,
+                      const uwspr_tx_fade *fade = nullptr, std::vector<tx_dfade> *fout = nullptr) {
   if (nsig < 0 || (nsig > 0 && !sig)) return tx_fail(c, UWSPR_ERR_ARG, "uwspr_tx: signals %p, nsig %d", (const void *)sig, nsig);
   out.clear();
   if (mout) mout->clear();
+  if (fout) fout->clear();
   if (other) *other = false;
   const int cutoff = c->opt[UWSPR_OPT_TX_CUTOFF];
   std::vector<int> distinct;
@@ -593,6 +766,10 @@ static int tx_prepare(uwspr_ctx *c, const uwspr_tx_signal *sig, const uwspr_tx_m
   }
   if ((int)distinct.size() > K7_MAX_CARRIERS)
     return tx_fail(c, UWSPR_ERR_ARG, "uwspr_tx: %zu distinct carriers (<= %d)", distinct.size(), K7_MAX_CARRIERS);
+  for (int i = 0; fade && i < nsig; i++)
+    if (fade[i].paths != 0 && !tx_fade_ok(fade[i]))
+      return tx_fail(c, UWSPR_ERR_ARG, "uwspr_tx: fade %d: spread %g Hz (0 .. 20), shift %g Hz (|.| <= 20), K %g (0 .. 1e6), paths %d (0 .. %d)",
+                     i, fade[i].spread_hz, fade[i].shift_hz, fade[i].k_factor, fade[i].paths, K7_FADE_MAX);
   for (int i = 0; i < nsig; i++) {
     const uwspr_tx_signal &s = sig[i];
     for (int k = 0; k < K7_NSYM; k++)
@@ -616,6 +793,16 @@ static int tx_prepare(uwspr_ctx *c, const uwspr_tx_signal *sig, const uwspr_tx_m
       dm.v1 = m.v1; dm.v2 = m.v2; dm.p1 = m.p1; dm.p2 = m.p2; dm.t_first = m.t_first;
       dm.lo = lo; dm.hi = hi; dm.model = m.model; dm.flags = m.flags;
       mout->push_back(dm);
+    }
+    if (fout) {
+      tx_dfade df;
+      memset(&df, 0, sizeof(df));
+      if (fade && fade[i].paths != 0) {
+        double a[2];
+        df.paths = tx_fade_design(fade[i], a, df.om, df.ph);
+        df.a0 = a[0]; df.a1 = a[1];
+      }
+      fout->push_back(df);
     }
     tx_dsig d;
     memset(&d, 0, sizeof(d));
@@ -725,16 +912,34 @@ static int tx_carrier_block(uwspr_ctx *c, const std::vector<tx_dsig> &v, int C, 
 
 using namespace uwspr;
 
-static int tx_baseband(uwspr_ctx *c, const uwspr_tx_signal *sig, const uwspr_tx_motion *mot, const int32_t *car, int nsig,
-                       int channel, long long t0, int n, float *iq, int where) {
+static bool tx_any_fading(const std::vector<tx_dfade> &f) {
+  for (const tx_dfade &d : f)
+    if (d.paths > 0) return true;
+  return false;
+}
+
+// the fades beside the signals
+static int tx_upload_fades(uwspr_ctx *c, const std::vector<tx_dfade> &f) {
+  tx_state *t = c->tx;
+  int rc = tx_grow(c, (void **)&t->d_fade, &t->cap_fade, f.size() * sizeof(tx_dfade));
+  if (rc) return rc;
+  if (!f.empty()) TXCHK(c, hipMemcpyAsync(t->d_fade, f.data(), f.size() * sizeof(tx_dfade), hipMemcpyHostToDevice, c->stream));
+  return UWSPR_OK;
+}
+
+static std::atomic<long long> k7_medium_launches[3];   // launches of the medium form since the process started (f32, s16, baseband)
+
+static int tx_baseband(uwspr_ctx *c, const uwspr_tx_signal *sig, const uwspr_tx_motion *mot, const int32_t *car,
+                       const uwspr_tx_fade *fade, int nsig, int channel, long long t0, int n, float *iq, int where) {
   if (!c) return UWSPR_ERR_ARG;
   if (n < 0 || (n > 0 && !iq) || channel < 0 || (where != UWSPR_HOST && where != UWSPR_DEVICE))
     return tx_fail(c, UWSPR_ERR_ARG, "uwspr_tx_baseband: n %d, iq %p, channel %d, where %d", n, (void *)iq, channel, where);
   std::vector<tx_dsig> v;
   std::vector<tx_dmot> mv;
+  std::vector<tx_dfade> fv;
   int rc = tx_prepare(c, sig, mot, car, nsig, 0, [&](const uwspr_tx_signal &s, long long lo, long long hi) {
     return s.channel == channel && s.start + lo < t0 + n && s.start + hi > t0;
-  }, v, mot ? &mv : nullptr);
+  }, v, mot ? &mv : nullptr, nullptr, fade, fade ? &fv : nullptr);
   if (rc) return rc;
   if (n == 0) return UWSPR_OK;
   if ((rc = tx_device_ready(c))) return rc;
@@ -744,6 +949,8 @@ static int tx_baseband(uwspr_ctx *c, const uwspr_tx_signal *sig, const uwspr_tx_
   if ((rc = tx_upload_signals(c, v))) return rc;
   const bool moving = tx_any_moving(mv);
   if (moving && (rc = tx_upload_motions(c, mv))) return rc;
+  const bool medium = tx_any_fading(fv);
+  if (medium && (rc = tx_upload_fades(c, fv))) return rc;
   tx_state *t = c->tx;
   float2 *dst = (float2 *)iq;
   if (where == UWSPR_HOST) {
@@ -752,10 +959,16 @@ static int tx_baseband(uwspr_ctx *c, const uwspr_tx_signal *sig, const uwspr_tx_
   }
   TXCHK(c, hipStreamSynchronize(c->stream));   // (the records live on this call's stack)
   const int blocks = (n + 255) / 256 < 2048 ? (n + 255) / 256 : 2048;
-  if (moving)
-    hipLaunchKernelGGL(k7_baseband<true>, dim3(blocks), dim3(256), 0, c->stream, t->d_sig, t->d_mot, (int)v.size(), channel, t0, n, dst);
+  const tx_dfade *nofade = nullptr;
+  if (medium && moving)
+    hipLaunchKernelGGL((k7_baseband<true, true>), dim3(blocks), dim3(256), 0, c->stream, t->d_sig, t->d_mot, (int)v.size(), channel, t0, n, dst, t->d_fade);
+  else if (medium)
+    hipLaunchKernelGGL((k7_baseband<false, true>), dim3(blocks), dim3(256), 0, c->stream, t->d_sig, (const tx_dmot *)nullptr, (int)v.size(), channel, t0, n, dst, t->d_fade);
+  else if (moving)
+    hipLaunchKernelGGL(k7_baseband<true>, dim3(blocks), dim3(256), 0, c->stream, t->d_sig, t->d_mot, (int)v.size(), channel, t0, n, dst, nofade);
   else
-    hipLaunchKernelGGL(k7_baseband<false>, dim3(blocks), dim3(256), 0, c->stream, t->d_sig, (const tx_dmot *)nullptr, (int)v.size(), channel, t0, n, dst);
+    hipLaunchKernelGGL(k7_baseband<false>, dim3(blocks), dim3(256), 0, c->stream, t->d_sig, (const tx_dmot *)nullptr, (int)v.size(), channel, t0, n, dst, nofade);
+  if (medium) k7_medium_launches[2]++;
   TXCHK(c, hipGetLastError());
   if (where == UWSPR_HOST) {
     TXCHK(c, hipMemcpyAsync(iq, dst, (size_t)n * sizeof(float2), hipMemcpyDeviceToHost, c->stream));
@@ -764,8 +977,9 @@ static int tx_baseband(uwspr_ctx *c, const uwspr_tx_signal *sig, const uwspr_tx_
   return UWSPR_OK;
 }
 
-static int tx_render(uwspr_ctx *c, const uwspr_tx_signal *sig, const uwspr_tx_motion *mot, const int32_t *car, int nsig,
-                     const uwspr_tx_channel *chan, int C, long long t0, long long nframes, int format, void *out, int where) {
+static int tx_render(uwspr_ctx *c, const uwspr_tx_signal *sig, const uwspr_tx_motion *mot, const int32_t *car,
+                     const uwspr_tx_fade *fade, int nsig, const uwspr_tx_channel *chan, const uwspr_tx_impulse *imp, int C,
+                     long long t0, long long nframes, int format, void *out, int where) {
   if (!c) return UWSPR_ERR_ARG;
   if (C < 1 || C > UWSPR_PIPE_MAX_CHANNELS || !chan || t0 < 0 || nframes < 0 || (nframes > 0 && !out) ||
       (format != UWSPR_AUDIO_F32 && format != UWSPR_AUDIO_S16) || (where != UWSPR_HOST && where != UWSPR_DEVICE))
@@ -779,19 +993,40 @@ static int tx_render(uwspr_ctx *c, const uwspr_tx_signal *sig, const uwspr_tx_mo
       return tx_fail(c, UWSPR_ERR_ARG, "uwspr_tx_render: channel %d: sigma %g, background %p len %lld format %d gain %g", k,
                      z.sigma, z.background, (long long)z.background_len, z.background_format, (double)z.background_gain);
   }
+  // impulses: thr = min(floor(rate 2^32), 2^32 - 1) in binary64; rate 0 or sigma 0 (thr 0 here): none
+  std::vector<tx_dimp> di;
+  bool impulsive = false;
+  if (imp) {
+    di.resize(C);
+    for (int k = 0; k < C; k++) {
+      const uwspr_tx_impulse &z = imp[k];
+      if (!tx_finite(z.rate) || z.rate < 0.0 || z.rate > 0.25 || !tx_finite(z.sigma) || z.sigma < 0.0 || z.length < 1 || z.length > 8)
+        return tx_fail(c, UWSPR_ERR_ARG, "uwspr_tx_render: channel %d: impulse rate %g (0 .. 0.25), sigma %g (>= 0), length %d (1 .. 8)",
+                       k, z.rate, z.sigma, z.length);
+      tx_dimp &d = di[k];
+      memset(&d, 0, sizeof(d));
+      d.seed = z.seed; d.sigma = (float)z.sigma; d.length = z.length;
+      d.thr = z.sigma > 0.0 ? (uint32_t)std::min(floor(z.rate * 4294967296.0), 4294967295.0) : 0u;
+      if (d.thr) impulsive = true;
+    }
+  }
   // signals that reach [t0, t0 + nframes): audio 32 (start + lo) .. 32 (start + hi - 1) + 3178, [lo, hi) = [0, N)
   // unless delayed (the others add exact zeros)
   std::vector<tx_dsig> v;
   std::vector<tx_dmot> mv;
+  std::vector<tx_dfade> fv;
   bool other = false;
   int rc = tx_prepare(c, sig, mot, car, nsig, C, [&](const uwspr_tx_signal &s, long long lo, long long hi) {
     return K7_DEC * (s.start + lo) < t0 + nframes && K7_DEC * (s.start + hi - 1) + K7_NT - 1 >= t0;
-  }, v, mot ? &mv : nullptr, &other);
+  }, v, mot ? &mv : nullptr, &other, fade, fade ? &fv : nullptr);
   if (rc) return rc;
   if (nframes == 0) return UWSPR_OK;
+  // the medium form: only when a kept signal fades or a channel has impulses; it is built on the carrier form
+  const bool fading = tx_any_fading(fv);
+  const bool medium = fading || impulsive;
   // the carrier form: asked for by a carrier, by the cut-off or by "tx_form"; otherwise the 1500 Hz kernels, as ever
   const int cutoff = c->opt[UWSPR_OPT_TX_CUTOFF];
-  const bool carrier = other || cutoff != UWSPR_TX_CUTOFF_DEFAULT || c->opt[UWSPR_OPT_TX_FORM] != 0;
+  const bool carrier = medium || other || cutoff != UWSPR_TX_CUTOFF_DEFAULT || c->opt[UWSPR_OPT_TX_FORM] != 0;
   const size_t esz = format == UWSPR_AUDIO_S16 ? 2 : 4;
   if ((rc = tx_device_ready(c))) return rc;
   if (where == UWSPR_DEVICE) {   // device pointers must be device memory: a host pointer would fault the kernel
@@ -809,14 +1044,19 @@ static int tx_render(uwspr_ctx *c, const uwspr_tx_signal *sig, const uwspr_tx_mo
   const auto before = [carrier](const tx_dsig &a, const tx_dsig &b) {
     return a.channel != b.channel ? a.channel < b.channel : (carrier && a.fc < b.fc);
   };
-  if (moving) {
+  if (moving || medium) {   // (a fade moves with its signal too)
     std::vector<int> ix(v.size());
     for (size_t i = 0; i < ix.size(); i++) ix[i] = (int)i;
     std::stable_sort(ix.begin(), ix.end(), [&](int a, int b) { return before(v[a], v[b]); });
     std::vector<tx_dsig> vs(v.size());
-    std::vector<tx_dmot> ms(v.size());
-    for (size_t i = 0; i < ix.size(); i++) { vs[i] = v[ix[i]]; ms[i] = mv[ix[i]]; }
-    v.swap(vs); mv.swap(ms);
+    std::vector<tx_dmot> ms(mv.size());
+    std::vector<tx_dfade> fs(fv.size());
+    for (size_t i = 0; i < ix.size(); i++) {
+      vs[i] = v[ix[i]];
+      if (!mv.empty()) ms[i] = mv[ix[i]];
+      if (!fv.empty()) fs[i] = fv[ix[i]];
+    }
+    v.swap(vs); mv.swap(ms); fv.swap(fs);
   } else {
     std::stable_sort(v.begin(), v.end(), before);
   }
@@ -824,6 +1064,21 @@ static int tx_render(uwspr_ctx *c, const uwspr_tx_signal *sig, const uwspr_tx_mo
   tx_state *t = c->tx;
   if ((rc = tx_upload_signals(c, v))) return rc;
   if (moving && (rc = tx_upload_motions(c, mv))) return rc;
+  if (medium) {
+    if (!t->med_ready) {   // the first use gives the four medium instances their LDS
+      if (hipFuncSetAttribute(reinterpret_cast<const void *>(k7_render<false, false, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)k7_lds_bytes()) != hipSuccess ||
+          hipFuncSetAttribute(reinterpret_cast<const void *>(k7_render<true, false, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)k7_lds_bytes()) != hipSuccess ||
+          hipFuncSetAttribute(reinterpret_cast<const void *>(k7_render<false, true, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)k7_lds_bytes()) != hipSuccess ||
+          hipFuncSetAttribute(reinterpret_cast<const void *>(k7_render<true, true, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)k7_lds_bytes()) != hipSuccess)
+        return tx_fail(c, UWSPR_ERR_HIP, "transmit kernel (medium form): %zu bytes of LDS refused", k7_lds_bytes());
+      t->med_ready = true;
+    }
+    if (fv.size() != v.size()) fv.assign(v.size(), tx_dfade());   // (impulses alone: no signal fades)
+    if ((rc = tx_upload_fades(c, fv))) return rc;
+    if (di.empty()) di.assign(C, tx_dimp());
+    if (!t->d_imp) TXCHK(c, hipMalloc((void **)&t->d_imp, UWSPR_PIPE_MAX_CHANNELS * sizeof(tx_dimp)));
+    TXCHK(c, hipMemcpyAsync(t->d_imp, di.data(), C * sizeof(tx_dimp), hipMemcpyHostToDevice, c->stream));
+  }
   // channels: host backgrounds are staged behind each other
   std::vector<tx_dchan> dc(C);
   size_t bg_bytes = 0;
@@ -873,33 +1128,50 @@ static int tx_render(uwspr_ctx *c, const uwspr_tx_signal *sig, const uwspr_tx_mo
     void *dst = where == UWSPR_HOST ? t->d_out : (void *)((char *)out + (size_t)k * C * esz);
     const dim3 grid((unsigned)(nblk * C));
     const tx_dmot *dm = moving ? t->d_mot : nullptr;
-    if (carrier) {
+    const tx_dfade *nofade = nullptr;
+    const tx_dimp *noimp = nullptr;
+    if (medium) {
+      const float2 *blk = static_cast<const float2 *>(t->d_car);
+      if (format == UWSPR_AUDIO_S16 && moving)
+        hipLaunchKernelGGL((k7_render<true, true, true, true>), grid, dim3(K7_WG), k7_lds_bytes(), c->stream, t->d_sig, dm, (int)v.size(),
+                           t->d_chan, C, blk, a, len, nb0, dst, t->d_fade, t->d_imp);
+      else if (format == UWSPR_AUDIO_S16)
+        hipLaunchKernelGGL((k7_render<true, false, true, true>), grid, dim3(K7_WG), k7_lds_bytes(), c->stream, t->d_sig, dm, (int)v.size(),
+                           t->d_chan, C, blk, a, len, nb0, dst, t->d_fade, t->d_imp);
+      else if (moving)
+        hipLaunchKernelGGL((k7_render<false, true, true, true>), grid, dim3(K7_WG), k7_lds_bytes(), c->stream, t->d_sig, dm, (int)v.size(),
+                           t->d_chan, C, blk, a, len, nb0, dst, t->d_fade, t->d_imp);
+      else
+        hipLaunchKernelGGL((k7_render<false, false, true, true>), grid, dim3(K7_WG), k7_lds_bytes(), c->stream, t->d_sig, dm, (int)v.size(),
+                           t->d_chan, C, blk, a, len, nb0, dst, t->d_fade, t->d_imp);
+      k7_medium_launches[format == UWSPR_AUDIO_S16 ? 1 : 0]++;
+    } else if (carrier) {
       const float2 *blk = static_cast<const float2 *>(t->d_car);
       if (format == UWSPR_AUDIO_S16 && moving)
         hipLaunchKernelGGL((k7_render<true, true, true>), grid, dim3(K7_WG), k7_lds_bytes(), c->stream, t->d_sig, dm, (int)v.size(),
-                           t->d_chan, C, blk, a, len, nb0, dst);
+                           t->d_chan, C, blk, a, len, nb0, dst, nofade, noimp);
       else if (format == UWSPR_AUDIO_S16)
         hipLaunchKernelGGL((k7_render<true, false, true>), grid, dim3(K7_WG), k7_lds_bytes(), c->stream, t->d_sig, dm, (int)v.size(),
-                           t->d_chan, C, blk, a, len, nb0, dst);
+                           t->d_chan, C, blk, a, len, nb0, dst, nofade, noimp);
       else if (moving)
         hipLaunchKernelGGL((k7_render<false, true, true>), grid, dim3(K7_WG), k7_lds_bytes(), c->stream, t->d_sig, dm, (int)v.size(),
-                           t->d_chan, C, blk, a, len, nb0, dst);
+                           t->d_chan, C, blk, a, len, nb0, dst, nofade, noimp);
       else
         hipLaunchKernelGGL((k7_render<false, false, true>), grid, dim3(K7_WG), k7_lds_bytes(), c->stream, t->d_sig, dm, (int)v.size(),
-                           t->d_chan, C, blk, a, len, nb0, dst);
+                           t->d_chan, C, blk, a, len, nb0, dst, nofade, noimp);
       k7_carrier_launches[format == UWSPR_AUDIO_S16 ? 1 : 0]++;
     } else if (format == UWSPR_AUDIO_S16 && moving)
       hipLaunchKernelGGL((k7_render<true, true>), grid, dim3(K7_WG), k7_lds_bytes(), c->stream, t->d_sig, dm, (int)v.size(),
-                         t->d_chan, C, t->d_taps, a, len, nb0, dst);
+                         t->d_chan, C, t->d_taps, a, len, nb0, dst, nofade, noimp);
     else if (format == UWSPR_AUDIO_S16)
       hipLaunchKernelGGL((k7_render<true, false>), grid, dim3(K7_WG), k7_lds_bytes(), c->stream, t->d_sig, dm, (int)v.size(),
-                         t->d_chan, C, t->d_taps, a, len, nb0, dst);
+                         t->d_chan, C, t->d_taps, a, len, nb0, dst, nofade, noimp);
     else if (moving)
       hipLaunchKernelGGL((k7_render<false, true>), grid, dim3(K7_WG), k7_lds_bytes(), c->stream, t->d_sig, dm, (int)v.size(),
-                         t->d_chan, C, t->d_taps, a, len, nb0, dst);
+                         t->d_chan, C, t->d_taps, a, len, nb0, dst, nofade, noimp);
     else
       hipLaunchKernelGGL((k7_render<false, false>), grid, dim3(K7_WG), k7_lds_bytes(), c->stream, t->d_sig, dm, (int)v.size(),
-                         t->d_chan, C, t->d_taps, a, len, nb0, dst);
+                         t->d_chan, C, t->d_taps, a, len, nb0, dst, nofade, noimp);
     TXCHK(c, hipGetLastError());
     if (where == UWSPR_HOST) {
       TXCHK(c, hipMemcpyAsync((char *)out + (size_t)k * C * esz, dst, (size_t)len * C * esz, hipMemcpyDeviceToHost, c->stream));
@@ -925,34 +1197,60 @@ extern "C" int uwspr_debug_tx_taps(double *g, float *image) {
 
 extern "C" int uwspr_tx_baseband(uwspr_ctx *c, const uwspr_tx_signal *sig, int nsig, int channel, long long t0, int n,
                                  float *iq, int where) {
-  return tx_baseband(c, sig, nullptr, nullptr, nsig, channel, t0, n, iq, where);
+  return tx_baseband(c, sig, nullptr, nullptr, nullptr, nsig, channel, t0, n, iq, where);
 }
 
 extern "C" int uwspr_tx_baseband_moving(uwspr_ctx *c, const uwspr_tx_signal *sig, const uwspr_tx_motion *motion, int nsig,
                                         int channel, long long t0, int n, float *iq, int where) {
-  return tx_baseband(c, sig, motion, nullptr, nsig, channel, t0, n, iq, where);
+  return tx_baseband(c, sig, motion, nullptr, nullptr, nsig, channel, t0, n, iq, where);
 }
 
 extern "C" int uwspr_tx_render(uwspr_ctx *c, const uwspr_tx_signal *sig, int nsig, const uwspr_tx_channel *chan, int C,
                                long long t0, long long nframes, int format, void *out, int where) {
-  return tx_render(c, sig, nullptr, nullptr, nsig, chan, C, t0, nframes, format, out, where);
+  return tx_render(c, sig, nullptr, nullptr, nullptr, nsig, chan, nullptr, C, t0, nframes, format, out, where);
 }
 
 extern "C" int uwspr_tx_render_moving(uwspr_ctx *c, const uwspr_tx_signal *sig, const uwspr_tx_motion *motion, int nsig,
                                       const uwspr_tx_channel *chan, int C, long long t0, long long nframes, int format,
                                       void *out, int where) {
-  return tx_render(c, sig, motion, nullptr, nsig, chan, C, t0, nframes, format, out, where);
+  return tx_render(c, sig, motion, nullptr, nullptr, nsig, chan, nullptr, C, t0, nframes, format, out, where);
 }
 
 extern "C" int uwspr_tx_baseband_at(uwspr_ctx *c, const uwspr_tx_signal *sig, const uwspr_tx_motion *motion,
                                     const int32_t *carrier_hz, int nsig, int channel, long long t0, int n, float *iq, int where) {
-  return tx_baseband(c, sig, motion, carrier_hz, nsig, channel, t0, n, iq, where);
+  return tx_baseband(c, sig, motion, carrier_hz, nullptr, nsig, channel, t0, n, iq, where);
 }
 
 extern "C" int uwspr_tx_render_at(uwspr_ctx *c, const uwspr_tx_signal *sig, const uwspr_tx_motion *motion, const int32_t *carrier_hz,
                                   int nsig, const uwspr_tx_channel *chan, int C, long long t0, long long nframes, int format,
                                   void *out, int where) {
-  return tx_render(c, sig, motion, carrier_hz, nsig, chan, C, t0, nframes, format, out, where);
+  return tx_render(c, sig, motion, carrier_hz, nullptr, nsig, chan, nullptr, C, t0, nframes, format, out, where);
+}
+
+extern "C" int uwspr_tx_baseband_medium(uwspr_ctx *c, const uwspr_tx_signal *sig, const uwspr_tx_motion *motion,
+                                        const int32_t *carrier_hz, const uwspr_tx_fade *fade, int nsig, int channel,
+                                        long long t0, int n, float *iq, int where) {
+  return tx_baseband(c, sig, motion, carrier_hz, fade, nsig, channel, t0, n, iq, where);
+}
+
+extern "C" int uwspr_tx_render_medium(uwspr_ctx *c, const uwspr_tx_signal *sig, const uwspr_tx_motion *motion,
+                                      const int32_t *carrier_hz, const uwspr_tx_fade *fade, int nsig, const uwspr_tx_channel *chan,
+                                      const uwspr_tx_impulse *impulse, int C, long long t0, long long nframes, int format,
+                                      void *out, int where) {
+  return tx_render(c, sig, motion, carrier_hz, fade, nsig, chan, impulse, C, t0, nframes, format, out, where);
+}
+
+extern "C" int uwspr_tx_fade_design(const uwspr_tx_fade *f, double a[2], double *omega, double *phi) {
+  if (!f) return UWSPR_ERR_ARG;
+  return tx_fade_design(*f, a, omega, phi);
+}
+
+// Test door (not part of the ABI): launches of K7's medium form since the process started: out[0] float32 output,
+// out[1] int16 output, out[2] baseband
+extern "C" int uwspr_debug_tx_medium_counts(long long *out) {
+  if (!out) return UWSPR_ERR_ARG;
+  for (int i = 0; i < 3; i++) out[i] = k7_medium_launches[i].load();
+  return 3;
 }
 
 extern "C" int uwspr_tx_design_at(int carrier_hz, int cutoff_hz, double *g, float *image) {

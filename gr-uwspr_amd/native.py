@@ -246,7 +246,18 @@ class TxMotion(C.Structure):
                 ("model", C.c_int32), ("flags", C.c_int32)]
 
 
+class TxFade(C.Structure):
+    _fields_ = [("spread_hz", C.c_double), ("shift_hz", C.c_double), ("k_factor", C.c_double), ("seed", C.c_uint64),
+                ("paths", C.c_int32), ("_pad", C.c_int32)]
+
+
+class TxImpulse(C.Structure):
+    _fields_ = [("rate", C.c_double), ("sigma", C.c_double), ("seed", C.c_uint64), ("length", C.c_int32), ("_pad", C.c_int32)]
+
+
 assert C.sizeof(TxSignal) == 208 and C.sizeof(TxChannel) == 40 and C.sizeof(TxMotion) == 48
+assert C.sizeof(TxFade) == 40 and C.sizeof(TxImpulse) == 32
+TX_FADE_MAX_PATHS = 32
 TX_STATIC, TX_DOPPLER, TX_DELAY = 0, 1, 2
 TX_ABSOLUTE, TX_SPREADING = 1, 2
 
@@ -283,6 +294,7 @@ ABI_SYMBOLS = [
     "uwspr_c2_read",
     "uwspr_wspr_pack", "uwspr_nhash", "uwspr_wspr_symbols", "uwspr_c2_write", "uwspr_tx_baseband", "uwspr_tx_render",
     "uwspr_tx_baseband_moving", "uwspr_tx_render_moving", "uwspr_tx_baseband_at", "uwspr_tx_render_at", "uwspr_tx_design_at",
+    "uwspr_tx_render_medium", "uwspr_tx_baseband_medium", "uwspr_tx_fade_design",
     "uwspr_subtract_batch", "uwspr_osd_batch", "uwspr_blockdemod_batch", "uwspr_deep_set_list", "uwspr_deep_batch",
     "uwspr_calls_set", "uwspr_calls_batch", "uwspr_call_message",
     "uwspr_dist_unique_id", "uwspr_dist_init", "uwspr_dist_gather", "uwspr_dist_finalize",
@@ -392,6 +404,9 @@ def lib():
     L.uwspr_tx_baseband_at.argtypes = [vp, vp, vp, vp, ip, ip, C.c_longlong, ip, vp, ip]
     L.uwspr_tx_render_at.argtypes = [vp, vp, vp, vp, ip, vp, ip, C.c_longlong, C.c_longlong, ip, vp, ip]
     L.uwspr_tx_design_at.argtypes = [ip, ip, vp, vp]
+    L.uwspr_tx_baseband_medium.argtypes = [vp, vp, vp, vp, vp, ip, ip, C.c_longlong, ip, vp, ip]
+    L.uwspr_tx_render_medium.argtypes = [vp, vp, vp, vp, vp, ip, vp, vp, ip, C.c_longlong, C.c_longlong, ip, vp, ip]
+    L.uwspr_tx_fade_design.argtypes = [vp, vp, vp, vp]
     L.uwspr_subtract_batch.argtypes = [vp, vp, ip, ip, vp, ip, ip, vp, vp]
     L.uwspr_osd_batch.argtypes = [vp, vp, ip, ip, ip, vp]
     L.uwspr_blockdemod_batch.argtypes = [vp, vp, ip, ip, vp, ip, vp]

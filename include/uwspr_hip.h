@@ -55,7 +55,10 @@ extern "C" {
                                     uwspr_pipe_set_list, the pipe options "deep_min" and "deep_gap", uwspr_decode.osd = 2;
                                     call search (only entry points and a value of uwspr_decode.osd are added, so the
                                     version stays what it is): uwspr_call_result, uwspr_calls_set, uwspr_calls_batch, uwspr_call_message,
-                                    uwspr_pipe_set_calls, the pipe options "call_min" and "call_gap", uwspr_decode.osd = 3 */
+                                    uwspr_pipe_set_calls, the pipe options "call_min" and "call_gap", uwspr_decode.osd = 3;
+                                    transmit through a medium (entry points and records only, so the version stays):
+                                    uwspr_tx_fade, uwspr_tx_impulse, uwspr_tx_render_medium, uwspr_tx_baseband_medium,
+                                    uwspr_tx_fade_design */
 
 typedef enum {
   UWSPR_OK = 0,
@@ -928,6 +931,73 @@ int uwspr_tx_render_at(uwspr_ctx *ctx, const uwspr_tx_signal *sig, const uwspr_t
 int uwspr_tx_baseband_at(uwspr_ctx *ctx, const uwspr_tx_signal *sig, const uwspr_tx_motion *motion, const int32_t *carrier_hz,
                          int nsig, int channel, long long t0, int n, float *iq, int where);
 int uwspr_tx_design_at(int carrier_hz, int cutoff_hz, double *g, float *image);
+
+/* Transmit through a medium (K7's medium form): Doppler-spread fading per signal, impulsive noise per audio channel.
+ *
+ * Fading.  fade is NULL (no signal fades) or has nsig entries beside sig / motion / carrier_hz.  A signal with paths = M > 0
+ * is multiplied by a sum of M sinusoids (a Gaussian Doppler spectrum of standard deviation spread_hz / 2 around shift_hz:
+ * spread_hz is the two-sigma Doppler spread, Watterson's convention) plus a fixed part (Rician; k_factor = 0: Rayleigh).
+ * Design, on the host in binary64 (uwspr_tx_fade_design: a [2] = (a0, a1), omega [M], phi [M]; any may be NULL; returns
+ * M, or UWSPR_ERR_ARG outside the ranges below or with paths = 0).  For path m = 0 .. M - 1 take words x, y, z of the
+ * Philox4x32-10 block with counter (m, 0, 0x46414445, 0) and key (seed low word, seed high word):
+ *     u1 = ((x >> 8) + 0.5) / 2^24,  u2 = (y >> 8) / 2^24,  u3 = (z >> 8) / 2^24,
+ *     nu_m = shift_hz + (spread_hz / 2) sqrt(-2 ln u1) cos(2 pi u2)        Hz
+ *     omega_m = 2 pi nu_m / 375                                            rad per baseband sample
+ *     phi_m = 2 pi u3
+ *     a0 = sqrt(K / (K + 1)),  a1 = sqrt(1 / ((K + 1) M)):  a0^2 + M a1^2 = 1, the signal's mean power is unchanged.
+ * Gain.  k = j - start, the reception index of baseband sample j (an integer under every motion model, ABSOLUTE
+ * included, and bounded by the signal's support):
+ *     h(k) = a0 + a1 sum_m e^{j (omega_m k + phi_m)}
+ * each angle fl64(fl64(omega_m k) + phi_m), the real and the imaginary sum in binary64 from +0 with m ascending, then
+ * hr = fl64(a0 + fl64(a1 sum cos)), hi = fl64(a1 sum sin).
+ * Application.  With theta and the gain g (SPREADING included) as the unfaded signal has them, in uwspr_tx_baseband's
+ * orientation, and (cs, sn) = (cos theta, sin theta):
+ *     yr = cs hr - sn hi,   yi = cs hi + sn hr      (binary64, in that order)
+ *     re += g (float) yr,   im += g (float) yi      (binary32; the render's staging holds the conjugate)
+ * where the unfaded code has re += g (float) cs, im += g (float) sn.  The support (0 <= k < N, a DELAY motion's
+ * 0 <= k' < N) is the unfaded one.  paths = 1 with K = 0 is a pure Doppler shift nu_0 with phase phi_0.  Multipath stays
+ * several signals, each with its own fade.
+ * Refused with UWSPR_ERR_ARG before any launch, the output untouched, also where the window drops the signal: paths
+ * outside 0 .. 32; with paths > 0 a non-finite field, spread_hz outside 0 .. 20, |shift_hz| > 20, k_factor outside
+ * 0 .. 1e6.  An entry with paths = 0 is not read further. */
+typedef struct uwspr_tx_fade {
+  double spread_hz;   /* Doppler spread, 2 sigma of a Gaussian Doppler spectrum, 0 .. 20 */
+  double shift_hz;    /* mean Doppler of the scattered part, |.| <= 20 */
+  double k_factor;    /* Rician K, linear power ratio fixed : scattered, 0 (Rayleigh) .. 1e6 */
+  uint64_t seed;
+  int32_t paths;      /* M sinusoids, 1 .. 32; 0: this signal does not fade (entry ignored) */
+  int32_t _pad;
+} uwspr_tx_fade;
+/* Impulsive noise: Bernoulli-Gaussian bursts (snapping shrimp, clicks).  impulse is NULL (none) or has C entries beside
+ * chan.  With thr = (uint32) min(floor(rate 2^32), 2^32 - 1), made on the host in binary64:
+ *   event    audio index e >= 0 of channel c is an event when word x of the Philox4x32-10 block with counter
+ *            (e low, e high, c, 1) and key (seed low, seed high) is below thr (the AWGN's blocks have 0 in counter word
+ *            3: equal seeds still give independent streams);
+ *   sample   an event at e adds fl32(sigma_f32 gauss) to samples e + d, d = 0 .. length - 1, gauss being the AWGN's
+ *            Box-Muller on words x, y of the block with counter (e low, e high, c, 2 + d);
+ *   order    sample n collects its events in ascending d (e = n - d >= 0), one binary32 add each, after the AWGN add
+ *            and before the background add; the quantiser is unchanged.
+ * rate = 0 or sigma = 0: no impulses.  Nothing depends on a tile or a call: an event before t0 whose burst reaches into
+ * the window contributes.  Refused with UWSPR_ERR_ARG before any launch: a non-finite field, rate outside 0 .. 0.25,
+ * sigma < 0, length outside 1 .. 8. */
+typedef struct uwspr_tx_impulse {
+  double rate;      /* probability of an event per audio sample, 0 .. 0.25 */
+  double sigma;     /* standard deviation of an impulse sample (same units as uwspr_tx_channel.sigma), >= 0 */
+  uint64_t seed;
+  int32_t length;   /* samples per event, 1 .. 8 */
+  int32_t _pad;
+} uwspr_tx_impulse;
+/* uwspr_tx_render_at / uwspr_tx_baseband_at through a medium.  The medium form (new instances of the kernels, built on
+ * the carrier form: a group's faded and unfaded signals add in ascending index as ever) runs only when some kept signal
+ * has paths > 0 or some channel has impulses; otherwise these calls are uwspr_tx_render_at / uwspr_tx_baseband_at -- the
+ * same kernels, the same bytes, nothing new allocated.  Pieces concatenate and host and device output are the same bytes,
+ * as for every render. */
+int uwspr_tx_render_medium(uwspr_ctx *ctx, const uwspr_tx_signal *sig, const uwspr_tx_motion *motion, const int32_t *carrier_hz,
+                           const uwspr_tx_fade *fade, int nsig, const uwspr_tx_channel *chan, const uwspr_tx_impulse *impulse,
+                           int C, long long t0, long long nframes, int format, void *out, int where);
+int uwspr_tx_baseband_medium(uwspr_ctx *ctx, const uwspr_tx_signal *sig, const uwspr_tx_motion *motion, const int32_t *carrier_hz,
+                             const uwspr_tx_fade *fade, int nsig, int channel, long long t0, int n, float *iq, int where);
+int uwspr_tx_fade_design(const uwspr_tx_fade *f, double a[2], double *omega, double *phi);
 
 /* ---- known-symbol subtraction (K8, k8_subtract.hip) --------------------------------------------------------------- */
 /* A decoded transmission is rebuilt from its 162 channel symbols, fitted to the samples and taken out of them, so that a
