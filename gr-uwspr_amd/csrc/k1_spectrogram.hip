@@ -44,20 +44,6 @@ __device__ __forceinline__ constexpr int k1_slotA(int r) { return r; }
 __device__ __forceinline__ constexpr int k1_slotB(int e) { return xidx(8 * e); }
 __device__ __forceinline__ constexpr int k1_slotC(int a) { return xidx(64 * a); }
 
-#ifdef UWSPR_K1_STAMPS   // tools/k1_stamps.py: per-wavefront begin/end on the 100 MHz wall clock + hardware id
-__device__ unsigned long long k1_stamp_buf[3 * 16384];
-#define K1_STAMP(slot)                                                                      \
-  if (L == 0) {                                                                             \
-    const int wid = blockIdx.x * K1_WAVES + wv;                  \
-    if (wid < 16384) k1_stamp_buf[3 * wid + (slot)] =                                       \
-        (slot) == 2 ? ((unsigned long long)__builtin_amdgcn_s_getreg(20 | (31 << 11)) << 32) |      \
-                      (unsigned)__builtin_amdgcn_s_getreg(4 | (31 << 11))                   \
-                    : wall_clock64();                                                       \
-  }
-#else
-#define K1_STAMP(slot)
-#endif
-
 // NARROW: the band lies within columns 192..319 (bins 0..63 and 448..511): pass C computes only
 // register slots 0 and 7 (fft512_lane.h: pass_c_narrow), 9 % of the kernel's arithmetic less.
 template <bool NARROW>
@@ -79,7 +65,6 @@ __global__ __launch_bounds__(64 * K1_WAVES, 3) void k1_spectrogram(
   // K2 (next on the stream) appends to the coarse-search work list: reset its counter
   if (blockIdx.x == 0 && tid == 0) *work_count = 0;
 
-  K1_STAMP(0) K1_STAMP(2)
   tw_s[tid] = cpx{twiddle[tid].x, twiddle[tid].y};
   __syncthreads();
 
@@ -93,7 +78,7 @@ __global__ __launch_bounds__(64 * K1_WAVES, 3) void k1_spectrogram(
   const float2 *x = frames + (size_t)b * fstride;
   cpx *lds = xch[wv];
   const int row0 = (item - b * gpf) * rpw;
-  if (b >= B) { K1_STAMP(1) return; }   // wave-uniform; no workgroup barrier below
+  if (b >= B) return;   // wave-uniform; no workgroup barrier below
 
   // raw[(q + 2 ph) & 7] = x[128 row + L + 64 q] with ph = row phase: the next row's two new blocks
   // land in the two slots this row's q = 0, 1 leave dead after the window multiply -- no moves
@@ -152,14 +137,7 @@ __global__ __launch_bounds__(64 * K1_WAVES, 3) void k1_spectrogram(
     if (row + 2 < rend) do_row(row + 2, std::integral_constant<int, 2>{});
     if (row + 3 < rend) do_row(row + 3, std::integral_constant<int, 3>{});
   }
-  K1_STAMP(1)
 }
-
-#ifdef UWSPR_K1_STAMPS
-extern "C" int uwspr_debug_k1_stamps(unsigned long long *out, int nwaves) {
-  return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(k1_stamp_buf), sizeof(unsigned long long) * 3 * nwaves);
-}
-#endif
 
 void launch_spectrogram(uwspr_ctx *c, const float *frames, int B) {
   const fdr_consts &f = c->fc;

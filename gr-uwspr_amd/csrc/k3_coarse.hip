@@ -52,10 +52,7 @@ namespace uwspr {
 // 8 wavefronts per candidate: alone the kernel is as fast as with 16 (52 vs 50 us: its rounds are latency-bound),
 // and it leaves half of a CU's register file to the other lanes' kernels while more than half of its own
 // wavefront cycles are waits (+2.4 % frames/s under three streams; 4 wavefronts: 74 us alone, slower overall)
-#ifndef K3_THREADS_N
-#define K3_THREADS_N 512
-#endif
-constexpr int K3_THREADS = K3_THREADS_N;
+constexpr int K3_THREADS = 512;
 // Offset sequences: per (ifr row, distinct sequence) K3_SEQ_WORDS words = 168 x u16 (162 used; 16-B loads), entry k =
 // byte offset of the symbol's float4 in the tile relative to the float4 of (row k0 + 2*32*(k/32), the
 // cell's own centre column): ((2*(k mod 32))*tp + (ifd-ifr)[k] - off_min) * 16, tp = tile row pitch in
@@ -63,8 +60,8 @@ constexpr int K3_THREADS = K3_THREADS_N;
 // Pitch: consecutive lanes are consecutive sequences of one cell (same row: offsets differ by < 16
 // float4, no conflict inside a ds_read_b128 lane group), but a group that straddles two cells reads
 // rows one apart, i.e. float4 indices tp + (difference of offsets) apart: with tp = nc = 13 every
-// pair three columns apart collides (27 % of the kernel's LDS cycles); tp = 8 (mod 16) leaves only the
-// pairs eight columns apart (option "k3_pitch"=24; see coarse_tile_pitch() for why it is not the default).
+// pair three columns apart collides (27 % of the kernel's LDS cycles; see coarse_plan() for why the
+// compact pitch stays).
 //
 // Three tile forms (fdr_consts::k3_mode, chosen at context creation by what fits the 160 KB of LDS):
 //   K3_TILE_F4     float4 {sqrt ps[c-3], [c-1], [c+1], [c+3]} per (row, centre c) in LDS: one
@@ -130,9 +127,6 @@ __global__ __launch_bounds__(K3_THREADS, 1024 / K3_THREADS) void k3_coarse(
   int &s_cstar = *reinterpret_cast<int *>(smem + lay.misc);
   const int tid = threadIdx.x;
   const int nwork = work[0];
-#ifdef K3_STAMPS
-  long long t_a = clock64(), t_b = 0, t_c = 0, t_d = 0;
-#endif
   // persistent workgroups: K2 compacted the (frame, candidate) pairs into a work
   // list, so no workgroup is launched only to find it has no candidate
   for (int wi = blockIdx.x; wi < nwork; wi += gridDim.x) {
@@ -169,9 +163,6 @@ __global__ __launch_bounds__(K3_THREADS, 1024 / K3_THREADS) void k3_coarse(
   for (int idx = tid; idx < UWSPR_NIFR * f.cell_hyps; idx += K3_THREADS)
     umap[idx] = umap_tab[(size_t)r0 * f.cell_hyps + idx];
   __syncthreads();
-#ifdef K3_STAMPS
-  t_b = clock64();
-#endif
 
   // ---- one lane per (cell, offset sequence) ------------------------------------------------
   // Work items: first the linear hypotheses' sequences of all cells (NCELL * nlin items, reference
@@ -275,9 +266,6 @@ __global__ __launch_bounds__(K3_THREADS, 1024 / K3_THREADS) void k3_coarse(
     }
   }
   __syncthreads();
-#ifdef K3_STAMPS
-  t_c = clock64();
-#endif
 
   if (want_grid) {   // (cstar == NCELL: every sequence was evaluated)
     float *gout = syncgrid + ((size_t)b * grid_cap + j) * f.ntot;
@@ -352,9 +340,6 @@ __global__ __launch_bounds__(K3_THREADS, 1024 / K3_THREADS) void k3_coarse(
     }
   }
   __syncthreads();
-#ifdef K3_STAMPS
-  long long t_c2 = clock64();
-#endif
   if (tid < 64) {
     float best = -1e30f;
     int gbest = -1;
@@ -419,10 +404,6 @@ __global__ __launch_bounds__(K3_THREADS, 1024 / K3_THREADS) void k3_coarse(
     }
   }
   __syncthreads();  // LDS is reused by the next work item
-#ifdef K3_STAMPS
-  t_d = clock64();
-  if (tid == 0 && blockIdx.x == 7) printf("K3 stamps (cycles): stage %lld eval %lld expand %lld fold %lld\n", t_b - t_a, t_c - t_b, t_c2 - t_c, t_d - t_c2);
-#endif
   }
 }
 
@@ -430,16 +411,12 @@ size_t coarse_lds_bytes(const fdr_consts &f) { return k3_layout(f).total; }
 int coarse_seq_words() { return K3_SEQ_WORDS; }
 // Picks the tile form and its row pitch (f.k3_mode, f.tp); returns the floats of HBM scratch one
 // workgroup needs (0 unless the tile lives in HBM).
-size_t coarse_plan(fdr_consts &f, int pitch_opt, int tile_opt) {   // options "k3_pitch", "k3_tile"
+size_t coarse_plan(fdr_consts &f, int tile_opt) {   // option "k3_tile"
   // measured: pitch 24 instead of 13 made the kernel 3 % faster for 61 KB more LDS (the conflicts
-  // are not what bounds the gather loop) -- the compact tile stays the default
-  int want = f.nc;
-  if (pitch_opt >= f.nc) want = pitch_opt;
+  // are not what bounds the gather loop) -- the compact tile it is
   const int force = tile_opt;   // tests: 0 / 1 / 2
   f.k3_mode = K3_TILE_F4;
   if (force <= K3_TILE_F4) {
-    f.tp = want;
-    if (k3_layout(f).total <= 160 * 1024) return 0;
     f.tp = f.nc;
     if (k3_layout(f).total <= 160 * 1024) return 0;
   }

@@ -28,12 +28,9 @@
 namespace uwspr {
 
 constexpr int K4J_WAVES = 2;          // wavefronts per workgroup (independent)
-#ifndef K4J_OCC
-#define K4J_OCC 2
-#endif
 constexpr int K4J_PT_STRIDE = 18;     // float2 per (group, tone) row of the table slice: 16 steps + pad
 
-__global__ __launch_bounds__(64 * K4J_WAVES, K4J_OCC) void k4_jig(
+__global__ __launch_bounds__(64 * K4J_WAVES, 2) void k4_jig(
     const float2 *__restrict__ frames, int fstride, int np, int nframes, const dev_grp *__restrict__ grps,
     int G, float *__restrict__ p_out, const float2 *__restrict__ ptab, int gps) {
   constexpr int NL = 6, PPW = 16;

@@ -18,7 +18,7 @@ namespace uwspr {
 int coarse_configure(const fdr_consts &f);
 size_t coarse_lds_bytes(const fdr_consts &f);
 int coarse_seq_words();
-size_t coarse_plan(fdr_consts &f, int pitch_opt, int tile_opt);
+size_t coarse_plan(fdr_consts &f, int tile_opt);
 uint32_t coarse_seq_entry(const fdr_consts &f, int k, int off);
 }  // namespace uwspr
 
@@ -98,12 +98,10 @@ static const struct { const char *name; int dflt, lo, hi; } kOptions[UWSPR_NOPT]
     {"k5_lanes", -1, -1, 1},        // fold: -1 by size, 0 wave form, 1 lanes form
     {"k1_rows", 0, 0, 348},         // spectrogram: rows per wavefront walk (0: default)
     {"k3_tile", -1, -1, 2},         // coarse search: tile form (-1: by size)
-    {"k3_pitch", 0, 0, 4096},       // coarse search: tile row pitch (0: default)
     {"sched_stamps", 0, 0, 1},      // diagnostics: phase times of the fused kernel (uwspr_debug_sched_stamps)
-    {"sched_grid", 0, 0, 65536},    // fused kernel: workgroups (0: one per CU)
     {"dist_force_comm", 0, 0, 1},   // tests: a one-rank communicator is really created
     {"frontend", 0, 0, 1},          // K0: 0 the flowgraph's GNU Radio chain as one polyphase FIR (grc:303-400,840-956,1767-1808), 1 compact single stage
-    {"k4_forms", 1, 0, 255},        // staged form: bit 0 = S5 (k4_ring<6,8>) keeps its sample pairs in a register ring
+    {"k4_forms", 1, 0, 1},          // staged form: 1 S5 through the register-ring kernel k4_jig, 0 through k4_ring<6,8>
     {"audio_rate", 12000, 8000, 192000},   // uwspr_stream_push_audio: the rate of the pushed audio (12000: no resampler, else K11 ahead of K0)
     {"blank", 0, 0, 1024},          // uwspr_stream_push_audio: K12 ahead of K11 / K0, threshold in quarters of the block median (0: off; 4 .. 1024)
     {"blank_guard", 2, 0, 64},      // K12: samples zeroed either side of a flagged one
@@ -121,7 +119,6 @@ static void refresh_options(uwspr_ctx *c) {
   // the fast variant exists for the staged launches only: derived here, opt[] stays as the caller set it, so
   // fast_search = 0 later brings the fused kernel back and get_option("sched") reports what was asked for
   c->use_fused = c->opt[UWSPR_OPT_SCHED] != 0 && !c->fast_search;
-  c->sched_grid = c->opt[UWSPR_OPT_SCHED_GRID];
 }
 
 static int option_index(const char *name) {
@@ -135,7 +132,7 @@ extern "C" int uwspr_set_option(uwspr_ctx *c, const char *name, int value) {
   if (!c) return UWSPR_ERR_ARG;
   const int i = option_index(name);
   if (i < 0) return fail(c, UWSPR_ERR_ARG, "unknown option '%s'", name ? name : "(null)");
-  if (i == UWSPR_OPT_K1_ROWS || i == UWSPR_OPT_K3_TILE || i == UWSPR_OPT_K3_PITCH)
+  if (i == UWSPR_OPT_K1_ROWS || i == UWSPR_OPT_K3_TILE)
     return fail(c, UWSPR_ERR_ARG, "option '%s' shapes the context when it is created: UWSPR_OPTIONS=%s=%d", name, name, value);
   if (value < kOptions[i].lo || value > kOptions[i].hi)
     return fail(c, UWSPR_ERR_ARG, "option '%s' = %d: allowed %d .. %d", name, value, kOptions[i].lo, kOptions[i].hi);
@@ -368,7 +365,7 @@ extern "C" int uwspr_ctx_create(const uwspr_params *p, int device, uwspr_ctx **o
   }
   // [ifr][u][84] words of 2 x u16 tile byte offsets (coarse_seq_entry); rows with fewer distinct
   // sequences repeat sequence 0
-  const size_t k3_scratch = coarse_plan(f, c->opt[UWSPR_OPT_K3_PITCH], c->opt[UWSPR_OPT_K3_TILE]);   // tile form + pitch (k3_coarse.hip)
+  const size_t k3_scratch = coarse_plan(f, c->opt[UWSPR_OPT_K3_TILE]);   // tile form + pitch (k3_coarse.hip)
   const int sw = coarse_seq_words();
   std::vector<uint32_t> offw((size_t)f.n_ifr * f.umax * sw, 0u);
   for (int r = 0; r < f.n_ifr; r++)
@@ -956,8 +953,7 @@ static int run_schedule_impl(uwspr_ctx *c, const float *dframes, int B, const uw
   if ((rc = ensure(c, &c->d_state, &c->cap_state, nslots))) return rc;
   const int njig = c->ntries < UWSPR_NJIG ? c->ntries : UWSPR_NJIG;
   if (c->use_fused || njig < UWSPR_NJIG) {   // (a lazy staged pass is resumed by the fused kernel)
-    if (c->sched_grid <= 0) c->sched_grid = c->num_cus;   // one 16-wave workgroup per CU
-    if ((rc = ensure(c, &c->d_tabs, &c->cap_tabs, (size_t)c->sched_grid * kSchedTabFloats))) return rc;
+    if ((rc = ensure(c, &c->d_tabs, &c->cap_tabs, (size_t)c->num_cus * kSchedTabFloats))) return rc;   // one 16-wave workgroup per CU
     if (!c->d_counter) HIPCHK(c, hipMalloc((void **)&c->d_counter, 64));
   }
   if (c->use_fused) {
@@ -998,7 +994,6 @@ static int run_schedule_impl(uwspr_ctx *c, const float *dframes, int B, const uw
     const int H = (int)(nslots * (s == 5 ? njig : hpc[s]));
     const dev_hyp *h = half[s & 1];
     if (sk == 0 || (lazy && s == 5)) launch_tonecorr(c, dframes, B, h, H, c->d_p);   // (lazy S5: few, unrelated lags)
-#if !defined(UWSPR_S2_PAIRS) || UWSPR_S2_PAIRS   // (0: experiment builds, the flat kernel as before)
     else if (s == 2) {
       // S2: candidates that came in without drift have mirrored tries: one phasor recurrence for both (k4_pair.hip);
       // the others through the flat kernel, which leaves the former alone -- not needed after this context's own FDR
@@ -1006,9 +1001,6 @@ static int run_schedule_impl(uwspr_ctx *c, const float *dframes, int B, const uw
       launch_tonecorr_dpair(c, dframes, B, h, (int)nslots, c->d_p);
       if (!(c->cands_from_fdr && c->p.maxdrift == 0)) launch_tonecorr(c, dframes, B, h, H, c->d_p, nullptr, 1, true);
     }
-#else
-    else if (s == 2) launch_tonecorr(c, dframes, B, h, H, c->d_p);
-#endif
     else if (s == 1 || s == 4) launch_tonecorr_fstage(c, dframes, B, h, (int)nslots, H, c->d_p);
     else if (s == 3) launch_tonecorr_ring(c, dframes, B, c->d_grps, (int)nslots, 5, 16, H, c->d_p, 1);
     else if (s == 5 && (c->opt[UWSPR_OPT_K4_FORMS] & 1))

@@ -21,12 +21,10 @@ enum {
   UWSPR_OPT_K5_LANES,           // fold form: -1 by size (default), 0 wave form, 1 lanes form
   UWSPR_OPT_K1_ROWS,            // spectrogram rows per wavefront walk (0 = default)
   UWSPR_OPT_K3_TILE,            // coarse-search tile form (-1 = by size)
-  UWSPR_OPT_K3_PITCH,           // coarse-search tile row pitch (0 = default)
   UWSPR_OPT_SCHED_STAMPS,       // diagnostics: phase times of the fused kernel
-  UWSPR_OPT_SCHED_GRID,         // fused kernel: workgroups (0 = one per CU)
   UWSPR_OPT_DIST_FORCE_COMM,    // tests: a one-rank communicator is really created
   UWSPR_OPT_FRONTEND,           // K0 taps: 0 the flowgraph's three-stage GNU Radio chain (default), 1 the compact single stage
-  UWSPR_OPT_K4_FORMS,           // staged form, bit mask of kernel forms (default: all that won their A/B): bit 0 = S5 register ring
+  UWSPR_OPT_K4_FORMS,           // staged form: 1 (default) S5 through the register-ring kernel k4_jig, 0 through k4_ring<6,8>
   UWSPR_OPT_AUDIO_RATE,         // rate of the audio uwspr_stream_push_audio takes (default 12000: no resampler; else K11 ahead of K0)
   UWSPR_OPT_BLANK,              // uwspr_stream_push_audio: K12's threshold in quarters of the block median (default 0: no blanker)
   UWSPR_OPT_BLANK_GUARD,        // K12's guard G: samples zeroed either side of a flagged one (default 2)
@@ -86,12 +84,8 @@ __device__ __forceinline__ float ieee_divf(float x, float y) { return x / y; }
 // so the blocks that re-read the same symbol windows (the hypotheses of one candidate)
 // share one L2 instead of each missing in its own.  Pure placement: results unchanged.
 __device__ __forceinline__ unsigned xcd_swizzle(unsigned bid, unsigned nwg) {
-#ifdef UWSPR_NO_XCD_SWIZZLE
-  return bid;
-#else
   const unsigned q = nwg >> 3, r = nwg & 7u, x = bid & 7u;
   return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (bid >> 3);
-#endif
 }
 
 // Instruction-issue priority of the short kernels' wavefronts (s_setprio, 0..3).  Under several streams the kernels
@@ -99,10 +93,8 @@ __device__ __forceinline__ unsigned xcd_swizzle(unsigned bid, unsigned nwg) {
 // transition that takes 6 us alone took 40-65 us beside the other lanes' correlation launches, and every lane's chain
 // waits on five of them per step.  With priority 3 in the K5 family (folds, schedule init / transitions / finish,
 // slab packing) `value` rises 2 % (profiles/r03_ab_experiments.txt); raising K1..K3 or the S0..S4 correlation
-// launches above the jiggered-shift ring as well adds nothing.  -DUWSPR_SMALL_PRIO=0 restores the default priority.
-#ifndef UWSPR_SMALL_PRIO
-#define UWSPR_SMALL_PRIO 3
-#endif
+// launches above the jiggered-shift ring as well adds nothing.
+constexpr int kSmallPrio = 3;
 #define UWSPR_SET_PRIO(level) do { if ((level) > 0) __builtin_amdgcn_s_setprio(level); } while (0)
 
 // fine-grid hypothesis as the kernels consume it (24 B)
@@ -254,8 +246,7 @@ struct uwspr_ctx {
   uint8_t *next_slab = nullptr; int next_slab_K = 0; bool next_slab_done = false;   // uwspr_pipeline_slabs (one shot)
   int sched_per_frame = 1;   // candidate slots per frame of the schedule being launched
   // fused schedule (k6_sched)
-  int sched_grid;
-  size_t cap_tabs; float *d_tabs;     // [sched_grid][2][5][4][256](c, s) phasor tables
+  size_t cap_tabs; float *d_tabs;     // [num_cus][2][5][4][256](c, s) phasor tables
   int *d_counter;                     // candidate queue head of the running launch
   size_t cap_tmpc; uwspr_candidate *d_tmpc; size_t cap_tmpn; int32_t *d_tmpn;   // uwspr_demod_batch: host records staged
   // pinned staging for host -> device copies (two halves, ping-pong)

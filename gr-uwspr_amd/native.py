@@ -16,7 +16,7 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 LIBDIR = os.path.join(_HERE, "lib")
-# Experiment builds (UWSPR_EXTRA_HIPFLAGS set: -DK6_EXP=..., stamps, flag A/Bs) go to their OWN
+# An experiment build (UWSPR_EXTRA_HIPFLAGS set: extra compiler flags for an A/B) goes to its OWN
 # library file, so the product libuwspr_hip.so is never replaced by a build whose results may be
 # invalid; with the variable unset the product library is (re)built from the default flags.
 _EXTRA = os.environ.get("UWSPR_EXTRA_HIPFLAGS", "").replace(",", " ").split()   # (commas: for shell A/B scripts)

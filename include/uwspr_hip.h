@@ -492,8 +492,8 @@ int uwspr_set_tries(uwspr_ctx *ctx, int ntries);
  *                    tolerance), integer results and soft symbols were identical on every frame tried
  *                    (tests/test_gpu_fast_search.py); stage 5 -- the soft symbols -- and every other entry
  *                    point stay exact.  Staged form only (it sets "sched" 0).
- * Further names ("k4_t", "k5_lanes", "sched_stamps", "sched_grid", "dist_force_comm", and the
- * creation-time "k1_rows", "k3_tile", "k3_pitch") are diagnostics: DESIGN.md section 9.  The one environment
+ * Further names ("k4_t", "k5_lanes", "sched_stamps", "dist_force_comm", and the
+ * creation-time "k1_rows", "k3_tile") are diagnostics: DESIGN.md section 9.  The one environment
  * variable the library reads, UWSPR_OPTIONS="name=value,...", presets options for every context the process
  * creates.  Unknown names: UWSPR_ERR_ARG. */
 int uwspr_set_option(uwspr_ctx *ctx, const char *name, int value);

@@ -299,10 +299,9 @@ def test_schedule_matches_oracle(ctx, oracle, frames, vec):
 
 def test_schedule_forms_are_identical(G, frames, vec):
     """The refinement schedule exists in three independent forms -- the fused kernel (k6_sched), the staged launches
-    with the packed / ring / pair kernels (k4_lag0, k4_fpack, k4_ring, k4_dpair) and the staged launches with the flat
-    kernel (k4_tonecorr) for every stage -- each with and without the phasor tables and the stage-winner reuse:
-    byte-identical records.  (A fourth, the rows form of round 4, lost under three streams and left the library in
-    round 5: profiles/HISTORY.md.)"""
+    with the packed / ring / pair kernels (k4_lag0, k4_fpack, k4_jig or k4_ring, k4_dpair) and the staged launches with
+    the flat kernel (k4_tonecorr) for every stage -- each with and without the phasor tables and the stage-winner reuse:
+    byte-identical records.  (The forms that lost their A/Bs have left the library: profiles/HISTORY.md.)"""
     cands = [vec["cands"][b, :int(vec["npk"][b])] for b in range(4)]
     per = max(len(c) for c in cands)
     outs = []
@@ -314,8 +313,6 @@ def test_schedule_forms_are_identical(G, frames, vec):
                  {"sched": 0, "stage_kernels": 1, "phasor_tables": 0},
                  {"sched": 0, "stage_kernels": 1, "k4_forms": 0},      # S5 through the LDS-ring kernel (round 4's form)
                  {"sched": 0, "stage_kernels": 1, "k4_forms": 0, "reuse": 0},
-                 {"sched": 0, "stage_kernels": 1, "k4_forms": 3},      # S0 double-buffered, one barrier per chunk (round 6)
-                 {"sched": 0, "stage_kernels": 1, "k4_forms": 5},      # S0: + its lags on two wavefronts per tone
                  {"sched": 1, "reuse": 0}):
         c = G.Context(options=opts)
         try:
@@ -333,6 +330,9 @@ def test_options_are_checked(G, ctx):
         ctx.set_option("no_such_option", 1)
     with pytest.raises(G.UwsprError):
         ctx.set_option("k3_tile", 1)          # shapes the context at creation: UWSPR_OPTIONS only
+    for name, v in (("sched_grid", 1), ("k3_pitch", 24), ("k4_forms", 2)):   # two removed names; k4_forms is 0 .. 1
+        pytest.raises(G.UwsprError, ctx.set_option, name, v)
+    pytest.raises(G.UwsprError, G.Context, options={"k4_forms": 3})
     assert ctx.get_option("sched") in (0, 1)
 
 
@@ -865,11 +865,10 @@ def test_coarse_search_pruning_is_exact_for_every_threshold(G, oracle, threshold
 
 
 def test_coarse_search_tile_forms_agree(G, frames, monkeypatch):
-    """K3's three tile forms (float4 per centre in LDS -- the default --, plain sqrt rows in LDS,
-    sqrt rows in HBM: option k3_tile = 0 / 1 / 2) and a padded row pitch (k3_pitch): identical
-    candidates and identical 16 380 metrics per candidate."""
+    """K3's three tile forms (float4 per centre in LDS -- the default --, plain sqrt rows in LDS, sqrt rows in HBM:
+    option k3_tile = 0 / 1 / 2; 1 and 2 with a row pitch other than nc): identical candidates and 16 380 metrics each."""
     res = []
-    for name, v in (("k3_tile", "0"), ("k3_tile", "1"), ("k3_tile", "2"), ("k3_pitch", "24")):
+    for name, v in (("k3_tile", "0"), ("k3_tile", "1"), ("k3_tile", "2")):
         monkeypatch.setenv("UWSPR_OPTIONS", name + "=" + v)      # (shape the context when it is created)
         c = G.Context()
         try:
