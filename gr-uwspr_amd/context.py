@@ -408,6 +408,33 @@ class Context:
                                              C.c_void_p(npk.ctypes.data)))
         return [cands[b, :npk[b]].copy() for b in range(B)]
 
+    def fdr_from_ps(self, ps_band):
+        """diagnostics: the spectrum kernel and the coarse search on a GIVEN spectrogram, ps_band [B, n, band_w] float32
+        (the layout fdr_spectrum returns; a numpy array or a torch CUDA tensor) -> what fdr_batch returns."""
+        i = self.info
+        if _is_torch(ps_band):
+            import torch
+            assert ps_band.is_cuda and ps_band.is_contiguous() and ps_band.dtype == torch.float32
+            B = ps_band.numel() // (i.n * i.band_w)
+            assert B * i.n * i.band_w == ps_band.numel()
+            if self._stream_ptr is None:
+                torch.cuda.current_stream(ps_band.device).synchronize()
+            cands = torch.empty(B * self.maxfreqs * 48, dtype=torch.uint8, device=ps_band.device)
+            npk = torch.empty(B, dtype=torch.int32, device=ps_band.device)
+            self._chk(self.L.uwspr_debug_fdr_from_ps(self.h, C.c_void_p(ps_band.data_ptr()), B, N.DEVICE,
+                                                     C.c_void_p(cands.data_ptr()), C.c_void_p(npk.data_ptr())))
+            self.synchronize()
+            cands = np.frombuffer(cands.cpu().numpy().tobytes(), N.CAND_DTYPE).reshape(B, -1)
+            npk = npk.cpu().numpy()
+        else:
+            a = np.ascontiguousarray(ps_band, dtype=np.float32).reshape(-1, i.n, i.band_w)
+            B = a.shape[0]
+            cands = np.zeros((B, self.maxfreqs), N.CAND_DTYPE)
+            npk = np.zeros(B, np.int32)
+            self._chk(self.L.uwspr_debug_fdr_from_ps(self.h, C.c_void_p(a.ctypes.data), B, N.HOST,
+                                                     C.c_void_p(cands.ctypes.data), C.c_void_p(npk.ctypes.data)))
+        return [cands[b, :npk[b]].copy() for b in range(B)]
+
     def fdr_spectrum(self, B):
         i = self.info
         ps = np.empty((B, i.n, i.band_w), np.float32)

@@ -700,8 +700,10 @@ static int ensure_fdr(uwspr_ctx *c, int B) {
   return UWSPR_OK;
 }
 
+// ps_band (uwspr_debug_fdr_from_ps): a given [B][n][band_w] spectrogram in host (ps_where = UWSPR_HOST) or device memory
+// takes the place of K1's
 static int run_fdr(uwspr_ctx *c, const float *dframes, int B, uwspr_candidate *user_cands = nullptr,
-                   int32_t *user_npk = nullptr) {
+                   int32_t *user_npk = nullptr, const float *ps_band = nullptr, int ps_where = UWSPR_HOST) {
   int rc = ensure_fdr(c, B);
   if (rc) return rc;
   c->cur_cands = user_cands ? user_cands : c->d_cands;
@@ -712,7 +714,13 @@ static int run_fdr(uwspr_ctx *c, const float *dframes, int B, uwspr_candidate *u
     c->cap_grid_bytes = cap * sizeof(float);
     if (rc) return rc;
   }
-  launch_spectrogram(c, dframes, B);
+  if (!ps_band) {
+    launch_spectrogram(c, dframes, B);
+  } else {
+    HIPCHK(c, hipMemcpyAsync(c->d_ps, ps_band, (size_t)B * c->fc.n * c->fc.band_w * sizeof(float),
+                             ps_where == UWSPR_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, c->stream));
+    HIPCHK(c, hipMemsetAsync(c->d_work, 0, sizeof(int32_t), c->stream));   // K1's part: K2 appends to the work list from 0
+  }
   launch_spectrum(c, B);
   launch_coarse(c, B);
   HIPCHK(c, hipGetLastError());
@@ -1545,5 +1553,45 @@ extern "C" int uwspr_debug_sweep_outputs(uwspr_ctx *c, int first, int n, float *
   HIPCHK(c, hipStreamSynchronize(c->stream));
   if (sync) HIPCHK(c, hipMemcpy(sync, c->d_sync + first, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
   if (symbols) HIPCHK(c, hipMemcpy(symbols, c->d_sym + (size_t)first * UWSPR_NSYM, (size_t)n * UWSPR_NSYM, hipMemcpyDeviceToHost));
+  return UWSPR_OK;
+}
+
+// The context's device and [p, p + bytes) inside one device allocation of it (as the transmit calls check their pointers):
+// pageable host memory handed over as device memory is refused here, before any launch.
+static bool dbg_device_range(uwspr_ctx *c, const void *p, size_t bytes) {
+  hipPointerAttribute_t a;
+  memset(&a, 0, sizeof(a));
+  const hipError_t e = hipPointerGetAttributes(&a, p);
+  (void)hipGetLastError();   // a refused query leaves no error behind for the calls that follow
+  if (e != hipSuccess || a.type != hipMemoryTypeDevice || a.device != c->device) return false;
+  hipDeviceptr_t base = nullptr;
+  size_t size = 0;
+  if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)p) != hipSuccess) { (void)hipGetLastError(); return false; }
+  const char *b = (const char *)base, *q = (const char *)p;
+  return q >= b && bytes <= size && (size_t)(q - b) <= size - bytes;
+}
+
+// diagnostics (not part of the ABI header): K2 and K3 on a GIVEN spectrogram.  ps_band is [B][n][band_w] binary32, the
+// layout uwspr_fdr_read_spectrum returns; where = UWSPR_HOST or UWSPR_DEVICE says where ps_band, cands and npk live.
+// What uwspr_fdr_batch does after K1: the tile goes into the context's own buffer, the work counter K1 would have reset
+// is reset on the stream, then the spectrum kernel and the coarse search run.  cands ([B][maxfreqs]) and npk ([B]) may
+// be null (not copied); uwspr_fdr_read_spectrum and uwspr_fdr_read_syncgrid work afterwards as after a batch.
+extern "C" int uwspr_debug_fdr_from_ps(uwspr_ctx *c, const float *ps_band, int B, int where, uwspr_candidate *cands,
+                                       int32_t *npk) {
+  int rc = ready(c);
+  if (rc) return rc;
+  if (!ps_band || B <= 0) return fail(c, UWSPR_ERR_ARG, "uwspr_debug_fdr_from_ps: ps_band=%p B=%d", (const void *)ps_band, B);
+  if (where != UWSPR_HOST && where != UWSPR_DEVICE) return fail(c, UWSPR_ERR_ARG, "where=%d", where);
+  const fdr_consts &f = c->fc;
+  const size_t bytes = (size_t)B * f.n * f.band_w * sizeof(float);
+  if (where == UWSPR_DEVICE &&
+      (!dbg_device_range(c, ps_band, bytes) || (cands && !dbg_device_range(c, cands, (size_t)B * f.maxfreqs * sizeof(uwspr_candidate))) ||
+       (npk && !dbg_device_range(c, npk, (size_t)B * sizeof(int32_t)))))
+    return fail(c, UWSPR_ERR_ARG, "uwspr_debug_fdr_from_ps: ps_band, cands or npk is not device memory of device %d holding B=%d frames",
+                c->device, B);
+  if ((rc = run_fdr(c, nullptr, B, nullptr, nullptr, ps_band, where))) return rc;
+  if ((rc = copy_out(c, cands, c->d_cands, (size_t)B * f.maxfreqs * sizeof(uwspr_candidate), where))) return rc;
+  if ((rc = copy_out(c, npk, c->d_npk, (size_t)B * sizeof(int32_t), where))) return rc;
+  if (where != UWSPR_DEVICE) HIPCHK(c, hipStreamSynchronize(c->stream));
   return UWSPR_OK;
 }

@@ -366,6 +366,7 @@ def lib():
     L.uwspr_fdr_read_spectrum.argtypes = [vp, ip, vp, vp, vp, vp, vp]
     L.uwspr_fdr_keep_syncgrid.argtypes = [vp, ip]
     L.uwspr_fdr_read_syncgrid.argtypes = [vp, ip, vp]
+    L.uwspr_debug_fdr_from_ps.argtypes = [vp, vp, ip, ip, vp, vp]     # diagnostics, outside the ABI header
     L.uwspr_sync_sweep.argtypes = [vp, vp, ip, vp, ip, ip, vp, vp]
     L.uwspr_sync_grid.argtypes = [vp, vp, ip, ip, vp, ip, vp, ip, vp, ip, vp, vp, vp]
     L.uwspr_sync_and_demodulate_batch.argtypes = [vp, vp, ip, ip, vp, ip, vp]
