@@ -703,7 +703,9 @@ __global__ void k_sched_finish(const cand_state *__restrict__ state,
       }
       rms = (float)sqrt((double)sq / 162.0);  // cc:474
     }
-    o->jig_sync[tid] = have ? sync5[q] : 0.0f;
+    // a mode-2 call returns syncmax (cc:241): the default -1e30 where the try's metric is NaN and never beat it (cc:227)
+    const float s5 = have ? sync5[q] : 0.0f;
+    o->jig_sync[tid] = (have && !(s5 > -1e30f)) ? -1e30f : s5;
     o->jig_rms[tid] = rms;
     o->jig_shift[tid] = have ? h5[q].lag : 0;
   }

@@ -475,7 +475,11 @@ __device__ __noinline__ void k6_fold(int nh, const int *slab_off, const lds_f *l
     }
   }
   __syncthreads();
-  if (tid < nh) sync_out[tid] = ieee_divf(F.sums[1][tid], F.sums[0][tid]);   // cc:226
+  if (tid < nh) {
+    const float ss = ieee_divf(F.sums[1][tid], F.sums[0][tid]);   // cc:226
+    // a mode-2 call returns syncmax (cc:241): the default -1e30 where ss is NaN and so never beat it (cc:227)
+    sync_out[tid] = (SOFT && !(ss > -1e30f)) ? -1e30f : ss;
+  }
   if (SOFT) {
     for (int e = tid; e < nh * UWSPR_NSYM; e += K6_THREADS) {
       const int j = e / UWSPR_NSYM, i = e - j * UWSPR_NSYM;
