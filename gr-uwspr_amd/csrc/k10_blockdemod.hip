@@ -17,6 +17,7 @@
 #include <stdio.h>
 #include <string.h>
 
+#include "ctx_util.h"
 #include "uwspr_internal.h"
 
 namespace uwspr {
@@ -163,9 +164,7 @@ struct blk_state {
   uwspr_block_item *h_items = nullptr; size_t cap_h = 0;
   hipEvent_t done = nullptr; bool pending = false;
   uint8_t *d_out = nullptr; size_t cap_out = 0;
-  // uwspr_debug_blockdemod_time: events around the K10 launch of the last call
-  bool timing = false, timed = false;
-  hipEvent_t ev[2] = {nullptr, nullptr};
+  launch_timer timer;   // uwspr_debug_blockdemod_time: events around the K10 launch of the last call
 };
 
 void blk_release(uwspr_ctx *c) {
@@ -175,53 +174,24 @@ void blk_release(uwspr_ctx *c) {
   if (t->d_out) (void)hipFree(t->d_out);
   if (t->h_items) (void)hipHostFree(t->h_items);
   if (t->done) (void)hipEventDestroy(t->done);
-  for (hipEvent_t e : t->ev) if (e) (void)hipEventDestroy(e);
+  t->timer.release();
   delete t;
   c->blk = nullptr;
-}
-
-static int blk_fail(uwspr_ctx *c, int status, const char *fmt, ...) {
-  if (c) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(c->err, sizeof(c->err), fmt, ap);
-    va_end(ap);
-  }
-  return status;
-}
-
-#define BLKCHK(c, call)                                                                                 \
-  do {                                                                                                  \
-    hipError_t e_ = (call);                                                                             \
-    if (e_ != hipSuccess)                                                                               \
-      return blk_fail((c), UWSPR_ERR_HIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); \
-  } while (0)
-
-template <typename T>
-static int blk_grow(uwspr_ctx *c, T **buf, size_t *cap, size_t elems) {
-  if (elems <= *cap && *buf) return UWSPR_OK;
-  BLKCHK(c, hipStreamSynchronize(c->stream));   // the old buffer may still be read by the call before
-  if (*buf) { BLKCHK(c, hipFree(*buf)); *buf = nullptr; *cap = 0; }
-  const size_t n = elems > 256 ? elems : 256;
-  const hipError_t e = hipMalloc((void **)buf, n * sizeof(T));
-  if (e != hipSuccess) { (void)hipGetLastError(); return blk_fail(c, UWSPR_ERR_NOMEM, "hipMalloc(%zu bytes): %s", n * sizeof(T), hipGetErrorString(e)); }
-  *cap = n;
-  return UWSPR_OK;
 }
 
 static bool blk_finite(float v) { return v == v && v - v == 0.0f; }
 
 // what makes a list of items acceptable (the rules of subtract_check): checked before anything is launched or written
 int blockdemod_check(uwspr_ctx *c, const uwspr_block_item *items, int nitems, int nframes) {
-  if (nitems < 0 || (nitems > 0 && !items)) return blk_fail(c, UWSPR_ERR_ARG, "uwspr_blockdemod_batch: items %p, nitems %d", (const void *)items, nitems);
+  if (nitems < 0 || (nitems > 0 && !items)) return ctx_fail(c, UWSPR_ERR_ARG, "uwspr_blockdemod_batch: items %p, nitems %d", (const void *)items, nitems);
   for (int i = 0; i < nitems; i++) {
     const uwspr_block_item &s = items[i];
-    if (s.frame < 0 || s.frame >= nframes) return blk_fail(c, UWSPR_ERR_ARG, "uwspr_blockdemod_batch: item %d: frame %d (0..%d)", i, s.frame, nframes - 1);
+    if (s.frame < 0 || s.frame >= nframes) return ctx_fail(c, UWSPR_ERR_ARG, "uwspr_blockdemod_batch: item %d: frame %d (0..%d)", i, s.frame, nframes - 1);
     if (i > 0 && s.frame < items[i - 1].frame)
-      return blk_fail(c, UWSPR_ERR_ARG, "uwspr_blockdemod_batch: item %d: frame %d after frame %d (items are sorted by frame)", i, s.frame, items[i - 1].frame);
+      return ctx_fail(c, UWSPR_ERR_ARG, "uwspr_blockdemod_batch: item %d: frame %d after frame %d (items are sorted by frame)", i, s.frame, items[i - 1].frame);
     if (!blk_finite(s.f_hz) || !blk_finite(s.drift_hz) || fabsf(s.f_hz) > 1e4f || fabsf(s.drift_hz) > 1e3f)
-      return blk_fail(c, UWSPR_ERR_ARG, "uwspr_blockdemod_batch: item %d: f %g Hz (|.| <= 1e4), drift %g Hz (|.| <= 1e3)", i, (double)s.f_hz, (double)s.drift_hz);
-    if (s.shift < -(1 << 20) || s.shift > (1 << 20)) return blk_fail(c, UWSPR_ERR_ARG, "uwspr_blockdemod_batch: item %d: shift %d (|.| <= 2^20)", i, s.shift);
+      return ctx_fail(c, UWSPR_ERR_ARG, "uwspr_blockdemod_batch: item %d: f %g Hz (|.| <= 1e4), drift %g Hz (|.| <= 1e3)", i, (double)s.f_hz, (double)s.drift_hz);
+    if (s.shift < -(1 << 20) || s.shift > (1 << 20)) return ctx_fail(c, UWSPR_ERR_ARG, "uwspr_blockdemod_batch: item %d: shift %d (|.| <= 2^20)", i, s.shift);
   }
   return UWSPR_OK;
 }
@@ -231,57 +201,38 @@ int blockdemod_check(uwspr_ctx *c, const uwspr_block_item *items, int nitems, in
 // through *out_dev.
 int blockdemod_run(uwspr_ctx *c, const float *src, size_t stride, const uwspr_block_item *items, int nitems, uint8_t *out,
                    uint8_t **out_dev) {
-  if (!c->own_stream) return blk_fail(c, UWSPR_ERR_NODEVICE, "context has no device (creation failed: %s)", c->err);
-  BLKCHK(c, hipSetDevice(c->device));
+  int rc = ctx_device_ready(c);
+  if (rc) return rc;
   if (!c->blk) c->blk = new blk_state();
   blk_state *t = c->blk;
-  int rc;
-  if ((rc = blk_grow(c, &t->d_items, &t->cap_items, (size_t)nitems))) return rc;
+  if ((rc = ctx_grow(c, &t->d_items, &t->cap_items, (size_t)nitems))) return rc;
   if (!out) {
-    if ((rc = blk_grow(c, &t->d_out, &t->cap_out, (size_t)nitems * 3 * K10_NSYM))) return rc;
+    if ((rc = ctx_grow(c, &t->d_out, &t->cap_out, (size_t)nitems * 3 * K10_NSYM))) return rc;
     out = t->d_out;
   }
   if (out_dev) *out_dev = out;
-  if (!t->done) BLKCHK(c, hipEventCreateWithFlags(&t->done, hipEventDisableTiming));
-  if (t->pending) { BLKCHK(c, hipEventSynchronize(t->done)); t->pending = false; }   // the call before has read both item buffers
+  if (!t->done) CTXCHK(c, hipEventCreateWithFlags(&t->done, hipEventDisableTiming));
+  if (t->pending) { CTXCHK(c, hipEventSynchronize(t->done)); t->pending = false; }   // the call before has read both item buffers
   if ((size_t)nitems > t->cap_h) {
-    if (t->h_items) { BLKCHK(c, hipHostFree(t->h_items)); t->h_items = nullptr; t->cap_h = 0; }
+    if (t->h_items) { CTXCHK(c, hipHostFree(t->h_items)); t->h_items = nullptr; t->cap_h = 0; }
     const size_t n = nitems > 256 ? (size_t)nitems : 256;
     if (hipHostMalloc((void **)&t->h_items, n * sizeof(uwspr_block_item), hipHostMallocDefault) != hipSuccess) {
       (void)hipGetLastError();
       t->h_items = nullptr;
-      return blk_fail(c, UWSPR_ERR_NOMEM, "hipHostMalloc(%zu bytes) for the items", n * sizeof(uwspr_block_item));
+      return ctx_fail(c, UWSPR_ERR_NOMEM, "hipHostMalloc(%zu bytes) for the items", n * sizeof(uwspr_block_item));
     }
     t->cap_h = n;
   }
   memcpy(t->h_items, items, (size_t)nitems * sizeof(uwspr_block_item));
-  BLKCHK(c, hipMemcpyAsync(t->d_items, t->h_items, (size_t)nitems * sizeof(uwspr_block_item), hipMemcpyHostToDevice, c->stream));
-  if (t->timing) {
-    for (hipEvent_t &e : t->ev) if (!e) BLKCHK(c, hipEventCreate(&e));
-    BLKCHK(c, hipEventRecord(t->ev[0], c->stream));
-  }
+  CTXCHK(c, hipMemcpyAsync(t->d_items, t->h_items, (size_t)nitems * sizeof(uwspr_block_item), hipMemcpyHostToDevice, c->stream));
+  if ((rc = t->timer.begin(c))) return rc;
   // c->np: the fine search's sample bound, min(fl, 45000) -- 45000 for every fl that holds a whole frame
   hipLaunchKernelGGL(k10_blockdemod, dim3((unsigned)nitems), dim3(K10_WG), 0, c->stream, reinterpret_cast<const float2 *>(src), stride,
                      c->np, t->d_items, out);
-  BLKCHK(c, hipGetLastError());
-  BLKCHK(c, hipEventRecord(t->done, c->stream));
+  CTXCHK(c, hipGetLastError());
+  CTXCHK(c, hipEventRecord(t->done, c->stream));
   t->pending = true;
-  if (t->timing) { BLKCHK(c, hipEventRecord(t->ev[1], c->stream)); t->timed = true; }
-  return UWSPR_OK;
-}
-
-// the context's device and [p, p + bytes) inside one device allocation of it (as uwspr_osd_batch checks its pointers)
-static bool blk_device_range(uwspr_ctx *c, const void *p, size_t bytes) {
-  hipPointerAttribute_t a;
-  memset(&a, 0, sizeof(a));
-  const hipError_t e = hipPointerGetAttributes(&a, p);
-  (void)hipGetLastError();
-  if (e != hipSuccess || a.type != hipMemoryTypeDevice || a.device != c->device) return false;
-  hipDeviceptr_t b0 = nullptr;
-  size_t size = 0;
-  if (hipMemGetAddressRange(&b0, &size, (hipDeviceptr_t)p) != hipSuccess) { (void)hipGetLastError(); return false; }
-  const char *b = (const char *)b0, *q = (const char *)p;
-  return q >= b && bytes <= size && (size_t)(q - b) <= size - bytes;
+  return t->timer.end(c);
 }
 
 }  // namespace uwspr
@@ -292,21 +243,20 @@ extern "C" int uwspr_blockdemod_batch(uwspr_ctx *c, const float *frames, int B, 
                                       uint8_t *symbols) {
   if (!c) return UWSPR_ERR_ARG;
   if (!frames || B <= 0 || (where != UWSPR_HOST && where != UWSPR_DEVICE && where != UWSPR_DEVICE_FRAMES) || (nitems > 0 && !symbols))
-    return blk_fail(c, UWSPR_ERR_ARG, "uwspr_blockdemod_batch: frames %p, B %d, where %d, symbols %p", (const void *)frames, B, where, (void *)symbols);
+    return ctx_fail(c, UWSPR_ERR_ARG, "uwspr_blockdemod_batch: frames %p, B %d, where %d, symbols %p", (const void *)frames, B, where, (void *)symbols);
   int rc = blockdemod_check(c, items, nitems, B);
   if (rc) return rc;
   if (nitems == 0) return UWSPR_OK;
-  if (!c->own_stream) return blk_fail(c, UWSPR_ERR_NODEVICE, "context has no device (creation failed: %s)", c->err);
-  BLKCHK(c, hipSetDevice(c->device));
+  if ((rc = ctx_device_ready(c))) return rc;
   const size_t bytes = (size_t)nitems * 3 * K10_NSYM;
-  if (where != UWSPR_HOST && !blk_device_range(c, symbols, bytes))
-    return blk_fail(c, UWSPR_ERR_ARG, "uwspr_blockdemod_batch: device output needs symbols (%zu bytes) inside a device allocation of device %d", bytes, c->device);
+  if (where != UWSPR_HOST && !ctx_device_range(c, symbols, bytes))
+    return ctx_fail(c, UWSPR_ERR_ARG, "uwspr_blockdemod_batch: device output needs symbols (%zu bytes) inside a device allocation of device %d", bytes, c->device);
   const float *src = nullptr;
   if ((rc = api_frames_on_device(c, frames, B, where, &src))) return rc;
   uint8_t *dev = nullptr;
   if ((rc = blockdemod_run(c, src, (size_t)c->fstride, items, nitems, where == UWSPR_HOST ? nullptr : symbols, &dev))) return rc;
-  if (where == UWSPR_HOST) BLKCHK(c, hipMemcpyAsync(symbols, dev, bytes, hipMemcpyDeviceToHost, c->stream));
-  if (where != UWSPR_DEVICE) BLKCHK(c, hipStreamSynchronize(c->stream));
+  if (where == UWSPR_HOST) CTXCHK(c, hipMemcpyAsync(symbols, dev, bytes, hipMemcpyDeviceToHost, c->stream));
+  if (where != UWSPR_DEVICE) CTXCHK(c, hipStreamSynchronize(c->stream));
   return UWSPR_OK;
 }
 
@@ -315,17 +265,6 @@ extern "C" int uwspr_blockdemod_batch(uwspr_ctx *c, const float *frames, int B, 
 // timed launch and returns its time.
 extern "C" int uwspr_debug_blockdemod_time(uwspr_ctx *c, int enable, double *ms) {
   if (!c) return UWSPR_ERR_ARG;
-  if (!c->blk) c->blk = new blk_state();
-  blk_state *t = c->blk;
-  if (enable >= 0) t->timing = enable != 0;
-  if (ms) {
-    *ms = 0.0;
-    if (t->timed) {
-      float f = 0.0f;
-      BLKCHK(c, hipEventSynchronize(t->ev[1]));
-      BLKCHK(c, hipEventElapsedTime(&f, t->ev[0], t->ev[1]));
-      *ms = f;
-    }
-  }
-  return UWSPR_OK;
+  if (!c->blk) c->blk = new blk_state();   // (no device asked: the hook only keeps the switch)
+  return c->blk->timer.read(c, enable, ms);
 }

@@ -21,6 +21,7 @@
 #include <algorithm>
 #include <vector>
 
+#include "ctx_util.h"
 #include "uwspr_internal.h"
 
 namespace uwspr {
@@ -125,51 +126,21 @@ __global__ void __launch_bounds__(64) k13_reduce(const k13_top *__restrict__ par
 // ---------------------------------------------------------------- host side
 struct deep_state {
   int8_t *d_tab = nullptr; int M = 0;                           // uwspr_deep_set_list's table
-  uint8_t *d_sym = nullptr; size_t cap_sym = 0;                 // host symbols staged
+  symbols_stage stage;                                          // host symbols staged
   uwspr_deep_result *d_res = nullptr; size_t cap_res = 0;
   unsigned long long *d_off = nullptr; size_t cap_off = 0;      // byte offsets of scattered items
   k13_top *d_part = nullptr; size_t cap_part = 0;
-  hipEvent_t ev[2] = {nullptr, nullptr};                        // uwspr_debug_deep_time
-  bool timing = false, timed = false;
+  launch_timer timer;                                           // uwspr_debug_deep_time
 };
 
 void deep_release(uwspr_ctx *c) {
   if (!c || !c->deep) return;
   deep_state *t = c->deep;
-  void *bufs[] = {t->d_tab, t->d_sym, t->d_res, t->d_off, t->d_part};
+  void *bufs[] = {t->d_tab, t->stage.d_sym, t->d_res, t->d_off, t->d_part};
   for (void *b : bufs) if (b) (void)hipFree(b);
-  for (hipEvent_t e : t->ev) if (e) (void)hipEventDestroy(e);
+  t->timer.release();
   delete t;
   c->deep = nullptr;
-}
-
-static int deep_fail(uwspr_ctx *c, int status, const char *fmt, ...) {
-  if (c) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(c->err, sizeof(c->err), fmt, ap);
-    va_end(ap);
-  }
-  return status;
-}
-
-#define DEEPCHK(c, call)                                                                                \
-  do {                                                                                                  \
-    hipError_t e_ = (call);                                                                             \
-    if (e_ != hipSuccess)                                                                               \
-      return deep_fail((c), UWSPR_ERR_HIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); \
-  } while (0)
-
-template <typename T>
-static int deep_grow(uwspr_ctx *c, T **buf, size_t *cap, size_t elems) {
-  if (elems <= *cap && *buf) return UWSPR_OK;
-  DEEPCHK(c, hipStreamSynchronize(c->stream));   // the old buffer may still be read by the call before
-  if (*buf) { DEEPCHK(c, hipFree(*buf)); *buf = nullptr; *cap = 0; }
-  const size_t n = elems > 256 ? elems : 256;
-  const hipError_t e = hipMalloc((void **)buf, n * sizeof(T));
-  if (e != hipSuccess) { (void)hipGetLastError(); return deep_fail(c, UWSPR_ERR_NOMEM, "hipMalloc(%zu bytes): %s", n * sizeof(T), hipGetErrorString(e)); }
-  *cap = n;
-  return UWSPR_OK;
 }
 
 // the list's rules (include/uwspr_hip.h): null on success, else what is wrong (into msg)
@@ -206,8 +177,7 @@ int deep_build_table(const int8_t *messages7, int M, std::vector<int8_t> &tab) {
 }
 
 static int deep_begin(uwspr_ctx *c) {
-  if (!c->own_stream) return deep_fail(c, UWSPR_ERR_NODEVICE, "context has no device (creation failed: %s)", c->err);
-  DEEPCHK(c, hipSetDevice(c->device));
+  if (const int rc = ctx_device_ready(c)) return rc;
   if (!c->deep) c->deep = new deep_state();
   return UWSPR_OK;
 }
@@ -221,10 +191,10 @@ int deep_run(uwspr_ctx *c, const int8_t *d_tab, int M, const uint8_t *base, cons
   if (rc) return rc;
   deep_state *t = c->deep;
   if (!d_tab) { d_tab = t->d_tab; M = t->M; }
-  if (!d_tab || M < 1) return deep_fail(c, UWSPR_ERR_ARG, "list search: no list is set");
-  if (n < 1 || n > (1 << 20)) return deep_fail(c, UWSPR_ERR_ARG, "list search: %d items in one call (1..%d)", n, 1 << 20);
+  if (!d_tab || M < 1) return ctx_fail(c, UWSPR_ERR_ARG, "list search: no list is set");
+  if (n < 1 || n > (1 << 20)) return ctx_fail(c, UWSPR_ERR_ARG, "list search: %d items in one call (1..%d)", n, 1 << 20);
   if (!res) {
-    if ((rc = deep_grow(c, &t->d_res, &t->cap_res, (size_t)n))) return rc;
+    if ((rc = ctx_grow(c, &t->d_res, &t->cap_res, (size_t)n))) return rc;
     res = t->d_res;
   }
   if (res_out) *res_out = res;
@@ -234,37 +204,15 @@ int deep_run(uwspr_ctx *c, const int8_t *d_tab, int M, const uint8_t *base, cons
   int per = (ntiles + want - 1) / want;
   if (per < K13_WAVES) per = K13_WAVES;
   const int nchunks = (ntiles + per - 1) / per;
-  if ((rc = deep_grow(c, &t->d_part, &t->cap_part, (size_t)n * nchunks))) return rc;
-  if (off) {
-    if ((rc = deep_grow(c, &t->d_off, &t->cap_off, (size_t)n))) return rc;
-    DEEPCHK(c, hipMemcpyAsync(t->d_off, off, (size_t)n * sizeof(unsigned long long), hipMemcpyHostToDevice, c->stream));
-    DEEPCHK(c, hipStreamSynchronize(c->stream));   // (off is the caller's host memory)
-  }
-  if (t->timing) {
-    for (hipEvent_t &e : t->ev) if (!e) DEEPCHK(c, hipEventCreate(&e));
-    DEEPCHK(c, hipEventRecord(t->ev[0], c->stream));
-  }
+  if ((rc = ctx_grow(c, &t->d_part, &t->cap_part, (size_t)n * nchunks))) return rc;
+  if (off && (rc = scattered_offsets(c, &t->d_off, &t->cap_off, off, n))) return rc;
+  if ((rc = t->timer.begin(c))) return rc;
   hipLaunchKernelGGL(k13_score, dim3((unsigned)nchunks, (unsigned)itiles), dim3(64 * K13_WAVES), 0, c->stream, base,
                      off ? t->d_off : (const unsigned long long *)nullptr, n, d_tab, M, per, t->d_part);
-  DEEPCHK(c, hipGetLastError());
+  CTXCHK(c, hipGetLastError());
   hipLaunchKernelGGL(k13_reduce, dim3((unsigned)n), dim3(64), 0, c->stream, t->d_part, nchunks, res);
-  DEEPCHK(c, hipGetLastError());
-  if (t->timing) { DEEPCHK(c, hipEventRecord(t->ev[1], c->stream)); t->timed = true; }
-  return UWSPR_OK;
-}
-
-// the context's device and [p, p + bytes) inside one device allocation of it (as uwspr_osd_batch checks its pointers)
-static bool deep_device_range(uwspr_ctx *c, const void *p, size_t bytes) {
-  hipPointerAttribute_t a;
-  memset(&a, 0, sizeof(a));
-  const hipError_t e = hipPointerGetAttributes(&a, p);
-  (void)hipGetLastError();
-  if (e != hipSuccess || a.type != hipMemoryTypeDevice || a.device != c->device) return false;
-  hipDeviceptr_t b0 = nullptr;
-  size_t size = 0;
-  if (hipMemGetAddressRange(&b0, &size, (hipDeviceptr_t)p) != hipSuccess) { (void)hipGetLastError(); return false; }
-  const char *b = (const char *)b0, *q = (const char *)p;
-  return q >= b && bytes <= size && (size_t)(q - b) <= size - bytes;
+  CTXCHK(c, hipGetLastError());
+  return t->timer.end(c);
 }
 
 }  // namespace uwspr
@@ -275,7 +223,7 @@ extern "C" int uwspr_deep_set_list(uwspr_ctx *c, const int8_t *messages7, int M)
   if (!c) return UWSPR_ERR_ARG;
   if (M != 0) {
     char why[160];
-    if (deep_check_list(messages7, M, why, sizeof(why))) return deep_fail(c, UWSPR_ERR_ARG, "uwspr_deep_set_list: %s", why);
+    if (deep_check_list(messages7, M, why, sizeof(why))) return ctx_fail(c, UWSPR_ERR_ARG, "uwspr_deep_set_list: %s", why);
   }
   if (M == 0 && !c->deep) return UWSPR_OK;
   int rc = deep_begin(c);
@@ -284,13 +232,13 @@ extern "C" int uwspr_deep_set_list(uwspr_ctx *c, const int8_t *messages7, int M)
   int8_t *d_new = nullptr;
   if (M > 0) {
     std::vector<int8_t> tab;
-    if (deep_build_table(messages7, M, tab)) return deep_fail(c, UWSPR_ERR_ARG, "uwspr_deep_set_list: symbols of a message");
+    if (deep_build_table(messages7, M, tab)) return ctx_fail(c, UWSPR_ERR_ARG, "uwspr_deep_set_list: symbols of a message");
     const hipError_t e = hipMalloc((void **)&d_new, tab.size());
-    if (e != hipSuccess) { (void)hipGetLastError(); return deep_fail(c, UWSPR_ERR_NOMEM, "hipMalloc(%zu bytes): %s", tab.size(), hipGetErrorString(e)); }
+    if (e != hipSuccess) { (void)hipGetLastError(); return ctx_fail(c, UWSPR_ERR_NOMEM, "hipMalloc(%zu bytes): %s", tab.size(), hipGetErrorString(e)); }
     const hipError_t e2 = hipMemcpy(d_new, tab.data(), tab.size(), hipMemcpyHostToDevice);
-    if (e2 != hipSuccess) { (void)hipFree(d_new); return deep_fail(c, UWSPR_ERR_HIP, "hipMemcpy of the table: %s", hipGetErrorString(e2)); }
+    if (e2 != hipSuccess) { (void)hipFree(d_new); return ctx_fail(c, UWSPR_ERR_HIP, "hipMemcpy of the table: %s", hipGetErrorString(e2)); }
   }
-  DEEPCHK(c, hipStreamSynchronize(c->stream));   // a call before may still read the old table
+  CTXCHK(c, hipStreamSynchronize(c->stream));   // a call before may still read the old table
   if (t->d_tab) (void)hipFree(t->d_tab);
   t->d_tab = d_new;
   t->M = M;
@@ -299,27 +247,10 @@ extern "C" int uwspr_deep_set_list(uwspr_ctx *c, const int8_t *messages7, int M)
 
 extern "C" int uwspr_deep_batch(uwspr_ctx *c, const uint8_t *symbols, int n, int where, uwspr_deep_result *res) {
   if (!c) return UWSPR_ERR_ARG;
-  if (n < 0 || (n > 0 && (!symbols || !res)) || (where != UWSPR_HOST && where != UWSPR_DEVICE))
-    return deep_fail(c, UWSPR_ERR_ARG, "uwspr_deep_batch: symbols %p, n %d, where %d, res %p", (const void *)symbols, n, where, (void *)res);
-  if (!c->deep || !c->deep->d_tab) return deep_fail(c, UWSPR_ERR_ARG, "uwspr_deep_batch: no list is set (uwspr_deep_set_list)");
-  if (n == 0) return UWSPR_OK;
-  if (!c->own_stream) return deep_fail(c, UWSPR_ERR_NODEVICE, "context has no device (creation failed: %s)", c->err);
-  DEEPCHK(c, hipSetDevice(c->device));
-  if (where == UWSPR_DEVICE) {
-    if (!deep_device_range(c, symbols, (size_t)n * K13_N) || !deep_device_range(c, res, (size_t)n * sizeof(uwspr_deep_result)))
-      return deep_fail(c, UWSPR_ERR_ARG, "uwspr_deep_batch: UWSPR_DEVICE needs symbols (%zu bytes) and res (%zu bytes) inside device allocations of device %d",
-                       (size_t)n * K13_N, (size_t)n * sizeof(uwspr_deep_result), c->device);
-    return deep_run(c, nullptr, 0, symbols, nullptr, n, res, nullptr);
-  }
-  deep_state *t = c->deep;
-  int rc;
-  if ((rc = deep_grow(c, &t->d_sym, &t->cap_sym, (size_t)n * K13_N))) return rc;
-  DEEPCHK(c, hipMemcpyAsync(t->d_sym, symbols, (size_t)n * K13_N, hipMemcpyHostToDevice, c->stream));
-  uwspr_deep_result *d_res = nullptr;
-  if ((rc = deep_run(c, nullptr, 0, t->d_sym, nullptr, n, nullptr, &d_res))) return rc;
-  DEEPCHK(c, hipMemcpyAsync(res, d_res, (size_t)n * sizeof(uwspr_deep_result), hipMemcpyDeviceToHost, c->stream));
-  DEEPCHK(c, hipStreamSynchronize(c->stream));
-  return UWSPR_OK;
+  return symbols_batch(c, "uwspr_deep_batch", symbols, n, where, res,
+                       !c->deep || !c->deep->d_tab ? "no list is set (uwspr_deep_set_list)" : nullptr,
+                       [&](symbols_stage **st) { *st = &c->deep->stage; return (int)UWSPR_OK; },
+                       [&](const uint8_t *d_sym, uwspr_deep_result *d_res, uwspr_deep_result **d_out) { return deep_run(c, nullptr, 0, d_sym, nullptr, n, d_res, d_out); });
 }
 
 // Measurement hook of tools/deep_probe.py (not part of the ABI, like uwspr_debug_osd_time): enable = 1 / 0 switches HIP
@@ -327,17 +258,6 @@ extern "C" int uwspr_deep_batch(uwspr_ctx *c, const uint8_t *symbols, int n, int
 // timed pair of launches and returns its time.
 extern "C" int uwspr_debug_deep_time(uwspr_ctx *c, int enable, double *ms) {
   if (!c) return UWSPR_ERR_ARG;
-  if (!c->deep) c->deep = new deep_state();
-  deep_state *t = c->deep;
-  if (enable >= 0) t->timing = enable != 0;
-  if (ms) {
-    *ms = 0.0;
-    if (t->timed) {
-      float f = 0.0f;
-      DEEPCHK(c, hipEventSynchronize(t->ev[1]));
-      DEEPCHK(c, hipEventElapsedTime(&f, t->ev[0], t->ev[1]));
-      *ms = f;
-    }
-  }
-  return UWSPR_OK;
+  if (!c->deep) c->deep = new deep_state();   // (no device asked: the hook only keeps the switch)
+  return c->deep->timer.read(c, enable, ms);
 }

@@ -27,6 +27,7 @@
 
 #include <vector>
 
+#include "ctx_util.h"
 #include "uwspr_internal.h"
 
 namespace uwspr {
@@ -173,12 +174,11 @@ struct calls_set {
 
 struct calls_state {
   calls_set *set = nullptr;                                     // uwspr_calls_set's
-  uint8_t *d_sym = nullptr; size_t cap_sym = 0;                 // host symbols staged
+  symbols_stage stage;                                          // host symbols staged
   uwspr_call_result *d_res = nullptr; size_t cap_res = 0;
   unsigned long long *d_off = nullptr; size_t cap_off = 0;      // byte offsets of scattered items
   k14_top *d_part = nullptr; size_t cap_part = 0;
-  hipEvent_t ev[2] = {nullptr, nullptr};                        // uwspr_debug_calls_time
-  bool timing = false, timed = false;
+  launch_timer timer;                                           // uwspr_debug_calls_time
 };
 
 void calls_free_set(calls_set *s) {
@@ -192,40 +192,11 @@ void calls_release(uwspr_ctx *c) {
   if (!c || !c->calls) return;
   calls_state *t = c->calls;
   calls_free_set(t->set);
-  void *bufs[] = {t->d_sym, t->d_res, t->d_off, t->d_part};
+  void *bufs[] = {t->stage.d_sym, t->d_res, t->d_off, t->d_part};
   for (void *b : bufs) if (b) (void)hipFree(b);
-  for (hipEvent_t e : t->ev) if (e) (void)hipEventDestroy(e);
+  t->timer.release();
   delete t;
   c->calls = nullptr;
-}
-
-static int calls_fail(uwspr_ctx *c, int status, const char *fmt, ...) {
-  if (c) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(c->err, sizeof(c->err), fmt, ap);
-    va_end(ap);
-  }
-  return status;
-}
-
-#define CALLSCHK(c, call)                                                                                \
-  do {                                                                                                   \
-    hipError_t e_ = (call);                                                                              \
-    if (e_ != hipSuccess)                                                                                \
-      return calls_fail((c), UWSPR_ERR_HIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); \
-  } while (0)
-
-template <typename T>
-static int calls_grow(uwspr_ctx *c, T **buf, size_t *cap, size_t elems) {
-  if (elems <= *cap && *buf) return UWSPR_OK;
-  CALLSCHK(c, hipStreamSynchronize(c->stream));   // the old buffer may still be read by the call before
-  if (*buf) { CALLSCHK(c, hipFree(*buf)); *buf = nullptr; *cap = 0; }
-  const size_t n = elems > 256 ? elems : 256;
-  const hipError_t e = hipMalloc((void **)buf, n * sizeof(T));
-  if (e != hipSuccess) { (void)hipGetLastError(); return calls_fail(c, UWSPR_ERR_NOMEM, "hipMalloc(%zu bytes): %s", n * sizeof(T), hipGetErrorString(e)); }
-  *cap = n;
-  return UWSPR_OK;
 }
 
 static void calls_put50(int32_t n1, int32_t n2, int8_t *m) {
@@ -338,8 +309,7 @@ calls_set *calls_build(const char *const *calls, int A, const uint8_t *grid_bitm
 }
 
 static int calls_begin(uwspr_ctx *c) {
-  if (!c->own_stream) return calls_fail(c, UWSPR_ERR_NODEVICE, "context has no device (creation failed: %s)", c->err);
-  CALLSCHK(c, hipSetDevice(c->device));
+  if (const int rc = ctx_device_ready(c)) return rc;
   if (!c->calls) c->calls = new calls_state();
   return UWSPR_OK;
 }
@@ -352,10 +322,10 @@ int calls_run(uwspr_ctx *c, const calls_set *set, const uint8_t *base, const uns
   if (rc) return rc;
   calls_state *t = c->calls;
   if (!set) set = t->set;
-  if (!set) return calls_fail(c, UWSPR_ERR_ARG, "call search: no call set is set");
-  if (n < 1 || n > (1 << 20)) return calls_fail(c, UWSPR_ERR_ARG, "call search: %d items in one call (1..%d)", n, 1 << 20);
+  if (!set) return ctx_fail(c, UWSPR_ERR_ARG, "call search: no call set is set");
+  if (n < 1 || n > (1 << 20)) return ctx_fail(c, UWSPR_ERR_ARG, "call search: %d items in one call (1..%d)", n, 1 << 20);
   if (!res) {
-    if ((rc = calls_grow(c, &t->d_res, &t->cap_res, (size_t)n))) return rc;
+    if ((rc = ctx_grow(c, &t->d_res, &t->cap_res, (size_t)n))) return rc;
     res = t->d_res;
   }
   if (res_out) *res_out = res;
@@ -365,42 +335,20 @@ int calls_run(uwspr_ctx *c, const calls_set *set, const uint8_t *base, const uns
   int per = (K14_TILES + want - 1) / want;
   if (per < K14_WAVES) per = K14_WAVES;
   const int nchunks = (K14_TILES + per - 1) / per, nparts = nchunks * set->A;
-  if ((rc = calls_grow(c, &t->d_part, &t->cap_part, (size_t)n * nparts))) return rc;
-  if (off) {
-    if ((rc = calls_grow(c, &t->d_off, &t->cap_off, (size_t)n))) return rc;
-    CALLSCHK(c, hipMemcpyAsync(t->d_off, off, (size_t)n * sizeof(unsigned long long), hipMemcpyHostToDevice, c->stream));
-    CALLSCHK(c, hipStreamSynchronize(c->stream));   // (off is the caller's host memory)
-  }
-  if (t->timing) {
-    for (hipEvent_t &e : t->ev) if (!e) CALLSCHK(c, hipEventCreate(&e));
-    CALLSCHK(c, hipEventRecord(t->ev[0], c->stream));
-  }
+  if ((rc = ctx_grow(c, &t->d_part, &t->cap_part, (size_t)n * nparts))) return rc;
+  if (off && (rc = scattered_offsets(c, &t->d_off, &t->cap_off, off, n))) return rc;
+  if ((rc = t->timer.begin(c))) return rc;
   // item tiles go in slices of at most 65535 on the grid's y
   for (int y0 = 0; y0 < itiles; y0 += 65535) {
     const int ny = itiles - y0 < 65535 ? itiles - y0 : 65535, i0 = y0 * K14_TILE;
     hipLaunchKernelGGL(k14_score, dim3((unsigned)nchunks, (unsigned)ny, (unsigned)set->A), dim3(64 * K14_WAVES), 0, c->stream,
                        off ? base : base + (size_t)i0 * K14_N, off ? t->d_off + i0 : (const unsigned long long *)nullptr, n - i0,
                        set->d_tab, set->d_bitmap, set->d_masks, set->d_pow, set->npow, per, t->d_part + (size_t)i0 * nparts);
-    CALLSCHK(c, hipGetLastError());
+    CTXCHK(c, hipGetLastError());
   }
   hipLaunchKernelGGL(k14_reduce, dim3((unsigned)n), dim3(64), 0, c->stream, t->d_part, nparts, res);
-  CALLSCHK(c, hipGetLastError());
-  if (t->timing) { CALLSCHK(c, hipEventRecord(t->ev[1], c->stream)); t->timed = true; }
-  return UWSPR_OK;
-}
-
-// the context's device and [p, p + bytes) inside one device allocation of it (as uwspr_deep_batch checks its pointers)
-static bool calls_device_range(uwspr_ctx *c, const void *p, size_t bytes) {
-  hipPointerAttribute_t a;
-  memset(&a, 0, sizeof(a));
-  const hipError_t e = hipPointerGetAttributes(&a, p);
-  (void)hipGetLastError();
-  if (e != hipSuccess || a.type != hipMemoryTypeDevice || a.device != c->device) return false;
-  hipDeviceptr_t b0 = nullptr;
-  size_t size = 0;
-  if (hipMemGetAddressRange(&b0, &size, (hipDeviceptr_t)p) != hipSuccess) { (void)hipGetLastError(); return false; }
-  const char *b = (const char *)b0, *q = (const char *)p;
-  return q >= b && bytes <= size && (size_t)(q - b) <= size - bytes;
+  CTXCHK(c, hipGetLastError());
+  return t->timer.end(c);
 }
 
 }  // namespace uwspr
@@ -418,7 +366,7 @@ extern "C" int uwspr_calls_set(uwspr_ctx *c, const char *const *calls, int A, co
   if (!c) return UWSPR_ERR_ARG;
   char why[200];
   if (A != 0 && calls_check(calls, A, grid_bitmap, power_mask, nullptr, why, sizeof(why)))
-    return calls_fail(c, UWSPR_ERR_ARG, "uwspr_calls_set: %s", why);
+    return ctx_fail(c, UWSPR_ERR_ARG, "uwspr_calls_set: %s", why);
   if (A == 0 && !c->calls) return UWSPR_OK;
   int rc = calls_begin(c);
   if (rc) return rc;
@@ -426,10 +374,10 @@ extern "C" int uwspr_calls_set(uwspr_ctx *c, const char *const *calls, int A, co
   calls_set *fresh = nullptr;
   if (A > 0) {
     fresh = calls_build(calls, A, grid_bitmap, power_mask, &rc, why, sizeof(why));
-    if (!fresh) return calls_fail(c, rc, "uwspr_calls_set: %s", why);
+    if (!fresh) return ctx_fail(c, rc, "uwspr_calls_set: %s", why);
   }
   const hipError_t e = hipStreamSynchronize(c->stream);   // a call before may still read the old set
-  if (e != hipSuccess) { calls_free_set(fresh); return calls_fail(c, UWSPR_ERR_HIP, "hipStreamSynchronize: %s", hipGetErrorString(e)); }
+  if (e != hipSuccess) { calls_free_set(fresh); return ctx_fail(c, UWSPR_ERR_HIP, "hipStreamSynchronize: %s", hipGetErrorString(e)); }
   calls_free_set(t->set);
   t->set = fresh;
   return UWSPR_OK;
@@ -437,43 +385,25 @@ extern "C" int uwspr_calls_set(uwspr_ctx *c, const char *const *calls, int A, co
 
 extern "C" int uwspr_calls_batch(uwspr_ctx *c, const uint8_t *symbols, int n, int where, uwspr_call_result *res) {
   if (!c) return UWSPR_ERR_ARG;
-  if (n < 0 || (n > 0 && (!symbols || !res)) || (where != UWSPR_HOST && where != UWSPR_DEVICE))
-    return calls_fail(c, UWSPR_ERR_ARG, "uwspr_calls_batch: symbols %p, n %d, where %d, res %p", (const void *)symbols, n, where, (void *)res);
-  if (!c->calls || !c->calls->set) return calls_fail(c, UWSPR_ERR_ARG, "uwspr_calls_batch: no call set is set (uwspr_calls_set)");
-  if (n == 0) return UWSPR_OK;
-  if (!c->own_stream) return calls_fail(c, UWSPR_ERR_NODEVICE, "context has no device (creation failed: %s)", c->err);
-  CALLSCHK(c, hipSetDevice(c->device));
-  if (where == UWSPR_DEVICE) {
-    if (!calls_device_range(c, symbols, (size_t)n * K14_N) || !calls_device_range(c, res, (size_t)n * sizeof(uwspr_call_result)))
-      return calls_fail(c, UWSPR_ERR_ARG, "uwspr_calls_batch: UWSPR_DEVICE needs symbols (%zu bytes) and res (%zu bytes) inside device allocations of device %d",
-                        (size_t)n * K14_N, (size_t)n * sizeof(uwspr_call_result), c->device);
-    return calls_run(c, nullptr, symbols, nullptr, n, res, nullptr);
-  }
-  calls_state *t = c->calls;
-  int rc;
-  if ((rc = calls_grow(c, &t->d_sym, &t->cap_sym, (size_t)n * K14_N))) return rc;
-  CALLSCHK(c, hipMemcpyAsync(t->d_sym, symbols, (size_t)n * K14_N, hipMemcpyHostToDevice, c->stream));
-  uwspr_call_result *d_res = nullptr;
-  if ((rc = calls_run(c, nullptr, t->d_sym, nullptr, n, nullptr, &d_res))) return rc;
-  CALLSCHK(c, hipMemcpyAsync(res, d_res, (size_t)n * sizeof(uwspr_call_result), hipMemcpyDeviceToHost, c->stream));
-  CALLSCHK(c, hipStreamSynchronize(c->stream));
-  return UWSPR_OK;
+  return symbols_batch(c, "uwspr_calls_batch", symbols, n, where, res,
+                       !c->calls || !c->calls->set ? "no call set is set (uwspr_calls_set)" : nullptr,
+                       [&](symbols_stage **st) { *st = &c->calls->stage; return (int)UWSPR_OK; },
+                       [&](const uint8_t *d_sym, uwspr_call_result *d_res, uwspr_call_result **d_out) { return calls_run(c, nullptr, d_sym, nullptr, n, d_res, d_out); });
 }
 
 // The pipe's item form for tests/test_gpu_calls.py (not part of the ABI): item i = the 162 bytes at base + off[i], base in
 // device memory, off and res in host memory; every item must lie inside base's allocation.
 extern "C" int uwspr_debug_calls_scattered(uwspr_ctx *c, const uint8_t *base, const unsigned long long *off, int n, uwspr_call_result *res) {
   if (!c) return UWSPR_ERR_ARG;
-  if (!base || !off || !res || n < 1 || !c->calls || !c->calls->set) return calls_fail(c, UWSPR_ERR_ARG, "uwspr_debug_calls_scattered: arguments, or no call set");
-  if (!c->own_stream) return calls_fail(c, UWSPR_ERR_NODEVICE, "context has no device (creation failed: %s)", c->err);
-  CALLSCHK(c, hipSetDevice(c->device));
+  if (!base || !off || !res || n < 1 || !c->calls || !c->calls->set) return ctx_fail(c, UWSPR_ERR_ARG, "uwspr_debug_calls_scattered: arguments, or no call set");
+  if (const int rc = ctx_device_ready(c)) return rc;
   unsigned long long last = 0;
   for (int i = 0; i < n; i++) last = off[i] > last ? off[i] : last;
-  if (!calls_device_range(c, base, (size_t)last + K14_N)) return calls_fail(c, UWSPR_ERR_ARG, "uwspr_debug_calls_scattered: an item lies outside base's allocation");
+  if (!ctx_device_range(c, base, (size_t)last + K14_N)) return ctx_fail(c, UWSPR_ERR_ARG, "uwspr_debug_calls_scattered: an item lies outside base's allocation");
   uwspr_call_result *d_res = nullptr;
   if (const int rc = calls_run(c, nullptr, base, off, n, nullptr, &d_res)) return rc;
-  CALLSCHK(c, hipMemcpyAsync(res, d_res, (size_t)n * sizeof(uwspr_call_result), hipMemcpyDeviceToHost, c->stream));
-  CALLSCHK(c, hipStreamSynchronize(c->stream));
+  CTXCHK(c, hipMemcpyAsync(res, d_res, (size_t)n * sizeof(uwspr_call_result), hipMemcpyDeviceToHost, c->stream));
+  CTXCHK(c, hipStreamSynchronize(c->stream));
   return UWSPR_OK;
 }
 
@@ -482,17 +412,6 @@ extern "C" int uwspr_debug_calls_scattered(uwspr_ctx *c, const uint8_t *base, co
 // timed run's launches and returns their time.
 extern "C" int uwspr_debug_calls_time(uwspr_ctx *c, int enable, double *ms) {
   if (!c) return UWSPR_ERR_ARG;
-  if (!c->calls) c->calls = new calls_state();
-  calls_state *t = c->calls;
-  if (enable >= 0) t->timing = enable != 0;
-  if (ms) {
-    *ms = 0.0;
-    if (t->timed) {
-      float f = 0.0f;
-      CALLSCHK(c, hipEventSynchronize(t->ev[1]));
-      CALLSCHK(c, hipEventElapsedTime(&f, t->ev[0], t->ev[1]));
-      *ms = f;
-    }
-  }
-  return UWSPR_OK;
+  if (!c->calls) c->calls = new calls_state();   // (no device asked: the hook only keeps the switch)
+  return c->calls->timer.read(c, enable, ms);
 }

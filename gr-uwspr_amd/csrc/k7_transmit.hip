@@ -57,6 +57,7 @@
 #include <map>
 #include <vector>
 
+#include "ctx_util.h"
 #include "uwspr_internal.h"
 
 namespace uwspr {
@@ -533,29 +534,13 @@ void tx_release(uwspr_ctx *c) {
   c->tx = nullptr;
 }
 
-static int tx_fail(uwspr_ctx *c, int status, const char *fmt, ...) {
-  if (c) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(c->err, sizeof(c->err), fmt, ap);
-    va_end(ap);
-  }
-  return status;
-}
-
-#define TXCHK(c, call)                                                                                  \
-  do {                                                                                                  \
-    hipError_t e_ = (call);                                                                             \
-    if (e_ != hipSuccess)                                                                               \
-      return tx_fail((c), UWSPR_ERR_HIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); \
-  } while (0)
-
+// (not ctx_grow: sized in bytes, and no synchronisation -- tx_begin has synchronised the stream)
 static int tx_grow(uwspr_ctx *c, void **buf, size_t *cap, size_t bytes) {
   if (bytes <= *cap && *buf) return UWSPR_OK;
-  if (*buf) { TXCHK(c, hipFree(*buf)); *buf = nullptr; *cap = 0; }
+  if (*buf) { CTXCHK(c, hipFree(*buf)); *buf = nullptr; *cap = 0; }
   const size_t n = bytes > 256 ? bytes : 256;
   const hipError_t e = hipMalloc(buf, n);
-  if (e != hipSuccess) return tx_fail(c, UWSPR_ERR_NOMEM, "hipMalloc(%zu bytes): %s", n, hipGetErrorString(e));
+  if (e != hipSuccess) return ctx_fail(c, UWSPR_ERR_NOMEM, "hipMalloc(%zu bytes): %s", n, hipGetErrorString(e));
   *cap = n;
   return UWSPR_OK;
 }
@@ -609,45 +594,23 @@ static std::vector<float2> tx_tap_image(const std::vector<std::complex<double>> 
 
 static int tx_begin(uwspr_ctx *c) {
   if (!c) return UWSPR_ERR_ARG;
-  if (!c->own_stream) return tx_fail(c, UWSPR_ERR_NODEVICE, "context has no device (creation failed: %s)", c->err);
-  TXCHK(c, hipSetDevice(c->device));
+  if (const int rc = ctx_device_ready(c)) return rc;
   if (!c->tx) c->tx = new tx_state();
-  TXCHK(c, hipStreamSynchronize(c->stream));   // the scratch below may still be read by the previous call's kernels
+  CTXCHK(c, hipStreamSynchronize(c->stream));   // the scratch below may still be read by the previous call's kernels
   if (!c->tx->d_taps) {
     const std::vector<std::complex<double>> g = tx_composite();
-    if ((int)g.size() != K7_NT) return tx_fail(c, UWSPR_ERR_HIP, "transmit taps: %zu, expected %d", g.size(), K7_NT);
+    if ((int)g.size() != K7_NT) return ctx_fail(c, UWSPR_ERR_HIP, "transmit taps: %zu, expected %d", g.size(), K7_NT);
     const std::vector<float2> img = tx_tap_image(g);
     if (hipFuncSetAttribute(reinterpret_cast<const void *>(k7_render<false, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)k7_lds_bytes()) != hipSuccess ||
         hipFuncSetAttribute(reinterpret_cast<const void *>(k7_render<true, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)k7_lds_bytes()) != hipSuccess ||
         hipFuncSetAttribute(reinterpret_cast<const void *>(k7_render<false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)k7_lds_bytes()) != hipSuccess ||
         hipFuncSetAttribute(reinterpret_cast<const void *>(k7_render<true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)k7_lds_bytes()) != hipSuccess)
-      return tx_fail(c, UWSPR_ERR_HIP, "transmit kernel: %zu bytes of LDS refused", k7_lds_bytes());
+      return ctx_fail(c, UWSPR_ERR_HIP, "transmit kernel: %zu bytes of LDS refused", k7_lds_bytes());
     float2 *d = nullptr;
-    TXCHK(c, hipMalloc((void **)&d, img.size() * sizeof(float2)));
+    CTXCHK(c, hipMalloc((void **)&d, img.size() * sizeof(float2)));
     c->tx->d_taps = d;
-    TXCHK(c, hipMemcpy(d, img.data(), img.size() * sizeof(float2), hipMemcpyHostToDevice));
+    CTXCHK(c, hipMemcpy(d, img.data(), img.size() * sizeof(float2), hipMemcpyHostToDevice));
   }
-  return UWSPR_OK;
-}
-
-// The context's device and [p, p + bytes) inside one device allocation of it: what a kernel may touch with XNACK off.
-// Pageable host memory, another device's memory and ranges past an allocation's end are refused here, before any launch.
-static bool tx_device_range(uwspr_ctx *c, const void *p, size_t bytes) {
-  hipPointerAttribute_t a;
-  memset(&a, 0, sizeof(a));
-  const hipError_t e = hipPointerGetAttributes(&a, p);
-  (void)hipGetLastError();   // a refused query leaves no error behind for the calls that follow
-  if (e != hipSuccess || a.type != hipMemoryTypeDevice || a.device != c->device) return false;
-  hipDeviceptr_t base = nullptr;
-  size_t size = 0;
-  if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)p) != hipSuccess) { (void)hipGetLastError(); return false; }
-  const char *b = (const char *)base, *q = (const char *)p;
-  return q >= b && bytes <= size && (size_t)(q - b) <= size - bytes;
-}
-
-static int tx_device_ready(uwspr_ctx *c) {
-  if (!c->own_stream) return tx_fail(c, UWSPR_ERR_NODEVICE, "context has no device (creation failed: %s)", c->err);
-  TXCHK(c, hipSetDevice(c->device));
   return UWSPR_OK;
 }
 
@@ -671,11 +634,11 @@ static void tx_r_range(const uwspr_tx_motion &m, double ta, double tb, double *r
 static int tx_motion_check(uwspr_ctx *c, int i, const uwspr_tx_motion &m, long long *lo, long long *hi) {
   *lo = 0; *hi = K7_NTX;
   if (!tx_finite(m.v1) || !tx_finite(m.v2) || !tx_finite(m.p1) || !tx_finite(m.p2) || !tx_finite(m.t_first))
-    return tx_fail(c, UWSPR_ERR_ARG, "uwspr_tx: motion %d has a non-finite field", i);
+    return ctx_fail(c, UWSPR_ERR_ARG, "uwspr_tx: motion %d has a non-finite field", i);
   if (m.model < UWSPR_TX_STATIC || m.model > UWSPR_TX_DELAY || (m.flags & ~(UWSPR_TX_ABSOLUTE | UWSPR_TX_SPREADING)))
-    return tx_fail(c, UWSPR_ERR_ARG, "uwspr_tx: motion %d: model %d, flags 0x%x", i, m.model, (unsigned)m.flags);
+    return ctx_fail(c, UWSPR_ERR_ARG, "uwspr_tx: motion %d: model %d, flags 0x%x", i, m.model, (unsigned)m.flags);
   if (hypot(m.v1, m.v2) > 100.0 || fabs(m.t_first) > 1e6 || fabs(m.p1) > 1e9 || fabs(m.p2) > 1e9)
-    return tx_fail(c, UWSPR_ERR_ARG, "uwspr_tx: motion %d: |v| %g m/s (<= 100), t_first %g s (|.| <= 1e6), p (%g, %g) m "
+    return ctx_fail(c, UWSPR_ERR_ARG, "uwspr_tx: motion %d: |v| %g m/s (<= 100), t_first %g s (|.| <= 1e6), p (%g, %g) m "
                    "(|.| <= 1e9)", i, hypot(m.v1, m.v2), m.t_first, m.p1, m.p2);
   if (m.model == UWSPR_TX_STATIC) return UWSPR_OK;
   double a = 0.0, b = (double)K7_NTX;
@@ -690,13 +653,13 @@ static int tx_motion_check(uwspr_ctx *c, int i, const uwspr_tx_motion &m, long l
       a = std::min(a, na); b = std::max(b, nb);
     }
     if (it == 200 || !(fabs(a) < 1e15 && fabs(b) < 1e15))
-      return tx_fail(c, UWSPR_ERR_ARG, "uwspr_tx: motion %d: no bound on the delayed support", i);
+      return ctx_fail(c, UWSPR_ERR_ARG, "uwspr_tx: motion %d: no bound on the delayed support", i);
     *lo = (long long)floor(a); *hi = (long long)ceil(b) + 1;
   }
   if (m.flags & UWSPR_TX_SPREADING) {   // R(t_first) / R(t) over the transmission
     double rmin, rmax;
     tx_r_range(m, m.t_first + (double)*lo / K7_FS, m.t_first + (double)(*hi - 1) / K7_FS, &rmin, &rmax);
-    if (!(rmin >= 1.0)) return tx_fail(c, UWSPR_ERR_ARG, "uwspr_tx: motion %d: SPREADING with R down to %g m (>= 1)", i, rmin);
+    if (!(rmin >= 1.0)) return ctx_fail(c, UWSPR_ERR_ARG, "uwspr_tx: motion %d: SPREADING with R down to %g m (>= 1)", i, rmin);
   }
   return UWSPR_OK;
 }
@@ -750,7 +713,7 @@ template <typename Keep>
 static int tx_prepare(uwspr_ctx *c, const uwspr_tx_signal *sig, const uwspr_tx_motion *mot, const int32_t *car, int nsig, int C,
                       Keep keep, std::vector<tx_dsig> &out, std::vector<tx_dmot> *mout, bool *other = nullptr,
                       const uwspr_tx_fade *fade = nullptr, std::vector<tx_dfade> *fout = nullptr) {
-  if (nsig < 0 || (nsig > 0 && !sig)) return tx_fail(c, UWSPR_ERR_ARG, "uwspr_tx: signals %p, nsig %d", (const void *)sig, nsig);
+  if (nsig < 0 || (nsig > 0 && !sig)) return ctx_fail(c, UWSPR_ERR_ARG, "uwspr_tx: signals %p, nsig %d", (const void *)sig, nsig);
   out.clear();
   if (mout) mout->clear();
   if (fout) fout->clear();
@@ -760,30 +723,30 @@ static int tx_prepare(uwspr_ctx *c, const uwspr_tx_signal *sig, const uwspr_tx_m
   for (int i = 0; i < nsig; i++) {
     const int fc = car ? car[i] : UWSPR_CARRIER_DEFAULT;
     if (!tx_carrier_ok(fc, cutoff))
-      return tx_fail(c, UWSPR_ERR_ARG, "uwspr_tx: signal %d carrier %d Hz (170 .. tx_cutoff - 250 = %d)", i, fc, cutoff - 250);
+      return ctx_fail(c, UWSPR_ERR_ARG, "uwspr_tx: signal %d carrier %d Hz (170 .. tx_cutoff - 250 = %d)", i, fc, cutoff - 250);
     if (fc != UWSPR_CARRIER_DEFAULT && other) *other = true;
     if (std::find(distinct.begin(), distinct.end(), fc) == distinct.end()) distinct.push_back(fc);
   }
   if ((int)distinct.size() > K7_MAX_CARRIERS)
-    return tx_fail(c, UWSPR_ERR_ARG, "uwspr_tx: %zu distinct carriers (<= %d)", distinct.size(), K7_MAX_CARRIERS);
+    return ctx_fail(c, UWSPR_ERR_ARG, "uwspr_tx: %zu distinct carriers (<= %d)", distinct.size(), K7_MAX_CARRIERS);
   for (int i = 0; fade && i < nsig; i++)
     if (fade[i].paths != 0 && !tx_fade_ok(fade[i]))
-      return tx_fail(c, UWSPR_ERR_ARG, "uwspr_tx: fade %d: spread %g Hz (0 .. 20), shift %g Hz (|.| <= 20), K %g (0 .. 1e6), paths %d (0 .. %d)",
+      return ctx_fail(c, UWSPR_ERR_ARG, "uwspr_tx: fade %d: spread %g Hz (0 .. 20), shift %g Hz (|.| <= 20), K %g (0 .. 1e6), paths %d (0 .. %d)",
                      i, fade[i].spread_hz, fade[i].shift_hz, fade[i].k_factor, fade[i].paths, K7_FADE_MAX);
   for (int i = 0; i < nsig; i++) {
     const uwspr_tx_signal &s = sig[i];
     for (int k = 0; k < K7_NSYM; k++)
-      if (s.symbols[k] > 3) return tx_fail(c, UWSPR_ERR_ARG, "uwspr_tx: signal %d symbol %d = %d (0..3)", i, k, s.symbols[k]);
-    if (s.channel < 0 || (C > 0 && s.channel >= C)) return tx_fail(c, UWSPR_ERR_ARG, "uwspr_tx: signal %d channel %d", i, s.channel);
+      if (s.symbols[k] > 3) return ctx_fail(c, UWSPR_ERR_ARG, "uwspr_tx: signal %d symbol %d = %d (0..3)", i, k, s.symbols[k]);
+    if (s.channel < 0 || (C > 0 && s.channel >= C)) return ctx_fail(c, UWSPR_ERR_ARG, "uwspr_tx: signal %d channel %d", i, s.channel);
     if (!tx_finite(s.f0_hz) || !tx_finite(s.drift_hz) || !tx_finite(s.phase0) || !tx_finite((double)s.gain))
-      return tx_fail(c, UWSPR_ERR_ARG, "uwspr_tx: signal %d has a non-finite f0 / drift / phase / gain", i);
-    if (s.start < -(1LL << 50) || s.start > (1LL << 50)) return tx_fail(c, UWSPR_ERR_ARG, "uwspr_tx: signal %d start %lld", i, (long long)s.start);
+      return ctx_fail(c, UWSPR_ERR_ARG, "uwspr_tx: signal %d has a non-finite f0 / drift / phase / gain", i);
+    if (s.start < -(1LL << 50) || s.start > (1LL << 50)) return ctx_fail(c, UWSPR_ERR_ARG, "uwspr_tx: signal %d start %lld", i, (long long)s.start);
     long long lo = 0, hi = K7_NTX;
     if (mot) {
       const int rc = tx_motion_check(c, i, mot[i], &lo, &hi);
       if (rc) return rc;
       if (s.start + lo < -(1LL << 52) || s.start + hi > (1LL << 52))
-        return tx_fail(c, UWSPR_ERR_ARG, "uwspr_tx: signal %d: delayed support [%lld, %lld)", i, s.start + lo, s.start + hi);
+        return ctx_fail(c, UWSPR_ERR_ARG, "uwspr_tx: signal %d: delayed support [%lld, %lld)", i, s.start + lo, s.start + hi);
     }
     if (!keep(s, lo, hi)) continue;
     if (mout) {
@@ -827,7 +790,7 @@ static int tx_upload_signals(uwspr_ctx *c, const std::vector<tx_dsig> &v) {
   tx_state *t = c->tx;
   int rc = tx_grow(c, (void **)&t->d_sig, &t->cap_sig, v.size() * sizeof(tx_dsig));
   if (rc) return rc;
-  if (!v.empty()) TXCHK(c, hipMemcpyAsync(t->d_sig, v.data(), v.size() * sizeof(tx_dsig), hipMemcpyHostToDevice, c->stream));
+  if (!v.empty()) CTXCHK(c, hipMemcpyAsync(t->d_sig, v.data(), v.size() * sizeof(tx_dsig), hipMemcpyHostToDevice, c->stream));
   return UWSPR_OK;
 }
 
@@ -843,9 +806,9 @@ static int tx_upload_motions(uwspr_ctx *c, const std::vector<tx_dmot> &m) {
   int rc = tx_grow(c, (void **)&t->d_mot, &t->cap_mot, m.size() * sizeof(tx_dmot));
   if (rc) return rc;
   if (m.empty()) return UWSPR_OK;
-  TXCHK(c, hipMemcpyAsync(t->d_mot, m.data(), m.size() * sizeof(tx_dmot), hipMemcpyHostToDevice, c->stream));
+  CTXCHK(c, hipMemcpyAsync(t->d_mot, m.data(), m.size() * sizeof(tx_dmot), hipMemcpyHostToDevice, c->stream));
   hipLaunchKernelGGL(k7_motion_prep, dim3((unsigned)((m.size() + 63) / 64)), dim3(64), 0, c->stream, t->d_mot, (int)m.size());
-  TXCHK(c, hipGetLastError());
+  CTXCHK(c, hipGetLastError());
   return UWSPR_OK;
 }
 
@@ -861,14 +824,14 @@ static int tx_carrier_block(uwspr_ctx *c, const std::vector<tx_dsig> &v, int C, 
         hipFuncSetAttribute(reinterpret_cast<const void *>(k7_render<true, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)k7_lds_bytes()) != hipSuccess ||
         hipFuncSetAttribute(reinterpret_cast<const void *>(k7_render<false, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)k7_lds_bytes()) != hipSuccess ||
         hipFuncSetAttribute(reinterpret_cast<const void *>(k7_render<true, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)k7_lds_bytes()) != hipSuccess)
-      return tx_fail(c, UWSPR_ERR_HIP, "transmit kernel (carrier form): %zu bytes of LDS refused", k7_lds_bytes());
+      return ctx_fail(c, UWSPR_ERR_HIP, "transmit kernel (carrier form): %zu bytes of LDS refused", k7_lds_bytes());
     t->car_ready = true;
   }
   std::vector<int> fcs;                       // the call's distinct carriers, ascending: image index = position
   for (const tx_dsig &s : v) fcs.push_back((int)s.fc);
   std::sort(fcs.begin(), fcs.end());
   fcs.erase(std::unique(fcs.begin(), fcs.end()), fcs.end());
-  if ((int)fcs.size() > K7_MAX_CARRIERS) return tx_fail(c, UWSPR_ERR_ARG, "uwspr_tx: %zu distinct carriers (<= %d)", fcs.size(), K7_MAX_CARRIERS);
+  if ((int)fcs.size() > K7_MAX_CARRIERS) return ctx_fail(c, UWSPR_ERR_ARG, "uwspr_tx: %zu distinct carriers (<= %d)", fcs.size(), K7_MAX_CARRIERS);
   std::vector<int> goff(K7_GOFF, 0);
   std::vector<tx_dgrp> grps;
   size_t i = 0;
@@ -886,7 +849,7 @@ static int tx_carrier_block(uwspr_ctx *c, const std::vector<tx_dsig> &v, int C, 
     }
   }
   for (int ch = C; ch < K7_GOFF; ch++) goff[ch] = (int)grps.size();
-  if (i != v.size()) return tx_fail(c, UWSPR_ERR_HIP, "uwspr_tx: carrier groups cover %zu of %zu signals", i, v.size());
+  if (i != v.size()) return ctx_fail(c, UWSPR_ERR_HIP, "uwspr_tx: carrier groups cover %zu of %zu signals", i, v.size());
   const size_t img_bytes = (size_t)K7_DEC * K7_T * sizeof(float2);
   const size_t at_goff = K7_NROT * sizeof(float2), at_grps = at_goff + K7_GOFF * sizeof(int);
   const size_t at_img = at_grps + grps.size() * sizeof(tx_dgrp);
@@ -900,7 +863,7 @@ static int tx_carrier_block(uwspr_ctx *c, const std::vector<tx_dsig> &v, int C, 
     if (it == t->images.end()) {
       if (t->images.size() >= 1024) t->images.clear();   // (a sweep over carriers does not grow the cache without bound)
       const std::vector<std::complex<double>> g = tx_composite(fcs[k], cutoff);
-      if ((int)g.size() != K7_NT) return tx_fail(c, UWSPR_ERR_HIP, "transmit taps at %d Hz, cut-off %d Hz: %zu, expected %d", fcs[k], cutoff, g.size(), K7_NT);
+      if ((int)g.size() != K7_NT) return ctx_fail(c, UWSPR_ERR_HIP, "transmit taps at %d Hz, cut-off %d Hz: %zu, expected %d", fcs[k], cutoff, g.size(), K7_NT);
       it = t->images.emplace(key, tx_tap_image(g)).first;
     }
     memcpy(block.data() + at_img + k * img_bytes, it->second.data(), img_bytes);
@@ -923,7 +886,7 @@ static int tx_upload_fades(uwspr_ctx *c, const std::vector<tx_dfade> &f) {
   tx_state *t = c->tx;
   int rc = tx_grow(c, (void **)&t->d_fade, &t->cap_fade, f.size() * sizeof(tx_dfade));
   if (rc) return rc;
-  if (!f.empty()) TXCHK(c, hipMemcpyAsync(t->d_fade, f.data(), f.size() * sizeof(tx_dfade), hipMemcpyHostToDevice, c->stream));
+  if (!f.empty()) CTXCHK(c, hipMemcpyAsync(t->d_fade, f.data(), f.size() * sizeof(tx_dfade), hipMemcpyHostToDevice, c->stream));
   return UWSPR_OK;
 }
 
@@ -933,7 +896,7 @@ static int tx_baseband(uwspr_ctx *c, const uwspr_tx_signal *sig, const uwspr_tx_
                        const uwspr_tx_fade *fade, int nsig, int channel, long long t0, int n, float *iq, int where) {
   if (!c) return UWSPR_ERR_ARG;
   if (n < 0 || (n > 0 && !iq) || channel < 0 || (where != UWSPR_HOST && where != UWSPR_DEVICE))
-    return tx_fail(c, UWSPR_ERR_ARG, "uwspr_tx_baseband: n %d, iq %p, channel %d, where %d", n, (void *)iq, channel, where);
+    return ctx_fail(c, UWSPR_ERR_ARG, "uwspr_tx_baseband: n %d, iq %p, channel %d, where %d", n, (void *)iq, channel, where);
   std::vector<tx_dsig> v;
   std::vector<tx_dmot> mv;
   std::vector<tx_dfade> fv;
@@ -942,9 +905,9 @@ static int tx_baseband(uwspr_ctx *c, const uwspr_tx_signal *sig, const uwspr_tx_
   }, v, mot ? &mv : nullptr, nullptr, fade, fade ? &fv : nullptr);
   if (rc) return rc;
   if (n == 0) return UWSPR_OK;
-  if ((rc = tx_device_ready(c))) return rc;
-  if (where == UWSPR_DEVICE && !tx_device_range(c, iq, (size_t)n * sizeof(float2)))
-    return tx_fail(c, UWSPR_ERR_ARG, "uwspr_tx_baseband: iq %p is not %zu bytes of this device's memory", (void *)iq, (size_t)n * sizeof(float2));
+  if ((rc = ctx_device_ready(c))) return rc;
+  if (where == UWSPR_DEVICE && !ctx_device_range(c, iq, (size_t)n * sizeof(float2)))
+    return ctx_fail(c, UWSPR_ERR_ARG, "uwspr_tx_baseband: iq %p is not %zu bytes of this device's memory", (void *)iq, (size_t)n * sizeof(float2));
   if ((rc = tx_begin(c))) return rc;
   if ((rc = tx_upload_signals(c, v))) return rc;
   const bool moving = tx_any_moving(mv);
@@ -957,7 +920,7 @@ static int tx_baseband(uwspr_ctx *c, const uwspr_tx_signal *sig, const uwspr_tx_
     if ((rc = tx_grow(c, &t->d_out, &t->cap_out, (size_t)n * sizeof(float2)))) return rc;
     dst = (float2 *)t->d_out;
   }
-  TXCHK(c, hipStreamSynchronize(c->stream));   // (the records live on this call's stack)
+  CTXCHK(c, hipStreamSynchronize(c->stream));   // (the records live on this call's stack)
   const int blocks = (n + 255) / 256 < 2048 ? (n + 255) / 256 : 2048;
   const tx_dfade *nofade = nullptr;
   if (medium && moving)
@@ -969,10 +932,10 @@ static int tx_baseband(uwspr_ctx *c, const uwspr_tx_signal *sig, const uwspr_tx_
   else
     hipLaunchKernelGGL(k7_baseband<false>, dim3(blocks), dim3(256), 0, c->stream, t->d_sig, (const tx_dmot *)nullptr, (int)v.size(), channel, t0, n, dst, nofade);
   if (medium) k7_medium_launches[2]++;
-  TXCHK(c, hipGetLastError());
+  CTXCHK(c, hipGetLastError());
   if (where == UWSPR_HOST) {
-    TXCHK(c, hipMemcpyAsync(iq, dst, (size_t)n * sizeof(float2), hipMemcpyDeviceToHost, c->stream));
-    TXCHK(c, hipStreamSynchronize(c->stream));
+    CTXCHK(c, hipMemcpyAsync(iq, dst, (size_t)n * sizeof(float2), hipMemcpyDeviceToHost, c->stream));
+    CTXCHK(c, hipStreamSynchronize(c->stream));
   }
   return UWSPR_OK;
 }
@@ -983,14 +946,14 @@ static int tx_render(uwspr_ctx *c, const uwspr_tx_signal *sig, const uwspr_tx_mo
   if (!c) return UWSPR_ERR_ARG;
   if (C < 1 || C > UWSPR_PIPE_MAX_CHANNELS || !chan || t0 < 0 || nframes < 0 || (nframes > 0 && !out) ||
       (format != UWSPR_AUDIO_F32 && format != UWSPR_AUDIO_S16) || (where != UWSPR_HOST && where != UWSPR_DEVICE))
-    return tx_fail(c, UWSPR_ERR_ARG, "uwspr_tx_render: C %d, chan %p, t0 %lld, nframes %lld, out %p, format %d, where %d",
+    return ctx_fail(c, UWSPR_ERR_ARG, "uwspr_tx_render: C %d, chan %p, t0 %lld, nframes %lld, out %p, format %d, where %d",
                    C, (const void *)chan, t0, nframes, out, format, where);
-  if (nframes > (1LL << 40) / C) return tx_fail(c, UWSPR_ERR_ARG, "uwspr_tx_render: %lld frames x %d channels", nframes, C);
+  if (nframes > (1LL << 40) / C) return ctx_fail(c, UWSPR_ERR_ARG, "uwspr_tx_render: %lld frames x %d channels", nframes, C);
   for (int k = 0; k < C; k++) {
     const uwspr_tx_channel &z = chan[k];
     if (!tx_finite(z.sigma) || z.sigma < 0 || !tx_finite((double)z.background_gain) ||
         (z.background && (z.background_len <= 0 || (z.background_format != UWSPR_AUDIO_F32 && z.background_format != UWSPR_AUDIO_S16))))
-      return tx_fail(c, UWSPR_ERR_ARG, "uwspr_tx_render: channel %d: sigma %g, background %p len %lld format %d gain %g", k,
+      return ctx_fail(c, UWSPR_ERR_ARG, "uwspr_tx_render: channel %d: sigma %g, background %p len %lld format %d gain %g", k,
                      z.sigma, z.background, (long long)z.background_len, z.background_format, (double)z.background_gain);
   }
   // impulses: thr = min(floor(rate 2^32), 2^32 - 1) in binary64; rate 0 or sigma 0 (thr 0 here): none
@@ -1001,7 +964,7 @@ static int tx_render(uwspr_ctx *c, const uwspr_tx_signal *sig, const uwspr_tx_mo
     for (int k = 0; k < C; k++) {
       const uwspr_tx_impulse &z = imp[k];
       if (!tx_finite(z.rate) || z.rate < 0.0 || z.rate > 0.25 || !tx_finite(z.sigma) || z.sigma < 0.0 || z.length < 1 || z.length > 8)
-        return tx_fail(c, UWSPR_ERR_ARG, "uwspr_tx_render: channel %d: impulse rate %g (0 .. 0.25), sigma %g (>= 0), length %d (1 .. 8)",
+        return ctx_fail(c, UWSPR_ERR_ARG, "uwspr_tx_render: channel %d: impulse rate %g (0 .. 0.25), sigma %g (>= 0), length %d (1 .. 8)",
                        k, z.rate, z.sigma, z.length);
       tx_dimp &d = di[k];
       memset(&d, 0, sizeof(d));
@@ -1028,14 +991,14 @@ static int tx_render(uwspr_ctx *c, const uwspr_tx_signal *sig, const uwspr_tx_mo
   const int cutoff = c->opt[UWSPR_OPT_TX_CUTOFF];
   const bool carrier = medium || other || cutoff != UWSPR_TX_CUTOFF_DEFAULT || c->opt[UWSPR_OPT_TX_FORM] != 0;
   const size_t esz = format == UWSPR_AUDIO_S16 ? 2 : 4;
-  if ((rc = tx_device_ready(c))) return rc;
+  if ((rc = ctx_device_ready(c))) return rc;
   if (where == UWSPR_DEVICE) {   // device pointers must be device memory: a host pointer would fault the kernel
-    if (!tx_device_range(c, out, (size_t)nframes * C * esz))
-      return tx_fail(c, UWSPR_ERR_ARG, "uwspr_tx_render: out %p is not %zu bytes of this device's memory", out, (size_t)nframes * C * esz);
+    if (!ctx_device_range(c, out, (size_t)nframes * C * esz))
+      return ctx_fail(c, UWSPR_ERR_ARG, "uwspr_tx_render: out %p is not %zu bytes of this device's memory", out, (size_t)nframes * C * esz);
     for (int k = 0; k < C; k++)
       if (chan[k].background &&
-          !tx_device_range(c, chan[k].background, (size_t)chan[k].background_len * (chan[k].background_format == UWSPR_AUDIO_S16 ? 2 : 4)))
-        return tx_fail(c, UWSPR_ERR_ARG, "uwspr_tx_render: channel %d: background %p is not %lld samples of this device's memory", k,
+          !ctx_device_range(c, chan[k].background, (size_t)chan[k].background_len * (chan[k].background_format == UWSPR_AUDIO_S16 ? 2 : 4)))
+        return ctx_fail(c, UWSPR_ERR_ARG, "uwspr_tx_render: channel %d: background %p is not %lld samples of this device's memory", k,
                        chan[k].background, (long long)chan[k].background_len);
   }
   // the kernel walks only its channel's signals: sorted by channel, ascending index within one (the order they add up in)
@@ -1070,14 +1033,14 @@ static int tx_render(uwspr_ctx *c, const uwspr_tx_signal *sig, const uwspr_tx_mo
           hipFuncSetAttribute(reinterpret_cast<const void *>(k7_render<true, false, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)k7_lds_bytes()) != hipSuccess ||
           hipFuncSetAttribute(reinterpret_cast<const void *>(k7_render<false, true, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)k7_lds_bytes()) != hipSuccess ||
           hipFuncSetAttribute(reinterpret_cast<const void *>(k7_render<true, true, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)k7_lds_bytes()) != hipSuccess)
-        return tx_fail(c, UWSPR_ERR_HIP, "transmit kernel (medium form): %zu bytes of LDS refused", k7_lds_bytes());
+        return ctx_fail(c, UWSPR_ERR_HIP, "transmit kernel (medium form): %zu bytes of LDS refused", k7_lds_bytes());
       t->med_ready = true;
     }
     if (fv.size() != v.size()) fv.assign(v.size(), tx_dfade());   // (impulses alone: no signal fades)
     if ((rc = tx_upload_fades(c, fv))) return rc;
     if (di.empty()) di.assign(C, tx_dimp());
-    if (!t->d_imp) TXCHK(c, hipMalloc((void **)&t->d_imp, UWSPR_PIPE_MAX_CHANNELS * sizeof(tx_dimp)));
-    TXCHK(c, hipMemcpyAsync(t->d_imp, di.data(), C * sizeof(tx_dimp), hipMemcpyHostToDevice, c->stream));
+    if (!t->d_imp) CTXCHK(c, hipMalloc((void **)&t->d_imp, UWSPR_PIPE_MAX_CHANNELS * sizeof(tx_dimp)));
+    CTXCHK(c, hipMemcpyAsync(t->d_imp, di.data(), C * sizeof(tx_dimp), hipMemcpyHostToDevice, c->stream));
   }
   // channels: host backgrounds are staged behind each other
   std::vector<tx_dchan> dc(C);
@@ -1098,7 +1061,7 @@ static int tx_render(uwspr_ctx *c, const uwspr_tx_signal *sig, const uwspr_tx_mo
       d.bg_len = z.background_len; d.bg_s16 = z.background_format == UWSPR_AUDIO_S16;
       if (where == UWSPR_HOST) {
         const size_t b = (size_t)z.background_len * (d.bg_s16 ? 2 : 4);
-        TXCHK(c, hipMemcpyAsync((char *)t->d_bg + off, z.background, b, hipMemcpyHostToDevice, c->stream));
+        CTXCHK(c, hipMemcpyAsync((char *)t->d_bg + off, z.background, b, hipMemcpyHostToDevice, c->stream));
         d.bg = (char *)t->d_bg + off;
         off += (b + 255) / 256 * 256;
       } else {
@@ -1106,15 +1069,15 @@ static int tx_render(uwspr_ctx *c, const uwspr_tx_signal *sig, const uwspr_tx_mo
       }
     }
   }
-  if (!t->d_chan) TXCHK(c, hipMalloc((void **)&t->d_chan, UWSPR_PIPE_MAX_CHANNELS * sizeof(tx_dchan)));
-  TXCHK(c, hipMemcpyAsync(t->d_chan, dc.data(), C * sizeof(tx_dchan), hipMemcpyHostToDevice, c->stream));
+  if (!t->d_chan) CTXCHK(c, hipMalloc((void **)&t->d_chan, UWSPR_PIPE_MAX_CHANNELS * sizeof(tx_dchan)));
+  CTXCHK(c, hipMemcpyAsync(t->d_chan, dc.data(), C * sizeof(tx_dchan), hipMemcpyHostToDevice, c->stream));
   std::vector<char> block;
   if (carrier) {
     if ((rc = tx_carrier_block(c, v, C, cutoff, block))) return rc;
     if ((rc = tx_grow(c, &t->d_car, &t->cap_car, block.size()))) return rc;
-    TXCHK(c, hipMemcpyAsync(t->d_car, block.data(), block.size(), hipMemcpyHostToDevice, c->stream));
+    CTXCHK(c, hipMemcpyAsync(t->d_car, block.data(), block.size(), hipMemcpyHostToDevice, c->stream));
   }
-  TXCHK(c, hipStreamSynchronize(c->stream));   // (the records above live on this call's stack)
+  CTXCHK(c, hipStreamSynchronize(c->stream));   // (the records above live on this call's stack)
 
   // device output: one launch; host output: pieces of at most 2^24 samples through a staging buffer (the render of any
   // piece is the same bytes as that part of a whole render)
@@ -1124,7 +1087,7 @@ static int tx_render(uwspr_ctx *c, const uwspr_tx_signal *sig, const uwspr_tx_mo
     const long long a = t0 + k, len = std::min(piece, nframes - k);
     const long long nb0 = a / K7_DEC;
     const long long nblk = (a + len - K7_DEC * nb0 + K7_OUT - 1) / K7_OUT;
-    if (nblk * C > 0x7fffffffLL) return tx_fail(c, UWSPR_ERR_ARG, "uwspr_tx_render: %lld workgroups", nblk * C);
+    if (nblk * C > 0x7fffffffLL) return ctx_fail(c, UWSPR_ERR_ARG, "uwspr_tx_render: %lld workgroups", nblk * C);
     void *dst = where == UWSPR_HOST ? t->d_out : (void *)((char *)out + (size_t)k * C * esz);
     const dim3 grid((unsigned)(nblk * C));
     const tx_dmot *dm = moving ? t->d_mot : nullptr;
@@ -1172,10 +1135,10 @@ static int tx_render(uwspr_ctx *c, const uwspr_tx_signal *sig, const uwspr_tx_mo
     else
       hipLaunchKernelGGL((k7_render<false, false>), grid, dim3(K7_WG), k7_lds_bytes(), c->stream, t->d_sig, dm, (int)v.size(),
                          t->d_chan, C, t->d_taps, a, len, nb0, dst, nofade, noimp);
-    TXCHK(c, hipGetLastError());
+    CTXCHK(c, hipGetLastError());
     if (where == UWSPR_HOST) {
-      TXCHK(c, hipMemcpyAsync((char *)out + (size_t)k * C * esz, dst, (size_t)len * C * esz, hipMemcpyDeviceToHost, c->stream));
-      TXCHK(c, hipStreamSynchronize(c->stream));
+      CTXCHK(c, hipMemcpyAsync((char *)out + (size_t)k * C * esz, dst, (size_t)len * C * esz, hipMemcpyDeviceToHost, c->stream));
+      CTXCHK(c, hipStreamSynchronize(c->stream));
     }
   }
   return UWSPR_OK;

@@ -31,6 +31,7 @@
 #include <algorithm>
 #include <vector>
 
+#include "ctx_util.h"
 #include "uwspr_internal.h"
 
 namespace uwspr {
@@ -335,39 +336,22 @@ void sub_release(uwspr_ctx *c) {
   c->sub = nullptr;
 }
 
-static int sub_fail(uwspr_ctx *c, int status, const char *fmt, ...) {
-  if (c) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(c->err, sizeof(c->err), fmt, ap);
-    va_end(ap);
-  }
-  return status;
-}
-
-#define SUBCHK(c, call)                                                                                 \
-  do {                                                                                                  \
-    hipError_t e_ = (call);                                                                             \
-    if (e_ != hipSuccess)                                                                               \
-      return sub_fail((c), UWSPR_ERR_HIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); \
-  } while (0)
-
+// (not ctx_grow: at least 64 elements, and no synchronisation -- sub_begin has synchronised the stream)
 template <typename T>
 static int sub_grow(uwspr_ctx *c, T **buf, size_t *cap, size_t elems) {
   if (elems <= *cap && *buf) return UWSPR_OK;
-  if (*buf) { SUBCHK(c, hipFree(*buf)); *buf = nullptr; *cap = 0; }
+  if (*buf) { CTXCHK(c, hipFree(*buf)); *buf = nullptr; *cap = 0; }
   const size_t n = elems > 64 ? elems : 64;
   const hipError_t e = hipMalloc((void **)buf, n * sizeof(T));
-  if (e != hipSuccess) return sub_fail(c, UWSPR_ERR_NOMEM, "hipMalloc(%zu bytes): %s", n * sizeof(T), hipGetErrorString(e));
+  if (e != hipSuccess) return ctx_fail(c, UWSPR_ERR_NOMEM, "hipMalloc(%zu bytes): %s", n * sizeof(T), hipGetErrorString(e));
   *cap = n;
   return UWSPR_OK;
 }
 
 static int sub_begin(uwspr_ctx *c) {
-  if (!c->own_stream) return sub_fail(c, UWSPR_ERR_NODEVICE, "context has no device (creation failed: %s)", c->err);
-  SUBCHK(c, hipSetDevice(c->device));
+  if (const int rc0 = ctx_device_ready(c)) return rc0;
   if (!c->sub) c->sub = new sub_state();
-  SUBCHK(c, hipStreamSynchronize(c->stream));   // the scratch below may still be read by the previous call's kernels
+  CTXCHK(c, hipStreamSynchronize(c->stream));   // the scratch below may still be read by the previous call's kernels
   sub_state *t = c->sub;
   if (!t->d_taps) {
     // np.hanning(1025)[1:-1]: w[m] = 0.5 - 0.5 cos(2 pi (m + 1) / 1024), m = 0..1022
@@ -381,12 +365,12 @@ static int sub_begin(uwspr_ctx *c) {
       w[m] = (float)v;
     }
     cw[K8_TAPS] = s;
-    SUBCHK(c, hipMalloc((void **)&t->d_cw, 1024 * sizeof(double)));
-    SUBCHK(c, hipMemcpy(t->d_cw, cw.data(), 1024 * sizeof(double), hipMemcpyHostToDevice));
+    CTXCHK(c, hipMalloc((void **)&t->d_cw, 1024 * sizeof(double)));
+    CTXCHK(c, hipMemcpy(t->d_cw, cw.data(), 1024 * sizeof(double), hipMemcpyHostToDevice));
     float *d = nullptr;
-    SUBCHK(c, hipMalloc((void **)&d, 1024 * sizeof(float)));
+    CTXCHK(c, hipMalloc((void **)&d, 1024 * sizeof(float)));
     t->d_taps = d;
-    SUBCHK(c, hipMemcpy(d, w.data(), 1024 * sizeof(float), hipMemcpyHostToDevice));
+    CTXCHK(c, hipMemcpy(d, w.data(), 1024 * sizeof(float), hipMemcpyHostToDevice));
   }
   return UWSPR_OK;
 }
@@ -396,17 +380,17 @@ static bool sub_finite(float v) { return v == v && v - v == 0.0f; }
 // what makes a list of items acceptable: sorted by frame, frames in [0, nframes), symbols 0..3, finite f and drift,
 // a shift no kernel index can overflow on.  Checked before anything is launched or written.
 int subtract_check(uwspr_ctx *c, const uwspr_sub_item *items, int nitems, int nframes) {
-  if (nitems < 0 || (nitems > 0 && !items)) return sub_fail(c, UWSPR_ERR_ARG, "uwspr_subtract_batch: items %p, nitems %d", (const void *)items, nitems);
+  if (nitems < 0 || (nitems > 0 && !items)) return ctx_fail(c, UWSPR_ERR_ARG, "uwspr_subtract_batch: items %p, nitems %d", (const void *)items, nitems);
   for (int i = 0; i < nitems; i++) {
     const uwspr_sub_item &s = items[i];
-    if (s.frame < 0 || s.frame >= nframes) return sub_fail(c, UWSPR_ERR_ARG, "uwspr_subtract_batch: item %d: frame %d (0..%d)", i, s.frame, nframes - 1);
+    if (s.frame < 0 || s.frame >= nframes) return ctx_fail(c, UWSPR_ERR_ARG, "uwspr_subtract_batch: item %d: frame %d (0..%d)", i, s.frame, nframes - 1);
     if (i > 0 && s.frame < items[i - 1].frame)
-      return sub_fail(c, UWSPR_ERR_ARG, "uwspr_subtract_batch: item %d: frame %d after frame %d (items are sorted by frame)", i, s.frame, items[i - 1].frame);
+      return ctx_fail(c, UWSPR_ERR_ARG, "uwspr_subtract_batch: item %d: frame %d after frame %d (items are sorted by frame)", i, s.frame, items[i - 1].frame);
     for (int k = 0; k < K8_NSYM; k++)
-      if (s.symbols[k] > 3) return sub_fail(c, UWSPR_ERR_ARG, "uwspr_subtract_batch: item %d symbol %d = %d (0..3)", i, k, s.symbols[k]);
+      if (s.symbols[k] > 3) return ctx_fail(c, UWSPR_ERR_ARG, "uwspr_subtract_batch: item %d symbol %d = %d (0..3)", i, k, s.symbols[k]);
     if (!sub_finite(s.f_hz) || !sub_finite(s.drift_hz) || fabsf(s.f_hz) > 1e4f || fabsf(s.drift_hz) > 1e3f)
-      return sub_fail(c, UWSPR_ERR_ARG, "uwspr_subtract_batch: item %d: f %g Hz (|.| <= 1e4), drift %g Hz (|.| <= 1e3)", i, (double)s.f_hz, (double)s.drift_hz);
-    if (s.shift < -(1 << 20) || s.shift > (1 << 20)) return sub_fail(c, UWSPR_ERR_ARG, "uwspr_subtract_batch: item %d: shift %d (|.| <= 2^20)", i, s.shift);
+      return ctx_fail(c, UWSPR_ERR_ARG, "uwspr_subtract_batch: item %d: f %g Hz (|.| <= 1e4), drift %g Hz (|.| <= 1e3)", i, (double)s.f_hz, (double)s.drift_hz);
+    if (s.shift < -(1 << 20) || s.shift > (1 << 20)) return ctx_fail(c, UWSPR_ERR_ARG, "uwspr_subtract_batch: item %d: shift %d (|.| <= 2^20)", i, s.shift);
   }
   return UWSPR_OK;
 }
@@ -444,42 +428,42 @@ int subtract_run(uwspr_ctx *c, const float *src, size_t stride, int nslots, cons
     if ((rc = sub_grow(c, &t->d_y, &t->cap_y, (size_t)rank_at[1] * K8_N))) return rc;
     if ((rc = sub_grow(c, &t->d_rem, &t->cap_rem, (size_t)nitems * K8_TILES))) return rc;
     if ((rc = sub_grow(c, &t->d_res, &t->cap_res, (size_t)nitems))) return rc;
-    SUBCHK(c, hipMemcpyAsync(t->d_items, items, (size_t)nitems * sizeof(uwspr_sub_item), hipMemcpyHostToDevice, c->stream));
-    SUBCHK(c, hipMemcpyAsync(t->d_order, order.data(), (size_t)nitems * sizeof(int), hipMemcpyHostToDevice, c->stream));
+    CTXCHK(c, hipMemcpyAsync(t->d_items, items, (size_t)nitems * sizeof(uwspr_sub_item), hipMemcpyHostToDevice, c->stream));
+    CTXCHK(c, hipMemcpyAsync(t->d_order, order.data(), (size_t)nitems * sizeof(int), hipMemcpyHostToDevice, c->stream));
   }
   if (slot_frame) {
     if ((rc = sub_grow(c, &t->d_map, &t->cap_map, (size_t)nslots))) return rc;
-    SUBCHK(c, hipMemcpyAsync(t->d_map, slot_frame, (size_t)nslots * sizeof(int), hipMemcpyHostToDevice, c->stream));
+    CTXCHK(c, hipMemcpyAsync(t->d_map, slot_frame, (size_t)nslots * sizeof(int), hipMemcpyHostToDevice, c->stream));
   }
-  SUBCHK(c, hipStreamSynchronize(c->stream));   // (the records above live in the caller's and this call's host memory)
+  CTXCHK(c, hipStreamSynchronize(c->stream));   // (the records above live in the caller's and this call's host memory)
   float2 *out = reinterpret_cast<float2 *>(dst);
   if (src != dst) {
     hipLaunchKernelGGL(k8_copy, dim3((unsigned)((fl + 1023) / 1024), (unsigned)nslots), dim3(256), 0, c->stream,
                        reinterpret_cast<const float2 *>(src), stride, slot_frame ? t->d_map : (const int *)nullptr, out, fl);
-    SUBCHK(c, hipGetLastError());
+    CTXCHK(c, hipGetLastError());
   }
   t->ev_used = 0;
   if (t->timing)
     while (t->ev.size() < 4 * (rank_at.empty() ? 0 : rank_at.size() - 1)) {
       hipEvent_t e;
-      SUBCHK(c, hipEventCreate(&e));
+      CTXCHK(c, hipEventCreate(&e));
       t->ev.push_back(e);
     }
   for (size_t r = 0; r + 1 < rank_at.size(); r++) {
     const int n = rank_at[r + 1] - rank_at[r];
     const int *ord = t->d_order + rank_at[r];
     hipEvent_t *ev = t->timing ? &t->ev[4 * r] : nullptr;
-    if (ev) SUBCHK(c, hipEventRecord(ev[0], c->stream));
+    if (ev) CTXCHK(c, hipEventRecord(ev[0], c->stream));
     if (refine) hipLaunchKernelGGL(k8_refine, dim3(K8_PARTS, (unsigned)n), dim3(128), 0, c->stream, out, fl, t->d_items, ord, t->d_part);
-    if (ev) SUBCHK(c, hipEventRecord(ev[1], c->stream));
+    if (ev) CTXCHK(c, hipEventRecord(ev[1], c->stream));
     hipLaunchKernelGGL(k8_pick, dim3((unsigned)n), dim3(64), 0, c->stream, t->d_items, ord, t->d_part, refine ? 1 : 0, fl, t->d_st);
-    if (ev) SUBCHK(c, hipEventRecord(ev[2], c->stream));
+    if (ev) CTXCHK(c, hipEventRecord(ev[2], c->stream));
     hipLaunchKernelGGL(k8_cancel, dim3(K8_TILES, (unsigned)n), dim3(K8_CWG), 0, c->stream, out, fl, t->d_items, ord, t->d_st,
                        t->d_taps, t->d_cw, t->d_y, t->d_rem);
-    if (ev) { SUBCHK(c, hipEventRecord(ev[3], c->stream)); t->ev_used = 4 * (r + 1); }
+    if (ev) { CTXCHK(c, hipEventRecord(ev[3], c->stream)); t->ev_used = 4 * (r + 1); }
     hipLaunchKernelGGL(k8_apply, dim3(K8_N / 256, (unsigned)n), dim3(256), 0, c->stream, out, fl, t->d_items, ord, t->d_st, t->d_y,
                        t->d_rem, t->d_res);
-    SUBCHK(c, hipGetLastError());
+    CTXCHK(c, hipGetLastError());
   }
   t->last_items = nitems;
   t->last_refine = refine != 0;
@@ -494,7 +478,7 @@ extern "C" int uwspr_subtract_batch(uwspr_ctx *c, const float *frames, int B, in
                                     int refine, float *frames_out, uwspr_sub_result *res) {
   if (!c) return UWSPR_ERR_ARG;
   if (!frames || !frames_out || B <= 0 || (where != UWSPR_HOST && where != UWSPR_DEVICE && where != UWSPR_DEVICE_FRAMES))
-    return sub_fail(c, UWSPR_ERR_ARG, "uwspr_subtract_batch: frames %p, frames_out %p, B %d, where %d", (const void *)frames,
+    return ctx_fail(c, UWSPR_ERR_ARG, "uwspr_subtract_batch: frames %p, frames_out %p, B %d, where %d", (const void *)frames,
                     (void *)frames_out, B, where);
   int rc = subtract_check(c, items, nitems, B);
   if (rc) return rc;
@@ -503,10 +487,9 @@ extern "C" int uwspr_subtract_batch(uwspr_ctx *c, const float *frames, int B, in
     const char *a0 = (const char *)frames, *a1 = a0 + ((size_t)(B - 1) * stride + fl) * sizeof(float2);
     const char *b0 = (const char *)frames_out, *b1 = b0 + (size_t)B * fl * sizeof(float2);
     if (a0 < b1 && b0 < a1 && !(a0 == b0 && stride == fl))
-      return sub_fail(c, UWSPR_ERR_ARG, "uwspr_subtract_batch: frames_out overlaps frames (in place only with the frame stride 0 or fl, it is %zu)", stride);
+      return ctx_fail(c, UWSPR_ERR_ARG, "uwspr_subtract_batch: frames_out overlaps frames (in place only with the frame stride 0 or fl, it is %zu)", stride);
   }
-  if (!c->own_stream) return sub_fail(c, UWSPR_ERR_NODEVICE, "context has no device (creation failed: %s)", c->err);
-  SUBCHK(c, hipSetDevice(c->device));
+  if (const int rc0 = ctx_device_ready(c)) return rc0;
   const float *src = nullptr;
   if ((rc = api_frames_on_device(c, frames, B, where, &src))) return rc;
   float *dst = frames_out;
@@ -517,11 +500,11 @@ extern "C" int uwspr_subtract_batch(uwspr_ctx *c, const float *frames, int B, in
   }
   if ((rc = subtract_run(c, src, stride, B, nullptr, items, nitems, refine, dst))) return rc;
   if (where == UWSPR_HOST)
-    SUBCHK(c, hipMemcpyAsync(frames_out, dst, (size_t)B * fl * sizeof(float2), hipMemcpyDeviceToHost, c->stream));
+    CTXCHK(c, hipMemcpyAsync(frames_out, dst, (size_t)B * fl * sizeof(float2), hipMemcpyDeviceToHost, c->stream));
   if (res && nitems > 0)
-    SUBCHK(c, hipMemcpyAsync(res, c->sub->d_res, (size_t)nitems * sizeof(uwspr_sub_result),
+    CTXCHK(c, hipMemcpyAsync(res, c->sub->d_res, (size_t)nitems * sizeof(uwspr_sub_result),
                              where == UWSPR_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, c->stream));
-  if (where != UWSPR_DEVICE) SUBCHK(c, hipStreamSynchronize(c->stream));
+  if (where != UWSPR_DEVICE) CTXCHK(c, hipStreamSynchronize(c->stream));
   return UWSPR_OK;
 }
 
@@ -537,10 +520,10 @@ extern "C" int uwspr_debug_subtract_times(uwspr_ctx *c, int enable, double *refi
     double a = 0.0, b = 0.0;
     for (size_t k = 0; k + 3 < t->ev_used; k += 4) {
       float ms = 0.0f;
-      SUBCHK(c, hipEventSynchronize(t->ev[k + 3]));
-      SUBCHK(c, hipEventElapsedTime(&ms, t->ev[k], t->ev[k + 1]));
+      CTXCHK(c, hipEventSynchronize(t->ev[k + 3]));
+      CTXCHK(c, hipEventElapsedTime(&ms, t->ev[k], t->ev[k + 1]));
       a += ms;
-      SUBCHK(c, hipEventElapsedTime(&ms, t->ev[k + 2], t->ev[k + 3]));
+      CTXCHK(c, hipEventElapsedTime(&ms, t->ev[k + 2], t->ev[k + 3]));
       b += ms;
     }
     if (refine_ms) *refine_ms = a;
@@ -557,13 +540,12 @@ extern "C" int uwspr_debug_subtract_surface(uwspr_ctx *c, int item, float *M) {
   if (!c) return UWSPR_ERR_ARG;
   sub_state *t = c->sub;
   if (!M || !t || !t->last_refine || item < 0 || item >= t->last_items)
-    return sub_fail(c, UWSPR_ERR_ARG, "uwspr_debug_subtract_surface: item %d, M %p (the last call: %d items, refine %d)", item, (void *)M,
+    return ctx_fail(c, UWSPR_ERR_ARG, "uwspr_debug_subtract_surface: item %d, M %p (the last call: %d items, refine %d)", item, (void *)M,
                     t ? t->last_items : 0, t ? (int)t->last_refine : 0);
-  if (!c->own_stream) return sub_fail(c, UWSPR_ERR_NODEVICE, "context has no device (creation failed: %s)", c->err);
-  SUBCHK(c, hipSetDevice(c->device));
-  SUBCHK(c, hipStreamSynchronize(c->stream));
+  if (const int rc0 = ctx_device_ready(c)) return rc0;
+  CTXCHK(c, hipStreamSynchronize(c->stream));
   std::vector<float> part((size_t)K8_PARTS * K8_NHYP);
-  SUBCHK(c, hipMemcpy(part.data(), t->d_part + (size_t)item * K8_PARTS * K8_NHYP, part.size() * sizeof(float), hipMemcpyDeviceToHost));
+  CTXCHK(c, hipMemcpy(part.data(), t->d_part + (size_t)item * K8_PARTS * K8_NHYP, part.size() * sizeof(float), hipMemcpyDeviceToHost));
   for (int h = 0; h < K8_NHYP; h++) {
     float s = 0.0f;
     for (int p = 0; p < K8_PARTS; p++) s += part[(size_t)p * K8_NHYP + h];

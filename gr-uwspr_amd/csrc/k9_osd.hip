@@ -14,6 +14,7 @@
 
 #include <vector>
 
+#include "ctx_util.h"
 #include "uwspr_internal.h"
 
 namespace uwspr {
@@ -25,11 +26,10 @@ constexpr int K9_TAB_WORDS = K9_K * K9_W + K9_N;
 
 struct osd_state {
   uint32_t *d_tab = nullptr;
-  uint8_t *d_sym = nullptr; size_t cap_sym = 0;                 // host symbols staged
+  symbols_stage stage;                                          // host symbols staged
   uwspr_osd_result *d_res = nullptr; size_t cap_res = 0;
   unsigned long long *d_off = nullptr; size_t cap_off = 0;      // byte offsets of scattered items
-  hipEvent_t ev[2] = {nullptr, nullptr};                        // uwspr_debug_osd_time
-  bool timing = false, timed = false;
+  launch_timer timer;                                           // uwspr_debug_osd_time
 };
 
 __device__ __forceinline__ uint32_t k9_pick(const uint32_t (&w)[K9_ROW], int wi) {   // wi is wave-uniform
@@ -191,46 +191,16 @@ __global__ void __launch_bounds__(64) k9_osd(const uint8_t *__restrict__ base, c
 void osd_release(uwspr_ctx *c) {
   if (!c || !c->osd) return;
   osd_state *t = c->osd;
-  void *bufs[] = {t->d_tab, t->d_sym, t->d_res, t->d_off};
+  void *bufs[] = {t->d_tab, t->stage.d_sym, t->d_res, t->d_off};
   for (void *b : bufs) if (b) (void)hipFree(b);
-  for (hipEvent_t e : t->ev) if (e) (void)hipEventDestroy(e);
+  t->timer.release();
   delete t;
   c->osd = nullptr;
 }
 
-static int osd_fail(uwspr_ctx *c, int status, const char *fmt, ...) {
-  if (c) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(c->err, sizeof(c->err), fmt, ap);
-    va_end(ap);
-  }
-  return status;
-}
-
-#define OSDCHK(c, call)                                                                                 \
-  do {                                                                                                  \
-    hipError_t e_ = (call);                                                                             \
-    if (e_ != hipSuccess)                                                                               \
-      return osd_fail((c), UWSPR_ERR_HIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); \
-  } while (0)
-
-template <typename T>
-static int osd_grow(uwspr_ctx *c, T **buf, size_t *cap, size_t elems) {
-  if (elems <= *cap && *buf) return UWSPR_OK;
-  OSDCHK(c, hipStreamSynchronize(c->stream));   // the old buffer may still be read by the call before
-  if (*buf) { OSDCHK(c, hipFree(*buf)); *buf = nullptr; *cap = 0; }
-  const size_t n = elems > 256 ? elems : 256;
-  const hipError_t e = hipMalloc((void **)buf, n * sizeof(T));
-  if (e != hipSuccess) { (void)hipGetLastError(); return osd_fail(c, UWSPR_ERR_NOMEM, "hipMalloc(%zu bytes): %s", n * sizeof(T), hipGetErrorString(e)); }
-  *cap = n;
-  return UWSPR_OK;
-}
-
 // G (row j = uwspr_fano_encode of the 81-bit input with only bit j set) and the de-interleave table, once per context
 static int osd_begin(uwspr_ctx *c) {
-  if (!c->own_stream) return osd_fail(c, UWSPR_ERR_NODEVICE, "context has no device (creation failed: %s)", c->err);
-  OSDCHK(c, hipSetDevice(c->device));
+  if (const int rc = ctx_device_ready(c)) return rc;
   if (!c->osd) c->osd = new osd_state();
   osd_state *t = c->osd;
   if (!t->d_tab) {
@@ -247,8 +217,8 @@ static int osd_begin(uwspr_ctx *c) {
     for (int i = 0; i < K9_N; i++) idx[i] = (uint8_t)i;
     uwspr_deinterleave(idx);   // idx[p] = the interleaved position destination p takes
     for (int p = 0; p < K9_N; p++) tab[K9_K * K9_W + p] = idx[p];
-    OSDCHK(c, hipMalloc((void **)&t->d_tab, tab.size() * sizeof(uint32_t)));
-    OSDCHK(c, hipMemcpy(t->d_tab, tab.data(), tab.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    CTXCHK(c, hipMalloc((void **)&t->d_tab, tab.size() * sizeof(uint32_t)));
+    CTXCHK(c, hipMemcpy(t->d_tab, tab.data(), tab.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
   }
   return UWSPR_OK;
 }
@@ -261,38 +231,16 @@ int osd_run(uwspr_ctx *c, const uint8_t *base, const unsigned long long *off, in
   if (rc) return rc;
   osd_state *t = c->osd;
   if (!res) {
-    if ((rc = osd_grow(c, &t->d_res, &t->cap_res, (size_t)n))) return rc;
+    if ((rc = ctx_grow(c, &t->d_res, &t->cap_res, (size_t)n))) return rc;
     res = t->d_res;
   }
   if (res_out) *res_out = res;
-  if (off) {
-    if ((rc = osd_grow(c, &t->d_off, &t->cap_off, (size_t)n))) return rc;
-    OSDCHK(c, hipMemcpyAsync(t->d_off, off, (size_t)n * sizeof(unsigned long long), hipMemcpyHostToDevice, c->stream));
-    OSDCHK(c, hipStreamSynchronize(c->stream));   // (off is the caller's host memory)
-  }
-  if (t->timing) {
-    for (hipEvent_t &e : t->ev) if (!e) OSDCHK(c, hipEventCreate(&e));
-    OSDCHK(c, hipEventRecord(t->ev[0], c->stream));
-  }
+  if (off && (rc = scattered_offsets(c, &t->d_off, &t->cap_off, off, n))) return rc;
+  if ((rc = t->timer.begin(c))) return rc;
   hipLaunchKernelGGL(k9_osd, dim3((unsigned)n), dim3(64), 0, c->stream, base, off ? t->d_off : (const unsigned long long *)nullptr,
                      t->d_tab, order, res);
-  OSDCHK(c, hipGetLastError());
-  if (t->timing) { OSDCHK(c, hipEventRecord(t->ev[1], c->stream)); t->timed = true; }
-  return UWSPR_OK;
-}
-
-// the context's device and [p, p + bytes) inside one device allocation of it (as the transmit calls check their pointers)
-static bool osd_device_range(uwspr_ctx *c, const void *p, size_t bytes) {
-  hipPointerAttribute_t a;
-  memset(&a, 0, sizeof(a));
-  const hipError_t e = hipPointerGetAttributes(&a, p);
-  (void)hipGetLastError();
-  if (e != hipSuccess || a.type != hipMemoryTypeDevice || a.device != c->device) return false;
-  hipDeviceptr_t b0 = nullptr;
-  size_t size = 0;
-  if (hipMemGetAddressRange(&b0, &size, (hipDeviceptr_t)p) != hipSuccess) { (void)hipGetLastError(); return false; }
-  const char *b = (const char *)b0, *q = (const char *)p;
-  return q >= b && bytes <= size && (size_t)(q - b) <= size - bytes;
+  CTXCHK(c, hipGetLastError());
+  return t->timer.end(c);
 }
 
 }  // namespace uwspr
@@ -301,28 +249,10 @@ using namespace uwspr;
 
 extern "C" int uwspr_osd_batch(uwspr_ctx *c, const uint8_t *symbols, int n, int where, int order, uwspr_osd_result *res) {
   if (!c) return UWSPR_ERR_ARG;
-  if (order < 0 || order > 2) return osd_fail(c, UWSPR_ERR_ARG, "uwspr_osd_batch: order %d (0..2)", order);
-  if (n < 0 || (n > 0 && (!symbols || !res)) || (where != UWSPR_HOST && where != UWSPR_DEVICE))
-    return osd_fail(c, UWSPR_ERR_ARG, "uwspr_osd_batch: symbols %p, n %d, where %d, res %p", (const void *)symbols, n, where, (void *)res);
-  if (n == 0) return UWSPR_OK;
-  if (!c->own_stream) return osd_fail(c, UWSPR_ERR_NODEVICE, "context has no device (creation failed: %s)", c->err);
-  OSDCHK(c, hipSetDevice(c->device));
-  if (where == UWSPR_DEVICE) {
-    if (!osd_device_range(c, symbols, (size_t)n * K9_N) || !osd_device_range(c, res, (size_t)n * sizeof(uwspr_osd_result)))
-      return osd_fail(c, UWSPR_ERR_ARG, "uwspr_osd_batch: UWSPR_DEVICE needs symbols (%zu bytes) and res (%zu bytes) inside device allocations of device %d",
-                      (size_t)n * K9_N, (size_t)n * sizeof(uwspr_osd_result), c->device);
-    return osd_run(c, symbols, nullptr, n, order, res, nullptr);
-  }
-  int rc = osd_begin(c);
-  if (rc) return rc;
-  osd_state *t = c->osd;
-  if ((rc = osd_grow(c, &t->d_sym, &t->cap_sym, (size_t)n * K9_N))) return rc;
-  OSDCHK(c, hipMemcpyAsync(t->d_sym, symbols, (size_t)n * K9_N, hipMemcpyHostToDevice, c->stream));
-  uwspr_osd_result *d_res = nullptr;
-  if ((rc = osd_run(c, t->d_sym, nullptr, n, order, nullptr, &d_res))) return rc;
-  OSDCHK(c, hipMemcpyAsync(res, d_res, (size_t)n * sizeof(uwspr_osd_result), hipMemcpyDeviceToHost, c->stream));
-  OSDCHK(c, hipStreamSynchronize(c->stream));
-  return UWSPR_OK;
+  if (order < 0 || order > 2) return ctx_fail(c, UWSPR_ERR_ARG, "uwspr_osd_batch: order %d (0..2)", order);
+  return symbols_batch(c, "uwspr_osd_batch", symbols, n, where, res, nullptr,
+                       [&](symbols_stage **st) { const int rc = osd_begin(c); if (!rc) *st = &c->osd->stage; return rc; },
+                       [&](const uint8_t *d_sym, uwspr_osd_result *d_res, uwspr_osd_result **d_out) { return osd_run(c, d_sym, nullptr, n, order, d_res, d_out); });
 }
 
 // Measurement hook of tools/osd_probe.py (not part of the ABI, like uwspr_debug_subtract_times): enable = 1 / 0 switches
@@ -330,17 +260,6 @@ extern "C" int uwspr_osd_batch(uwspr_ctx *c, const uint8_t *symbols, int n, int 
 // timed launch and returns its time.
 extern "C" int uwspr_debug_osd_time(uwspr_ctx *c, int enable, double *ms) {
   if (!c) return UWSPR_ERR_ARG;
-  if (!c->osd) c->osd = new osd_state();
-  osd_state *t = c->osd;
-  if (enable >= 0) t->timing = enable != 0;
-  if (ms) {
-    *ms = 0.0;
-    if (t->timed) {
-      float f = 0.0f;
-      OSDCHK(c, hipEventSynchronize(t->ev[1]));
-      OSDCHK(c, hipEventElapsedTime(&f, t->ev[0], t->ev[1]));
-      *ms = f;
-    }
-  }
-  return UWSPR_OK;
+  if (!c->osd) c->osd = new osd_state();   // (no device asked: the hook only keeps the switch)
+  return c->osd->timer.read(c, enable, ms);
 }

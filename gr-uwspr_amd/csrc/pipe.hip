@@ -30,6 +30,7 @@
 #include <vector>
 
 #include "host_pool.h"
+#include "pipe_rules.h"
 #include "uwspr_internal.h"
 
 using namespace uwspr;
@@ -67,24 +68,15 @@ struct pipe_lane {
   std::vector<int> slot_frame;           // slot -> frame of the batch
   std::vector<uwspr_sub_item> items;     // the decoded records as subtraction items (frame = slot)
   std::vector<uwspr_decode> extra;       // the second pass's records, frame = index in the batch until they are merged
-  // ordered-statistics decoding (option "osd"): the records Fano gave up on, one item each
-  std::vector<uint8_t> osdf;                 // [B*per] 1: decoded by K9
-  std::vector<int> osd_rec, osd_idt;         // item -> record, try
-  std::vector<unsigned long long> osd_off;   // item -> byte offset of its symbols in d_out
-  std::vector<uwspr_osd_result> osd_res;
-  // list search (uwspr_pipe_set_list): the same records, one K13 item each (osdf = 2: decoded by it)
-  std::vector<int> deep_rec, deep_idt;
-  std::vector<unsigned long long> deep_off;
-  std::vector<uwspr_deep_result> deep_res;
-  // call search (uwspr_pipe_set_calls): the records the list search left, one K14 item each (osdf = 3: decoded by it)
-  std::vector<int> call_rec, call_idt;
-  std::vector<unsigned long long> call_off;
-  std::vector<uwspr_call_result> call_res;
-  // block demodulation (option "block"): the same records, one K10 item each
+  // The fallbacks (option "block", the list search, the call search, option "osd"): the records Fano gave up on, one item
+  // each.  They run one after the other on a lane, so they share one set of item vectors.
+  std::vector<uint8_t> osdf;                 // [B*per] 1, 2, 3: decoded by K9, K13, K14
   std::vector<uint8_t> blkf;                 // [B*per] 2, 3: decoded from the soft symbols of that block length
-  std::vector<int> blk_rec, blk_idt;         // item -> record, try
+  std::vector<int> fb_rec, fb_idt;           // item -> record, try (collect_items)
+  std::vector<unsigned long long> fb_off;    // item -> byte offset of its symbols in d_out
+  std::vector<uint8_t> fb_res;               // the running fallback's results as the kernel wrote them: [items] of its result
+                                             // record (scored_tail), or K10's [items][3][162] soft symbols (block_tail)
   std::vector<uwspr_block_item> blk_items;
-  std::vector<uint8_t> blk_sym;              // [items][3][162]
   std::vector<uint8_t> blk_n;                // item -> the block length that decoded (0: none)
   std::vector<int8_t> blk_msg;               // [items][7]
 };
@@ -188,14 +180,196 @@ static int parg(uwspr_pipe *q, const char *fmt, ...) {
   } while (0)
 
 // ---- coordinator: finishes the batches in launch order ------------------------------------------
-// The host tail of one search of B frames (the batch itself, first = true; or its second pass over the residual frames):
-// waits for the lane's event, runs Fano on what the GPU produced, resumes what try 0 did not decode.  Leaves L.dec /
-// L.idt / L.msg for the B * per records of L.h_out.
-static int osd_tail(uwspr_pipe *q, pipe_lane &L, int nrec, tail_acc &ta);
-static int deep_tail(uwspr_pipe *q, pipe_lane &L, int nrec, tail_acc &ta);
-static int calls_tail(uwspr_pipe *q, pipe_lane &L, int nrec, tail_acc &ta);
-static int block_tail(uwspr_pipe *q, pipe_lane &L, const float *frames, int nrec, tail_acc &ta);
+// record i of the lane's search (frame i / per, slot i % per) holds a candidate
+static bool lane_valid(const uwspr_pipe *q, const pipe_lane &L, int i) {
+  const int b = i / q->per, j = i - b * q->per;
+  return j < L.h_npk[b] && j < q->maxfreqs;
+}
 
+// device -> host on the lane's stream, waited for on the lane's event (the coordinator sleeps on it)
+static int lane_fetch(uwspr_pipe *q, pipe_lane &L, void *dst, const void *src, size_t bytes) {
+  PHIP(q, hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, L.stream));
+  PHIP(q, hipEventRecord(L.ev_done, L.stream));
+  PHIP(q, hipEventSynchronize(L.ev_done));
+  return UWSPR_OK;
+}
+
+// what a search of n frames left in the lane's device buffers -> its host records; the lane's event is behind the copies
+static int fetch_first_pass(uwspr_pipe *q, pipe_lane &L, int n) {
+  const int per = q->per;
+  PHIP(q, hipMemcpyAsync(L.h_npk, L.d_npk, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, L.stream));
+  PHIP(q, hipMemcpy2DAsync(L.h_cands, (size_t)per * sizeof(uwspr_candidate), L.d_cands,
+                           (size_t)q->maxfreqs * sizeof(uwspr_candidate), (size_t)per * sizeof(uwspr_candidate), n,
+                           hipMemcpyDeviceToHost, L.stream));
+  PHIP(q, hipMemcpyAsync(L.h_out, L.d_out, (size_t)n * per * sizeof(uwspr_demod_out), hipMemcpyDeviceToHost, L.stream));
+  PHIP(q, hipEventRecord(L.ev_done, L.stream));
+  return UWSPR_OK;
+}
+
+// ---- the fallback path: what runs on the records Fano gave up on.  A fallback supplies a kernel call on the lane's
+// context, a failure prefix, an acceptance rule (pipe_rules.h) and where the 7 message bytes come from (scored_fallback); one
+// whose results need host work of their own is written out like block_tail, on the same collection and fetch.
+// The item rule of all of them: record i is an item when it was worth a try, no try decoded and at least one try passed the
+// gates of cc:470; its try is rules::fallback_pick's (-1: no item).  All 17 tries are in L.d_out by now (the resume, or the
+// eager first pass).
+static int fallback_try(const uwspr_pipe *q, const pipe_lane &L, int i) {
+  if (!lane_valid(q, L, i) || !L.h_out[i].worth_a_try || L.dec[i]) return -1;
+  return rules::fallback_pick(L.h_out[i]);
+}
+
+// the items of the fallback that runs next, into L.fb_rec / L.fb_idt: collected afresh by each one, so that a record the
+// fallback before decoded is no item any more
+static int collect_items(const uwspr_pipe *q, pipe_lane &L, int nrec) {
+  L.fb_rec.clear(); L.fb_idt.clear();
+  for (int i = 0; i < nrec; i++) {
+    const int pick = fallback_try(q, L, i);
+    if (pick < 0) continue;
+    L.fb_rec.push_back(i); L.fb_idt.push_back(pick);
+  }
+  return (int)L.fb_rec.size();
+}
+
+// where the symbols of try `pick` of record i lie in the lane's device records: they are read in place
+static unsigned long long symbols_offset(const pipe_lane &L, int i, int pick) {
+  return (unsigned long long)((const char *)&L.d_out[i].symbols[pick][0] - (const char *)L.d_out);
+}
+
+// A fallback that scores an item's 162 soft symbols and answers with one result record per item.
+struct scored_fallback {
+  const char *what;     // prefix of a failure's message
+  uint8_t osdf;         // uwspr_decode::osd of a record it decodes
+  size_t res_size;      // bytes of its result record
+  int (*run)(uwspr_pipe *q, pipe_lane &L, int n, const void **d_res);           // n items at L.fb_off -> device results
+  bool (*accept)(const uwspr_pipe *q, const void *res);                         // the result makes its record a decoded one
+  void (*message)(const uwspr_pipe *q, const void *res, int8_t *message7);      // ... with these bytes
+};
+
+// Option "osd": K9.  An item whose runner-up is at least osd_gap behind and whose bytes unpack.
+static const scored_fallback kOsdFallback = {
+    "ordered-statistics decoding", 1, sizeof(uwspr_osd_result),
+    [](uwspr_pipe *q, pipe_lane &L, int n, const void **d_res) {
+      return osd_run(L.ctx, (const uint8_t *)L.d_out, L.fb_off.data(), n, q->osd, nullptr, (uwspr_osd_result **)d_res);
+    },
+    [](const uwspr_pipe *q, const void *res) {
+      const uwspr_osd_result &r = *(const uwspr_osd_result *)res;
+      char text[32];
+      return rules::osd_accepts(r, q->osd_gap) && uwspr_unpack_message(r.message, text, sizeof(text)) == 0;
+    },
+    [](const uwspr_pipe *, const void *res, int8_t *message7) { memcpy(message7, ((const uwspr_osd_result *)res)->message, 7); }};
+
+// The list search (uwspr_pipe_set_list): K13 against the pipe's table.  An item with sbest >= deep_min and (M == 1 or
+// sbest - snext >= deep_gap), with the list's bytes (no unpacking: the list is the user's word).
+static const scored_fallback kListFallback = {
+    "list search", 2, sizeof(uwspr_deep_result),
+    [](uwspr_pipe *q, pipe_lane &L, int n, const void **d_res) {
+      return deep_run(L.ctx, q->d_deep_tab, q->deep_M, (const uint8_t *)L.d_out, L.fb_off.data(), n, nullptr, (uwspr_deep_result **)d_res);
+    },
+    [](const uwspr_pipe *q, const void *res) { return rules::list_accepts(*(const uwspr_deep_result *)res, q->deep_M, q->deep_min, q->deep_gap); },
+    [](const uwspr_pipe *q, const void *res, int8_t *message7) {
+      memcpy(message7, &q->deep_msgs[7 * (size_t)((const uwspr_deep_result *)res)->best], 7);
+    }};
+
+// The call search (uwspr_pipe_set_calls): K14 against the pipe's call set.  An item with sbest >= call_min and (one allowed
+// hypothesis or sbest - snext >= call_gap), with message(best) (no unpacking: the message is valid by construction).
+static const scored_fallback kCallFallback = {
+    "call search", 3, sizeof(uwspr_call_result),
+    [](uwspr_pipe *q, pipe_lane &L, int n, const void **d_res) {
+      return calls_run(L.ctx, q->call_set, (const uint8_t *)L.d_out, L.fb_off.data(), n, nullptr, (uwspr_call_result **)d_res);
+    },
+    [](const uwspr_pipe *q, const void *res) {
+      return rules::calls_accepts(*(const uwspr_call_result *)res, calls_count(q->call_set), q->call_min, q->call_gap);
+    },
+    [](const uwspr_pipe *q, const void *res, int8_t *message7) { calls_message(q->call_set, ((const uwspr_call_result *)res)->best, message7); }};
+
+// One scored fallback over the batch's records.  Its time counts as resume time; without items it touches no stream.
+static int scored_tail(uwspr_pipe *q, pipe_lane &L, int nrec, const scored_fallback &f, tail_acc &ta) {
+  const int n = collect_items(q, L, nrec);
+  if (n == 0) return UWSPR_OK;
+  const double t0 = now_s();
+  L.fb_off.clear();
+  for (int k = 0; k < n; k++) L.fb_off.push_back(symbols_offset(L, L.fb_rec[k], L.fb_idt[k]));
+  const void *d_res = nullptr;
+  int rc = f.run(q, L, n, &d_res);
+  if (rc) return pfail(q, rc, "%s: %s", f.what, uwspr_last_error(L.ctx));
+  L.fb_res.resize((size_t)n * f.res_size);
+  if ((rc = lane_fetch(q, L, L.fb_res.data(), d_res, L.fb_res.size()))) return rc;
+  for (int k = 0; k < n; k++) {
+    const void *r = &L.fb_res[(size_t)k * f.res_size];
+    if (!f.accept(q, r)) continue;
+    const int i = L.fb_rec[k];
+    L.dec[i] = 1; L.idt[i] = L.fb_idt[k]; L.osdf[i] = f.osdf;
+    f.message(q, r, &L.msg[7 * (size_t)i]);
+  }
+  ta.resume_s += now_s() - t0;
+  return UWSPR_OK;
+}
+
+// Option "block".  K10 makes each item's soft symbols for the block lengths 1, 2, 3 from the frames the search itself read,
+// at the try's jig_shift and the frequency model the fine search correlated with (rules::fine_model).  On the host pool, per
+// item: for n = 2 .. block, a vector above the rms gate of cc:470 goes through Fano; the first that decodes to bytes that
+// unpack makes the record a decoded one.  Its time counts as resume time, its Fano calls as the batch's.
+static int block_tail(uwspr_pipe *q, pipe_lane &L, const float *frames, int nrec, tail_acc &ta) {
+  const int per = q->per;
+  const int n = collect_items(q, L, nrec);
+  if (n == 0) return UWSPR_OK;
+  L.blk_items.clear();
+  for (int k = 0; k < n; k++) {
+    const int i = L.fb_rec[k];
+    uwspr_block_item it;
+    it.frame = i / per;
+    it.shift = L.h_out[i].jig_shift[L.fb_idt[k]];
+    rules::fine_model(L.h_cands[i], L.h_out[i], (float)q->p.cf, &it.f_hz, &it.drift_hz);   // (h_cands is [B][per], as h_out)
+    L.blk_items.push_back(it);
+  }
+  const double t0 = now_s();
+  uint8_t *d_sym = nullptr;
+  int rc = blockdemod_check(L.ctx, L.blk_items.data(), n, (nrec + per - 1) / per);
+  if (!rc) rc = blockdemod_run(L.ctx, frames, (size_t)L.ctx->fstride, L.blk_items.data(), n, nullptr, &d_sym);
+  if (rc) return pfail(q, rc, "block demodulation: %s", uwspr_last_error(L.ctx));
+  std::vector<uint8_t> &blk_sym = L.fb_res;   // [items][3][162]
+  blk_sym.resize((size_t)n * 3 * UWSPR_NSYM);
+  if ((rc = lane_fetch(q, L, blk_sym.data(), d_sym, blk_sym.size()))) return rc;
+  L.blk_n.assign((size_t)n, 0);
+  L.blk_msg.assign((size_t)n * 7, 0);
+  std::atomic<long long> calls(0), fails(0);
+  const int nmax = q->block;
+  auto one = [&](int k) {
+    for (int nb = 2; nb <= nmax; nb++) {
+      uint8_t sym[UWSPR_NSYM], data[11];
+      memcpy(sym, &blk_sym[((size_t)k * 3 + (nb - 1)) * UWSPR_NSYM], UWSPR_NSYM);
+      float sq = 0.0f;   // cc:469-474
+      for (int i = 0; i < UWSPR_NSYM; i++) { const float y = (float)((double)(float)sym[i] - 128.0); sq += y * y; }
+      if (!((float)sqrt((double)sq / 162.0) > rules::kMinRms)) continue;
+      uwspr_deinterleave(sym);
+      memset(data, 0, sizeof(data));
+      uint32_t metric, cycles, maxnp;
+      calls.fetch_add(1, std::memory_order_relaxed);
+      if (uwspr_fano_decode(sym, data, &metric, &cycles, &maxnp, 60, 10000) != 0) { fails.fetch_add(1, std::memory_order_relaxed); continue; }
+      int8_t msg[7];
+      char text[32];
+      for (int i = 0; i < 7; i++) msg[i] = (int8_t)data[i];
+      if (uwspr_unpack_message(msg, text, sizeof(text)) != 0) continue;
+      L.blk_n[k] = (uint8_t)nb;
+      memcpy(&L.blk_msg[7 * (size_t)k], msg, 7);
+      return;
+    }
+  };
+  if (n <= 2) for (int k = 0; k < n; k++) one(k);
+  else q->pool->run(n, q->o.host_threads, one);
+  for (int k = 0; k < n; k++) {
+    if (!L.blk_n[k]) continue;
+    const int i = L.fb_rec[k];
+    L.dec[i] = 1; L.idt[i] = L.fb_idt[k]; L.blkf[i] = L.blk_n[k];
+    memcpy(&L.msg[7 * (size_t)i], &L.blk_msg[7 * (size_t)k], 7);
+  }
+  ta.calls += calls.load(); ta.fails += fails.load();
+  ta.resume_s += now_s() - t0;
+  return UWSPR_OK;
+}
+
+// The host tail of one search of B frames (the batch itself, first = true; or its second pass over the residual frames):
+// waits for the lane's event, runs Fano on what the GPU produced, resumes what try 0 did not decode, then the fallbacks.
+// Leaves L.dec / L.idt / L.msg / L.osdf / L.blkf for the B * per records of L.h_out.
 static int host_tail(uwspr_pipe *q, pipe_lane &L, const float *frames, int B, bool first, tail_acc &ta) {
   const int per = q->per, nrec = B * per;
   double t0 = now_s();
@@ -206,7 +380,6 @@ static int host_tail(uwspr_pipe *q, pipe_lane &L, const float *frames, int B, bo
     std::lock_guard<std::mutex> lk(q->m);
     L.host_since = t1;   // the host tail of this batch starts: the producer may open a spare lane if it lasts (take_lane)
   }
-  auto valid = [&](int i) { const int b = i / per, j = i - b * per; return j < L.h_npk[b] && j < q->maxfreqs; };
   // cc:457-490 on what the first pass produced (try 0 alone in the lazy flow)
   std::atomic<long long> calls(0), fails(0);
   // only the records that are worth a try go to the pool (a quiet stream has almost none: no wake-ups for it)
@@ -214,7 +387,7 @@ static int host_tail(uwspr_pipe *q, pipe_lane &L, const float *frames, int B, bo
   for (int i = 0; i < nrec; i++) {
     L.dec[i] = 0; L.idt[i] = -1;
     memset(&L.msg[7 * (size_t)i], 0, 7);
-    if (valid(i) && L.h_out[i].worth_a_try) L.first.push_back(i);
+    if (lane_valid(q, L, i) && L.h_out[i].worth_a_try) L.first.push_back(i);
   }
   auto first_pass = [&](int k) {
     const int i = L.first[k];
@@ -232,7 +405,7 @@ static int host_tail(uwspr_pipe *q, pipe_lane &L, const float *frames, int B, bo
   L.redo.clear();
   if (!q->o.eager) {
     for (int i = 0; i < nrec; i++) {
-      const bool need = valid(i) && L.h_out[i].worth_a_try && !L.dec[i];
+      const bool need = lane_valid(q, L, i) && L.h_out[i].worth_a_try && !L.dec[i];
       L.h_need[i] = need ? 1 : 0;
       if (need) L.redo.push_back(i);
     }
@@ -283,202 +456,36 @@ static int host_tail(uwspr_pipe *q, pipe_lane &L, const float *frames, int B, bo
   ta.gpu_wait_s += (t1 - t0);
   ta.fano_s += (t2 - t1) + (t4 - t3);
   ta.resume_s += (t3 - t2);
+  // block -> list -> calls -> OSD; a record one of them decoded is no item of the next
   memset(L.osdf.data(), 0, (size_t)nrec);
   memset(L.blkf.data(), 0, (size_t)nrec);
   if (q->block > 0)
     if (const int rc = block_tail(q, L, frames, nrec, ta)) return rc;
   if (q->deep_M > 0)
-    if (const int rc = deep_tail(q, L, nrec, ta)) return rc;
+    if (const int rc = scored_tail(q, L, nrec, kListFallback, ta)) return rc;
   if (q->call_set)
-    if (const int rc = calls_tail(q, L, nrec, ta)) return rc;
-  if (q->osd > 0) return osd_tail(q, L, nrec, ta);
+    if (const int rc = scored_tail(q, L, nrec, kCallFallback, ta)) return rc;
+  if (q->osd > 0) return scored_tail(q, L, nrec, kOsdFallback, ta);
   return UWSPR_OK;
 }
 
-// The item rule of the options "block" and "osd", of the list search and of the call search: record i is an item when it was worth a try, no try decoded and at least
-// one try passed the gates of cc:470; its try is the gated one with the largest jig_sync, the first one on ties (-1: no item).
-static int fallback_try(const uwspr_pipe *q, const pipe_lane &L, int i) {
-  const float minsync2 = 0.12f, minrms = (float)(52.0 * (50 / 64.0));   // the gates of decode_try (host_tail.cpp)
-  const int per = q->per, b = i / per, j = i - b * per;
-  if (!(j < L.h_npk[b] && j < q->maxfreqs) || !L.h_out[i].worth_a_try || L.dec[i]) return -1;
+// Record i of the lane's search as the pipe emits it: frame b of the batch, candidate number cand of that frame's npk.
+static uwspr_decode make_record(const pipe_lane &L, int b, int i, int cand, int32_t npk, int pass) {
+  uwspr_decode d;
+  memset(&d, 0, sizeof(d));
+  d.frame = L.frame0 + b;
+  d.channel = (int16_t)L.channel;
+  d.stream_pos = L.pos0 >= 0 ? L.pos0 + (int64_t)b * L.stride : -1;
+  d.cand = cand; d.npk = npk;
+  d.coarse = L.h_cands[i];   // [B][per], as h_out
   const uwspr_demod_out &o = L.h_out[i];
-  int pick = -1;
-  for (int idt = 0; idt < UWSPR_NJIG; idt++)
-    if (o.jig_sync[idt] > minsync2 && o.jig_rms[idt] > minrms && (pick < 0 || o.jig_sync[idt] > o.jig_sync[pick])) pick = idt;
-  return pick;
-}
-
-// Option "osd".  The records that were worth a try and that Fano did not decode have all 17 tries in L.d_out by now (the
-// resume, or the eager first pass).  Each with a gated try (cc:470) is one K9 item: the gated try with the largest
-// jig_sync, the first one on ties, its symbols read in place in the lane's device records.  An item whose runner-up is
-// at least osd_gap behind and whose bytes unpack makes its record a decoded one.  Its time counts as resume time.
-static int osd_tail(uwspr_pipe *q, pipe_lane &L, int nrec, tail_acc &ta) {
-  L.osd_rec.clear(); L.osd_idt.clear(); L.osd_off.clear();
-  for (int i = 0; i < nrec; i++) {
-    const int pick = fallback_try(q, L, i);
-    if (pick < 0) continue;
-    L.osd_rec.push_back(i); L.osd_idt.push_back(pick);
-    L.osd_off.push_back((unsigned long long)((const char *)&L.d_out[i].symbols[pick][0] - (const char *)L.d_out));
-  }
-  const int n = (int)L.osd_rec.size();
-  if (n == 0) return UWSPR_OK;
-  const double t0 = now_s();
-  uwspr_osd_result *d_res = nullptr;
-  const int rc = osd_run(L.ctx, (const uint8_t *)L.d_out, L.osd_off.data(), n, q->osd, nullptr, &d_res);
-  if (rc) return pfail(q, rc, "ordered-statistics decoding: %s", uwspr_last_error(L.ctx));
-  L.osd_res.resize((size_t)n);
-  PHIP(q, hipMemcpyAsync(L.osd_res.data(), d_res, (size_t)n * sizeof(uwspr_osd_result), hipMemcpyDeviceToHost, L.stream));
-  PHIP(q, hipEventRecord(L.ev_done, L.stream));
-  PHIP(q, hipEventSynchronize(L.ev_done));
-  for (int k = 0; k < n; k++) {
-    const uwspr_osd_result &r = L.osd_res[k];
-    char text[32];
-    if ((long long)r.dnext - (long long)r.dmin < (long long)q->osd_gap || uwspr_unpack_message(r.message, text, sizeof(text)) != 0) continue;
-    const int i = L.osd_rec[k];
-    L.dec[i] = 1; L.idt[i] = L.osd_idt[k]; L.osdf[i] = 1;
-    memcpy(&L.msg[7 * (size_t)i], r.message, 7);
-  }
-  ta.resume_s += now_s() - t0;
-  return UWSPR_OK;
-}
-
-// The list search (uwspr_pipe_set_list).  The items are osd_tail's (fallback_try), their symbols read in place likewise; K13
-// scores each against the pipe's table.  An item with sbest >= deep_min and (M == 1 or sbest - snext >= deep_gap) makes its
-// record a decoded one with the list's bytes (no unpacking: the list is the user's word).  Its time counts as resume time.
-static int deep_tail(uwspr_pipe *q, pipe_lane &L, int nrec, tail_acc &ta) {
-  L.deep_rec.clear(); L.deep_idt.clear(); L.deep_off.clear();
-  for (int i = 0; i < nrec; i++) {
-    const int pick = fallback_try(q, L, i);
-    if (pick < 0) continue;
-    L.deep_rec.push_back(i); L.deep_idt.push_back(pick);
-    L.deep_off.push_back((unsigned long long)((const char *)&L.d_out[i].symbols[pick][0] - (const char *)L.d_out));
-  }
-  const int n = (int)L.deep_rec.size();
-  if (n == 0) return UWSPR_OK;
-  const double t0 = now_s();
-  uwspr_deep_result *d_res = nullptr;
-  const int rc = deep_run(L.ctx, q->d_deep_tab, q->deep_M, (const uint8_t *)L.d_out, L.deep_off.data(), n, nullptr, &d_res);
-  if (rc) return pfail(q, rc, "list search: %s", uwspr_last_error(L.ctx));
-  L.deep_res.resize((size_t)n);
-  PHIP(q, hipMemcpyAsync(L.deep_res.data(), d_res, (size_t)n * sizeof(uwspr_deep_result), hipMemcpyDeviceToHost, L.stream));
-  PHIP(q, hipEventRecord(L.ev_done, L.stream));
-  PHIP(q, hipEventSynchronize(L.ev_done));
-  for (int k = 0; k < n; k++) {
-    const uwspr_deep_result &r = L.deep_res[k];
-    if (r.best < 0 || r.best >= q->deep_M || r.sbest < q->deep_min) continue;
-    if (q->deep_M > 1 && (long long)r.sbest - (long long)r.snext < (long long)q->deep_gap) continue;
-    const int i = L.deep_rec[k];
-    L.dec[i] = 1; L.idt[i] = L.deep_idt[k]; L.osdf[i] = 2;
-    memcpy(&L.msg[7 * (size_t)i], &q->deep_msgs[7 * (size_t)r.best], 7);
-  }
-  ta.resume_s += now_s() - t0;
-  return UWSPR_OK;
-}
-
-// The call search (uwspr_pipe_set_calls), behind the list search: the items are again fallback_try's (a record the list
-// search decoded is none any more), their symbols read in place; K14 scores each against the pipe's call set.  An item with
-// sbest >= call_min and (one allowed hypothesis or sbest - snext >= call_gap) makes its record a decoded one with
-// message(best) (no unpacking: the message is valid by construction).  Its time counts as resume time.
-static int calls_tail(uwspr_pipe *q, pipe_lane &L, int nrec, tail_acc &ta) {
-  L.call_rec.clear(); L.call_idt.clear(); L.call_off.clear();
-  for (int i = 0; i < nrec; i++) {
-    const int pick = fallback_try(q, L, i);
-    if (pick < 0) continue;
-    L.call_rec.push_back(i); L.call_idt.push_back(pick);
-    L.call_off.push_back((unsigned long long)((const char *)&L.d_out[i].symbols[pick][0] - (const char *)L.d_out));
-  }
-  const int n = (int)L.call_rec.size();
-  if (n == 0) return UWSPR_OK;
-  const double t0 = now_s();
-  uwspr_call_result *d_res = nullptr;
-  const int rc = calls_run(L.ctx, q->call_set, (const uint8_t *)L.d_out, L.call_off.data(), n, nullptr, &d_res);
-  if (rc) return pfail(q, rc, "call search: %s", uwspr_last_error(L.ctx));
-  L.call_res.resize((size_t)n);
-  PHIP(q, hipMemcpyAsync(L.call_res.data(), d_res, (size_t)n * sizeof(uwspr_call_result), hipMemcpyDeviceToHost, L.stream));
-  PHIP(q, hipEventRecord(L.ev_done, L.stream));
-  PHIP(q, hipEventSynchronize(L.ev_done));
-  const long long nhyp = calls_count(q->call_set);
-  for (int k = 0; k < n; k++) {
-    const uwspr_call_result &r = L.call_res[k];
-    if (r.best < 0 || r.best >= UWSPR_CALLS_MAX * UWSPR_CALL_NGRID * UWSPR_CALL_NPOW || r.sbest < q->call_min) continue;
-    if (nhyp > 1 && (long long)r.sbest - (long long)r.snext < (long long)q->call_gap) continue;
-    const int i = L.call_rec[k];
-    L.dec[i] = 1; L.idt[i] = L.call_idt[k]; L.osdf[i] = 3;
-    calls_message(q->call_set, r.best, &L.msg[7 * (size_t)i]);
-  }
-  ta.resume_s += now_s() - t0;
-  return UWSPR_OK;
-}
-
-static float slm_at_zero(const uwspr_candidate &c, float cf);
-
-// Option "block".  The items are osd_tail's (fallback_try); K10 makes each one's soft symbols for the block lengths 1, 2, 3
-// from the frames the search itself read, at the try's jig_shift and the frequency model the fine search correlated with
-// (second_pass's).  On the host pool, per item: for n = 2 .. block, a vector above the rms gate of cc:470 goes through
-// Fano; the first that decodes to bytes that unpack makes the record a decoded one.  Its time counts as resume time.
-static int block_tail(uwspr_pipe *q, pipe_lane &L, const float *frames, int nrec, tail_acc &ta) {
-  const int per = q->per;
-  L.blk_rec.clear(); L.blk_idt.clear(); L.blk_items.clear();
-  for (int i = 0; i < nrec; i++) {
-    const int pick = fallback_try(q, L, i);
-    if (pick < 0) continue;
-    const uwspr_demod_out &o = L.h_out[i];
-    const uwspr_candidate &cd = L.h_cands[i];   // [B][per], as h_out
-    uwspr_block_item it;
-    it.frame = i / per;
-    it.shift = o.jig_shift[pick];
-    if (cd.m_type == UWSPR_NONLINEAR) { it.f_hz = o.f1 + slm_at_zero(cd, (float)q->p.cf); it.drift_hz = 0.0f; }
-    else { it.f_hz = o.f1; it.drift_hz = o.drift1; }
-    L.blk_rec.push_back(i); L.blk_idt.push_back(pick); L.blk_items.push_back(it);
-  }
-  const int n = (int)L.blk_rec.size();
-  if (n == 0) return UWSPR_OK;
-  const double t0 = now_s();
-  uint8_t *d_sym = nullptr;
-  int rc = blockdemod_check(L.ctx, L.blk_items.data(), n, (nrec + per - 1) / per);
-  if (!rc) rc = blockdemod_run(L.ctx, frames, (size_t)L.ctx->fstride, L.blk_items.data(), n, nullptr, &d_sym);
-  if (rc) return pfail(q, rc, "block demodulation: %s", uwspr_last_error(L.ctx));
-  L.blk_sym.resize((size_t)n * 3 * UWSPR_NSYM);
-  PHIP(q, hipMemcpyAsync(L.blk_sym.data(), d_sym, L.blk_sym.size(), hipMemcpyDeviceToHost, L.stream));
-  PHIP(q, hipEventRecord(L.ev_done, L.stream));
-  PHIP(q, hipEventSynchronize(L.ev_done));
-  L.blk_n.assign((size_t)n, 0);
-  L.blk_msg.assign((size_t)n * 7, 0);
-  std::atomic<long long> calls(0), fails(0);
-  const int nmax = q->block;
-  auto one = [&](int k) {
-    const float minrms = (float)(52.0 * (50 / 64.0));
-    for (int nb = 2; nb <= nmax; nb++) {
-      uint8_t sym[UWSPR_NSYM], data[11];
-      memcpy(sym, &L.blk_sym[((size_t)k * 3 + (nb - 1)) * UWSPR_NSYM], UWSPR_NSYM);
-      float sq = 0.0f;   // cc:469-474
-      for (int i = 0; i < UWSPR_NSYM; i++) { const float y = (float)((double)(float)sym[i] - 128.0); sq += y * y; }
-      if (!((float)sqrt((double)sq / 162.0) > minrms)) continue;
-      uwspr_deinterleave(sym);
-      memset(data, 0, sizeof(data));
-      uint32_t metric, cycles, maxnp;
-      calls.fetch_add(1, std::memory_order_relaxed);
-      if (uwspr_fano_decode(sym, data, &metric, &cycles, &maxnp, 60, 10000) != 0) { fails.fetch_add(1, std::memory_order_relaxed); continue; }
-      int8_t msg[7];
-      char text[32];
-      for (int i = 0; i < 7; i++) msg[i] = (int8_t)data[i];
-      if (uwspr_unpack_message(msg, text, sizeof(text)) != 0) continue;
-      L.blk_n[k] = (uint8_t)nb;
-      memcpy(&L.blk_msg[7 * (size_t)k], msg, 7);
-      return;
-    }
-  };
-  if (n <= 2) for (int k = 0; k < n; k++) one(k);
-  else q->pool->run(n, q->o.host_threads, one);
-  for (int k = 0; k < n; k++) {
-    if (!L.blk_n[k]) continue;
-    const int i = L.blk_rec[k];
-    L.dec[i] = 1; L.idt[i] = L.blk_idt[k]; L.blkf[i] = L.blk_n[k];
-    memcpy(&L.msg[7 * (size_t)i], &L.blk_msg[7 * (size_t)k], 7);
-  }
-  ta.calls += calls.load(); ta.fails += fails.load();
-  ta.resume_s += now_s() - t0;
-  return UWSPR_OK;
+  d.f1 = o.f1; d.drift1 = o.drift1; d.sync1 = o.sync1; d.shift1 = o.shift1; d.worth_a_try = o.worth_a_try;
+  d.decoded = L.dec[i]; d.idt = L.idt[i];
+  memcpy(d.message, &L.msg[7 * (size_t)i], 7);
+  d.pass = (uint8_t)pass;
+  d.osd = L.osdf[i];
+  d.block = L.blkf[i];
+  return d;
 }
 
 static int second_pass(uwspr_pipe *q, pipe_lane &L, tail_acc &ta, int *ncand, int *ndec);
@@ -488,31 +495,14 @@ static int finish_batch(uwspr_pipe *q, pipe_lane &L) {
   L.recs.clear();   // (a failure below emits nothing for this batch)
   tail_acc ta;
   if (const int rc = host_tail(q, L, L.frames, B, true, ta)) return rc;
-  auto valid = [&](int i) { const int b = i / per, j = i - b * per; return j < L.h_npk[b] && j < q->maxfreqs; };
   int ncand = 0, ndec = 0;
-  {
-    for (int b = 0; b < B; b++) {
-      for (int j = 0; j < per; j++) {
-        const int i = b * per + j;
-        if (!valid(i)) continue;
-        uwspr_decode d;
-        memset(&d, 0, sizeof(d));
-        d.frame = L.frame0 + b;
-        d.channel = (int16_t)L.channel;
-        d.stream_pos = L.pos0 >= 0 ? L.pos0 + (int64_t)b * L.stride : -1;
-        d.cand = j; d.npk = L.h_npk[b];
-        d.coarse = L.h_cands[(size_t)b * per + j];
-        const uwspr_demod_out &o = L.h_out[i];
-        d.f1 = o.f1; d.drift1 = o.drift1; d.sync1 = o.sync1; d.shift1 = o.shift1; d.worth_a_try = o.worth_a_try;
-        d.decoded = L.dec[i]; d.idt = L.idt[i];
-        memcpy(d.message, &L.msg[7 * (size_t)i], 7);
-        d.osd = L.osdf[i];
-        d.block = L.blkf[i];
-        L.recs.push_back(d);
-        ncand++; ndec += L.dec[i];
-      }
+  for (int b = 0; b < B; b++)
+    for (int j = 0; j < per; j++) {
+      const int i = b * per + j;
+      if (!lane_valid(q, L, i)) continue;
+      L.recs.push_back(make_record(L, b, i, j, L.h_npk[b], 0));
+      ncand++; ndec += L.dec[i];
     }
-  }
   if (q->passes == 2 && ndec > 0) {
     const int rc = second_pass(q, L, ta, &ncand, &ndec);
     if (rc) { L.recs.clear(); return rc; }
@@ -534,34 +524,20 @@ static int finish_batch(uwspr_pipe *q, pipe_lane &L) {
 // the samples -- into the lane's own buffer (the ring is only read), and that buffer through FDR + schedule + Fano as the
 // batch itself went.  What decodes there and is not one of its frame's first-pass messages becomes a record with
 // pass = 1 behind the frame's first-pass records.
-// slmFrequencyDrift (lib/slm.cc:36-73) at t = 0: the constant the fine search adds to a nonlinear candidate's f0
-static float slm_at_zero(const uwspr_candidate &c, float cf) {
-  const double V1 = c.m_nonlinear.V1, V2 = c.m_nonlinear.V2, q1 = (double)c.m_nonlinear.p1, q2 = (double)c.m_nonlinear.p2;
-  const float sign = (float)(((q1 * V1 + q2 * V2) > 0) * 2 - 1);
-  const double num = fabs(V1 * q1 + V2 * q2), den = sqrt(q1 * q1 + q2 * q2);
-  if (den == 0) return 0.0f;
-  return (float)((double)(-sign) * num / den * (double)cf / 1500.0);
-}
-
 static int second_pass(uwspr_pipe *q, pipe_lane &L, tail_acc &ta, int *ncand, int *ndec) {
   const int per = q->per, B = L.B;
   L.slot_frame.clear(); L.items.clear(); L.extra.clear();
   for (int b = 0; b < B; b++)
     for (int j = 0; j < per; j++) {
       const int i = b * per + j;
-      if (!(j < L.h_npk[b] && j < q->maxfreqs) || !L.dec[i]) continue;
+      if (!lane_valid(q, L, i) || !L.dec[i]) continue;
       if (L.slot_frame.empty() || L.slot_frame.back() != b) L.slot_frame.push_back(b);
       const uwspr_demod_out &o = L.h_out[i];
       uwspr_sub_item it;
       memset(&it, 0, sizeof(it));
       it.frame = (int32_t)L.slot_frame.size() - 1;
       it.shift = o.jig_shift[L.idt[i] >= 0 && L.idt[i] < UWSPR_NJIG ? L.idt[i] : 0];
-      // the frequency model the fine search itself correlated with: f1 and drift1 for a LINEAR candidate; for a
-      // NONLINEAR one the constant f1 + slmFrequencyDrift(t = 0) (sync_and_demodulate_impl.cc:170-180 evaluates it at
-      // t = 0 for every symbol), without drift
-      const uwspr_candidate &cd = L.h_cands[(size_t)b * per + j];
-      if (cd.m_type == UWSPR_NONLINEAR) { it.f_hz = o.f1 + slm_at_zero(cd, (float)q->p.cf); it.drift_hz = 0.0f; }
-      else { it.f_hz = o.f1; it.drift_hz = o.drift1; }
+      rules::fine_model(L.h_cands[i], o, (float)q->p.cf, &it.f_hz, &it.drift_hz);
       if (uwspr_wspr_symbols(&L.msg[7 * (size_t)i], it.symbols)) return pfail(q, UWSPR_ERR_ARG, "second pass: symbols of a decoded message");
       L.items.push_back(it);
     }
@@ -583,12 +559,7 @@ static int second_pass(uwspr_pipe *q, pipe_lane &L, tail_acc &ta, int *ncand, in
   if (!rc) rc = uwspr_set_tries(L.ctx, q->o.eager ? UWSPR_NJIG : 1);
   if (!rc) rc = uwspr_pipeline_batch(L.ctx, L.d_res2, ns, UWSPR_DEVICE, per, L.d_cands, L.d_npk, L.d_out);
   if (rc) return pfail(q, rc, "second pass, uwspr_pipeline_batch: %s", uwspr_last_error(L.ctx));
-  PHIP(q, hipMemcpyAsync(L.h_npk, L.d_npk, (size_t)ns * sizeof(int32_t), hipMemcpyDeviceToHost, L.stream));
-  PHIP(q, hipMemcpy2DAsync(L.h_cands, (size_t)per * sizeof(uwspr_candidate), L.d_cands,
-                           (size_t)q->maxfreqs * sizeof(uwspr_candidate), (size_t)per * sizeof(uwspr_candidate), ns,
-                           hipMemcpyDeviceToHost, L.stream));
-  PHIP(q, hipMemcpyAsync(L.h_out, L.d_out, (size_t)ns * per * sizeof(uwspr_demod_out), hipMemcpyDeviceToHost, L.stream));
-  PHIP(q, hipEventRecord(L.ev_done, L.stream));
+  if ((rc = fetch_first_pass(q, L, ns))) return rc;
   if ((rc = host_tail(q, L, L.d_res2, ns, false, ta))) return rc;
   // merge: the records of frame b, then what the second pass adds to it
   std::vector<uwspr_decode> merged;
@@ -602,25 +573,11 @@ static int second_pass(uwspr_pipe *q, pipe_lane &L, tail_acc &ta, int *ncand, in
     int cand = (int)(r0 - first);
     for (int j = 0; j < per; j++) {
       const int i = s * per + j;
-      if (!(j < L.h_npk[s] && j < q->maxfreqs) || !L.dec[i]) continue;
+      if (!lane_valid(q, L, i) || !L.dec[i]) continue;
       bool known = false;   // one of the frame's first-pass messages, or of the second-pass records already made for it
       for (size_t r = mfirst; r < merged.size() && !known; r++) known = merged[r].decoded && !memcmp(merged[r].message, &L.msg[7 * (size_t)i], 7);
       if (known) continue;
-      uwspr_decode d;
-      memset(&d, 0, sizeof(d));
-      d.frame = fr;
-      d.channel = (int16_t)L.channel;
-      d.stream_pos = L.pos0 >= 0 ? L.pos0 + (int64_t)L.slot_frame[s] * L.stride : -1;
-      d.cand = cand++; d.npk = npk1[s];
-      d.coarse = L.h_cands[(size_t)s * per + j];
-      const uwspr_demod_out &o = L.h_out[i];
-      d.f1 = o.f1; d.drift1 = o.drift1; d.sync1 = o.sync1; d.shift1 = o.shift1; d.worth_a_try = o.worth_a_try;
-      d.decoded = 1; d.idt = L.idt[i];
-      memcpy(d.message, &L.msg[7 * (size_t)i], 7);
-      d.pass = 1;
-      d.osd = L.osdf[i];
-      d.block = L.blkf[i];
-      merged.push_back(d);
+      merged.push_back(make_record(L, L.slot_frame[s], i, cand++, npk1[s], 1));
       (*ncand)++; (*ndec)++;
     }
   }
@@ -707,12 +664,7 @@ static int launch(uwspr_pipe *q, pipe_lane &L, const float *frames, int B, int s
   if (!rc) rc = uwspr_set_tries(L.ctx, q->o.eager ? UWSPR_NJIG : 1);
   if (!rc) rc = uwspr_pipeline_batch(L.ctx, frames, B, UWSPR_DEVICE, per, L.d_cands, L.d_npk, L.d_out);
   if (rc) return pfail(q, rc, "uwspr_pipeline_batch: %s", uwspr_last_error(L.ctx));
-  PHIP(q, hipMemcpyAsync(L.h_npk, L.d_npk, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost, L.stream));
-  PHIP(q, hipMemcpy2DAsync(L.h_cands, (size_t)per * sizeof(uwspr_candidate), L.d_cands,
-                           (size_t)q->maxfreqs * sizeof(uwspr_candidate), (size_t)per * sizeof(uwspr_candidate), B,
-                           hipMemcpyDeviceToHost, L.stream));
-  PHIP(q, hipMemcpyAsync(L.h_out, L.d_out, (size_t)B * per * sizeof(uwspr_demod_out), hipMemcpyDeviceToHost, L.stream));
-  PHIP(q, hipEventRecord(L.ev_done, L.stream));
+  if ((rc = fetch_first_pass(q, L, B))) return rc;
   if (ringbuf >= 0) q->ring.reader_done(ringbuf, L.ev_done);
   {
     std::lock_guard<std::mutex> lk(q->m);
@@ -1038,46 +990,45 @@ extern "C" int uwspr_pipe_set_carriers(uwspr_pipe *q, const int *hz, int n) {
   return UWSPR_OK;
 }
 
-// An option of every lane's context (uwspr_set_option).  Only while nothing is in flight -- the lanes read their
-// options when they launch -- and not "sched": the pipe picks the schedule form by its lane count (opts.sched_form).
+// What the pipe's lanes read may change only while no batch is in flight.  Called with q->m held -- a lane is marked busy
+// under the same lock when a batch is launched on it, so none starts between this check and the change that follows it (the
+// producer is single-threaded by contract, the coordinators are not).  false: the refusal is in q->err, in the name of
+// what = the call, or call(option).
+static bool lanes_idle_locked(uwspr_pipe *q, const char *call, const char *option = nullptr) {
+  for (auto &L : q->lanes)
+    if (L.busy) {
+      snprintf(q->err, sizeof(q->err), option ? "%s(%s): batches in flight (flush first)" : "%s%s: batches in flight (flush first)", call, option ? option : "");
+      return false;
+    }
+  return true;
+}
+
+// The pipe's own integer options that its host tails read: allowed values, how the refusal says so, where the value goes.
+struct pipe_int_option { const char *name; bool (*ok)(int); const char *rule; int uwspr_pipe::*target; };
+static const pipe_int_option kPipeIntOptions[] = {
+    {"passes", [](int v) { return v == 1 || v == 2; }, "is 1 or 2", &uwspr_pipe::passes},   // 2 = subtract what decoded and search the residual
+    {"osd", [](int v) { return v >= 0 && v <= 2; }, "is 0, 1 or 2", &uwspr_pipe::osd},      // K9 on the records Fano gave up on
+    {"osd_gap", [](int v) { return v >= 0; }, "is >= 0", &uwspr_pipe::osd_gap},
+    {"deep_min", [](int v) { return v >= 0; }, "is >= 0", &uwspr_pipe::deep_min},           // the list search's acceptance thresholds
+    {"deep_gap", [](int v) { return v >= 0; }, "is >= 0", &uwspr_pipe::deep_gap},
+    {"call_min", [](int v) { return v >= 0; }, "is >= 0", &uwspr_pipe::call_min},           // the call search's acceptance thresholds
+    {"call_gap", [](int v) { return v >= 0; }, "is >= 0", &uwspr_pipe::call_gap},
+    {"block", [](int v) { return v == 0 || v == 2 || v == 3; }, "is 0, 2 or 3", &uwspr_pipe::block},   // K10's block soft symbols for those records
+};
+
+// An option of the pipe (the table above; the audio chain's, latched by the first push) or of every lane's context
+// (uwspr_set_option).  The latter and the table's only while nothing is in flight -- the lanes read their options when they
+// launch -- and not "sched": the pipe picks the schedule form by its lane count (opts.sched_form).
 extern "C" int uwspr_pipe_set_option(uwspr_pipe *q, const char *name, int value) {
   if (!q || !name) return UWSPR_ERR_ARG;
   if (const int f = q->failed.load()) return f;
   if (!strcmp(name, "sched")) return parg(q, "uwspr_pipe_set_option: \"sched\" belongs to uwspr_pipe_opts.sched_form");
-  if (!strcmp(name, "passes")) {   // the pipe's own: 1 (default), or 2 = subtract what decoded and search the residual
-    if (value != 1 && value != 2) return parg(q, "uwspr_pipe_set_option: \"passes\" is 1 or 2, not %d", value);
+  for (const pipe_int_option &po : kPipeIntOptions) {
+    if (strcmp(name, po.name)) continue;
+    if (!po.ok(value)) return parg(q, "uwspr_pipe_set_option: \"%s\" %s, not %d", name, po.rule, value);
     std::lock_guard<std::mutex> lk(q->m);
-    for (auto &L : q->lanes)
-      if (L.busy) { snprintf(q->err, sizeof(q->err), "uwspr_pipe_set_option(passes): batches in flight (flush first)"); return UWSPR_ERR_ARG; }
-    q->passes = value;
-    return UWSPR_OK;
-  }
-  if (!strcmp(name, "osd") || !strcmp(name, "osd_gap")) {   // the pipe's own: K9 on the records Fano gave up on
-    const bool gap = name[3] != 0;
-    if (gap ? value < 0 : (value < 0 || value > 2))
-      return parg(q, gap ? "uwspr_pipe_set_option: \"osd_gap\" is >= 0, not %d" : "uwspr_pipe_set_option: \"osd\" is 0, 1 or 2, not %d", value);
-    std::lock_guard<std::mutex> lk(q->m);
-    for (auto &L : q->lanes)
-      if (L.busy) { snprintf(q->err, sizeof(q->err), "uwspr_pipe_set_option(%s): batches in flight (flush first)", name); return UWSPR_ERR_ARG; }
-    (gap ? q->osd_gap : q->osd) = value;
-    return UWSPR_OK;
-  }
-  if (!strcmp(name, "deep_min") || !strcmp(name, "deep_gap")) {   // the pipe's own: the list search's acceptance thresholds
-    const bool gap = name[5] == 'g';
-    if (value < 0) return parg(q, "uwspr_pipe_set_option: \"%s\" is >= 0, not %d", name, value);
-    std::lock_guard<std::mutex> lk(q->m);
-    for (auto &L : q->lanes)
-      if (L.busy) { snprintf(q->err, sizeof(q->err), "uwspr_pipe_set_option(%s): batches in flight (flush first)", name); return UWSPR_ERR_ARG; }
-    (gap ? q->deep_gap : q->deep_min) = value;
-    return UWSPR_OK;
-  }
-  if (!strcmp(name, "call_min") || !strcmp(name, "call_gap")) {   // the pipe's own: the call search's acceptance thresholds
-    const bool gap = name[5] == 'g';
-    if (value < 0) return parg(q, "uwspr_pipe_set_option: \"%s\" is >= 0, not %d", name, value);
-    std::lock_guard<std::mutex> lk(q->m);
-    for (auto &L : q->lanes)
-      if (L.busy) { snprintf(q->err, sizeof(q->err), "uwspr_pipe_set_option(%s): batches in flight (flush first)", name); return UWSPR_ERR_ARG; }
-    (gap ? q->call_gap : q->call_min) = value;
+    if (!lanes_idle_locked(q, "uwspr_pipe_set_option", name)) return UWSPR_ERR_ARG;
+    q->*po.target = value;
     return UWSPR_OK;
   }
   if (!strcmp(name, "audio_rate")) {   // the pipe's own: the rate of the audio its pushes carry, latched by the first push
@@ -1108,20 +1059,9 @@ extern "C" int uwspr_pipe_set_option(uwspr_pipe *q, const char *name, int value)
     (g ? q->blank_guard : q->blank) = value;
     return UWSPR_OK;
   }
-  if (!strcmp(name, "block")) {   // the pipe's own: K10's block soft symbols for the records Fano gave up on
-    if (value != 0 && value != 2 && value != 3) return parg(q, "uwspr_pipe_set_option: \"block\" is 0, 2 or 3, not %d", value);
-    std::lock_guard<std::mutex> lk(q->m);
-    for (auto &L : q->lanes)
-      if (L.busy) { snprintf(q->err, sizeof(q->err), "uwspr_pipe_set_option(block): batches in flight (flush first)"); return UWSPR_ERR_ARG; }
-    q->block = value;
-    return UWSPR_OK;
-  }
-  // checked AND applied under q->m: a lane is marked busy under the same lock when a batch is launched on it, so no
-  // batch starts between the check and the last lane's option (the producer is single-threaded by contract, the
-  // coordinators are not)
+  // checked AND applied under q->m (lanes_idle_locked)
   std::lock_guard<std::mutex> lk(q->m);
-  for (auto &L : q->lanes)
-    if (L.busy) { snprintf(q->err, sizeof(q->err), "uwspr_pipe_set_option(%s): batches in flight (flush first)", name); return UWSPR_ERR_ARG; }
+  if (!lanes_idle_locked(q, "uwspr_pipe_set_option", name)) return UWSPR_ERR_ARG;
   for (auto &L : q->lanes) {
     const int rc = uwspr_set_option(L.ctx, name, value);
     if (rc) {
@@ -1151,12 +1091,10 @@ extern "C" int uwspr_pipe_set_list(uwspr_pipe *q, const int8_t *messages7, int M
     if (e != hipSuccess) { (void)hipFree(d_new); return pfail(q, UWSPR_ERR_HIP, "uwspr_pipe_set_list: upload of the table: %s", hipGetErrorString(e)); }
   }
   std::lock_guard<std::mutex> lk(q->m);
-  for (auto &L : q->lanes)
-    if (L.busy) {
-      if (d_new) (void)hipFree(d_new);
-      snprintf(q->err, sizeof(q->err), "uwspr_pipe_set_list: batches in flight (flush first)");
-      return UWSPR_ERR_ARG;
-    }
+  if (!lanes_idle_locked(q, "uwspr_pipe_set_list")) {
+    if (d_new) (void)hipFree(d_new);
+    return UWSPR_ERR_ARG;
+  }
   if (q->d_deep_tab) (void)hipFree(q->d_deep_tab);   // (nothing in flight: no lane reads it)
   q->d_deep_tab = d_new;
   q->deep_M = M;
@@ -1180,12 +1118,10 @@ extern "C" int uwspr_pipe_set_calls(uwspr_pipe *q, const char *const *calls, int
     if (!fresh) return rc == UWSPR_ERR_ARG ? parg(q, "uwspr_pipe_set_calls: %s", why) : pfail(q, rc, "uwspr_pipe_set_calls: %s", why);
   }
   std::lock_guard<std::mutex> lk(q->m);
-  for (auto &L : q->lanes)
-    if (L.busy) {
-      calls_free_set(fresh);
-      snprintf(q->err, sizeof(q->err), "uwspr_pipe_set_calls: batches in flight (flush first)");
-      return UWSPR_ERR_ARG;
-    }
+  if (!lanes_idle_locked(q, "uwspr_pipe_set_calls")) {
+    calls_free_set(fresh);
+    return UWSPR_ERR_ARG;
+  }
   calls_free_set(q->call_set);   // (nothing in flight: no lane reads it)
   q->call_set = fresh;
   return UWSPR_OK;

@@ -12,6 +12,7 @@
 #include <algorithm>
 #include <vector>
 
+#include "ctx_util.h"
 #include "uwspr_internal.h"
 
 namespace uwspr {
@@ -25,31 +26,13 @@ uint32_t coarse_seq_entry(const fdr_consts &f, int k, int off);
 using namespace uwspr;
 
 // --------------------------------------------------------------- utilities
-static int fail(uwspr_ctx *c, int status, const char *fmt, ...) {
-  if (c) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(c->err, sizeof(c->err), fmt, ap);
-    va_end(ap);
-  }
-  return status;
-}
-
-#define HIPCHK(c, call)                                                                  \
-  do {                                                                                   \
-    hipError_t e_ = (call);                                                              \
-    if (e_ != hipSuccess)                                                                \
-      return fail((c), UWSPR_ERR_HIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), \
-                  __FILE__, __LINE__);                                                   \
-  } while (0)
-
 template <typename T>
 static int ensure(uwspr_ctx *c, T **buf, size_t *cap, size_t need_elems) {
   if (need_elems <= *cap && *buf) return UWSPR_OK;
-  if (*buf) { HIPCHK(c, hipStreamSynchronize(c->stream)); HIPCHK(c, hipFree(*buf)); *buf = nullptr; *cap = 0; }
+  if (*buf) { CTXCHK(c, hipStreamSynchronize(c->stream)); CTXCHK(c, hipFree(*buf)); *buf = nullptr; *cap = 0; }
   size_t n = std::max<size_t>(need_elems, 1);
   hipError_t e = hipMalloc((void **)buf, n * sizeof(T));
-  if (e != hipSuccess) return fail(c, UWSPR_ERR_NOMEM, "hipMalloc(%zu bytes): %s", n * sizeof(T), hipGetErrorString(e));
+  if (e != hipSuccess) return ctx_fail(c, UWSPR_ERR_NOMEM, "hipMalloc(%zu bytes): %s", n * sizeof(T), hipGetErrorString(e));
   *cap = n;
   return UWSPR_OK;
 }
@@ -131,24 +114,24 @@ static int option_index(const char *name) {
 extern "C" int uwspr_set_option(uwspr_ctx *c, const char *name, int value) {
   if (!c) return UWSPR_ERR_ARG;
   const int i = option_index(name);
-  if (i < 0) return fail(c, UWSPR_ERR_ARG, "unknown option '%s'", name ? name : "(null)");
+  if (i < 0) return ctx_fail(c, UWSPR_ERR_ARG, "unknown option '%s'", name ? name : "(null)");
   if (i == UWSPR_OPT_K1_ROWS || i == UWSPR_OPT_K3_TILE)
-    return fail(c, UWSPR_ERR_ARG, "option '%s' shapes the context when it is created: UWSPR_OPTIONS=%s=%d", name, name, value);
+    return ctx_fail(c, UWSPR_ERR_ARG, "option '%s' shapes the context when it is created: UWSPR_OPTIONS=%s=%d", name, name, value);
   if (value < kOptions[i].lo || value > kOptions[i].hi)
-    return fail(c, UWSPR_ERR_ARG, "option '%s' = %d: allowed %d .. %d", name, value, kOptions[i].lo, kOptions[i].hi);
+    return ctx_fail(c, UWSPR_ERR_ARG, "option '%s' = %d: allowed %d .. %d", name, value, kOptions[i].lo, kOptions[i].hi);
   if (i == UWSPR_OPT_AUDIO_RATE) {
     resample_plan pl;
     if (resample_design(value, pl))
-      return fail(c, UWSPR_ERR_ARG, "option 'audio_rate' = %d: not a supported rate (12000 / gcd(rate, 12000) <= 160)", value);
+      return ctx_fail(c, UWSPR_ERR_ARG, "option 'audio_rate' = %d: not a supported rate (12000 / gcd(rate, 12000) <= 160)", value);
   }
   if (i == UWSPR_OPT_BLANK && value != 0 && value < 4)
-    return fail(c, UWSPR_ERR_ARG, "option 'blank' = %d: 0 (off) or 4 .. 1024 quarters of the median", value);
+    return ctx_fail(c, UWSPR_ERR_ARG, "option 'blank' = %d: 0 (off) or 4 .. 1024 quarters of the median", value);
   if (i == UWSPR_OPT_CARRIER || i == UWSPR_OPT_FRONTEND_HBW || i == UWSPR_OPT_FRONTEND) {   // the three together
     const int mode = i == UWSPR_OPT_FRONTEND ? value : c->opt[UWSPR_OPT_FRONTEND];
     const int fc = i == UWSPR_OPT_CARRIER ? value : c->opt[UWSPR_OPT_CARRIER];
     const int hb = i == UWSPR_OPT_FRONTEND_HBW ? value : c->opt[UWSPR_OPT_FRONTEND_HBW];
     if (!frontend_carrier_ok(mode, fc, hb))
-      return fail(c, UWSPR_ERR_ARG, "option '%s' = %d: carrier %d Hz with half-bandwidth %d Hz (hb + 20 <= carrier <= 6000 - hb - 20)", name,
+      return ctx_fail(c, UWSPR_ERR_ARG, "option '%s' = %d: carrier %d Hz with half-bandwidth %d Hz (hb + 20 <= carrier <= 6000 - hb - 20)", name,
                   value, fc, hb);
   }
   c->opt[i] = value; c->opt_set[i] = true;
@@ -159,7 +142,7 @@ extern "C" int uwspr_set_option(uwspr_ctx *c, const char *name, int value) {
 extern "C" int uwspr_get_option(uwspr_ctx *c, const char *name, int *value) {
   if (!c || !value) return UWSPR_ERR_ARG;
   const int i = option_index(name);
-  if (i < 0) return fail(c, UWSPR_ERR_ARG, "unknown option '%s'", name ? name : "(null)");
+  if (i < 0) return ctx_fail(c, UWSPR_ERR_ARG, "unknown option '%s'", name ? name : "(null)");
   *value = c->opt[i];
   return UWSPR_OK;
 }
@@ -173,7 +156,7 @@ static int options_from_environment(uwspr_ctx *c) {
     // strtol with an end check and the option's range, an over-long string is an error, not a truncation
     char buf[512];
     const size_t len = strlen(e);
-    if (len >= sizeof(buf)) return fail(c, UWSPR_ERR_ARG, "UWSPR_OPTIONS: %zu characters (at most %zu)", len, sizeof(buf) - 1);
+    if (len >= sizeof(buf)) return ctx_fail(c, UWSPR_ERR_ARG, "UWSPR_OPTIONS: %zu characters (at most %zu)", len, sizeof(buf) - 1);
     memcpy(buf, e, len + 1);
     char *tok = buf;
     while (*tok) {
@@ -184,16 +167,16 @@ static int options_from_environment(uwspr_ctx *c) {
       const bool last = *end == 0;
       *end = 0;
       char *eq = strchr(tok, '=');
-      if (!eq) return fail(c, UWSPR_ERR_ARG, "UWSPR_OPTIONS: '%s' is not name=value", tok);
+      if (!eq) return ctx_fail(c, UWSPR_ERR_ARG, "UWSPR_OPTIONS: '%s' is not name=value", tok);
       *eq = 0;
       const int i = option_index(tok);
-      if (i < 0) return fail(c, UWSPR_ERR_ARG, "UWSPR_OPTIONS: unknown option '%s'", tok);
+      if (i < 0) return ctx_fail(c, UWSPR_ERR_ARG, "UWSPR_OPTIONS: unknown option '%s'", tok);
       char *vend = nullptr;
       errno = 0;
       const long v = strtol(eq + 1, &vend, 10);
       if (vend == eq + 1 || *vend || errno || v < kOptions[i].lo || v > kOptions[i].hi)
-        return fail(c, UWSPR_ERR_ARG, "UWSPR_OPTIONS: %s='%s' is not an integer in %d .. %d", tok, eq + 1, kOptions[i].lo, kOptions[i].hi);
-      if (i == UWSPR_OPT_BLANK && v != 0 && v < 4) return fail(c, UWSPR_ERR_ARG, "UWSPR_OPTIONS: blank=%ld is not 0 or 4 .. 1024", v);
+        return ctx_fail(c, UWSPR_ERR_ARG, "UWSPR_OPTIONS: %s='%s' is not an integer in %d .. %d", tok, eq + 1, kOptions[i].lo, kOptions[i].hi);
+      if (i == UWSPR_OPT_BLANK && v != 0 && v < 4) return ctx_fail(c, UWSPR_ERR_ARG, "UWSPR_OPTIONS: blank=%ld is not 0 or 4 .. 1024", v);
       c->opt[i] = (int)v; c->opt_set[i] = true;
       if (last) break;
       tok = end + 1;
@@ -256,11 +239,11 @@ extern "C" int uwspr_ctx_create(const uwspr_params *p, int device, uwspr_ctx **o
   const int size = 2 * p->spb;
   const int maxfreq = (int)((float)p->fs / 2.0);
   if (p->halfbandwidth > maxfreq)
-    return fail(c, UWSPR_ERR_PARAM, "Half pass bandwidth (%d) must be lower than max freq range (%d)",
+    return ctx_fail(c, UWSPR_ERR_PARAM, "Half pass bandwidth (%d) must be lower than max freq range (%d)",
                 p->halfbandwidth, maxfreq);
-  if (p->spb != 256) return fail(c, UWSPR_ERR_UNSUPPORTED, "spb=%d: this build implements the 512-point transform (spb=256)", p->spb);
+  if (p->spb != 256) return ctx_fail(c, UWSPR_ERR_UNSUPPORTED, "spb=%d: this build implements the 512-point transform (spb=256)", p->spb);
   if (p->fs <= 0 || p->fl <= 0 || p->maxdrift < 0 || p->maxfreqs < 1 || p->halfbandwidth < 1 || p->cf <= 0)
-    return fail(c, UWSPR_ERR_ARG, "non-positive constructor argument");
+    return ctx_fail(c, UWSPR_ERR_ARG, "non-positive constructor argument");
   f.fl = p->fl; f.size = size; f.m = size / 2; f.maxfreqs = p->maxfreqs; f.maxdrift = p->maxdrift;
   f.df = (float)p->fs / (float)size;
   f.hpbm = (int)ceil((float)(int)(float)p->halfbandwidth / f.df);
@@ -271,8 +254,8 @@ extern "C" int uwspr_ctx_create(const uwspr_params *p, int device, uwspr_ctx **o
   f.min_snr_floor = (float)(0.1 * (double)f.min_snr);
   f.threshold = (float)p->threshold;
   if (f.n < 2 * (UWSPR_NSYM - 1) + UWSPR_NK0 || (f.n - 1) * (p->spb / 2) + size > p->fl)
-    return fail(c, UWSPR_ERR_UNSUPPORTED, "fl=%d too short for 162 symbols + 26 half-symbol offsets", p->fl);
-  if (f.finpb > 512 || f.finpb < 3) return fail(c, UWSPR_ERR_RANGE, "pass band of %d bins", f.finpb);
+    return ctx_fail(c, UWSPR_ERR_UNSUPPORTED, "fl=%d too short for 162 symbols + 26 half-symbol offsets", p->fl);
+  if (f.finpb > 512 || f.finpb < 3) return ctx_fail(c, UWSPR_ERR_RANGE, "pass band of %d bins", f.finpb);
 
   // ---- offset table: ifd - ifr for every (ifr, hypothesis, symbol) --------
   f.nlin = 2 * p->maxdrift + 1;
@@ -307,7 +290,7 @@ extern "C" int uwspr_ctx_create(const uwspr_params *p, int device, uwspr_ctx **o
           ifd = (int)((float)ifr + slm[(size_t)(h - f.nlin) * 111 + t] / f.df);
         }
         const int o = ifd - ifr;
-        if (o < -128 || o > 127) return fail(c, UWSPR_ERR_RANGE, "search reach %d bins", o);
+        if (o < -128 || o > 127) return ctx_fail(c, UWSPR_ERR_RANGE, "search reach %d bins", o);
         omin = std::min(omin, o); omax = std::max(omax, o);
         off[((size_t)r * f.cell_hyps + h) * 164 + k] = (int8_t)o;
       }
@@ -317,7 +300,7 @@ extern "C" int uwspr_ctx_create(const uwspr_params *p, int device, uwspr_ctx **o
   const int lo = std::min(f.m - f.hpbm - 3, f.ifr_lo + omin - 3);
   const int hi = std::max(f.m + f.hpbm - 1 + 3, ifr_hi + omax + 3);
   if (lo < 0 || hi > size - 1)
-    return fail(c, UWSPR_ERR_RANGE,
+    return ctx_fail(c, UWSPR_ERR_RANGE,
                 "halfbandwidth=%d: pass band + search reach needs columns %d..%d of 0..%d "
                 "(the reference reads out of bounds here)", p->halfbandwidth, lo, hi, size - 1);
   f.band_lo = lo; f.band_w = hi - lo + 1;
@@ -326,17 +309,17 @@ extern "C" int uwspr_ctx_create(const uwspr_params *p, int device, uwspr_ctx **o
   // ---- device -------------------------------------------------------------
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-    return fail(c, UWSPR_ERR_NODEVICE, "no HIP device visible; this library has no CPU fallback");
-  if (device < 0 || device >= ndev) return fail(c, UWSPR_ERR_ARG, "device %d of %d", device, ndev);
-  HIPCHK(c, hipSetDevice(device));
+    return ctx_fail(c, UWSPR_ERR_NODEVICE, "no HIP device visible; this library has no CPU fallback");
+  if (device < 0 || device >= ndev) return ctx_fail(c, UWSPR_ERR_ARG, "device %d of %d", device, ndev);
+  CTXCHK(c, hipSetDevice(device));
   hipDeviceProp_t prop;
-  HIPCHK(c, hipGetDeviceProperties(&prop, device));
+  CTXCHK(c, hipGetDeviceProperties(&prop, device));
   snprintf(c->device_name, sizeof(c->device_name), "%s", prop.gcnArchName);
   c->num_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
   if (strncmp(prop.gcnArchName, "gfx950", 6) != 0)
-    return fail(c, UWSPR_ERR_NODEVICE, "device %d is %s; kernels are built for gfx950 only", device,
+    return ctx_fail(c, UWSPR_ERR_NODEVICE, "device %d is %s; kernels are built for gfx950 only", device,
                 prop.gcnArchName);
-  HIPCHK(c, hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking));
+  CTXCHK(c, hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking));
   c->stream = c->own_stream;
 
   // window (FDR_impl.cc:101-105) and twiddles (exp(-2*pi*i*k/512), k<256; k=0,128 exact)
@@ -373,23 +356,23 @@ extern "C" int uwspr_ctx_create(const uwspr_params *p, int device, uwspr_ctx **o
       const int h = u < (int)uniq_of[r].size() ? uniq_of[r][u] : uniq_of[r][0];
       for (int k = 0; k < UWSPR_NSYM; k++) {
         const uint32_t e = coarse_seq_entry(f, k, off[((size_t)r * f.cell_hyps + h) * 164 + k]);
-        if (e > 0xffffu) return fail(c, UWSPR_ERR_UNSUPPORTED, "coarse tile of %d centre columns", f.nc);
+        if (e > 0xffffu) return ctx_fail(c, UWSPR_ERR_UNSUPPORTED, "coarse tile of %d centre columns", f.nc);
         offw[((size_t)r * f.umax + u) * sw + k / 2] |= e << (16 * (k & 1));
       }
     }
   if (coarse_lds_bytes(f) > 160 * 1024)
-    return fail(c, UWSPR_ERR_UNSUPPORTED, "coarse search needs %zu B of LDS (> 160 KiB): reduce maxdrift/cf",
+    return ctx_fail(c, UWSPR_ERR_UNSUPPORTED, "coarse search needs %zu B of LDS (> 160 KiB): reduce maxdrift/cf",
                 coarse_lds_bytes(f));
-  if (k3_scratch) HIPCHK(c, hipMalloc((void **)&c->d_k3_tile, k3_scratch * sizeof(float) * (size_t)c->num_cus));
-  HIPCHK(c, hipMalloc((void **)&c->d_umap, umap.size() * sizeof(uint16_t)));
-  HIPCHK(c, hipMemcpy(c->d_umap, umap.data(), umap.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
-  HIPCHK(c, hipMalloc((void **)&c->d_window, size * sizeof(float)));
-  HIPCHK(c, hipMalloc((void **)&c->d_twiddle, size * sizeof(float)));
-  HIPCHK(c, hipMalloc((void **)&c->d_off, offw.size() * sizeof(uint32_t)));
-  HIPCHK(c, hipMemcpy(c->d_window, w.data(), size * sizeof(float), hipMemcpyHostToDevice));
-  HIPCHK(c, hipMemcpy(c->d_twiddle, tw.data(), size * sizeof(float), hipMemcpyHostToDevice));
-  HIPCHK(c, hipMemcpy(c->d_off, offw.data(), offw.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-  if (coarse_configure(f) != 0) return fail(c, UWSPR_ERR_HIP, "cannot reserve %zu B of LDS for the coarse search", coarse_lds_bytes(f));
+  if (k3_scratch) CTXCHK(c, hipMalloc((void **)&c->d_k3_tile, k3_scratch * sizeof(float) * (size_t)c->num_cus));
+  CTXCHK(c, hipMalloc((void **)&c->d_umap, umap.size() * sizeof(uint16_t)));
+  CTXCHK(c, hipMemcpy(c->d_umap, umap.data(), umap.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
+  CTXCHK(c, hipMalloc((void **)&c->d_window, size * sizeof(float)));
+  CTXCHK(c, hipMalloc((void **)&c->d_twiddle, size * sizeof(float)));
+  CTXCHK(c, hipMalloc((void **)&c->d_off, offw.size() * sizeof(uint32_t)));
+  CTXCHK(c, hipMemcpy(c->d_window, w.data(), size * sizeof(float), hipMemcpyHostToDevice));
+  CTXCHK(c, hipMemcpy(c->d_twiddle, tw.data(), size * sizeof(float), hipMemcpyHostToDevice));
+  CTXCHK(c, hipMemcpy(c->d_off, offw.data(), offw.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+  if (coarse_configure(f) != 0) return ctx_fail(c, UWSPR_ERR_HIP, "cannot reserve %zu B of LDS for the coarse search", coarse_lds_bytes(f));
   return UWSPR_OK;
 }
 
@@ -449,9 +432,9 @@ extern "C" int uwspr_get_info(const uwspr_ctx *c, uwspr_info *o) {
 
 static int ready(uwspr_ctx *c) {
   if (!c) return UWSPR_ERR_ARG;
-  if (!c->own_stream) return fail(c, UWSPR_ERR_NODEVICE, "context has no device (creation failed: %s)", c->err);
+  if (!c->own_stream) return ctx_fail(c, UWSPR_ERR_NODEVICE, "context has no device (creation failed: %s)", c->err);
   hipError_t e = hipSetDevice(c->device);
-  if (e != hipSuccess) return fail(c, UWSPR_ERR_HIP, "hipSetDevice: %s", hipGetErrorString(e));
+  if (e != hipSuccess) return ctx_fail(c, UWSPR_ERR_HIP, "hipSetDevice: %s", hipGetErrorString(e));
   return UWSPR_OK;
 }
 
@@ -465,7 +448,7 @@ extern "C" int uwspr_set_stream(uwspr_ctx *c, void *s) {
 extern "C" int uwspr_synchronize(uwspr_ctx *c) {
   int rc = ready(c);
   if (rc) return rc;
-  HIPCHK(c, hipStreamSynchronize(c->stream));
+  CTXCHK(c, hipStreamSynchronize(c->stream));
   return UWSPR_OK;
 }
 
@@ -477,24 +460,24 @@ static int upload(uwspr_ctx *c, void *dst, const void *src, size_t bytes) {
   {   // the caller's buffer is already page-locked (uwspr_host_alloc, hipHostMalloc, hipHostRegister): plain DMA
     hipPointerAttribute_t at;
     if (hipPointerGetAttributes(&at, src) == hipSuccess && at.type == hipMemoryTypeHost) {
-      HIPCHK(c, hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, c->stream));
+      CTXCHK(c, hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, c->stream));
       return UWSPR_OK;
     }
     (void)hipGetLastError();   // an ordinary pointer is "invalid value" to the query: not an error here
   }
   if (bytes > 4 * PIECE) {   // a whole batch of frames: one host thread's memcpy into pinned memory (~10 GB/s)
-    HIPCHK(c, hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, c->stream));   // would be slower than the runtime's own staging (measured 57 k vs 87 k frames/s)
+    CTXCHK(c, hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, c->stream));   // would be slower than the runtime's own staging (measured 57 k vs 87 k frames/s)
     return UWSPR_OK;
   }
   if (!c->h_pin) {
     if (hipHostMalloc((void **)&c->h_pin, 2 * PIECE, hipHostMallocDefault) != hipSuccess) {
       c->h_pin = nullptr;
       (void)hipGetLastError();
-      HIPCHK(c, hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, c->stream));
+      CTXCHK(c, hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, c->stream));
       return UWSPR_OK;
     }
-    HIPCHK(c, hipEventCreateWithFlags(&c->pin_ev[0], hipEventDisableTiming));
-    HIPCHK(c, hipEventCreateWithFlags(&c->pin_ev[1], hipEventDisableTiming));
+    CTXCHK(c, hipEventCreateWithFlags(&c->pin_ev[0], hipEventDisableTiming));
+    CTXCHK(c, hipEventCreateWithFlags(&c->pin_ev[1], hipEventDisableTiming));
     c->pin_busy[0] = c->pin_busy[1] = false;
   }
   size_t off = 0;
@@ -502,10 +485,10 @@ static int upload(uwspr_ctx *c, void *dst, const void *src, size_t bytes) {
   while (off < bytes) {
     const size_t n = bytes - off < PIECE ? bytes - off : PIECE;
     char *half = (char *)c->h_pin + (size_t)(k & 1) * PIECE;
-    if (c->pin_busy[k & 1]) HIPCHK(c, hipEventSynchronize(c->pin_ev[k & 1]));   // its previous DMA is done
+    if (c->pin_busy[k & 1]) CTXCHK(c, hipEventSynchronize(c->pin_ev[k & 1]));   // its previous DMA is done
     memcpy(half, (const char *)src + off, n);
-    HIPCHK(c, hipMemcpyAsync((char *)dst + off, half, n, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipEventRecord(c->pin_ev[k & 1], c->stream));
+    CTXCHK(c, hipMemcpyAsync((char *)dst + off, half, n, hipMemcpyHostToDevice, c->stream));
+    CTXCHK(c, hipEventRecord(c->pin_ev[k & 1], c->stream));
     c->pin_busy[k & 1] = true;
     off += n;
     k++;
@@ -515,9 +498,9 @@ static int upload(uwspr_ctx *c, void *dst, const void *src, size_t bytes) {
 
 // frames -> device pointer (staged when they are host memory)
 static int frames_on_device(uwspr_ctx *c, const float *frames, int B, int where, const float **dev) {
-  if (!frames || B <= 0) return fail(c, UWSPR_ERR_ARG, "frames=%p B=%d", (const void *)frames, B);
+  if (!frames || B <= 0) return ctx_fail(c, UWSPR_ERR_ARG, "frames=%p B=%d", (const void *)frames, B);
   if (where == UWSPR_DEVICE || where == UWSPR_DEVICE_FRAMES) { *dev = frames; return UWSPR_OK; }
-  if (where != UWSPR_HOST) return fail(c, UWSPR_ERR_ARG, "where=%d", where);
+  if (where != UWSPR_HOST) return ctx_fail(c, UWSPR_ERR_ARG, "where=%d", where);
   // frame b starts at frames + 2 * fstride * b: what is uploaded is the span the B frames cover
   const size_t bytes = ((size_t)(B - 1) * c->fstride + c->fc.fl) * 2 * sizeof(float);
   size_t cap = c->cap_frames_bytes / sizeof(float);
@@ -535,7 +518,7 @@ int uwspr::api_frames_on_device(uwspr_ctx *c, const float *frames, int B, int wh
 
 static int copy_out(uwspr_ctx *c, void *dst, const void *src, size_t bytes, int where) {
   if (!dst || bytes == 0) return UWSPR_OK;
-  HIPCHK(c, hipMemcpyAsync(dst, src, bytes, where != UWSPR_DEVICE ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, c->stream));
+  CTXCHK(c, hipMemcpyAsync(dst, src, bytes, where != UWSPR_DEVICE ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, c->stream));
   return UWSPR_OK;
 }
 
@@ -552,12 +535,12 @@ static int frontend_taps(uwspr_ctx *c) {
   int J = 0, dcols = 0;
   if (frontend_default_set(c) ? frontend_tap_image(c->opt[UWSPR_OPT_FRONTEND], img, &J, &dcols)
                               : frontend_carrier_tables(c->opt[UWSPR_OPT_FRONTEND], std::vector<int>(1, fc), hb, img, &J, &dcols))
-    return fail(c, UWSPR_ERR_ARG, "front-end mode %d at %d Hz, half-bandwidth %d Hz", c->opt[UWSPR_OPT_FRONTEND], fc, hb);
-  if (frontend_prepare()) return fail(c, UWSPR_ERR_HIP, "front-end kernel: %zu bytes of LDS refused", (size_t)160 * 1024);
-  HIPCHK(c, hipStreamSynchronize(c->stream));          // (a launch with the other mode's taps may be in flight)
-  if (c->d_fe_taps) { HIPCHK(c, hipFree(c->d_fe_taps)); c->d_fe_taps = nullptr; }
-  HIPCHK(c, hipMalloc((void **)&c->d_fe_taps, img.size() * sizeof(float)));
-  HIPCHK(c, hipMemcpy(c->d_fe_taps, img.data(), img.size() * sizeof(float), hipMemcpyHostToDevice));
+    return ctx_fail(c, UWSPR_ERR_ARG, "front-end mode %d at %d Hz, half-bandwidth %d Hz", c->opt[UWSPR_OPT_FRONTEND], fc, hb);
+  if (frontend_prepare()) return ctx_fail(c, UWSPR_ERR_HIP, "front-end kernel: %zu bytes of LDS refused", (size_t)160 * 1024);
+  CTXCHK(c, hipStreamSynchronize(c->stream));          // (a launch with the other mode's taps may be in flight)
+  if (c->d_fe_taps) { CTXCHK(c, hipFree(c->d_fe_taps)); c->d_fe_taps = nullptr; }
+  CTXCHK(c, hipMalloc((void **)&c->d_fe_taps, img.size() * sizeof(float)));
+  CTXCHK(c, hipMemcpy(c->d_fe_taps, img.data(), img.size() * sizeof(float), hipMemcpyHostToDevice));
   c->fe_mode = c->opt[UWSPR_OPT_FRONTEND]; c->fe_J = J; c->fe_dcols = dcols; c->fe_fc = fc; c->fe_hb = hb;
   return UWSPR_OK;
 }
@@ -567,8 +550,8 @@ extern "C" int uwspr_frontend_batch(uwspr_ctx *c, const float *audio, int B, int
   int rc = ready(c);
   if (rc) return rc;
   const int nout = c->fc.fl;
-  if (!audio || !frames_out || B <= 0 || nin <= 0) return fail(c, UWSPR_ERR_ARG, "uwspr_frontend_batch: audio/out/B/nin");
-  if (c->p.fs != 375) return fail(c, UWSPR_ERR_UNSUPPORTED, "front-end is 12000 -> 375 S/s (fs=%d)", c->p.fs);
+  if (!audio || !frames_out || B <= 0 || nin <= 0) return ctx_fail(c, UWSPR_ERR_ARG, "uwspr_frontend_batch: audio/out/B/nin");
+  if (c->p.fs != 375) return ctx_fail(c, UWSPR_ERR_UNSUPPORTED, "front-end is 12000 -> 375 S/s (fs=%d)", c->p.fs);
   if ((rc = frontend_taps(c))) return rc;
   const float *da = audio;
   float *dout = frames_out;
@@ -578,10 +561,10 @@ extern "C" int uwspr_frontend_batch(uwspr_ctx *c, const float *audio, int B, int
     rc = ensure(c, &c->d_frames, &cap, (size_t)B * nout * 2);
     c->cap_frames_bytes = cap * sizeof(float);
     if (rc) return rc;
-    HIPCHK(c, hipMemcpyAsync(c->d_audio, audio, (size_t)B * nin * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    CTXCHK(c, hipMemcpyAsync(c->d_audio, audio, (size_t)B * nin * sizeof(float), hipMemcpyHostToDevice, c->stream));
     da = c->d_audio; dout = c->d_frames;
   } else if (where != UWSPR_DEVICE) {
-    return fail(c, UWSPR_ERR_ARG, "where=%d", where);
+    return ctx_fail(c, UWSPR_ERR_ARG, "where=%d", where);
   }
   if (frontend_default_set(c)) {
     launch_frontend(c, da, B, nin, (float2 *)dout, nout);
@@ -591,10 +574,10 @@ extern "C" int uwspr_frontend_batch(uwspr_ctx *c, const float *audio, int B, int
       launch_frontend_carrier(c->stream, da + (size_t)b * nin, false, nin, 0LL, c->d_fe_taps, c->fe_J, c->fe_dcols,
                               dout + 2 * (size_t)b * nout, nout, 0LL, 1, 1, (long long)nout);
   }
-  HIPCHK(c, hipGetLastError());
+  CTXCHK(c, hipGetLastError());
   if (where == UWSPR_HOST) {
-    HIPCHK(c, hipMemcpyAsync(frames_out, c->d_frames, (size_t)B * nout * 2 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    CTXCHK(c, hipMemcpyAsync(frames_out, c->d_frames, (size_t)B * nout * 2 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    CTXCHK(c, hipStreamSynchronize(c->stream));
   }
   return UWSPR_OK;
 }
@@ -643,8 +626,8 @@ extern "C" int uwspr_resample_batch(uwspr_ctx *c, const void *audio, long long n
   if (rc) return rc;
   if (!audio || !out || nin <= 0 || nout <= 0 || nchannels < 1 || nchannels > UWSPR_PIPE_MAX_CHANNELS ||
       (format != UWSPR_AUDIO_F32 && format != UWSPR_AUDIO_S16))
-    return fail(c, UWSPR_ERR_ARG, "uwspr_resample_batch: audio/out/nin %lld/nout %lld/nchannels %d/format %d", nin, nout, nchannels, format);
-  if (where != UWSPR_HOST && where != UWSPR_DEVICE) return fail(c, UWSPR_ERR_ARG, "where=%d", where);
+    return ctx_fail(c, UWSPR_ERR_ARG, "uwspr_resample_batch: audio/out/nin %lld/nout %lld/nchannels %d/format %d", nin, nout, nchannels, format);
+  if (where != UWSPR_HOST && where != UWSPR_DEVICE) return ctx_fail(c, UWSPR_ERR_ARG, "where=%d", where);
   return rs_batch(c, audio, nin, nchannels, format == UWSPR_AUDIO_S16, rate, where, out, nout);
 }
 
@@ -655,10 +638,10 @@ extern "C" int uwspr_blank_batch(uwspr_ctx *c, const void *audio, long long nin,
   if (rc) return rc;
   if (!audio || !out || nin <= 0 || nchannels < 1 || nchannels > UWSPR_PIPE_MAX_CHANNELS ||
       (format != UWSPR_AUDIO_F32 && format != UWSPR_AUDIO_S16))
-    return fail(c, UWSPR_ERR_ARG, "uwspr_blank_batch: audio/out/nin %lld/nchannels %d/format %d", nin, nchannels, format);
+    return ctx_fail(c, UWSPR_ERR_ARG, "uwspr_blank_batch: audio/out/nin %lld/nchannels %d/format %d", nin, nchannels, format);
   if (blank < 4 || blank > 1024 || guard < 0 || guard > 64)
-    return fail(c, UWSPR_ERR_ARG, "uwspr_blank_batch: blank %d (4 .. 1024) / guard %d (0 .. 64)", blank, guard);
-  if (where != UWSPR_HOST && where != UWSPR_DEVICE) return fail(c, UWSPR_ERR_ARG, "where=%d", where);
+    return ctx_fail(c, UWSPR_ERR_ARG, "uwspr_blank_batch: blank %d (4 .. 1024) / guard %d (0 .. 64)", blank, guard);
+  if (where != UWSPR_HOST && where != UWSPR_DEVICE) return ctx_fail(c, UWSPR_ERR_ARG, "where=%d", where);
   return bk_batch(c, audio, nin, nchannels, format == UWSPR_AUDIO_S16, where, blank, guard, out, med, nzero);
 }
 
@@ -673,8 +656,8 @@ extern "C" int uwspr_stream_blank_stats(uwspr_ctx *c, long long *samples, long l
   int rc = ready(c);
   if (rc) return rc;
   rc = ring_blank_stats(c->ring, samples, zeroed, cap);
-  if (rc == UWSPR_ERR_ARG) return fail(c, UWSPR_ERR_ARG, "uwspr_stream_blank_stats: samples/zeroed/cap %d", cap);
-  if (rc < 0) return fail(c, rc, "uwspr_stream_blank_stats: %s", hipGetErrorString(c->ring.err));
+  if (rc == UWSPR_ERR_ARG) return ctx_fail(c, UWSPR_ERR_ARG, "uwspr_stream_blank_stats: samples/zeroed/cap %d", cap);
+  if (rc < 0) return ctx_fail(c, rc, "uwspr_stream_blank_stats: %s", hipGetErrorString(c->ring.err));
   return rc;
 }
 
@@ -685,7 +668,7 @@ static int ensure_fdr(uwspr_ctx *c, int B) {
   size_t cap;
   int rc;
   c->cap_B = 0;   // a failed allocation below leaves no capacity behind that the null buffers cannot back
-#define GROW(ptr, elems) cap = 0; if (ptr) { HIPCHK(c, hipStreamSynchronize(c->stream)); HIPCHK(c, hipFree(ptr)); ptr = nullptr; } \
+#define GROW(ptr, elems) cap = 0; if (ptr) { CTXCHK(c, hipStreamSynchronize(c->stream)); CTXCHK(c, hipFree(ptr)); ptr = nullptr; } \
   rc = ensure(c, &ptr, &cap, (size_t)(elems)); if (rc) return rc;
   GROW(c->d_ps, (size_t)B * f.n * f.band_w);
   GROW(c->d_psavg, (size_t)B * f.band_w);
@@ -717,13 +700,13 @@ static int run_fdr(uwspr_ctx *c, const float *dframes, int B, uwspr_candidate *u
   if (!ps_band) {
     launch_spectrogram(c, dframes, B);
   } else {
-    HIPCHK(c, hipMemcpyAsync(c->d_ps, ps_band, (size_t)B * c->fc.n * c->fc.band_w * sizeof(float),
+    CTXCHK(c, hipMemcpyAsync(c->d_ps, ps_band, (size_t)B * c->fc.n * c->fc.band_w * sizeof(float),
                              ps_where == UWSPR_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, c->stream));
-    HIPCHK(c, hipMemsetAsync(c->d_work, 0, sizeof(int32_t), c->stream));   // K1's part: K2 appends to the work list from 0
+    CTXCHK(c, hipMemsetAsync(c->d_work, 0, sizeof(int32_t), c->stream));   // K1's part: K2 appends to the work list from 0
   }
   launch_spectrum(c, B);
   launch_coarse(c, B);
-  HIPCHK(c, hipGetLastError());
+  CTXCHK(c, hipGetLastError());
   c->last_B = B;
   return UWSPR_OK;
 }
@@ -740,7 +723,7 @@ extern "C" int uwspr_fdr_batch(uwspr_ctx *c, const float *frames, int B, int whe
     if ((rc = copy_out(c, cands, c->d_cands, (size_t)B * c->fc.maxfreqs * sizeof(uwspr_candidate), where))) return rc;
     if ((rc = copy_out(c, npk, c->d_npk, (size_t)B * sizeof(int32_t), where))) return rc;
   }
-  if (where != UWSPR_DEVICE) HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (where != UWSPR_DEVICE) CTXCHK(c, hipStreamSynchronize(c->stream));
   return UWSPR_OK;
 }
 
@@ -748,25 +731,25 @@ extern "C" int uwspr_fdr_read_spectrum(uwspr_ctx *c, int B, float *ps_band, floa
                                        float *smspec, float *noise) {
   int rc = ready(c);
   if (rc) return rc;
-  if (B <= 0 || B > c->last_B) return fail(c, UWSPR_ERR_ARG, "B=%d but the last FDR batch held %d frames", B, c->last_B);
+  if (B <= 0 || B > c->last_B) return ctx_fail(c, UWSPR_ERR_ARG, "B=%d but the last FDR batch held %d frames", B, c->last_B);
   const fdr_consts &f = c->fc;
   if ((rc = copy_out(c, ps_band, c->d_ps, (size_t)B * f.n * f.band_w * 4, UWSPR_HOST))) return rc;
   if ((rc = copy_out(c, psavg, c->d_psavg, (size_t)B * f.band_w * 4, UWSPR_HOST))) return rc;
   if ((rc = copy_out(c, smraw, c->d_smraw, (size_t)B * f.finpb * 4, UWSPR_HOST))) return rc;
   if ((rc = copy_out(c, smspec, c->d_smspec, (size_t)B * f.finpb * 4, UWSPR_HOST))) return rc;
   if ((rc = copy_out(c, noise, c->d_noise, (size_t)B * 4, UWSPR_HOST))) return rc;
-  HIPCHK(c, hipStreamSynchronize(c->stream));
+  CTXCHK(c, hipStreamSynchronize(c->stream));
   return UWSPR_OK;
 }
 
 extern "C" int uwspr_fdr_keep_syncgrid(uwspr_ctx *c, int ncand_cap) {
   int rc = ready(c);
   if (rc) return rc;
-  if (ncand_cap < 0) return fail(c, UWSPR_ERR_ARG, "ncand_cap=%d", ncand_cap);
+  if (ncand_cap < 0) return ctx_fail(c, UWSPR_ERR_ARG, "ncand_cap=%d", ncand_cap);
   c->grid_cap = std::min(ncand_cap, c->fc.cand_slots);
   if (c->grid_cap == 0 && c->d_syncgrid) {
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, hipFree(c->d_syncgrid));
+    CTXCHK(c, hipStreamSynchronize(c->stream));
+    CTXCHK(c, hipFree(c->d_syncgrid));
     c->d_syncgrid = nullptr; c->cap_grid_bytes = 0;
   }
   return UWSPR_OK;
@@ -775,10 +758,10 @@ extern "C" int uwspr_fdr_keep_syncgrid(uwspr_ctx *c, int ncand_cap) {
 extern "C" int uwspr_fdr_read_syncgrid(uwspr_ctx *c, int B, float *grid) {
   int rc = ready(c);
   if (rc) return rc;
-  if (!c->d_syncgrid || c->grid_cap <= 0) return fail(c, UWSPR_ERR_ARG, "sync grid not kept: call uwspr_fdr_keep_syncgrid first");
-  if (B <= 0 || B > c->last_B) return fail(c, UWSPR_ERR_ARG, "B=%d but the last FDR batch held %d frames", B, c->last_B);
+  if (!c->d_syncgrid || c->grid_cap <= 0) return ctx_fail(c, UWSPR_ERR_ARG, "sync grid not kept: call uwspr_fdr_keep_syncgrid first");
+  if (B <= 0 || B > c->last_B) return ctx_fail(c, UWSPR_ERR_ARG, "B=%d but the last FDR batch held %d frames", B, c->last_B);
   if ((rc = copy_out(c, grid, c->d_syncgrid, (size_t)B * c->grid_cap * c->fc.ntot * 4, UWSPR_HOST))) return rc;
-  HIPCHK(c, hipStreamSynchronize(c->stream));
+  CTXCHK(c, hipStreamSynchronize(c->stream));
   return UWSPR_OK;
 }
 
@@ -795,17 +778,17 @@ extern "C" int uwspr_sync_sweep(uwspr_ctx *c, const float *frames, int B, const 
                                 int where, float *sync, uint8_t *symbols) {
   int rc = ready(c);
   if (rc) return rc;
-  if (!hyps || H <= 0) return fail(c, UWSPR_ERR_ARG, "hyps=%p H=%d", (const void *)hyps, H);
-  if (where == UWSPR_DEVICE_FRAMES) return fail(c, UWSPR_ERR_ARG, "uwspr_sync_sweep: where is UWSPR_HOST or UWSPR_DEVICE");
+  if (!hyps || H <= 0) return ctx_fail(c, UWSPR_ERR_ARG, "hyps=%p H=%d", (const void *)hyps, H);
+  if (where == UWSPR_DEVICE_FRAMES) return ctx_fail(c, UWSPR_ERR_ARG, "uwspr_sync_sweep: where is UWSPR_HOST or UWSPR_DEVICE");
   const float *d;
   if ((rc = frames_on_device(c, frames, B, where, &d))) return rc;
   if ((rc = ensure(c, &c->d_hyps, &c->cap_hyps, (size_t)H))) return rc;
   const uwspr_hyp *dabi = hyps;
   if (where == UWSPR_HOST) {
     for (int h = 0; h < H; h++)
-      if (hyps[h].frame >= B) return fail(c, UWSPR_ERR_ARG, "hyps[%d].frame=%d >= B=%d", h, hyps[h].frame, B);
+      if (hyps[h].frame >= B) return ctx_fail(c, UWSPR_ERR_ARG, "hyps[%d].frame=%d >= B=%d", h, hyps[h].frame, B);
     if ((rc = ensure(c, &c->d_abi_hyps, &c->cap_abi_hyps, (size_t)H))) return rc;
-    HIPCHK(c, hipMemcpyAsync(c->d_abi_hyps, hyps, (size_t)H * sizeof(uwspr_hyp), hipMemcpyHostToDevice, c->stream));
+    CTXCHK(c, hipMemcpyAsync(c->d_abi_hyps, hyps, (size_t)H * sizeof(uwspr_hyp), hipMemcpyHostToDevice, c->stream));
     dabi = c->d_abi_hyps;
   }
   const bool soft = symbols != nullptr;
@@ -813,10 +796,10 @@ extern "C" int uwspr_sync_sweep(uwspr_ctx *c, const float *frames, int B, const 
   launch_prep_hyps(c, dabi, c->d_hyps, H);
   launch_tonecorr(c, d, B, c->d_hyps, H, c->d_p);
   launch_fold(c, c->d_hyps, c->d_p, H, c->d_sync, soft ? c->d_sym : nullptr);
-  HIPCHK(c, hipGetLastError());
+  CTXCHK(c, hipGetLastError());
   if ((rc = copy_out(c, sync, c->d_sync, (size_t)H * 4, where))) return rc;
   if (soft && (rc = copy_out(c, symbols, c->d_sym, (size_t)H * UWSPR_NSYM, where))) return rc;
-  if (where == UWSPR_HOST) HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (where == UWSPR_HOST) CTXCHK(c, hipStreamSynchronize(c->stream));
   return UWSPR_OK;
 }
 
@@ -827,12 +810,12 @@ extern "C" int uwspr_sync_grid(uwspr_ctx *c, const float *frames, int B, int whe
   int rc = ready(c);
   if (rc) return rc;
   if (!centres || !df || !ddrift || !dlag || nf < 1 || ndrift < 1 || nlag < 1 || nf > 32 || ndrift > 32 || nlag > 4096)
-    return fail(c, UWSPR_ERR_ARG, "uwspr_sync_grid: nf=%d ndrift=%d nlag=%d (nf, ndrift <= 32)", nf, ndrift, nlag);
-  if (where == UWSPR_DEVICE_FRAMES) return fail(c, UWSPR_ERR_ARG, "uwspr_sync_grid: where is UWSPR_HOST or UWSPR_DEVICE");
+    return ctx_fail(c, UWSPR_ERR_ARG, "uwspr_sync_grid: nf=%d ndrift=%d nlag=%d (nf, ndrift <= 32)", nf, ndrift, nlag);
+  if (where == UWSPR_DEVICE_FRAMES) return ctx_fail(c, UWSPR_ERR_ARG, "uwspr_sync_grid: where is UWSPR_HOST or UWSPR_DEVICE");
   const float *d;
   if ((rc = frames_on_device(c, frames, B, where, &d))) return rc;
   const long long H = (long long)B * nf * ndrift * nlag;
-  if (H > (1LL << 27)) return fail(c, UWSPR_ERR_ARG, "uwspr_sync_grid: %lld hypotheses in one call", H);
+  if (H > (1LL << 27)) return ctx_fail(c, UWSPR_ERR_ARG, "uwspr_sync_grid: %lld hypotheses in one call", H);
   const bool soft = symbols != nullptr;
   if ((rc = ensure(c, &c->d_hyps, &c->cap_hyps, (size_t)H))) return rc;
   if ((rc = ensure_sweep(c, (size_t)H, soft))) return rc;
@@ -841,19 +824,19 @@ extern "C" int uwspr_sync_grid(uwspr_ctx *c, const float *frames, int B, int whe
   if ((rc = ensure(c, &c->d_abi_hyps, &c->cap_abi_hyps, need_abi))) return rc;
   uwspr_candidate *dcent = reinterpret_cast<uwspr_candidate *>(c->d_abi_hyps);
   int32_t *ddl = reinterpret_cast<int32_t *>(dcent + B);
-  HIPCHK(c, hipMemcpyAsync(dcent, centres, (size_t)B * sizeof(uwspr_candidate),
+  CTXCHK(c, hipMemcpyAsync(dcent, centres, (size_t)B * sizeof(uwspr_candidate),
                            where == UWSPR_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(ddl, dlag, (size_t)nlag * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+  CTXCHK(c, hipMemcpyAsync(ddl, dlag, (size_t)nlag * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
   if (!launch_tonecorr_grid(c, d, B, dcent, nf, df, ndrift, ddrift, nlag, dlag, ddl, c->d_hyps, c->d_p)) {
     // window scheme does not fit (huge lag span): the flat kernel on the same hypothesis list
     c->launch_forms[UWSPR_FORM_GRID_FALLBACK]++;
     launch_tonecorr(c, d, B, c->d_hyps, (int)H, c->d_p);
   }
   launch_fold(c, c->d_hyps, c->d_p, (int)H, c->d_sync, soft ? c->d_sym : nullptr);
-  HIPCHK(c, hipGetLastError());
+  CTXCHK(c, hipGetLastError());
   if ((rc = copy_out(c, sync, c->d_sync, (size_t)H * 4, where))) return rc;
   if (soft && (rc = copy_out(c, symbols, c->d_sym, (size_t)H * UWSPR_NSYM, where))) return rc;
-  if (where == UWSPR_HOST) HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (where == UWSPR_HOST) CTXCHK(c, hipStreamSynchronize(c->stream));
   return UWSPR_OK;
 }
 
@@ -862,22 +845,22 @@ extern "C" int uwspr_sync_and_demodulate_batch(uwspr_ctx *c, const float *frames
                                                uwspr_sync_result *results) {
   int rc = ready(c);
   if (rc) return rc;
-  if (!calls || !results || ncalls <= 0) return fail(c, UWSPR_ERR_ARG, "calls/results/ncalls");
+  if (!calls || !results || ncalls <= 0) return ctx_fail(c, UWSPR_ERR_ARG, "calls/results/ncalls");
   // expand each call into its (ifreq, lag) loop, cc:160-165
   std::vector<uwspr_hyp> hyps;
   std::vector<size_t> first(ncalls + 1, 0);
   bool soft = false;
   for (int q = 0; q < ncalls; q++) {
     const uwspr_sync_call &k = calls[q];
-    if (k.mode < 0 || k.mode > 2) return fail(c, UWSPR_ERR_ARG, "calls[%d].mode=%d", q, k.mode);
-    if (k.symfac != 50) return fail(c, UWSPR_ERR_UNSUPPORTED, "calls[%d].symfac=%d (the path uses 50)", q, k.symfac);
-    if (k.frame < 0 || k.frame >= B) return fail(c, UWSPR_ERR_ARG, "calls[%d].frame=%d", q, k.frame);
+    if (k.mode < 0 || k.mode > 2) return ctx_fail(c, UWSPR_ERR_ARG, "calls[%d].mode=%d", q, k.mode);
+    if (k.symfac != 50) return ctx_fail(c, UWSPR_ERR_UNSUPPORTED, "calls[%d].symfac=%d (the path uses 50)", q, k.symfac);
+    if (k.frame < 0 || k.frame >= B) return ctx_fail(c, UWSPR_ERR_ARG, "calls[%d].frame=%d", q, k.frame);
     int ifmin = k.ifmin, ifmax = k.ifmax, lagmin = k.lagmin, lagmax = k.lagmax;
     float fstep = k.fstep;
     if (k.mode == 0) { ifmin = 0; ifmax = 0; fstep = 0.0f; }
     if (k.mode == 1) { lagmin = k.shift1; lagmax = k.shift1; }
     if (k.mode == 2) { lagmin = k.shift1; lagmax = k.shift1; ifmin = 0; ifmax = 0; soft = true; }
-    if (k.lagstep <= 0) return fail(c, UWSPR_ERR_ARG, "calls[%d].lagstep=%d", q, k.lagstep);
+    if (k.lagstep <= 0) return ctx_fail(c, UWSPR_ERR_ARG, "calls[%d].lagstep=%d", q, k.lagstep);
     first[q] = hyps.size();
     for (int ifreq = ifmin; ifreq <= ifmax; ifreq++) {
       const float f0 = k.f1 + (float)ifreq * fstep;  // cc:164
@@ -891,7 +874,7 @@ extern "C" int uwspr_sync_and_demodulate_batch(uwspr_ctx *c, const float *frames
           h.p1 = k.candidate.m_nonlinear.p1; h.p2 = k.candidate.m_nonlinear.p2;
         }
         hyps.push_back(h);
-        if (hyps.size() > (size_t)1 << 26) return fail(c, UWSPR_ERR_ARG, "more than 2^26 hypotheses in one batch");
+        if (hyps.size() > (size_t)1 << 26) return ctx_fail(c, UWSPR_ERR_ARG, "more than 2^26 hypotheses in one batch");
       }
     }
   }
@@ -906,14 +889,14 @@ extern "C" int uwspr_sync_and_demodulate_batch(uwspr_ctx *c, const float *frames
     if ((rc = ensure(c, &c->d_hyps, &c->cap_hyps, (size_t)H))) return rc;
     if ((rc = ensure(c, &c->d_abi_hyps, &c->cap_abi_hyps, (size_t)H))) return rc;
     if ((rc = ensure_sweep(c, (size_t)H, soft))) return rc;
-    HIPCHK(c, hipMemcpyAsync(c->d_abi_hyps, hyps.data(), (size_t)H * sizeof(uwspr_hyp), hipMemcpyHostToDevice, c->stream));
+    CTXCHK(c, hipMemcpyAsync(c->d_abi_hyps, hyps.data(), (size_t)H * sizeof(uwspr_hyp), hipMemcpyHostToDevice, c->stream));
     launch_prep_hyps(c, c->d_abi_hyps, c->d_hyps, H);
     launch_tonecorr(c, d, B, c->d_hyps, H, c->d_p);
     launch_fold(c, c->d_hyps, c->d_p, H, c->d_sync, soft ? c->d_sym : nullptr);
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(sync.data(), c->d_sync, (size_t)H * 4, hipMemcpyDeviceToHost, c->stream));
-    if (soft) HIPCHK(c, hipMemcpyAsync(sym.data(), c->d_sym, (size_t)H * UWSPR_NSYM, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    CTXCHK(c, hipGetLastError());
+    CTXCHK(c, hipMemcpyAsync(sync.data(), c->d_sync, (size_t)H * 4, hipMemcpyDeviceToHost, c->stream));
+    if (soft) CTXCHK(c, hipMemcpyAsync(sym.data(), c->d_sym, (size_t)H * UWSPR_NSYM, hipMemcpyDeviceToHost, c->stream));
+    CTXCHK(c, hipStreamSynchronize(c->stream));
   }
   for (int q = 0; q < ncalls; q++) {
     const uwspr_sync_call &k = calls[q];
@@ -962,7 +945,7 @@ static int run_schedule_impl(uwspr_ctx *c, const float *dframes, int B, const uw
   const int njig = c->ntries < UWSPR_NJIG ? c->ntries : UWSPR_NJIG;
   if (c->use_fused || njig < UWSPR_NJIG) {   // (a lazy staged pass is resumed by the fused kernel)
     if ((rc = ensure(c, &c->d_tabs, &c->cap_tabs, (size_t)c->num_cus * kSchedTabFloats))) return rc;   // one 16-wave workgroup per CU
-    if (!c->d_counter) HIPCHK(c, hipMalloc((void **)&c->d_counter, 64));
+    if (!c->d_counter) CTXCHK(c, hipMalloc((void **)&c->d_counter, 64));
   }
   if (c->use_fused) {
     // k6_sched: one workgroup per candidate, S0..S5 back to back
@@ -975,7 +958,7 @@ static int run_schedule_impl(uwspr_ctx *c, const float *dframes, int B, const uw
     }
     launch_sched_fused(c, dframes, B, dcands, dnpk, cand_stride, per_frame, c->cur_dout,
                        c->ntries < UWSPR_NJIG ? c->ntries : UWSPR_NJIG);
-    HIPCHK(c, hipGetLastError());
+    CTXCHK(c, hipGetLastError());
     return UWSPR_OK;
   }
   if ((rc = ensure(c, &c->d_hyps, &c->cap_hyps, 2 * nslots * UWSPR_NJIG))) return rc;
@@ -1031,7 +1014,7 @@ static int run_schedule_impl(uwspr_ctx *c, const float *dframes, int B, const uw
       if (lazy) launch_keep_try0(c, (int)nslots, njig);   // what uwspr_demod_resume starts from
     }
   }
-  HIPCHK(c, hipGetLastError());
+  CTXCHK(c, hipGetLastError());
   return UWSPR_OK;
 }
 
@@ -1041,7 +1024,7 @@ extern "C" int uwspr_demod_batch(uwspr_ctx *c, const float *frames, int B, int w
   int rc = ready(c);
   if (rc) return rc;
   if (!cands || !npk || cand_stride <= 0 || max_per_frame <= 0 || !out)
-    return fail(c, UWSPR_ERR_ARG, "cands/npk/cand_stride/max_per_frame/out");
+    return ctx_fail(c, UWSPR_ERR_ARG, "cands/npk/cand_stride/max_per_frame/out");
   const float *d;
   if ((rc = frames_on_device(c, frames, B, where, &d))) return rc;
   const uwspr_candidate *dc = cands;
@@ -1050,8 +1033,8 @@ extern "C" int uwspr_demod_batch(uwspr_ctx *c, const float *frames, int B, int w
   if (host_recs) {
     if ((rc = ensure(c, &c->d_tmpc, &c->cap_tmpc, (size_t)B * cand_stride))) return rc;
     if ((rc = ensure(c, &c->d_tmpn, &c->cap_tmpn, (size_t)B))) return rc;
-    HIPCHK(c, hipMemcpyAsync(c->d_tmpc, cands, (size_t)B * cand_stride * sizeof(uwspr_candidate), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->d_tmpn, npk, (size_t)B * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    CTXCHK(c, hipMemcpyAsync(c->d_tmpc, cands, (size_t)B * cand_stride * sizeof(uwspr_candidate), hipMemcpyHostToDevice, c->stream));
+    CTXCHK(c, hipMemcpyAsync(c->d_tmpn, npk, (size_t)B * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
     dc = c->d_tmpc; dn = c->d_tmpn;
   }
   c->cands_from_fdr = false;   // the caller's candidates: any drift
@@ -1069,7 +1052,7 @@ extern "C" int uwspr_pipeline_batch(uwspr_ctx *c, const float *frames, int B, in
                                     uwspr_demod_out *out) {
   int rc = ready(c);
   if (rc) return rc;
-  if (max_per_frame <= 0) return fail(c, UWSPR_ERR_ARG, "max_per_frame=%d", max_per_frame);
+  if (max_per_frame <= 0) return ctx_fail(c, UWSPR_ERR_ARG, "max_per_frame=%d", max_per_frame);
   const float *d;
   if ((rc = frames_on_device(c, frames, B, where, &d))) return rc;
   // device callers get the results written straight into their buffers
@@ -1082,14 +1065,14 @@ extern "C" int uwspr_pipeline_batch(uwspr_ctx *c, const float *frames, int B, in
   if (c->next_slab) {   // uwspr_pipeline_slabs: packed by the schedule's last kernel (staged form) or here
     if (!c->next_slab_done) launch_pack_slabs(c, c->cur_cands, c->cur_npk, c->cur_dout, max_per_frame, c->next_slab_K, c->next_slab, B);
     c->next_slab = nullptr; c->next_slab_done = false;
-    HIPCHK(c, hipGetLastError());
+    CTXCHK(c, hipGetLastError());
   }
   if (c->cur_cands == c->d_cands &&
       (rc = copy_out(c, cands, c->d_cands, (size_t)B * c->fc.maxfreqs * sizeof(uwspr_candidate), where))) return rc;
   if (c->cur_npk == c->d_npk && (rc = copy_out(c, npk, c->d_npk, (size_t)B * sizeof(int32_t), where))) return rc;
   if (c->cur_dout == c->d_dout &&
       (rc = copy_out(c, out, c->d_dout, (size_t)B * max_per_frame * sizeof(uwspr_demod_out), where))) return rc;
-  if (where != UWSPR_DEVICE) HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (where != UWSPR_DEVICE) CTXCHK(c, hipStreamSynchronize(c->stream));
   return UWSPR_OK;
 }
 
@@ -1104,7 +1087,7 @@ __global__ void k_cut_frames(const float2 *__restrict__ src, float2 *__restrict_
 extern "C" int uwspr_set_frame_stride(uwspr_ctx *c, int stride) {
   int rc = ready(c);
   if (rc) return rc;
-  if (stride < 0) return fail(c, UWSPR_ERR_ARG, "stride=%d", stride);
+  if (stride < 0) return ctx_fail(c, UWSPR_ERR_ARG, "stride=%d", stride);
   c->fstride = stride > 0 ? stride : c->fc.fl;
   return UWSPR_OK;
 }
@@ -1112,11 +1095,11 @@ extern "C" int uwspr_set_frame_stride(uwspr_ctx *c, int stride) {
 extern "C" int uwspr_stream_open(uwspr_ctx *c, int hop, int max_frames) {
   int rc = ready(c);
   if (rc) return rc;
-  if (hop <= 0 || hop > c->fc.fl || max_frames <= 0) return fail(c, UWSPR_ERR_ARG, "hop=%d max_frames=%d", hop, max_frames);
-  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (hop <= 0 || hop > c->fc.fl || max_frames <= 0) return ctx_fail(c, UWSPR_ERR_ARG, "hop=%d max_frames=%d", hop, max_frames);
+  CTXCHK(c, hipStreamSynchronize(c->stream));
   if (!c->ring.open(c->fc.fl, hop, max_frames))
-    return fail(c, UWSPR_ERR_NOMEM, "stream buffers (%d frames, hop %d): %s", max_frames, hop, hipGetErrorString(c->ring.err));
-  if (!c->ring_ev) HIPCHK(c, hipEventCreateWithFlags(&c->ring_ev, hipEventDisableTiming));
+    return ctx_fail(c, UWSPR_ERR_NOMEM, "stream buffers (%d frames, hop %d): %s", max_frames, hop, hipGetErrorString(c->ring.err));
+  if (!c->ring_ev) CTXCHK(c, hipEventCreateWithFlags(&c->ring_ev, hipEventDisableTiming));
   return UWSPR_OK;
 }
 
@@ -1124,17 +1107,17 @@ extern "C" int uwspr_stream_push(uwspr_ctx *c, const float *iq, int nsamples, in
   int rc = ready(c);
   if (rc) return rc;
   stream_ring &r = c->ring;
-  if (!r.is_open()) return fail(c, UWSPR_ERR_ARG, "uwspr_stream_push before uwspr_stream_open");
-  if (nsamples < 0 || (nsamples > 0 && !iq)) return fail(c, UWSPR_ERR_ARG, "iq/nsamples");
-  if (where != UWSPR_HOST && where != UWSPR_DEVICE && where != UWSPR_HOST_ASYNC) return fail(c, UWSPR_ERR_ARG, "where=%d", where);
-  if (r.kind == RING_AUDIO && nsamples > 0) return fail(c, UWSPR_ERR_ARG, "uwspr_stream_push on an audio stream (reset it first)");
+  if (!r.is_open()) return ctx_fail(c, UWSPR_ERR_ARG, "uwspr_stream_push before uwspr_stream_open");
+  if (nsamples < 0 || (nsamples > 0 && !iq)) return ctx_fail(c, UWSPR_ERR_ARG, "iq/nsamples");
+  if (where != UWSPR_HOST && where != UWSPR_DEVICE && where != UWSPR_HOST_ASYNC) return ctx_fail(c, UWSPR_ERR_ARG, "where=%d", where);
+  if (r.kind == RING_AUDIO && nsamples > 0) return ctx_fail(c, UWSPR_ERR_ARG, "uwspr_stream_push on an audio stream (reset it first)");
   if (r.have + (size_t)nsamples > r.cap)
-    return fail(c, UWSPR_ERR_ARG, "stream buffer full (%zu + %d > %zu samples): take frames first", r.have, nsamples, r.cap);
+    return ctx_fail(c, UWSPR_ERR_ARG, "stream buffer full (%zu + %d > %zu samples): take frames first", r.have, nsamples, r.cap);
   if (nsamples > 0) {
     r.kind = RING_IQ;
     bool ok;
     if (where == UWSPR_DEVICE) {   // produced by work on the context's stream
-      HIPCHK(c, hipEventRecord(c->ring_ev, c->stream));
+      CTXCHK(c, hipEventRecord(c->ring_ev, c->stream));
       ok = r.append(iq, (size_t)nsamples, true, c->ring_ev);
     } else {
       ok = r.append(iq, (size_t)nsamples, false);
@@ -1144,7 +1127,7 @@ extern "C" int uwspr_stream_push(uwspr_ctx *c, const float *iq, int nsamples, in
       // UWSPR_HOST_ASYNC leaves that to uwspr_stream_wait_uploads.
       if (ok && where == UWSPR_HOST && r.last_direct) ok = r.wait_uploads();
     }
-    if (!ok) return fail(c, UWSPR_ERR_HIP, "stream upload: %s", hipGetErrorString(r.err));
+    if (!ok) return ctx_fail(c, UWSPR_ERR_HIP, "stream upload: %s", hipGetErrorString(r.err));
   }
   if (nready) *nready = r.ready();
   return UWSPR_OK;
@@ -1173,36 +1156,36 @@ extern "C" int uwspr_stream_push_audio(uwspr_ctx *c, const void *audio, int nsam
   int rc = ready(c);
   if (rc) return rc;
   stream_ring &r = c->ring;
-  if (!r.is_open()) return fail(c, UWSPR_ERR_ARG, "uwspr_stream_push_audio before uwspr_stream_open");
-  if (nsamples < 0 || (nsamples > 0 && !audio)) return fail(c, UWSPR_ERR_ARG, "audio/nsamples");
-  if (format != UWSPR_AUDIO_F32 && format != UWSPR_AUDIO_S16) return fail(c, UWSPR_ERR_ARG, "audio format %d", format);
-  if (where != UWSPR_HOST && where != UWSPR_DEVICE && where != UWSPR_HOST_ASYNC) return fail(c, UWSPR_ERR_ARG, "where=%d", where);
-  if (c->p.fs != 375) return fail(c, UWSPR_ERR_UNSUPPORTED, "front-end is 12000 -> 375 S/s (fs=%d)", c->p.fs);
-  if (nsamples > 0 && r.kind == RING_IQ) return fail(c, UWSPR_ERR_ARG, "uwspr_stream_push_audio on an (I,Q) stream (reset it first)");
+  if (!r.is_open()) return ctx_fail(c, UWSPR_ERR_ARG, "uwspr_stream_push_audio before uwspr_stream_open");
+  if (nsamples < 0 || (nsamples > 0 && !audio)) return ctx_fail(c, UWSPR_ERR_ARG, "audio/nsamples");
+  if (format != UWSPR_AUDIO_F32 && format != UWSPR_AUDIO_S16) return ctx_fail(c, UWSPR_ERR_ARG, "audio format %d", format);
+  if (where != UWSPR_HOST && where != UWSPR_DEVICE && where != UWSPR_HOST_ASYNC) return ctx_fail(c, UWSPR_ERR_ARG, "where=%d", where);
+  if (c->p.fs != 375) return ctx_fail(c, UWSPR_ERR_UNSUPPORTED, "front-end is 12000 -> 375 S/s (fs=%d)", c->p.fs);
+  if (nsamples > 0 && r.kind == RING_IQ) return ctx_fail(c, UWSPR_ERR_ARG, "uwspr_stream_push_audio on an (I,Q) stream (reset it first)");
   // options "frontend", "carrier" / "frontend_hbw", "audio_rate", "blank" / "blank_guard": latched by the stream's first push
   const audio_chain_cfg cfg = {c->opt[UWSPR_OPT_FRONTEND], std::vector<int>(1, c->opt[UWSPR_OPT_CARRIER]), c->opt[UWSPR_OPT_FRONTEND_HBW],
                                c->opt[UWSPR_OPT_AUDIO_RATE], c->opt[UWSPR_OPT_BLANK], c->opt[UWSPR_OPT_BLANK_GUARD]};
   char why[160];
   if (const chain_part d = nsamples > 0 ? r.chain_mismatch(cfg) : CHAIN_OK)
-    return fail(c, UWSPR_ERR_ARG, "%s (reset it first)", chain_refusal(d, cfg, r.chain_latched(), why));
+    return ctx_fail(c, UWSPR_ERR_ARG, "%s (reset it first)", chain_refusal(d, cfg, r.chain_latched(), why));
   const long long nout = r.chain_outputs((size_t)nsamples, cfg);
-  if (nout < 0) return fail(c, UWSPR_ERR_ARG, "option audio_rate = %d: not a supported rate", cfg.rate);
+  if (nout < 0) return ctx_fail(c, UWSPR_ERR_ARG, "option audio_rate = %d: not a supported rate", cfg.rate);
   if (r.have + (size_t)nout > r.cap)
-    return fail(c, UWSPR_ERR_ARG, "stream buffer full (%zu + %lld > %zu samples): take frames first", r.have, nout, r.cap);
+    return ctx_fail(c, UWSPR_ERR_ARG, "stream buffer full (%zu + %lld > %zu samples): take frames first", r.have, nout, r.cap);
   if (nsamples > 0) {
     const bool s16 = format == UWSPR_AUDIO_S16;
     if (const chain_part f = r.chain_latch(cfg, s16))
-      return fail(c, r.err == hipErrorOutOfMemory ? UWSPR_ERR_NOMEM : UWSPR_ERR_HIP, "%s set-up (%d S/s): %s", chain_part_name(f), cfg.rate,
+      return ctx_fail(c, r.err == hipErrorOutOfMemory ? UWSPR_ERR_NOMEM : UWSPR_ERR_HIP, "%s set-up (%d S/s): %s", chain_part_name(f), cfg.rate,
                   hipGetErrorString(r.err));
     bool ok;
     if (where == UWSPR_DEVICE) {   // produced by work on the context's stream
-      HIPCHK(c, hipEventRecord(c->ring_ev, c->stream));
+      CTXCHK(c, hipEventRecord(c->ring_ev, c->stream));
       ok = r.chain_push(audio, (size_t)nsamples, s16, true, c->ring_ev);
     } else {
       ok = r.chain_push(audio, (size_t)nsamples, s16, false);
       if (ok && where == UWSPR_HOST && r.last_direct) ok = r.wait_uploads();   // as uwspr_stream_push
     }
-    if (!ok) return fail(c, UWSPR_ERR_HIP, "audio stream: %s", hipGetErrorString(r.err));
+    if (!ok) return ctx_fail(c, UWSPR_ERR_HIP, "audio stream: %s", hipGetErrorString(r.err));
   }
   if (nready) *nready = r.ready();
   return UWSPR_OK;
@@ -1211,7 +1194,7 @@ extern "C" int uwspr_stream_push_audio(uwspr_ctx *c, const void *audio, int nsam
 extern "C" int uwspr_stream_wait_uploads(uwspr_ctx *c) {
   int rc = ready(c);
   if (rc) return rc;
-  if (c->ring.is_open() && !c->ring.wait_uploads()) return fail(c, UWSPR_ERR_HIP, "stream upload: %s", hipGetErrorString(c->ring.err));
+  if (c->ring.is_open() && !c->ring.wait_uploads()) return ctx_fail(c, UWSPR_ERR_HIP, "stream upload: %s", hipGetErrorString(c->ring.err));
   return UWSPR_OK;
 }
 
@@ -1219,18 +1202,18 @@ extern "C" int uwspr_stream_wait_uploads(uwspr_ctx *c) {
 static int stream_view(uwspr_ctx *c, int nframes, const float **view, long long *first_pos) {
   stream_ring &r = c->ring;
   if (!r.is_open() || nframes <= 0 || nframes > r.ready())
-    return fail(c, UWSPR_ERR_ARG, "uwspr_stream_take(%d): %d frames are complete", nframes, r.is_open() ? r.ready() : 0);
+    return ctx_fail(c, UWSPR_ERR_ARG, "uwspr_stream_take(%d): %d frames are complete", nframes, r.is_open() ? r.ready() : 0);
   // whatever read earlier views has been enqueued on the stream by now (a view is valid until the next take)
-  HIPCHK(c, hipEventRecord(c->ring_ev, c->stream));
+  CTXCHK(c, hipEventRecord(c->ring_ev, c->stream));
   r.reader_done(0, c->ring_ev); r.reader_done(1, c->ring_ev);
-  if (!r.view(nframes, c->stream, view, first_pos, nullptr)) return fail(c, UWSPR_ERR_HIP, "stream view: %s", hipGetErrorString(r.err));
+  if (!r.view(nframes, c->stream, view, first_pos, nullptr)) return ctx_fail(c, UWSPR_ERR_HIP, "stream view: %s", hipGetErrorString(r.err));
   return UWSPR_OK;
 }
 
 extern "C" int uwspr_stream_take_view(uwspr_ctx *c, int nframes, const float **frames, int *stride, long long *first_pos) {
   int rc = ready(c);
   if (rc) return rc;
-  if (!frames) return fail(c, UWSPR_ERR_ARG, "frames");
+  if (!frames) return ctx_fail(c, UWSPR_ERR_ARG, "frames");
   if ((rc = stream_view(c, nframes, frames, first_pos))) return rc;
   if (stride) *stride = c->ring.hop;
   return UWSPR_OK;
@@ -1251,7 +1234,7 @@ extern "C" int uwspr_stream_take(uwspr_ctx *c, int nframes, float *dev_dst, cons
     hipLaunchKernelGGL(k_cut_frames, dim3(44, nf), dim3(256), 0, c->stream, (const float2 *)src, (float2 *)dst,
                        c->ring.hop, c->fc.fl, f0);
   }
-  HIPCHK(c, hipGetLastError());
+  CTXCHK(c, hipGetLastError());
   if (frames) *frames = dst;
   return UWSPR_OK;
 }
@@ -1263,7 +1246,7 @@ extern "C" int uwspr_stream_reset(uwspr_ctx *c, long long pos) {
   // buffers' next writer -- an append after the reset switches buffers, a second reset switches back -- behind
   // everything the stream holds now, as a take does.
   if (c->ring.is_open() && c->ring_ev) {
-    HIPCHK(c, hipEventRecord(c->ring_ev, c->stream));
+    CTXCHK(c, hipEventRecord(c->ring_ev, c->stream));
     c->ring.reader_done(0, c->ring_ev); c->ring.reader_done(1, c->ring_ev);
   }
   c->ring.reset(pos);
@@ -1285,7 +1268,7 @@ extern "C" void uwspr_host_free(void *ptr) { if (ptr) (void)hipHostFree(ptr); }
 extern "C" int uwspr_set_tries(uwspr_ctx *c, int ntries) {
   int rc = ready(c);
   if (rc) return rc;
-  if (ntries < 1 || ntries > UWSPR_NJIG) return fail(c, UWSPR_ERR_ARG, "ntries=%d (1..%d)", ntries, UWSPR_NJIG);
+  if (ntries < 1 || ntries > UWSPR_NJIG) return ctx_fail(c, UWSPR_ERR_ARG, "ntries=%d (1..%d)", ntries, UWSPR_NJIG);
   c->ntries = ntries;
   return UWSPR_OK;
 }
@@ -1294,12 +1277,12 @@ extern "C" int uwspr_demod_resume(uwspr_ctx *c, const float *frames, int B, int 
                                   int max_per_frame, uwspr_demod_out *out) {
   int rc = ready(c);
   if (rc) return rc;
-  if (!need || !out || B <= 0 || max_per_frame <= 0) return fail(c, UWSPR_ERR_ARG, "need/out/B/max_per_frame");
+  if (!need || !out || B <= 0 || max_per_frame <= 0) return ctx_fail(c, UWSPR_ERR_ARG, "need/out/B/max_per_frame");
   if (!c->d_pwin || !c->last_sched_lazy || c->last_sched_B != B || c->last_sched_per_frame != max_per_frame)
-    return fail(c, UWSPR_ERR_ARG, "uwspr_demod_resume follows a schedule call of the same batch made with uwspr_set_tries(< %d)", UWSPR_NJIG);
+    return ctx_fail(c, UWSPR_ERR_ARG, "uwspr_demod_resume follows a schedule call of the same batch made with uwspr_set_tries(< %d)", UWSPR_NJIG);
   // the records of the first pass must be where this call patches them
   if (where == UWSPR_DEVICE ? (out != c->last_sched_out) : (c->last_sched_out != c->d_dout))
-    return fail(c, UWSPR_ERR_ARG, "uwspr_demod_resume: the first pass wrote its records to %s; resume with %s",
+    return ctx_fail(c, UWSPR_ERR_ARG, "uwspr_demod_resume: the first pass wrote its records to %s; resume with %s",
                 c->last_sched_out == c->d_dout ? "the context (a host-record call)" : "the caller's device buffer",
                 c->last_sched_out == c->d_dout ? "where = UWSPR_HOST / UWSPR_DEVICE_FRAMES" : "where = UWSPR_DEVICE and that buffer");
   const float *d;
@@ -1310,15 +1293,15 @@ extern "C" int uwspr_demod_resume(uwspr_ctx *c, const float *frames, int B, int 
   const bool host_io = where != UWSPR_DEVICE;   // UWSPR_DEVICE_FRAMES: frames in HBM, need / out in host memory
   if (host_io) {
     if ((rc = ensure(c, &c->d_need, &c->cap_need, nslots))) return rc;
-    HIPCHK(c, hipMemcpyAsync(c->d_need, need, nslots, hipMemcpyHostToDevice, c->stream));
+    CTXCHK(c, hipMemcpyAsync(c->d_need, need, nslots, hipMemcpyHostToDevice, c->stream));
     dneed = c->d_need;
     dout = c->d_dout;   // the records of the first pass are still there
   }
   launch_sched_fused(c, d, B, nullptr, nullptr, 0, max_per_frame, dout, UWSPR_NJIG, dneed);
-  HIPCHK(c, hipGetLastError());
+  CTXCHK(c, hipGetLastError());
   if (host_io) {
-    HIPCHK(c, hipMemcpyAsync(out, c->d_dout, nslots * sizeof(uwspr_demod_out), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    CTXCHK(c, hipMemcpyAsync(out, c->d_dout, nslots * sizeof(uwspr_demod_out), hipMemcpyDeviceToHost, c->stream));
+    CTXCHK(c, hipStreamSynchronize(c->stream));
   }
   return UWSPR_OK;
 }
@@ -1326,7 +1309,7 @@ extern "C" int uwspr_demod_resume(uwspr_ctx *c, const float *frames, int B, int 
 extern "C" int uwspr_pipeline_slabs(uwspr_ctx *c, int K, void *slabs_device) {
   int rc = ready(c);
   if (rc) return rc;
-  if (slabs_device && (K < 1 || K > c->fc.maxfreqs)) return fail(c, UWSPR_ERR_ARG, "uwspr_pipeline_slabs: K=%d", K);
+  if (slabs_device && (K < 1 || K > c->fc.maxfreqs)) return ctx_fail(c, UWSPR_ERR_ARG, "uwspr_pipeline_slabs: K=%d", K);
   c->next_slab = (uint8_t *)slabs_device; c->next_slab_K = K; c->next_slab_done = false;
   return UWSPR_OK;
 }
@@ -1335,7 +1318,7 @@ extern "C" int uwspr_pack_slabs(uwspr_ctx *c, int B, int K, void *slabs, int whe
   int rc = ready(c);
   if (rc) return rc;
   if (!slabs || K < 1 || K > c->fc.maxfreqs || B <= 0 || B > c->last_B || c->last_per_frame < 1 || !c->cur_dout)
-    return fail(c, UWSPR_ERR_ARG, "uwspr_pack_slabs: needs a preceding uwspr_pipeline_batch of >= %d frames", B);
+    return ctx_fail(c, UWSPR_ERR_ARG, "uwspr_pack_slabs: needs a preceding uwspr_pipeline_batch of >= %d frames", B);
   const size_t bytes = (size_t)B * (16 + (size_t)K * 48 + 16);
   uint8_t *dst = (uint8_t *)slabs;
   if (where == UWSPR_HOST) {
@@ -1345,10 +1328,10 @@ extern "C" int uwspr_pack_slabs(uwspr_ctx *c, int B, int K, void *slabs, int whe
     dst = c->d_slab;
   }
   launch_pack_slabs(c, c->cur_cands, c->cur_npk, c->cur_dout, c->last_per_frame, K, dst, B);
-  HIPCHK(c, hipGetLastError());
+  CTXCHK(c, hipGetLastError());
   if (where == UWSPR_HOST) {
-    HIPCHK(c, hipMemcpyAsync(slabs, c->d_slab, bytes, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    CTXCHK(c, hipMemcpyAsync(slabs, c->d_slab, bytes, hipMemcpyDeviceToHost, c->stream));
+    CTXCHK(c, hipStreamSynchronize(c->stream));
   }
   return UWSPR_OK;
 }
@@ -1357,8 +1340,8 @@ extern "C" int uwspr_pack_slabs(uwspr_ctx *c, int B, int K, void *slabs, int whe
 // diagnostics (not part of the ABI header): phase boundary times of the last fused schedule launch
 extern "C" int uwspr_debug_sched_stamps(uwspr_ctx *c, unsigned long long *out, int nslots) {
   if (!c || !out || !c->d_sched_stamps || (size_t)nslots * 64 > c->cap_sched_stamps) return UWSPR_ERR_ARG;
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  HIPCHK(c, hipMemcpy(out, c->d_sched_stamps, (size_t)nslots * 64 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+  CTXCHK(c, hipStreamSynchronize(c->stream));
+  CTXCHK(c, hipMemcpy(out, c->d_sched_stamps, (size_t)nslots * 64 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
   return UWSPR_OK;
 }
 
@@ -1374,7 +1357,7 @@ extern "C" int uwspr_prof_intervals(uwspr_ctx *c, int kind, void *epoch_event, d
   int rc = ready(c);
   if (rc) return rc;
   if (!epoch_event || !start_ms || !stop_ms || !n || cap < 0) return UWSPR_ERR_ARG;
-  HIPCHK(c, hipStreamSynchronize(c->stream));
+  CTXCHK(c, hipStreamSynchronize(c->stream));
   int k = 0;
   for (auto &e : c->prof_events) {
     if (e.kind != kind) continue;
@@ -1394,7 +1377,7 @@ extern "C" int uwspr_prof_read(uwspr_ctx *c, uwspr_prof *o) {
   if (rc) return rc;
   if (!o) return UWSPR_ERR_ARG;
   memset(o, 0, sizeof(*o));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
+  CTXCHK(c, hipStreamSynchronize(c->stream));
   for (auto &e : c->prof_events) {
     float ms = 0.0f;
     if (hipEventElapsedTime(&ms, e.a, e.b) == hipSuccess) {
@@ -1435,12 +1418,12 @@ extern "C" int uwspr_debug_frontend_launch(uwspr_ctx *c, const void *audio_dev, 
   if (rc) return rc;
   if (!audio_dev || !out_dev || nin < 1 || nout < 1 || nch < 1 || nch > UWSPR_PIPE_MAX_CHANNELS ||
       (format != UWSPR_AUDIO_F32 && format != UWSPR_AUDIO_S16) || (nch > 1 && plane < nout))
-    return fail(c, UWSPR_ERR_ARG, "uwspr_debug_frontend_launch: audio/out/format %d/nin %d/nout %d/nch %d/plane %lld", format, nin, nout, nch, plane);
+    return ctx_fail(c, UWSPR_ERR_ARG, "uwspr_debug_frontend_launch: audio/out/format %d/nin %d/nout %d/nch %d/plane %lld", format, nin, nout, nch, plane);
   if ((rc = frontend_taps(c))) return rc;
   launch_frontend_stream(c->stream, audio_dev, format == UWSPR_AUDIO_S16, nin, in0, c->d_fe_taps, c->fe_J, c->fe_dcols, out_dev,
                          nout, m_first, nch, plane);
-  HIPCHK(c, hipGetLastError());
-  HIPCHK(c, hipStreamSynchronize(c->stream));
+  CTXCHK(c, hipGetLastError());
+  CTXCHK(c, hipStreamSynchronize(c->stream));
   return UWSPR_OK;
 }
 
@@ -1457,27 +1440,27 @@ extern "C" int uwspr_debug_frontend_carrier_launch(uwspr_ctx *c, const void *aud
   const long long lim = 1LL << 46;
   if (!audio_dev || !out_dev || !carriers || nin < 1 || nout < 1 || nch < 1 || NC < 1 || (long long)nch * NC > UWSPR_PIPE_MAX_CHANNELS ||
       (format != UWSPR_AUDIO_F32 && format != UWSPR_AUDIO_S16) || plane < nout || in0 < -lim || in0 > lim || m_first < -lim || m_first > lim)
-    return fail(c, UWSPR_ERR_ARG, "uwspr_debug_frontend_carrier_launch: audio/out/carriers/format %d/nin %d/in0 %lld/nout %d/m_first %lld/nch %d/NC %d/plane %lld",
+    return ctx_fail(c, UWSPR_ERR_ARG, "uwspr_debug_frontend_carrier_launch: audio/out/carriers/format %d/nin %d/in0 %lld/nout %d/m_first %lld/nch %d/NC %d/plane %lld",
                 format, nin, in0, nout, m_first, nch, NC, plane);
   const int mode = c->opt[UWSPR_OPT_FRONTEND], hb = c->opt[UWSPR_OPT_FRONTEND_HBW];
   const std::vector<int> car(carriers, carriers + NC);
   for (int fc : car)
-    if (!frontend_carrier_ok(mode, fc, hb)) return fail(c, UWSPR_ERR_ARG, "uwspr_debug_frontend_carrier_launch: carrier %d Hz, half-bandwidth %d Hz", fc, hb);
+    if (!frontend_carrier_ok(mode, fc, hb)) return ctx_fail(c, UWSPR_ERR_ARG, "uwspr_debug_frontend_carrier_launch: carrier %d Hz, half-bandwidth %d Hz", fc, hb);
   if (!c->d_dbg_taps || c->dbg_mode != mode || c->dbg_hb != hb || c->dbg_car != car) {
     std::vector<float> all;
     int J = 0, dcols = 0;
-    if (frontend_carrier_tables(mode, car, hb, all, &J, &dcols)) return fail(c, UWSPR_ERR_ARG, "front-end mode %d, %d carriers", mode, NC);
-    if (frontend_prepare()) return fail(c, UWSPR_ERR_HIP, "front-end kernel: %zu bytes of LDS refused", (size_t)160 * 1024);
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (c->d_dbg_taps) { HIPCHK(c, hipFree(c->d_dbg_taps)); c->d_dbg_taps = nullptr; }
-    HIPCHK(c, hipMalloc((void **)&c->d_dbg_taps, all.size() * sizeof(float)));
-    HIPCHK(c, hipMemcpy(c->d_dbg_taps, all.data(), all.size() * sizeof(float), hipMemcpyHostToDevice));
+    if (frontend_carrier_tables(mode, car, hb, all, &J, &dcols)) return ctx_fail(c, UWSPR_ERR_ARG, "front-end mode %d, %d carriers", mode, NC);
+    if (frontend_prepare()) return ctx_fail(c, UWSPR_ERR_HIP, "front-end kernel: %zu bytes of LDS refused", (size_t)160 * 1024);
+    CTXCHK(c, hipStreamSynchronize(c->stream));
+    if (c->d_dbg_taps) { CTXCHK(c, hipFree(c->d_dbg_taps)); c->d_dbg_taps = nullptr; }
+    CTXCHK(c, hipMalloc((void **)&c->d_dbg_taps, all.size() * sizeof(float)));
+    CTXCHK(c, hipMemcpy(c->d_dbg_taps, all.data(), all.size() * sizeof(float), hipMemcpyHostToDevice));
     c->dbg_mode = mode; c->dbg_hb = hb; c->dbg_car = car; c->dbg_J = J; c->dbg_dcols = dcols;
   }
   launch_frontend_carrier(c->stream, audio_dev, format == UWSPR_AUDIO_S16, nin, in0, c->d_dbg_taps, c->dbg_J, c->dbg_dcols, out_dev,
                           nout, m_first, nch, NC, plane);
-  HIPCHK(c, hipGetLastError());
-  HIPCHK(c, hipStreamSynchronize(c->stream));
+  CTXCHK(c, hipGetLastError());
+  CTXCHK(c, hipStreamSynchronize(c->stream));
   return UWSPR_OK;
 }
 
@@ -1499,7 +1482,7 @@ extern "C" int uwspr_debug_resample_launch(uwspr_ctx *c, const void *audio_dev, 
   if (!audio_dev || !out_dev || nin < 1 || nout < 1 || nch < 1 || nch > UWSPR_PIPE_MAX_CHANNELS || in0 < -(1LL << 46) ||
       in0 > (1LL << 46) || j_first < 0 || j_first > (1LL << 41) || nout > (1LL << 22) ||
       (format != UWSPR_AUDIO_F32 && format != UWSPR_AUDIO_S16))
-    return fail(c, UWSPR_ERR_ARG, "uwspr_debug_resample_launch: audio/out/format %d/nin %lld/in0 %lld/nout %lld/j_first %lld/nch %d", format,
+    return ctx_fail(c, UWSPR_ERR_ARG, "uwspr_debug_resample_launch: audio/out/format %d/nin %lld/in0 %lld/nout %lld/j_first %lld/nch %d", format,
                 nin, in0, nout, j_first, nch);
   return rs_debug_launch(c, audio_dev, format == UWSPR_AUDIO_S16, nin, in0, nch, rate, out_dev, nout, j_first);
 }
@@ -1522,7 +1505,7 @@ extern "C" int uwspr_debug_blank_launch(uwspr_ctx *c, const void *audio_dev, int
       y_first > lim || (level_n > 0 && (level_first < blk0 || level_first + level_n > blk0 + nlev)) ||
       (nout > 0 && (!out_dev || !nz_dev)) || blank < 4 || blank > 1024 || guard < 0 || guard > 64 ||
       (format != UWSPR_AUDIO_F32 && format != UWSPR_AUDIO_S16))
-    return fail(c, UWSPR_ERR_ARG, "uwspr_debug_blank_launch: audio/lev/out/nz/format %d/nin %lld/in0 %lld/nch %d/nlev %lld/blk0 %lld/"
+    return ctx_fail(c, UWSPR_ERR_ARG, "uwspr_debug_blank_launch: audio/lev/out/nz/format %d/nin %lld/in0 %lld/nch %d/nlev %lld/blk0 %lld/"
                 "level %lld+%lld/blank %d/guard %d/nout %lld/y_first %lld", format, nin, in0, nch, nlev, blk0, level_first, level_n,
                 blank, guard, nout, y_first);
   return bk_debug_launch(c, audio_dev, format == UWSPR_AUDIO_S16, nin, in0, nch, lev_dev, nlev, blk0, level_first, level_n, blank,
@@ -1550,25 +1533,10 @@ extern "C" int uwspr_debug_sweep_outputs(uwspr_ctx *c, int first, int n, float *
   if (!c || first < 0 || n <= 0) return UWSPR_ERR_ARG;
   if (sync && (!c->d_sync || (size_t)first + n > c->cap_sync)) return UWSPR_ERR_ARG;
   if (symbols && (!c->d_sym || ((size_t)first + n) * UWSPR_NSYM > c->cap_sym)) return UWSPR_ERR_ARG;
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  if (sync) HIPCHK(c, hipMemcpy(sync, c->d_sync + first, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
-  if (symbols) HIPCHK(c, hipMemcpy(symbols, c->d_sym + (size_t)first * UWSPR_NSYM, (size_t)n * UWSPR_NSYM, hipMemcpyDeviceToHost));
+  CTXCHK(c, hipStreamSynchronize(c->stream));
+  if (sync) CTXCHK(c, hipMemcpy(sync, c->d_sync + first, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
+  if (symbols) CTXCHK(c, hipMemcpy(symbols, c->d_sym + (size_t)first * UWSPR_NSYM, (size_t)n * UWSPR_NSYM, hipMemcpyDeviceToHost));
   return UWSPR_OK;
-}
-
-// The context's device and [p, p + bytes) inside one device allocation of it (as the transmit calls check their pointers):
-// pageable host memory handed over as device memory is refused here, before any launch.
-static bool dbg_device_range(uwspr_ctx *c, const void *p, size_t bytes) {
-  hipPointerAttribute_t a;
-  memset(&a, 0, sizeof(a));
-  const hipError_t e = hipPointerGetAttributes(&a, p);
-  (void)hipGetLastError();   // a refused query leaves no error behind for the calls that follow
-  if (e != hipSuccess || a.type != hipMemoryTypeDevice || a.device != c->device) return false;
-  hipDeviceptr_t base = nullptr;
-  size_t size = 0;
-  if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)p) != hipSuccess) { (void)hipGetLastError(); return false; }
-  const char *b = (const char *)base, *q = (const char *)p;
-  return q >= b && bytes <= size && (size_t)(q - b) <= size - bytes;
 }
 
 // diagnostics (not part of the ABI header): K2 and K3 on a GIVEN spectrogram.  ps_band is [B][n][band_w] binary32, the
@@ -1580,18 +1548,18 @@ extern "C" int uwspr_debug_fdr_from_ps(uwspr_ctx *c, const float *ps_band, int B
                                        int32_t *npk) {
   int rc = ready(c);
   if (rc) return rc;
-  if (!ps_band || B <= 0) return fail(c, UWSPR_ERR_ARG, "uwspr_debug_fdr_from_ps: ps_band=%p B=%d", (const void *)ps_band, B);
-  if (where != UWSPR_HOST && where != UWSPR_DEVICE) return fail(c, UWSPR_ERR_ARG, "where=%d", where);
+  if (!ps_band || B <= 0) return ctx_fail(c, UWSPR_ERR_ARG, "uwspr_debug_fdr_from_ps: ps_band=%p B=%d", (const void *)ps_band, B);
+  if (where != UWSPR_HOST && where != UWSPR_DEVICE) return ctx_fail(c, UWSPR_ERR_ARG, "where=%d", where);
   const fdr_consts &f = c->fc;
   const size_t bytes = (size_t)B * f.n * f.band_w * sizeof(float);
   if (where == UWSPR_DEVICE &&
-      (!dbg_device_range(c, ps_band, bytes) || (cands && !dbg_device_range(c, cands, (size_t)B * f.maxfreqs * sizeof(uwspr_candidate))) ||
-       (npk && !dbg_device_range(c, npk, (size_t)B * sizeof(int32_t)))))
-    return fail(c, UWSPR_ERR_ARG, "uwspr_debug_fdr_from_ps: ps_band, cands or npk is not device memory of device %d holding B=%d frames",
+      (!ctx_device_range(c, ps_band, bytes) || (cands && !ctx_device_range(c, cands, (size_t)B * f.maxfreqs * sizeof(uwspr_candidate))) ||
+       (npk && !ctx_device_range(c, npk, (size_t)B * sizeof(int32_t)))))
+    return ctx_fail(c, UWSPR_ERR_ARG, "uwspr_debug_fdr_from_ps: ps_band, cands or npk is not device memory of device %d holding B=%d frames",
                 c->device, B);
   if ((rc = run_fdr(c, nullptr, B, nullptr, nullptr, ps_band, where))) return rc;
   if ((rc = copy_out(c, cands, c->d_cands, (size_t)B * f.maxfreqs * sizeof(uwspr_candidate), where))) return rc;
   if ((rc = copy_out(c, npk, c->d_npk, (size_t)B * sizeof(int32_t), where))) return rc;
-  if (where != UWSPR_DEVICE) HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (where != UWSPR_DEVICE) CTXCHK(c, hipStreamSynchronize(c->stream));
   return UWSPR_OK;
 }
