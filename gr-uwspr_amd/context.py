@@ -10,9 +10,48 @@ import numpy as np
 
 from . import native as N
 
+AUDIO_RATE = 12000
+BLANK_BLOCK = 4096   # UWSPR_BLANK_BLOCK: samples per block of the blanker's level
+FRONTEND_GRC, FRONTEND_COMPACT = 0, 1
+
 
 def _is_torch(x):
     return hasattr(x, "data_ptr") and hasattr(x, "is_cuda")
+
+
+def _ptr(x):
+    """the data pointer of a numpy array or a torch tensor"""
+    return C.c_void_p(x.data_ptr() if _is_torch(x) else x.ctypes.data)
+
+
+def _empty(like, shape, dtype):
+    """an uninitialised array of a numpy dtype where `like` lives: numpy, or a tensor on the tensor's device"""
+    if _is_torch(like):
+        import torch
+        return torch.empty(tuple(shape), dtype=getattr(torch, np.dtype(dtype).name), device=like.device)
+    return np.empty(tuple(shape), dtype)
+
+
+def _audio_format(x):
+    """AUDIO_F32 / AUDIO_S16 for a float32 / int16 numpy array or torch tensor, None for any other type"""
+    if _is_torch(x):
+        import torch
+        return {torch.float32: N.AUDIO_F32, torch.int16: N.AUDIO_S16}.get(x.dtype)
+    return {np.dtype(np.float32): N.AUDIO_F32, np.dtype(np.int16): N.AUDIO_S16}.get(x.dtype)
+
+
+def _audio_block(x, who):
+    """`who`'s audio: [n] or [n, C], float32 or int16, a numpy array (made contiguous) or a contiguous torch CUDA tensor
+    -> (x, format, C)"""
+    if _is_torch(x):
+        if _audio_format(x) is None or x.dim() not in (1, 2) or not x.is_cuda or not x.is_contiguous() or x.shape[0] < 1:
+            raise TypeError("%s: a contiguous [n] or [n, C] float32 or int16 CUDA tensor, not %s %s" % (who, x.dtype, tuple(x.shape)))
+    else:
+        x = np.asarray(x)
+        if x.ndim not in (1, 2) or _audio_format(x) is None or x.shape[0] < 1:
+            raise TypeError("%s: a [n] or [n, C] float32 or int16 array, not %s %s" % (who, x.dtype, x.shape))
+        x = np.ascontiguousarray(x)
+    return x, _audio_format(x), 1 if len(x.shape) == 1 else x.shape[1]
 
 
 def _audio_array(x):
@@ -21,6 +60,45 @@ def _audio_array(x):
     if a.ndim != 1 or a.dtype not in (np.float32, np.int16):
         raise TypeError("audio: a 1-D float32 or int16 array, not %s %s" % (a.dtype, a.shape))
     return np.ascontiguousarray(a)
+
+
+def _launch_tensors(who, audio, out=None):
+    """what the debug_*_launch methods check of their tensors (the library sees pointers only) -> audio's format"""
+    import torch
+    fmt = _audio_format(audio)
+    if fmt is None or not audio.is_cuda or not audio.is_contiguous():
+        raise TypeError("%s: a contiguous float32 or int16 CUDA tensor, not %s" % (who, audio.dtype))
+    if out is not None and (out.dtype != torch.float32 or not out.is_cuda or not out.is_contiguous()):
+        raise TypeError("%s: out is a contiguous float32 CUDA tensor, not %s" % (who, out.dtype))
+    return fmt
+
+
+def _tx_call(L, kind, h, sig, mot, car, fad, imp, *rest):
+    """One uwspr_tx_<kind>* call, kind "baseband" or "render", routed by what the transmissions carry (the arrays of
+    tx_motions, tx_carriers, tx_fades, tx_impulses, or None): _medium with any fading or impulses, else _at with any
+    carrier, else _moving with any motion, else the plain entry.  A route's arrays follow `signals`; render_medium's
+    impulses follow the channels (rest[1]).  `rest`: the arguments every route takes behind those."""
+    sp = C.c_void_p(C.addressof(sig)) if len(sig) else None
+    mp = None if mot is None else C.c_void_p(C.addressof(mot))
+    cp = None if car is None else C.c_void_p(car.ctypes.data)
+    if fad is not None or imp is not None:
+        fp = None if fad is None else C.c_void_p(C.addressof(fad))
+        if kind == "render":
+            rest = rest[:2] + (None if imp is None else C.c_void_p(C.addressof(imp)),) + rest[2:]
+        return getattr(L, "uwspr_tx_%s_medium" % kind)(h, sp, mp, cp, fp, *rest)
+    if car is not None:
+        return getattr(L, "uwspr_tx_%s_at" % kind)(h, sp, mp, cp, *rest)
+    if mot is not None:
+        return getattr(L, "uwspr_tx_%s_moving" % kind)(h, sp, mp, *rest)
+    return getattr(L, "uwspr_tx_" + kind)(h, sp, *rest)
+
+
+def _cand_lists(cands, npk):
+    """the (cands, npk) buffers of Context._cand_buffers after the call -> per frame, its candidate records"""
+    if _is_torch(cands):
+        cands = np.frombuffer(cands.cpu().numpy().tobytes(), N.CAND_DTYPE).reshape(npk.numel(), -1)
+        npk = npk.cpu().numpy()
+    return [cands[b, :npk[b]].copy() for b in range(len(npk))]
 
 
 class FrameView:
@@ -62,7 +140,6 @@ class Context:
         self.info = N.Info()
         self._chk(self.L.uwspr_get_info(self.h, C.byref(self.info)))
         self.fl, self.maxfreqs = fl, maxfreqs
-        self._keep = []
         self._stream_ptr = None
         for k, v in (options or {}).items():
             self.set_option(k, v)
@@ -101,14 +178,19 @@ class Context:
             assert frames.is_cuda and frames.is_contiguous() and frames.dtype.is_floating_point
             assert frames.element_size() == 4
             B = frames.numel() // (2 * self.fl)
-            if self._stream_ptr is None:
-                # the library runs on the context's own stream: whatever torch queued on
-                # its current stream to produce `frames` must have finished first
-                import torch
-                torch.cuda.current_stream(frames.device).synchronize()
+            if self._stream_ptr is None:   # (asked here as well: with a caller's stream the timed calls pay for nothing more)
+                self._wait_torch(frames.device)
             return C.c_void_p(frames.data_ptr()), B, N.DEVICE, frames
         a = np.ascontiguousarray(frames, dtype=np.float32).reshape(-1, self.fl, 2)
         return C.c_void_p(a.ctypes.data), a.shape[0], N.HOST, a
+
+    def _cand_buffers(self, B, device=None):
+        """(cands, npk) for B frames' candidates: numpy arrays, or for a torch device byte / int32 tensors there"""
+        if device is None:
+            return np.zeros((B, self.maxfreqs), N.CAND_DTYPE), np.zeros(B, np.int32)
+        import torch
+        return (torch.empty(B * self.maxfreqs * 48, dtype=torch.uint8, device=device),
+                torch.empty(B, dtype=torch.int32, device=device))
 
     def set_stream(self, stream_ptr):
         """Run on a caller's hipStream_t (e.g. torch.cuda.Stream().cuda_stream); the caller
@@ -119,16 +201,29 @@ class Context:
     def synchronize(self):
         self._chk(self.L.uwspr_synchronize(self.h))
 
+    # -- the door between torch's stream and the context's (DESIGN.md lists each method's variant) ----
+    def _wait_torch(self, device, always=False):
+        """Before a call on device tensors: the library runs on the context's own stream, so whatever torch queued on its
+        current stream of `device` (None: the current device) to produce them must have finished first -- unless the
+        caller set a stream and so owns the ordering, and the call site does not say `always`."""
+        if self._stream_ptr is None or always:
+            import torch
+            torch.cuda.current_stream(device).synchronize()
+
+    def _wait_self(self, always):
+        """After a call that left results on the device: synchronize the context -- always (the method reads them on the
+        host next), or (always=False) only when the context runs on its own stream, a caller's stream being the
+        caller's to wait for."""
+        if self._stream_ptr is None or always:
+            self.synchronize()
+
     def debug_snr_db(self, x):
         """diagnostics: 10 * log10f(x) as K2 computes a candidate's `snr` (FDR_impl.cc:303); x, result: float32 CUDA tensors"""
         import torch
         out = torch.empty_like(x)
-        f = self.L.uwspr_debug_snr_db
-        f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong]
-        f.restype = C.c_int
-        torch.cuda.current_stream().synchronize()
-        self._chk(f(self.h, C.c_void_p(x.data_ptr()), C.c_void_p(out.data_ptr()), x.numel()))
-        self.synchronize()
+        self._wait_torch(None, always=True)
+        self._chk(self.L.uwspr_debug_snr_db(self.h, C.c_void_p(x.data_ptr()), C.c_void_p(out.data_ptr()), x.numel()))
+        self._wait_self(always=True)
         return out
 
     LAUNCH_FORMS = ("flat_t1", "flat_t2", "flat_t4", "flat_fast", "fold_wave", "fold_lanes",
@@ -142,11 +237,8 @@ class Context:
         {name: count}: the flat kernel by tones per lane, the fold by form (and, of those, the launches with soft
         symbols and with the stage winner's magnitudes), the grid kernel by lags per block and by wavefronts per
         workgroup, and the grid calls that fell back to the flat kernel."""
-        f = self.L.uwspr_debug_launch_forms
-        f.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
-        f.restype = C.c_int
         out = np.zeros(len(self.LAUNCH_FORMS), np.int64)
-        n = f(self.h, C.c_void_p(out.ctypes.data), out.size)
+        n = self.L.uwspr_debug_launch_forms(self.h, C.c_void_p(out.ctypes.data), out.size)
         if n != out.size:
             raise N.UwsprError(n if n < 0 else -1, "uwspr_debug_launch_forms: %d slots, this binding names %d" % (n, out.size))
         return {k: int(v) for k, v in zip(self.LAUNCH_FORMS, out)}
@@ -154,22 +246,16 @@ class Context:
     # -- front-end ---------------------------------------------------------
     def frontend(self, audio):
         """12 kS/s real audio [B, nin] -> frames [B, fl, 2] at 375 S/s (uwspr_frontend_batch)."""
-        if _is_torch(audio):
-            import torch
-            B, nin = audio.shape
-            out = torch.empty((B, self.fl, 2), dtype=torch.float32, device=audio.device)
-            if self._stream_ptr is None:
-                torch.cuda.current_stream(audio.device).synchronize()
-            self._chk(self.L.uwspr_frontend_batch(self.h, C.c_void_p(audio.data_ptr()), B, nin, N.DEVICE,
-                                                  C.c_void_p(out.data_ptr())))
-            if self._stream_ptr is None:
-                self.synchronize()
-            return out
-        a = np.ascontiguousarray(audio, dtype=np.float32)
-        a = a.reshape(1, -1) if a.ndim == 1 else a
-        out = np.empty((a.shape[0], self.fl, 2), np.float32)
-        self._chk(self.L.uwspr_frontend_batch(self.h, C.c_void_p(a.ctypes.data), a.shape[0], a.shape[1],
-                                              N.HOST, C.c_void_p(out.ctypes.data)))
+        dev = _is_torch(audio)
+        a = audio if dev else np.ascontiguousarray(audio, dtype=np.float32)
+        a = a.reshape(1, -1) if not dev and a.ndim == 1 else a
+        B, nin = a.shape
+        out = _empty(a, (B, self.fl, 2), np.float32)
+        if dev:
+            self._wait_torch(a.device)
+        self._chk(self.L.uwspr_frontend_batch(self.h, _ptr(a), B, nin, N.DEVICE if dev else N.HOST, _ptr(out)))
+        if dev:
+            self._wait_self(always=False)
         return out
 
     def debug_frontend_launch(self, audio, in0, out, m_first, nch=1, plane=None, nout=None, nin=None):
@@ -178,12 +264,7 @@ class Context:
         nch interleaved channels (nin defaults to all of it); out: float32, receives outputs [m_first, m_first + nout)
         of channel b at pair b * plane (nout defaults to what `out` holds per channel, plane to nout).  The tensors
         must hold what the launch reads and writes: that is checked here, the library sees pointers only."""
-        import torch
-        fmt = {torch.float32: N.AUDIO_F32, torch.int16: N.AUDIO_S16}.get(audio.dtype)
-        if fmt is None or not audio.is_cuda or not audio.is_contiguous():
-            raise TypeError("debug_frontend_launch: a contiguous float32 or int16 CUDA tensor, not %s" % audio.dtype)
-        if out.dtype != torch.float32 or not out.is_cuda or not out.is_contiguous():
-            raise TypeError("debug_frontend_launch: out is a contiguous float32 CUDA tensor, not %s" % out.dtype)
+        fmt = _launch_tensors("debug_frontend_launch", audio, out)
         nch = int(nch)
         if nin is None:
             nin = audio.numel() // max(nch, 1)
@@ -196,14 +277,9 @@ class Context:
         nin, nout, plane = int(nin), int(nout), int(plane)
         if nin * nch > audio.numel() or 2 * ((nch - 1) * plane + nout) > out.numel():
             raise ValueError("debug_frontend_launch: nin %d x nch %d / nout %d, plane %d do not fit the tensors" % (nin, nch, nout, plane))
-        f = self.L.uwspr_debug_frontend_launch
-        f.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_longlong, C.c_int, C.c_void_p, C.c_int,
-                      C.c_longlong, C.c_longlong]
-        f.restype = C.c_int
-        if self._stream_ptr is None:
-            torch.cuda.current_stream(audio.device).synchronize()
-        self._chk(f(self.h, C.c_void_p(audio.data_ptr()), fmt, nin, int(in0), nch, C.c_void_p(out.data_ptr()), nout,
-                    int(m_first), plane))
+        self._wait_torch(audio.device)
+        self._chk(self.L.uwspr_debug_frontend_launch(self.h, C.c_void_p(audio.data_ptr()), fmt, nin, int(in0), nch,
+                                                     C.c_void_p(out.data_ptr()), nout, int(m_first), plane))
 
     def debug_frontend_carrier_launch(self, audio, in0, out, m_first, carriers, nch=1, plane=None, nout=None, nin=None):
         """diagnostics: ONE launch of the carrier form of K0 (uwspr_debug_frontend_carrier_launch; what a stream's audio
@@ -211,12 +287,7 @@ class Context:
         "frontend_hbw".  audio: float32 or int16, nin frames [in0, in0 + nin) of nch interleaved channels; carriers: Hz;
         out: float32, receives outputs [m_first, m_first + nout) of plane c * len(carriers) + k at pair plane_index *
         plane.  The tensors must hold what the launch reads and writes: that is checked here."""
-        import torch
-        fmt = {torch.float32: N.AUDIO_F32, torch.int16: N.AUDIO_S16}.get(audio.dtype)
-        if fmt is None or not audio.is_cuda or not audio.is_contiguous():
-            raise TypeError("debug_frontend_carrier_launch: a contiguous float32 or int16 CUDA tensor, not %s" % audio.dtype)
-        if out.dtype != torch.float32 or not out.is_cuda or not out.is_contiguous():
-            raise TypeError("debug_frontend_carrier_launch: out is a contiguous float32 CUDA tensor, not %s" % out.dtype)
+        fmt = _launch_tensors("debug_frontend_carrier_launch", audio, out)
         car = np.ascontiguousarray(carriers, np.int32).reshape(-1)
         nch, NC = int(nch), int(car.size)
         if nch < 1 or NC < 1:
@@ -234,14 +305,10 @@ class Context:
         if nin < 1 or nout < 1 or plane < nout or nin * nch > audio.numel() or 2 * ((npl - 1) * plane + nout) > out.numel():
             raise ValueError("debug_frontend_carrier_launch: nin %d x nch %d / nout %d, plane %d x %d do not fit the tensors"
                              % (nin, nch, nout, plane, npl))
-        f = self.L.uwspr_debug_frontend_carrier_launch
-        f.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_longlong, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
-                      C.c_int, C.c_longlong, C.c_longlong]
-        f.restype = C.c_int
-        if self._stream_ptr is None:
-            torch.cuda.current_stream(audio.device).synchronize()
-        self._chk(f(self.h, C.c_void_p(audio.data_ptr()), fmt, nin, int(in0), nch, NC, C.c_void_p(car.ctypes.data),
-                    C.c_void_p(out.data_ptr()), nout, int(m_first), plane))
+        self._wait_torch(audio.device)
+        self._chk(self.L.uwspr_debug_frontend_carrier_launch(self.h, C.c_void_p(audio.data_ptr()), fmt, nin, int(in0), nch, NC,
+                                                             C.c_void_p(car.ctypes.data), C.c_void_p(out.data_ptr()), nout,
+                                                             int(m_first), plane))
 
     # -- resampler (K11) ----------------------------------------------------
     def resample(self, audio, rate, nout=None):
@@ -249,34 +316,17 @@ class Context:
         int16 array (zero outside it) -> [nout] or [nout, C]; nout defaults to ceil(n * 12000 / rate), the outputs
         whose audio time lies inside the record.  A contiguous torch CUDA tensor of those shapes and types stays on the
         device (-> a CUDA tensor)."""
-        if _is_torch(audio):
-            import torch
-            fmt = {torch.float32: N.AUDIO_F32, torch.int16: N.AUDIO_S16}.get(audio.dtype)
-            if fmt is None or audio.dim() not in (1, 2) or not audio.is_cuda or not audio.is_contiguous() or audio.shape[0] < 1:
-                raise TypeError("resample: a contiguous [n] or [n, C] float32 or int16 CUDA tensor, not %s %s" %
-                                (audio.dtype, tuple(audio.shape)))
-            nch = 1 if audio.dim() == 1 else audio.shape[1]
-            if nout is None:
-                nout = -(-audio.shape[0] * AUDIO_RATE // int(rate))
-            out = torch.empty((int(nout),) + tuple(audio.shape[1:]), dtype=torch.float32, device=audio.device)
-            if self._stream_ptr is None:
-                torch.cuda.current_stream(audio.device).synchronize()
-            self._chk(self.L.uwspr_resample_batch(self.h, C.c_void_p(audio.data_ptr()), audio.shape[0], nch, fmt, int(rate),
-                                                  N.DEVICE, C.c_void_p(out.data_ptr()), int(nout)))
-            if self._stream_ptr is None:
-                self.synchronize()
-            return out
-        a = np.asarray(audio)
-        if a.ndim not in (1, 2) or a.dtype not in (np.float32, np.int16) or a.shape[0] < 1:
-            raise TypeError("resample: a [n] or [n, C] float32 or int16 array, not %s %s" % (a.dtype, a.shape))
-        a = np.ascontiguousarray(a)
-        nch = 1 if a.ndim == 1 else a.shape[1]
+        a, fmt, nch = _audio_block(audio, "resample")
+        dev = _is_torch(a)
         if nout is None:
             nout = -(-a.shape[0] * AUDIO_RATE // int(rate))
-        out = np.empty((int(nout),) + a.shape[1:], np.float32)
-        self._chk(self.L.uwspr_resample_batch(self.h, C.c_void_p(a.ctypes.data), a.shape[0], nch,
-                                              N.AUDIO_S16 if a.dtype == np.int16 else N.AUDIO_F32, int(rate), N.HOST,
-                                              C.c_void_p(out.ctypes.data), int(nout)))
+        out = _empty(a, (int(nout),) + tuple(a.shape[1:]), np.float32)
+        if dev:
+            self._wait_torch(a.device)
+        self._chk(self.L.uwspr_resample_batch(self.h, _ptr(a), a.shape[0], nch, fmt, int(rate), N.DEVICE if dev else N.HOST,
+                                              _ptr(out), int(nout)))
+        if dev:
+            self._wait_self(always=False)
         return out
 
     def debug_resample_launch(self, audio, rate, in0, out, j_first, nch=1, nin=None, nout=None):
@@ -284,25 +334,15 @@ class Context:
         frames [in0, in0 + nin) of nch interleaved samples (nin defaults to all of it); out: float32, receives outputs
         [j_first, j_first + nout) as [nout, nch] (nout defaults to what it holds).  The input format picks the kernel's
         instantiation.  The tensors must hold what the launch reads and writes: checked here."""
-        import torch
-        fmt = {torch.float32: N.AUDIO_F32, torch.int16: N.AUDIO_S16}.get(audio.dtype)
-        if fmt is None or not audio.is_cuda or not audio.is_contiguous():
-            raise TypeError("debug_resample_launch: a contiguous float32 or int16 CUDA tensor, not %s" % audio.dtype)
-        if out.dtype != torch.float32 or not out.is_cuda or not out.is_contiguous():
-            raise TypeError("debug_resample_launch: out is a contiguous float32 CUDA tensor, not %s" % out.dtype)
+        fmt = _launch_tensors("debug_resample_launch", audio, out)
         nch = int(nch)
         nin = audio.numel() // nch if nin is None else int(nin)
         nout = out.numel() // nch if nout is None else int(nout)
         if nin * nch > audio.numel() or nout * nch > out.numel():
             raise ValueError("debug_resample_launch: nin %d / nout %d x nch %d do not fit the tensors" % (nin, nout, nch))
-        f = self.L.uwspr_debug_resample_launch
-        f.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_longlong, C.c_longlong, C.c_int, C.c_int, C.c_void_p,
-                      C.c_longlong, C.c_longlong]
-        f.restype = C.c_int
-        if self._stream_ptr is None:
-            torch.cuda.current_stream(audio.device).synchronize()
-        self._chk(f(self.h, C.c_void_p(audio.data_ptr()), fmt, nin, int(in0), nch, int(rate), C.c_void_p(out.data_ptr()),
-                    nout, int(j_first)))
+        self._wait_torch(audio.device)
+        self._chk(self.L.uwspr_debug_resample_launch(self.h, C.c_void_p(audio.data_ptr()), fmt, nin, int(in0), nch, int(rate),
+                                                     C.c_void_p(out.data_ptr()), nout, int(j_first)))
 
     # -- blanker (K12) ------------------------------------------------------
     def blank(self, x, blank=24, guard=2):
@@ -310,36 +350,16 @@ class Context:
         -> (y float32 of the same shape, med float32 [nblocks] or [nblocks, C]: the level of every complete block of
         4096 samples, nzero int32 of that shape: the outputs of the block set to zero).  A contiguous torch CUDA tensor
         of those shapes and types stays on the device (-> CUDA tensors)."""
-        if _is_torch(x):
-            import torch
-            fmt = {torch.float32: N.AUDIO_F32, torch.int16: N.AUDIO_S16}.get(x.dtype)
-            if fmt is None or x.dim() not in (1, 2) or not x.is_cuda or not x.is_contiguous() or x.shape[0] < 1:
-                raise TypeError("blank: a contiguous [n] or [n, C] float32 or int16 CUDA tensor, not %s %s" % (x.dtype, tuple(x.shape)))
-            nch = 1 if x.dim() == 1 else x.shape[1]
-            nb = -(-x.shape[0] // BLANK_BLOCK)
-            y = torch.empty(tuple(x.shape), dtype=torch.float32, device=x.device)
-            med = torch.empty((nb,) + tuple(x.shape[1:]), dtype=torch.float32, device=x.device)
-            nz = torch.empty((nb,) + tuple(x.shape[1:]), dtype=torch.int32, device=x.device)
-            if self._stream_ptr is None:
-                torch.cuda.current_stream(x.device).synchronize()
-            self._chk(self.L.uwspr_blank_batch(self.h, C.c_void_p(x.data_ptr()), x.shape[0], nch, fmt, N.DEVICE, int(blank),
-                                               int(guard), C.c_void_p(y.data_ptr()), C.c_void_p(med.data_ptr()),
-                                               C.c_void_p(nz.data_ptr())))
-            if self._stream_ptr is None:
-                self.synchronize()
-            return y, med, nz
-        a = np.asarray(x)
-        if a.ndim not in (1, 2) or a.dtype not in (np.float32, np.int16) or a.shape[0] < 1:
-            raise TypeError("blank: a [n] or [n, C] float32 or int16 array, not %s %s" % (a.dtype, a.shape))
-        a = np.ascontiguousarray(a)
-        nch = 1 if a.ndim == 1 else a.shape[1]
-        nb = -(-a.shape[0] // BLANK_BLOCK)
-        y = np.empty(a.shape, np.float32)
-        med = np.empty((nb,) + a.shape[1:], np.float32)
-        nz = np.empty((nb,) + a.shape[1:], np.int32)
-        self._chk(self.L.uwspr_blank_batch(self.h, C.c_void_p(a.ctypes.data), a.shape[0], nch,
-                                           N.AUDIO_S16 if a.dtype == np.int16 else N.AUDIO_F32, N.HOST, int(blank), int(guard),
-                                           C.c_void_p(y.ctypes.data), C.c_void_p(med.ctypes.data), C.c_void_p(nz.ctypes.data)))
+        a, fmt, nch = _audio_block(x, "blank")
+        dev = _is_torch(a)
+        blocks = (-(-a.shape[0] // BLANK_BLOCK),) + tuple(a.shape[1:])
+        y, med, nz = _empty(a, a.shape, np.float32), _empty(a, blocks, np.float32), _empty(a, blocks, np.int32)
+        if dev:
+            self._wait_torch(a.device)
+        self._chk(self.L.uwspr_blank_batch(self.h, _ptr(a), a.shape[0], nch, fmt, N.DEVICE if dev else N.HOST, int(blank),
+                                           int(guard), _ptr(y), _ptr(med), _ptr(nz)))
+        if dev:
+            self._wait_self(always=False)
         return y, med, nz
 
     def stream_blank_stats(self, channels=1):
@@ -360,9 +380,7 @@ class Context:
         (float32 [nout, nch]; nout defaults to what it holds, 0 or out=None: no launch) and their zero counts into nz
         (int32 [blocks touched, nch]).  The tensors must hold what the launches read and write: checked here."""
         import torch
-        fmt = {torch.float32: N.AUDIO_F32, torch.int16: N.AUDIO_S16}.get(audio.dtype)
-        if fmt is None or not audio.is_cuda or not audio.is_contiguous():
-            raise TypeError("debug_blank_launch: a contiguous float32 or int16 CUDA tensor, not %s" % audio.dtype)
+        fmt = _launch_tensors("debug_blank_launch", audio)
         if lev.dtype != torch.float32 or not lev.is_cuda or not lev.is_contiguous():
             raise TypeError("debug_blank_launch: lev is a contiguous float32 CUDA tensor")
         nch = int(nch)
@@ -377,36 +395,21 @@ class Context:
         nblk = (int(y_first) + nout - 1) // BLANK_BLOCK - int(y_first) // BLANK_BLOCK + 1 if nout > 0 else 0
         if nin * nch > audio.numel() or (nout > 0 and (nout * nch > out.numel() or nblk * nch > nz.numel())):
             raise ValueError("debug_blank_launch: nin %d / nout %d x nch %d do not fit the tensors" % (nin, nout, nch))
-        f = self.L.uwspr_debug_blank_launch
-        ll = C.c_longlong
-        f.argtypes = [C.c_void_p, C.c_void_p, C.c_int, ll, ll, C.c_int, C.c_void_p, ll, ll, ll, ll, C.c_int, C.c_int, C.c_void_p, ll, ll,
-                      C.c_void_p]
-        f.restype = C.c_int
-        if self._stream_ptr is None:
-            torch.cuda.current_stream(audio.device).synchronize()
-        self._chk(f(self.h, C.c_void_p(audio.data_ptr()), fmt, nin, int(in0), nch, C.c_void_p(lev.data_ptr()), nlev, int(blk0),
-                    int(level_first), int(level_n), int(blank), int(guard), C.c_void_p(out.data_ptr() if nout > 0 else None), nout,
-                    int(y_first), C.c_void_p(nz.data_ptr() if nout > 0 else None)))
+        self._wait_torch(audio.device)
+        self._chk(self.L.uwspr_debug_blank_launch(self.h, C.c_void_p(audio.data_ptr()), fmt, nin, int(in0), nch,
+                                                  C.c_void_p(lev.data_ptr()), nlev, int(blk0), int(level_first), int(level_n),
+                                                  int(blank), int(guard), C.c_void_p(out.data_ptr() if nout > 0 else None), nout,
+                                                  int(y_first), C.c_void_p(nz.data_ptr() if nout > 0 else None)))
 
     # -- FDR ---------------------------------------------------------------
     def fdr_batch(self, frames):
         """-> list (per frame) of candidate record arrays, FDR_impl.cc:214-456."""
         p, B, where, keep = self._frames(frames)
+        cands, npk = self._cand_buffers(B, frames.device if where == N.DEVICE else None)
+        self._chk(self.L.uwspr_fdr_batch(self.h, p, B, where, _ptr(cands), _ptr(npk)))
         if where == N.DEVICE:
-            import torch
-            cands = torch.empty(B * self.maxfreqs * 48, dtype=torch.uint8, device=frames.device)
-            npk = torch.empty(B, dtype=torch.int32, device=frames.device)
-            self._chk(self.L.uwspr_fdr_batch(self.h, p, B, where, C.c_void_p(cands.data_ptr()),
-                                             C.c_void_p(npk.data_ptr())))
-            self.synchronize()
-            cands = np.frombuffer(cands.cpu().numpy().tobytes(), N.CAND_DTYPE).reshape(B, -1)
-            npk = npk.cpu().numpy()
-        else:
-            cands = np.zeros((B, self.maxfreqs), N.CAND_DTYPE)
-            npk = np.zeros(B, np.int32)
-            self._chk(self.L.uwspr_fdr_batch(self.h, p, B, where, C.c_void_p(cands.ctypes.data),
-                                             C.c_void_p(npk.ctypes.data)))
-        return [cands[b, :npk[b]].copy() for b in range(B)]
+            self._wait_self(always=True)
+        return _cand_lists(cands, npk)
 
     def fdr_from_ps(self, ps_band):
         """diagnostics: the spectrum kernel and the coarse search on a GIVEN spectrogram, ps_band [B, n, band_w] float32
@@ -415,25 +418,17 @@ class Context:
         if _is_torch(ps_band):
             import torch
             assert ps_band.is_cuda and ps_band.is_contiguous() and ps_band.dtype == torch.float32
-            B = ps_band.numel() // (i.n * i.band_w)
+            a, B, where = ps_band, ps_band.numel() // (i.n * i.band_w), N.DEVICE
             assert B * i.n * i.band_w == ps_band.numel()
-            if self._stream_ptr is None:
-                torch.cuda.current_stream(ps_band.device).synchronize()
-            cands = torch.empty(B * self.maxfreqs * 48, dtype=torch.uint8, device=ps_band.device)
-            npk = torch.empty(B, dtype=torch.int32, device=ps_band.device)
-            self._chk(self.L.uwspr_debug_fdr_from_ps(self.h, C.c_void_p(ps_band.data_ptr()), B, N.DEVICE,
-                                                     C.c_void_p(cands.data_ptr()), C.c_void_p(npk.data_ptr())))
-            self.synchronize()
-            cands = np.frombuffer(cands.cpu().numpy().tobytes(), N.CAND_DTYPE).reshape(B, -1)
-            npk = npk.cpu().numpy()
+            self._wait_torch(ps_band.device)
         else:
             a = np.ascontiguousarray(ps_band, dtype=np.float32).reshape(-1, i.n, i.band_w)
-            B = a.shape[0]
-            cands = np.zeros((B, self.maxfreqs), N.CAND_DTYPE)
-            npk = np.zeros(B, np.int32)
-            self._chk(self.L.uwspr_debug_fdr_from_ps(self.h, C.c_void_p(a.ctypes.data), B, N.HOST,
-                                                     C.c_void_p(cands.ctypes.data), C.c_void_p(npk.ctypes.data)))
-        return [cands[b, :npk[b]].copy() for b in range(B)]
+            B, where = a.shape[0], N.HOST
+        cands, npk = self._cand_buffers(B, a.device if where == N.DEVICE else None)
+        self._chk(self.L.uwspr_debug_fdr_from_ps(self.h, _ptr(a), B, where, _ptr(cands), _ptr(npk)))
+        if where == N.DEVICE:
+            self._wait_self(always=True)
+        return _cand_lists(cands, npk)
 
     def fdr_spectrum(self, B):
         i = self.info
@@ -469,7 +464,7 @@ class Context:
             self._chk(self.L.uwspr_sync_sweep(self.h, p, B, C.c_void_p(dh.data_ptr()), H, where,
                                               C.c_void_p(sync.data_ptr()),
                                               C.c_void_p(sym.data_ptr()) if soft else None))
-            self.synchronize()
+            self._wait_self(always=True)
             return sync.cpu().numpy(), (sym.cpu().numpy().reshape(H, N.NSYM) if soft else None)
         sync = np.empty(H, np.float32)
         sym = np.empty((H, N.NSYM), np.uint8) if soft else None
@@ -507,7 +502,7 @@ class Context:
                                              C.c_void_p(sym_t.data_ptr()) if sym_t is not None else None))
             if into is not None:
                 return None
-            self.synchronize()
+            self._wait_self(always=True)
             return (sync_t.cpu().numpy().reshape(shape),
                     sym_t.cpu().numpy().reshape(shape + (N.NSYM,)) if soft else None)
         cent = np.ascontiguousarray(centres, dtype=N.CAND_DTYPE)
@@ -566,21 +561,18 @@ class Context:
         stream_wait_uploads())."""
         n = C.c_int(0)
         if _is_torch(x):
-            import torch
-            fmt = {torch.float32: N.AUDIO_F32, torch.int16: N.AUDIO_S16}.get(x.dtype)
+            fmt = _audio_format(x)
             if fmt is None or x.dim() != 1 or not x.is_cuda:
                 raise TypeError("stream_push_audio: a 1-D float32 or int16 CUDA tensor, not %s %s" % (x.dtype, tuple(x.shape)))
             copied = not x.is_contiguous()
             x = x.contiguous()
-            if self._stream_ptr is None:
-                torch.cuda.current_stream(x.device).synchronize()
+            self._wait_torch(x.device)
             self._chk(self.L.uwspr_stream_push_audio(self.h, C.c_void_p(x.data_ptr()), x.numel(), fmt, N.DEVICE, C.byref(n)))
             if copied:   # the copy stream reads the temporary after this call returns: keep it until it has
                 self.stream_wait_uploads()
             return n.value
         a = _audio_array(x)
-        self._chk(self.L.uwspr_stream_push_audio(self.h, C.c_void_p(a.ctypes.data), a.size,
-                                                 N.AUDIO_S16 if a.dtype == np.int16 else N.AUDIO_F32,
+        self._chk(self.L.uwspr_stream_push_audio(self.h, C.c_void_p(a.ctypes.data), a.size, _audio_format(a),
                                                  {"host": N.HOST, "async": N.HOST_ASYNC}[where], C.byref(n)))
         return n.value
 
@@ -642,28 +634,16 @@ class Context:
                 self._chk(self.L.uwspr_pipeline_batch(self.h, p, B, where, max_per_frame, None,
                                                       None, None))
                 return None
-            dev = frames.device
-            cands = torch.empty(B * self.maxfreqs * 48, dtype=torch.uint8, device=dev)
-            npk = torch.empty(B, dtype=torch.int32, device=dev)
-            out = torch.empty(B * max_per_frame * N.DEMOD_DTYPE.itemsize, dtype=torch.uint8,
-                              device=dev)
-            self._chk(self.L.uwspr_pipeline_batch(self.h, p, B, where, max_per_frame,
-                                                  C.c_void_p(cands.data_ptr()),
-                                                  C.c_void_p(npk.data_ptr()),
-                                                  C.c_void_p(out.data_ptr())))
-            self.synchronize()
-            cands = np.frombuffer(cands.cpu().numpy().tobytes(), N.CAND_DTYPE).reshape(B, -1)
-            npk = npk.cpu().numpy()
-            out = np.frombuffer(out.cpu().numpy().tobytes(), N.DEMOD_DTYPE).reshape(B, -1)
+            cands, npk = self._cand_buffers(B, frames.device)
+            out = torch.empty(B * max_per_frame * N.DEMOD_DTYPE.itemsize, dtype=torch.uint8, device=frames.device)
         else:
-            cands = np.zeros((B, self.maxfreqs), N.CAND_DTYPE)
-            npk = np.zeros(B, np.int32)
+            cands, npk = self._cand_buffers(B)
             out = np.zeros((B, max_per_frame), N.DEMOD_DTYPE)
-            self._chk(self.L.uwspr_pipeline_batch(self.h, p, B, where, max_per_frame,
-                                                  C.c_void_p(cands.ctypes.data),
-                                                  C.c_void_p(npk.ctypes.data),
-                                                  C.c_void_p(out.ctypes.data)))
-        return [cands[b, :npk[b]].copy() for b in range(B)], out.copy()
+        self._chk(self.L.uwspr_pipeline_batch(self.h, p, B, where, max_per_frame, _ptr(cands), _ptr(npk), _ptr(out)))
+        if where == N.DEVICE:
+            self._wait_self(always=True)
+            out = np.frombuffer(out.cpu().numpy().tobytes(), N.DEMOD_DTYPE).reshape(B, -1)
+        return _cand_lists(cands, npk), out.copy()
 
     def pipeline_batch_into(self, frames, cands_t, npk_t, out_t, max_per_frame=1):
         """Device-resident form used by bench.py: frames and the three output
@@ -729,27 +709,31 @@ class Context:
                                               C.c_void_p(out.ctypes.data), rp))
         return out, res
 
+    # -- the scored fallbacks: K9, K13, K14 on soft-symbol vectors -------------
+    def _scored(self, fn, R, symbols, *extra):
+        """fn(ctx, symbols, n, where, *extra, results) on [n, 162] uint8 soft-symbol vectors, a numpy array or a torch CUDA
+        tensor (read in place) -> the n results, a numpy array of dtype R"""
+        if _is_torch(symbols):
+            import torch
+            assert symbols.is_cuda and symbols.is_contiguous() and symbols.dtype == torch.uint8
+            n = symbols.numel() // N.NSYM
+            out = torch.zeros(max(n, 1) * R.itemsize, dtype=torch.uint8, device=symbols.device)
+            self._wait_torch(symbols.device)
+            self._chk(fn(self.h, C.c_void_p(symbols.data_ptr()), n, N.DEVICE, *extra, C.c_void_p(out.data_ptr())))
+            self._wait_self(always=True)
+            return out.cpu().numpy()[:n * R.itemsize].view(R).copy()
+        a = np.ascontiguousarray(symbols, dtype=np.uint8).reshape(-1, N.NSYM)
+        res = np.zeros(len(a), R)
+        self._chk(fn(self.h, C.c_void_p(a.ctypes.data) if len(a) else None, len(a), N.HOST, *extra,
+                     C.c_void_p(res.ctypes.data) if len(a) else None))
+        return res
+
     # -- ordered-statistics decoding (K9: uwspr_osd_batch) -------------------
     def osd(self, symbols, order=2):
         """Ordered-statistics decoding of soft-symbol vectors as uwspr_demod_out.symbols[idt] holds them: [n, 162] uint8, a
         numpy array or a torch CUDA tensor (read in place).  -> an OSD_RESULT_DTYPE array: dmin, dnext, nhard, nflip and
         the 7 message bytes per vector (include/uwspr_hip.h states the definition)."""
-        if _is_torch(symbols):
-            import torch
-            assert symbols.is_cuda and symbols.is_contiguous() and symbols.dtype == torch.uint8
-            n = symbols.numel() // N.NSYM
-            out = torch.zeros(max(n, 1) * N.OSD_RESULT_DTYPE.itemsize, dtype=torch.uint8, device=symbols.device)
-            if self._stream_ptr is None:
-                torch.cuda.current_stream(symbols.device).synchronize()
-            self._chk(self.L.uwspr_osd_batch(self.h, C.c_void_p(symbols.data_ptr()), n, N.DEVICE, int(order),
-                                             C.c_void_p(out.data_ptr())))
-            self.synchronize()
-            return out.cpu().numpy()[:n * N.OSD_RESULT_DTYPE.itemsize].view(N.OSD_RESULT_DTYPE).copy()
-        a = np.ascontiguousarray(symbols, dtype=np.uint8).reshape(-1, N.NSYM)
-        res = np.zeros(len(a), N.OSD_RESULT_DTYPE)
-        self._chk(self.L.uwspr_osd_batch(self.h, C.c_void_p(a.ctypes.data) if len(a) else None, len(a), N.HOST, int(order),
-                                         C.c_void_p(res.ctypes.data) if len(a) else None))
-        return res
+        return self._scored(self.L.uwspr_osd_batch, N.OSD_RESULT_DTYPE, symbols, int(order))
 
     # -- list search (K13: uwspr_deep_set_list, uwspr_deep_batch) -------------
     def deep_set_list(self, known):
@@ -762,22 +746,7 @@ class Context:
         """Soft-symbol vectors as uwspr_demod_out.symbols[idt] holds them -- [n, 162] uint8, a numpy array or a torch CUDA
         tensor (read in place) -- scored against every codeword of the list.  -> a DEEP_RESULT_DTYPE array: best (index
         in the list), sbest, snext per vector (include/uwspr_hip.h states the definition)."""
-        R = N.DEEP_RESULT_DTYPE
-        if _is_torch(symbols):
-            import torch
-            assert symbols.is_cuda and symbols.is_contiguous() and symbols.dtype == torch.uint8
-            n = symbols.numel() // N.NSYM
-            out = torch.zeros(max(n, 1) * R.itemsize, dtype=torch.uint8, device=symbols.device)
-            if self._stream_ptr is None:
-                torch.cuda.current_stream(symbols.device).synchronize()
-            self._chk(self.L.uwspr_deep_batch(self.h, C.c_void_p(symbols.data_ptr()), n, N.DEVICE, C.c_void_p(out.data_ptr())))
-            self.synchronize()
-            return out.cpu().numpy()[:n * R.itemsize].view(R).copy()
-        a = np.ascontiguousarray(symbols, dtype=np.uint8).reshape(-1, N.NSYM)
-        res = np.zeros(len(a), R)
-        self._chk(self.L.uwspr_deep_batch(self.h, C.c_void_p(a.ctypes.data) if len(a) else None, len(a), N.HOST,
-                                          C.c_void_p(res.ctypes.data) if len(a) else None))
-        return res
+        return self._scored(self.L.uwspr_deep_batch, N.DEEP_RESULT_DTYPE, symbols)
 
     # -- call search (K14: uwspr_calls_set, uwspr_calls_batch) -----------------
     def calls_set(self, calls, grids=None, powers=None):
@@ -791,22 +760,7 @@ class Context:
         """Soft-symbol vectors as at Context.deep -- [n, 162] uint8, a numpy array or a torch CUDA tensor (read in place) --
         scored against every allowed (callsign, locator, power) of the call set.  -> a CALL_RESULT_DTYPE array: best (the
         hypothesis index h), call (index), ngrid, dbm, sbest, snext per vector (include/uwspr_hip.h states the definition)."""
-        R = N.CALL_RESULT_DTYPE
-        if _is_torch(symbols):
-            import torch
-            assert symbols.is_cuda and symbols.is_contiguous() and symbols.dtype == torch.uint8
-            n = symbols.numel() // N.NSYM
-            out = torch.zeros(max(n, 1) * R.itemsize, dtype=torch.uint8, device=symbols.device)
-            if self._stream_ptr is None:
-                torch.cuda.current_stream(symbols.device).synchronize()
-            self._chk(self.L.uwspr_calls_batch(self.h, C.c_void_p(symbols.data_ptr()), n, N.DEVICE, C.c_void_p(out.data_ptr())))
-            self.synchronize()
-            return out.cpu().numpy()[:n * R.itemsize].view(R).copy()
-        a = np.ascontiguousarray(symbols, dtype=np.uint8).reshape(-1, N.NSYM)
-        res = np.zeros(len(a), R)
-        self._chk(self.L.uwspr_calls_batch(self.h, C.c_void_p(a.ctypes.data) if len(a) else None, len(a), N.HOST,
-                                           C.c_void_p(res.ctypes.data) if len(a) else None))
-        return res
+        return self._scored(self.L.uwspr_calls_batch, N.CALL_RESULT_DTYPE, symbols)
 
     # -- block demodulation (K10: uwspr_blockdemod_batch) ---------------------
     def blockdemod(self, frames, items):
@@ -820,7 +774,7 @@ class Context:
         if where == N.DEVICE:   # device frames: the bytes are written to device memory and copied back
             import torch
             dev = torch.zeros(max(3 * N.NSYM * len(it), 1), dtype=torch.uint8, device=frames.device)
-            torch.cuda.current_stream(dev.device).synchronize()
+            self._wait_torch(dev.device, always=True)
             self._chk(self.L.uwspr_blockdemod_batch(self.h, p, B, N.DEVICE_FRAMES, ip, len(it), C.c_void_p(dev.data_ptr())))
             return dev.cpu().numpy()[:3 * N.NSYM * len(it)].reshape(len(it), 3, N.NSYM).copy()
         out = np.zeros((len(it), 3, N.NSYM), np.uint8)
@@ -836,30 +790,18 @@ class Context:
         (tx_fades) through uwspr_tx_baseband_medium."""
         signals = list(signals)
         sig, mot, car, fad = tx_signals(signals), tx_motions(signals), tx_carriers(signals), tx_fades(signals)
-        sp = C.c_void_p(C.addressof(sig)) if len(sig) else None
-        if fad is not None:
-            mp = None if mot is None else C.c_void_p(C.addressof(mot))
-            cp = None if car is None else C.c_void_p(car.ctypes.data)
-            call = lambda h, *a: self.L.uwspr_tx_baseband_medium(h, a[0], mp, cp, C.c_void_p(C.addressof(fad)), *a[1:])  # noqa: E731
-        elif car is not None:
-            mp = None if mot is None else C.c_void_p(C.addressof(mot))
-            call = lambda h, *a: self.L.uwspr_tx_baseband_at(h, a[0], mp, C.c_void_p(car.ctypes.data), *a[1:])  # noqa: E731
-        else:
-            call = self.L.uwspr_tx_baseband if mot is None else \
-                (lambda h, *a: self.L.uwspr_tx_baseband_moving(h, a[0], C.c_void_p(C.addressof(mot)), *a[1:]))
+        route = (self.L, "baseband", self.h, sig, mot, car, fad, None)
         if out is not None and _is_torch(out):
             import torch
             if not (out.is_cuda and out.is_contiguous() and out.dtype == torch.float32 and out.numel() >= 2 * n):
                 raise TypeError("tx_baseband: out must be a contiguous float32 CUDA tensor of >= %d elements, not %s %s"
                                 % (2 * n, out.dtype, tuple(out.shape)))
-            if self._stream_ptr is None:
-                torch.cuda.current_stream(out.device).synchronize()
-            self._chk(call(self.h, sp, len(sig), int(channel), int(t0), int(n), C.c_void_p(out.data_ptr()), N.DEVICE))
-            if self._stream_ptr is None:
-                self.synchronize()
+            self._wait_torch(out.device)
+            self._chk(_tx_call(*route, len(sig), int(channel), int(t0), int(n), C.c_void_p(out.data_ptr()), N.DEVICE))
+            self._wait_self(always=False)
             return out
         iq = np.empty((n, 2), np.float32)
-        self._chk(call(self.h, sp, len(sig), int(channel), int(t0), int(n), C.c_void_p(iq.ctypes.data), N.HOST))
+        self._chk(_tx_call(*route, len(sig), int(channel), int(t0), int(n), C.c_void_p(iq.ctypes.data), N.HOST))
         return iq
 
     def tx_render(self, signals, nframes, t0=0, channels=1, sigma=0.0, seed=0, background=None, background_gain=1.0,
@@ -879,18 +821,7 @@ class Context:
         signals = list(signals)
         sig, mot, car, fad = tx_signals(signals), tx_motions(signals), tx_carriers(signals), tx_fades(signals)
         imp = tx_impulses(impulses, int(channels))
-        if fad is not None or imp is not None:
-            mp = None if mot is None else C.c_void_p(C.addressof(mot))
-            cp = None if car is None else C.c_void_p(car.ctypes.data)
-            fp = None if fad is None else C.c_void_p(C.addressof(fad))
-            ip_ = None if imp is None else C.c_void_p(C.addressof(imp))
-            call = lambda h, *a: self.L.uwspr_tx_render_medium(h, a[0], mp, cp, fp, a[1], a[2], ip_, *a[3:])  # noqa: E731
-        elif car is not None:
-            mp = None if mot is None else C.c_void_p(C.addressof(mot))
-            call = lambda h, *a: self.L.uwspr_tx_render_at(h, a[0], mp, C.c_void_p(car.ctypes.data), *a[1:])  # noqa: E731
-        else:
-            call = self.L.uwspr_tx_render if mot is None else \
-                (lambda h, *a: self.L.uwspr_tx_render_moving(h, a[0], C.c_void_p(C.addressof(mot)), *a[1:]))
+        route = (self.L, "render", self.h, sig, mot, car, fad, imp)
         dev_out = out is not None and _is_torch(out)
         if dev_out and not out.is_cuda:
             raise TypeError("tx_render: out must be a CUDA tensor (or None for a numpy result)")
@@ -911,34 +842,27 @@ class Context:
                     raise TypeError("background: a 1-D float32 or int16 array, not %s %s" % (b.dtype, tuple(b.shape)))
                 moved = moved or not b.is_cuda or b.device != out.device or not b.is_contiguous()
                 b = b.to(out.device).contiguous()
-                fmt = N.AUDIO_S16 if b.dtype == torch.int16 else N.AUDIO_F32
                 ch[k].background, ch[k].background_len = b.data_ptr(), b.numel()
             else:
                 if _is_torch(b):
                     b = b.detach().cpu().numpy()
                 b = _audio_array(b)
-                fmt = N.AUDIO_S16 if b.dtype == np.int16 else N.AUDIO_F32
                 ch[k].background, ch[k].background_len = b.ctypes.data, b.size
-            ch[k].background_format = fmt
+            ch[k].background_format = _audio_format(b)
             keep.append(b)
         fmt = {"f32": N.AUDIO_F32, "s16": N.AUDIO_S16}[format]
-        sp = C.c_void_p(C.addressof(sig)) if len(sig) else None
         if dev_out:
             import torch
             if not (out.is_contiguous() and out.numel() >= int(nframes) * Cn and
                     out.dtype == (torch.int16 if fmt == N.AUDIO_S16 else torch.float32)):
                 raise TypeError("tx_render: out must be a contiguous %s CUDA tensor of >= %d elements, not %s %s"
                                 % ("int16" if fmt == N.AUDIO_S16 else "float32", int(nframes) * Cn, out.dtype, tuple(out.shape)))
-            if self._stream_ptr is None or moved:   # (a moved background was copied on torch's stream)
-                torch.cuda.current_stream(out.device).synchronize()
-            self._chk(call(self.h, sp, len(sig), C.byref(ch), Cn, int(t0), int(nframes), fmt,
-                           C.c_void_p(out.data_ptr()), N.DEVICE))
-            if self._stream_ptr is None or moved:   # (the moved copies are freed when this call returns)
-                self.synchronize()
+            self._wait_torch(out.device, always=moved)   # (a moved background was copied on torch's stream)
+            self._chk(_tx_call(*route, len(sig), C.byref(ch), Cn, int(t0), int(nframes), fmt, C.c_void_p(out.data_ptr()), N.DEVICE))
+            self._wait_self(always=moved)                # (the moved copies are freed when this call returns)
             return out
         a = np.empty((int(nframes), Cn), np.int16 if fmt == N.AUDIO_S16 else np.float32)
-        self._chk(call(self.h, sp, len(sig), C.byref(ch), Cn, int(t0), int(nframes), fmt,
-                       C.c_void_p(a.ctypes.data), N.HOST))
+        self._chk(_tx_call(*route, len(sig), C.byref(ch), Cn, int(t0), int(nframes), fmt, C.c_void_p(a.ctypes.data), N.HOST))
         return a
 
     # -- multi-GPU gather over RCCL (uwspr_dist_*) ---------------------------
@@ -1063,9 +987,6 @@ def unpack_message(message7):
     return rc, buf.value.decode("ascii", "replace")
 
 
-FRONTEND_GRC, FRONTEND_COMPACT = 0, 1
-
-
 def host_alloc(nbytes):
     """uwspr_host_alloc: page-locked host memory as a writable ctypes byte array (np.frombuffer it); release with
     host_free."""
@@ -1103,12 +1024,9 @@ def tx_taps():
     """diagnostics: K7's filter (uwspr_debug_tx_taps; host only, no device) -> (g complex128 [3179], the composite of
     c2ToWaveFile.grc's chain designed in binary64; image float32 [32, 104, 2], the (Re g, -Im g) tap image the render
     kernel reads: image[p, i] is tap p + 32 i, +0 behind the last one)"""
-    f = N.lib().uwspr_debug_tx_taps
-    f.argtypes = [C.c_void_p, C.c_void_p]
-    f.restype = C.c_int
     g = np.zeros((3179, 2), np.float64)
     image = np.full((32, 104, 2), np.nan, np.float32)
-    n = f(C.c_void_p(g.ctypes.data), C.c_void_p(image.ctypes.data))
+    n = N.lib().uwspr_debug_tx_taps(C.c_void_p(g.ctypes.data), C.c_void_p(image.ctypes.data))
     if n != 3179:
         raise N.UwsprError(n if n < 0 else -1, "uwspr_debug_tx_taps: %d taps, this binding holds 3179" % n)
     return g[:, 0] + 1j * g[:, 1], image
@@ -1129,24 +1047,21 @@ def tx_design(carrier=1500, cutoff=2500):
     return g[:, 0] + 1j * g[:, 1], image
 
 
+def _launch_counts(name, n):
+    """the n process-wide launch counters uwspr_debug_<name>_counts reads -> a tuple of ints"""
+    out = np.zeros(n, np.int64)
+    getattr(N.lib(), "uwspr_debug_%s_counts" % name)(C.c_void_p(out.ctypes.data))
+    return tuple(int(v) for v in out)
+
+
 def tx_carrier_launch_counts():
     """diagnostics: launches of K7's carrier form since the process started -> (float32 output, int16 output)"""
-    f = N.lib().uwspr_debug_tx_carrier_counts
-    f.argtypes = [C.c_void_p]
-    f.restype = C.c_int
-    out = np.zeros(2, np.int64)
-    f(C.c_void_p(out.ctypes.data))
-    return int(out[0]), int(out[1])
+    return _launch_counts("tx_carrier", 2)
 
 
 def tx_medium_launch_counts():
     """diagnostics: launches of K7's medium form since the process started -> (float32 output, int16 output, baseband)"""
-    f = N.lib().uwspr_debug_tx_medium_counts
-    f.argtypes = [C.c_void_p]
-    f.restype = C.c_int
-    out = np.zeros(3, np.int64)
-    f(C.c_void_p(out.ctypes.data))
-    return int(out[0]), int(out[1]), int(out[2])
+    return _launch_counts("tx_medium", 3)
 
 
 def tx_fade_design(fade):
@@ -1176,12 +1091,7 @@ def frontend_rotator():
 
 def frontend_carrier_launch_counts():
     """diagnostics: launches of K0's carrier form since the process started -> (with float32 input, with int16 input)"""
-    f = N.lib().uwspr_debug_frontend_carrier_counts
-    f.argtypes = [C.c_void_p]
-    f.restype = C.c_int
-    out = np.zeros(2, np.int64)
-    f(C.c_void_p(out.ctypes.data))
-    return int(out[0]), int(out[1])
+    return _launch_counts("frontend_carrier", 2)
 
 
 def resample_design(rate):
@@ -1199,23 +1109,13 @@ def resample_design(rate):
 
 def resample_launch_counts():
     """diagnostics: launches of K11 since the process started -> (with float32 input, with int16 input)"""
-    f = N.lib().uwspr_debug_resample_counts
-    f.argtypes = [C.c_void_p]
-    f.restype = C.c_int
-    out = np.zeros(2, np.int64)
-    f(C.c_void_p(out.ctypes.data))
-    return int(out[0]), int(out[1])
+    return _launch_counts("resample", 2)
 
 
 def blank_launch_counts():
     """diagnostics: launches of K12 since the process started -> (k12_level with float32 input, with int16 input,
     k12_apply with float32 input, with int16 input)"""
-    f = N.lib().uwspr_debug_blank_counts
-    f.argtypes = [C.c_void_p]
-    f.restype = C.c_int
-    out = np.zeros(4, np.int64)
-    f(C.c_void_p(out.ctypes.data))
-    return tuple(int(v) for v in out)
+    return _launch_counts("blank", 4)
 
 
 def c2_read(path):
@@ -1569,37 +1469,28 @@ class Pipe:
             self.h = None
             raise N.UwsprError(rc, msg)
         self.batch_frames, self.hop = batch_frames, hop
-        try:
-            if passes != 1:   # 2: what decodes is subtracted and the residual searched again (records with pass = 1)
-                self.set_option("passes", passes)
-            if osd:           # 1, 2: ordered-statistics decoding of that order on what Fano timed out on (records with osd = 1)
-                self.set_option("osd", osd)
-            if osd_gap is not None:
-                self.set_option("osd_gap", osd_gap)
-            if block:         # 2, 3: block demodulation up to that length on what Fano timed out on (records with block = 2, 3)
-                self.set_option("block", block)
-            if audio_rate is not None and int(audio_rate) != AUDIO_RATE:   # push_audio takes audio at that rate (K11 ahead of the front-end)
-                self.set_option("audio_rate", audio_rate)
-            if blank:         # 4 .. 1024: the noise blanker K12 ahead of everything push_audio feeds, threshold blank / 4 block medians
-                self.set_option("blank", blank)
-            if blank_guard is not None:
-                self.set_option("blank_guard", blank_guard)
+        def options(*rows):   # (keyword's value, option, whether to set it), in order
+            for value, name, wanted in rows:
+                if wanted:
+                    self.set_option(name, value)
+        try:   # in this order: the carriers before frontend_hbw, a list before its thresholds
+            options((passes, "passes", passes != 1),   # 2: what decodes is subtracted and the residual searched again (records with pass = 1)
+                    (osd, "osd", osd),                 # 1, 2: ordered-statistics decoding of that order on what Fano timed out on (records with osd = 1)
+                    (osd_gap, "osd_gap", osd_gap is not None),
+                    (block, "block", block),           # 2, 3: block demodulation up to that length on what Fano timed out on (records with block = 2, 3)
+                    # push_audio takes audio at that rate (K11 ahead of the front-end)
+                    (audio_rate, "audio_rate", audio_rate is not None and int(audio_rate) != AUDIO_RATE),
+                    (blank, "blank", blank),           # 4 .. 1024: the noise blanker K12 ahead of everything push_audio feeds, threshold blank / 4 block medians
+                    (blank_guard, "blank_guard", blank_guard is not None))
             if carriers is not None:   # K0's centres in Hz: every pushed channel is heard at every one of them
                 self.set_carriers(carriers)
-            if frontend_hbw is not None:
-                self.set_option("frontend_hbw", frontend_hbw)
+            options((frontend_hbw, "frontend_hbw", frontend_hbw is not None))
             if known is not None and len(known):   # the list of expected messages: K13 on what Fano timed out on (records with osd = 2)
                 self.set_list(known)
-            if deep_min is not None:
-                self.set_option("deep_min", deep_min)
-            if deep_gap is not None:
-                self.set_option("deep_gap", deep_gap)
+            options((deep_min, "deep_min", deep_min is not None), (deep_gap, "deep_gap", deep_gap is not None))
             if calls is not None and len(calls):   # the call set: K14 on what Fano timed out on and the list left (records with osd = 3)
                 self.set_calls(calls, call_grids, call_powers)
-            if call_min is not None:
-                self.set_option("call_min", call_min)
-            if call_gap is not None:
-                self.set_option("call_gap", call_gap)
+            options((call_min, "call_min", call_min is not None), (call_gap, "call_gap", call_gap is not None))
         except N.UwsprError:
             self.close()
             raise
@@ -1634,11 +1525,10 @@ class Pipe:
                 raise TypeError("audio: a [n, C] float32 or int16 array, not %s %s" % (a.dtype, a.shape))
             a = np.ascontiguousarray(a)
             self._chk(self.L.uwspr_pipe_push_audio_channels(self.h, C.c_void_p(a.ctypes.data), a.shape[0], a.shape[1],
-                                                            N.AUDIO_S16 if a.dtype == np.int16 else N.AUDIO_F32))
+                                                            _audio_format(a)))
             return
         a = _audio_array(a)
-        self._chk(self.L.uwspr_pipe_push_audio(self.h, C.c_void_p(a.ctypes.data), a.size,
-                                               N.AUDIO_S16 if a.dtype == np.int16 else N.AUDIO_F32))
+        self._chk(self.L.uwspr_pipe_push_audio(self.h, C.c_void_p(a.ctypes.data), a.size, _audio_format(a)))
 
     def acquire(self, nsamples):
         """-> numpy view [nsamples, 2] of the page-locked staging buffer to fill; then commit(nsamples)."""
@@ -1713,10 +1603,6 @@ class Pipe:
 
 
 # ---- recordings ---------------------------------------------------------------------------------------------------
-AUDIO_RATE = 12000
-BLANK_BLOCK = 4096   # UWSPR_BLANK_BLOCK: samples per block of the blanker's level
-
-
 def supported_rate(rate):
     """whether the resampler takes audio at `rate` S/s (include/uwspr_hip.h; 12000 = no resampler)"""
     rate = int(rate)

@@ -68,7 +68,6 @@ def _compiler_id():
 def _digest(paths):
     """Content hash of the build inputs: what decides whether the library is current (file
     times do not survive a copy to another machine; contents do)."""
-    import hashlib
     h = hashlib.sha256()
     for q in sorted(paths):
         h.update(os.path.basename(q).encode())
@@ -77,13 +76,18 @@ def _digest(paths):
     return h.hexdigest()
 
 
-def source_digest():
-    """sha256 over the sources the product library is built from (what a profile taken with
-    tools/run_profiles.sh is valid for)."""
+def _sources():
+    """-> (the sources of the product library, everything its build reads: those, csrc's headers and the ABI header)"""
     srcs = [os.path.join(CSRC, s) for s in SOURCES]
     deps = srcs + [os.path.join(CSRC, h) for h in os.listdir(CSRC) if h.endswith(".h")]
     deps.append(os.path.join(_HERE, "..", "include", "uwspr_hip.h"))
-    return _digest(deps)
+    return srcs, deps
+
+
+def source_digest():
+    """sha256 over the sources the product library is built from (what a profile taken with
+    tools/run_profiles.sh is valid for)."""
+    return _digest(_sources()[1])
 
 
 def build(force=False, verbose=False):
@@ -97,9 +101,7 @@ def build(force=False, verbose=False):
     import fcntl
     if not os.path.isdir(LIBDIR):
         os.makedirs(LIBDIR, exist_ok=True)
-    srcs = [os.path.join(CSRC, s) for s in SOURCES]
-    deps = srcs + [os.path.join(CSRC, h) for h in os.listdir(CSRC) if h.endswith(".h")]
-    deps.append(os.path.join(_HERE, "..", "include", "uwspr_hip.h"))
+    srcs, deps = _sources()
     extra = _EXTRA   # experiments only (separate output file, see LIBPATH)
     flags = HIPFLAGS + extra + ["-shared", "-pthread"]
     hostdir = os.path.join(_HERE, "host")
@@ -280,28 +282,125 @@ class Prof(C.Structure):
     _fields_ = [("ms", C.c_double * 6), ("launches", C.c_int64 * 6), ("units", C.c_int64 * 6)]
 
 
-# every symbol include/uwspr_hip.h declares
-ABI_SYMBOLS = [
-    "uwspr_ctx_create", "uwspr_ctx_destroy", "uwspr_last_error", "uwspr_status_string",
-    "uwspr_get_info", "uwspr_set_stream", "uwspr_synchronize", "uwspr_frontend_batch",
-    "uwspr_frontend_design", "uwspr_frontend_design_at", "uwspr_frontend_rotator", "uwspr_resample_design", "uwspr_resample_batch", "uwspr_blank_batch", "uwspr_stream_blank_stats", "uwspr_pipe_blank_stats", "uwspr_set_frame_stride", "uwspr_stream_open", "uwspr_stream_push", "uwspr_stream_push_audio", "uwspr_stream_wait_uploads",
-    "uwspr_stream_take_view", "uwspr_stream_take", "uwspr_stream_reset",
-    "uwspr_device_alloc", "uwspr_device_free", "uwspr_host_alloc", "uwspr_host_free", "uwspr_fdr_batch",
-    "uwspr_fdr_read_spectrum", "uwspr_fdr_keep_syncgrid", "uwspr_fdr_read_syncgrid",
-    "uwspr_sync_sweep", "uwspr_sync_grid", "uwspr_sync_and_demodulate_batch", "uwspr_demod_batch",
-    "uwspr_pipeline_batch", "uwspr_set_tries", "uwspr_set_option", "uwspr_get_option", "uwspr_demod_resume", "uwspr_pack_slabs", "uwspr_pipeline_slabs", "uwspr_prof_enable", "uwspr_prof_read", "uwspr_prof_intervals", "uwspr_deinterleave",
-    "uwspr_fano_decode", "uwspr_fano_encode", "uwspr_decode_candidate", "uwspr_host_threads", "uwspr_host_set_ranks", "uwspr_decode_batch", "uwspr_unpack_message",
-    "uwspr_c2_read",
-    "uwspr_wspr_pack", "uwspr_nhash", "uwspr_wspr_symbols", "uwspr_c2_write", "uwspr_tx_baseband", "uwspr_tx_render",
-    "uwspr_tx_baseband_moving", "uwspr_tx_render_moving", "uwspr_tx_baseband_at", "uwspr_tx_render_at", "uwspr_tx_design_at",
-    "uwspr_tx_render_medium", "uwspr_tx_baseband_medium", "uwspr_tx_fade_design",
-    "uwspr_subtract_batch", "uwspr_osd_batch", "uwspr_blockdemod_batch", "uwspr_deep_set_list", "uwspr_deep_batch",
-    "uwspr_calls_set", "uwspr_calls_batch", "uwspr_call_message",
-    "uwspr_dist_unique_id", "uwspr_dist_init", "uwspr_dist_gather", "uwspr_dist_finalize",
-    "uwspr_pipe_open", "uwspr_pipe_close", "uwspr_pipe_last_error", "uwspr_pipe_acquire", "uwspr_pipe_commit",
-    "uwspr_pipe_push", "uwspr_pipe_push_audio", "uwspr_pipe_push_audio_channels", "uwspr_pipe_submit_device", "uwspr_pipe_flush", "uwspr_pipe_collect", "uwspr_pipe_get_stats",
-    "uwspr_pipe_inject_failure", "uwspr_pipe_set_option", "uwspr_pipe_set_carriers", "uwspr_pipe_set_list", "uwspr_pipe_set_calls",
-]
+# ---- the signatures: name -> (restype, argtypes).  A new C entry point is declared here, in one line, and nowhere else.
+_vp, _ip, _ll, _u32, _sz, _str, _P = C.c_void_p, C.c_int, C.c_longlong, C.c_uint32, C.c_size_t, C.c_char_p, C.POINTER
+_vp2, _vp3, _vp4 = [_vp] * 2, [_vp] * 3, [_vp] * 4
+SIGNATURES = {
+    # every symbol include/uwspr_hip.h declares
+    "uwspr_ctx_create": (_ip, [_P(Params), _ip, _P(_vp)]),
+    "uwspr_ctx_destroy": (None, [_vp]),
+    "uwspr_last_error": (_str, [_vp]),
+    "uwspr_status_string": (_str, [_ip]),
+    "uwspr_get_info": (_ip, [_vp, _P(Info)]),
+    "uwspr_set_stream": (_ip, _vp2),
+    "uwspr_synchronize": (_ip, [_vp]),
+    "uwspr_frontend_batch": (_ip, [_vp, _vp, _ip, _ip, _ip, _vp]),
+    "uwspr_frontend_design": (_ip, [_ip, _ip, _vp, _ip, _vp]),
+    "uwspr_frontend_design_at": (_ip, [_ip, _ip, _ip, _ip, _vp, _ip, _vp]),
+    "uwspr_frontend_rotator": (_ip, [_vp]),
+    "uwspr_resample_design": (_ip, [_ip, _vp, _ip] + _vp4),
+    "uwspr_resample_batch": (_ip, [_vp, _vp, _ll, _ip, _ip, _ip, _ip, _vp, _ll]),
+    "uwspr_blank_batch": (_ip, [_vp, _vp, _ll, _ip, _ip, _ip, _ip, _ip] + _vp3),
+    "uwspr_stream_blank_stats": (_ip, _vp3 + [_ip]),
+    "uwspr_pipe_blank_stats": (_ip, _vp3 + [_ip]),
+    "uwspr_stream_open": (_ip, [_vp, _ip, _ip]),
+    "uwspr_stream_push": (_ip, [_vp, _vp, _ip, _ip, _P(_ip)]),
+    "uwspr_stream_push_audio": (_ip, [_vp, _vp, _ip, _ip, _ip, _P(_ip)]),
+    "uwspr_stream_take": (_ip, [_vp, _ip, _vp, _P(_vp), _P(_ll)]),
+    "uwspr_stream_reset": (_ip, [_vp, _ll]),
+    "uwspr_set_frame_stride": (_ip, [_vp, _ip]),
+    "uwspr_stream_wait_uploads": (_ip, [_vp]),
+    "uwspr_stream_take_view": (_ip, [_vp, _ip, _P(_vp), _P(_ip), _P(_ll)]),
+    "uwspr_device_alloc": (_ip, [_sz, _P(_vp)]),
+    "uwspr_device_free": (None, [_vp]),
+    "uwspr_host_alloc": (_ip, [_sz, _P(_vp)]),
+    "uwspr_host_free": (None, [_vp]),
+    "uwspr_fdr_batch": (_ip, [_vp, _vp, _ip, _ip, _vp, _vp]),
+    "uwspr_fdr_read_spectrum": (_ip, [_vp, _ip] + _vp4 + [_vp]),
+    "uwspr_fdr_keep_syncgrid": (_ip, [_vp, _ip]),
+    "uwspr_fdr_read_syncgrid": (_ip, [_vp, _ip, _vp]),
+    "uwspr_sync_sweep": (_ip, [_vp, _vp, _ip, _vp, _ip, _ip, _vp, _vp]),
+    "uwspr_sync_grid": (_ip, [_vp, _vp, _ip, _ip, _vp, _ip, _vp, _ip, _vp, _ip] + _vp3),
+    "uwspr_sync_and_demodulate_batch": (_ip, [_vp, _vp, _ip, _ip, _vp, _ip, _vp]),
+    "uwspr_demod_batch": (_ip, [_vp, _vp, _ip, _ip, _vp, _vp, _ip, _ip, _vp]),
+    "uwspr_pipeline_batch": (_ip, [_vp, _vp, _ip, _ip, _ip] + _vp3),
+    "uwspr_set_tries": (_ip, [_vp, _ip]),
+    "uwspr_set_option": (_ip, [_vp, _str, _ip]),
+    "uwspr_get_option": (_ip, [_vp, _str, _vp]),
+    "uwspr_demod_resume": (_ip, [_vp, _vp, _ip, _ip, _vp, _ip, _vp]),
+    "uwspr_pack_slabs": (_ip, [_vp, _ip, _ip, _vp, _ip]),
+    "uwspr_pipeline_slabs": (_ip, [_vp, _ip, _vp]),
+    "uwspr_prof_enable": (_ip, [_vp, _ip]),
+    "uwspr_prof_read": (_ip, [_vp, _P(Prof)]),
+    "uwspr_prof_intervals": (_ip, [_vp, _ip] + _vp3 + [_ip, _P(_ip)]),
+    "uwspr_deinterleave": (None, [_vp]),
+    "uwspr_fano_decode": (_ip, [_vp, _vp, _P(_u32), _P(_u32), _P(_u32), _ip, _u32]),
+    "uwspr_fano_encode": (_ip, [_vp, _vp, _u32]),
+    "uwspr_decode_candidate": (_ip, [_vp, _vp, _P(C.c_int32)]),
+    "uwspr_decode_batch": (_ip, [_vp, _ip, _ip] + _vp3),
+    "uwspr_host_threads": (_ip, []),
+    "uwspr_host_set_ranks": (_ip, [_ip]),
+    "uwspr_unpack_message": (_ip, [_vp, _str, _sz]),
+    "uwspr_c2_read": (_ip, [_str, _vp, _P(C.c_double), _P(C.c_int32)]),
+    "uwspr_wspr_pack": (_ip, [_str, _vp]),
+    "uwspr_nhash": (_u32, [_str, _sz, _u32]),
+    "uwspr_wspr_symbols": (_ip, _vp2),
+    "uwspr_c2_write": (_ip, [_str, _vp, _ip, C.c_double, C.c_int32]),
+    "uwspr_tx_baseband": (_ip, _vp2 + [_ip, _ip, _ll, _ip, _vp, _ip]),
+    "uwspr_tx_baseband_moving": (_ip, _vp3 + [_ip, _ip, _ll, _ip, _vp, _ip]),
+    "uwspr_tx_baseband_at": (_ip, _vp4 + [_ip, _ip, _ll, _ip, _vp, _ip]),
+    "uwspr_tx_baseband_medium": (_ip, _vp4 + [_vp, _ip, _ip, _ll, _ip, _vp, _ip]),
+    "uwspr_tx_render": (_ip, _vp2 + [_ip, _vp, _ip, _ll, _ll, _ip, _vp, _ip]),
+    "uwspr_tx_render_moving": (_ip, _vp3 + [_ip, _vp, _ip, _ll, _ll, _ip, _vp, _ip]),
+    "uwspr_tx_render_at": (_ip, _vp4 + [_ip, _vp, _ip, _ll, _ll, _ip, _vp, _ip]),
+    "uwspr_tx_render_medium": (_ip, _vp4 + [_vp, _ip, _vp, _vp, _ip, _ll, _ll, _ip, _vp, _ip]),
+    "uwspr_tx_design_at": (_ip, [_ip, _ip, _vp, _vp]),
+    "uwspr_tx_fade_design": (_ip, _vp4),
+    "uwspr_subtract_batch": (_ip, [_vp, _vp, _ip, _ip, _vp, _ip, _ip, _vp, _vp]),
+    "uwspr_osd_batch": (_ip, [_vp, _vp, _ip, _ip, _ip, _vp]),
+    "uwspr_blockdemod_batch": (_ip, [_vp, _vp, _ip, _ip, _vp, _ip, _vp]),
+    "uwspr_deep_set_list": (_ip, [_vp, _vp, _ip]),
+    "uwspr_deep_batch": (_ip, [_vp, _vp, _ip, _ip, _vp]),
+    "uwspr_calls_set": (_ip, [_vp, _vp, _ip, _vp, _u32]),
+    "uwspr_calls_batch": (_ip, [_vp, _vp, _ip, _ip, _vp]),
+    "uwspr_call_message": (_ip, [_str, _ip, _ip, _vp]),
+    "uwspr_dist_unique_id": (_ip, [_vp]),
+    "uwspr_dist_init": (_ip, [_vp, _ip, _ip, _vp]),
+    "uwspr_dist_gather": (_ip, [_vp, _vp, _sz, _vp, _ip, _ip]),
+    "uwspr_dist_finalize": (_ip, [_vp]),
+    "uwspr_pipe_open": (_ip, [_P(Params), _ip, _P(PipeOpts), _P(_vp)]),
+    "uwspr_pipe_close": (None, [_vp]),
+    "uwspr_pipe_last_error": (_str, [_vp]),
+    "uwspr_pipe_acquire": (_ip, [_vp, _ip, _P(_vp)]),
+    "uwspr_pipe_commit": (_ip, [_vp, _ip]),
+    "uwspr_pipe_push": (_ip, [_vp, _vp, _ip]),
+    "uwspr_pipe_push_audio": (_ip, [_vp, _vp, _ip, _ip]),
+    "uwspr_pipe_push_audio_channels": (_ip, [_vp, _vp, _ip, _ip, _ip]),
+    "uwspr_pipe_submit_device": (_ip, [_vp, _vp, _ip, _ip]),
+    "uwspr_pipe_flush": (_ip, [_vp]),
+    "uwspr_pipe_collect": (_ip, [_vp, _vp, _ip, _ip]),
+    "uwspr_pipe_get_stats": (_ip, [_vp, _P(PipeStats)]),
+    "uwspr_pipe_inject_failure": (_ip, [_vp, _ll, _ip]),
+    "uwspr_pipe_set_option": (_ip, [_vp, _str, _ip]),
+    "uwspr_pipe_set_carriers": (_ip, [_vp, _vp, _ip]),
+    "uwspr_pipe_set_list": (_ip, [_vp, _vp, _ip]),
+    "uwspr_pipe_set_calls": (_ip, [_vp, _vp, _ip, _vp, _u32]),
+    # diagnostics, outside the ABI header (defined extern "C" under csrc/)
+    "uwspr_debug_fdr_from_ps": (_ip, [_vp, _vp, _ip, _ip, _vp, _vp]),
+    "uwspr_debug_snr_db": (_ip, _vp3 + [_ll]),
+    "uwspr_debug_launch_forms": (_ip, [_vp, _vp, _ip]),
+    "uwspr_debug_frontend_launch": (_ip, [_vp, _vp, _ip, _ip, _ll, _ip, _vp, _ip, _ll, _ll]),
+    "uwspr_debug_frontend_carrier_launch": (_ip, [_vp, _vp, _ip, _ip, _ll, _ip, _ip, _vp, _vp, _ip, _ll, _ll]),
+    "uwspr_debug_resample_launch": (_ip, [_vp, _vp, _ip, _ll, _ll, _ip, _ip, _vp, _ll, _ll]),
+    "uwspr_debug_blank_launch": (_ip, [_vp, _vp, _ip, _ll, _ll, _ip, _vp, _ll, _ll, _ll, _ll, _ip, _ip, _vp, _ll, _ll, _vp]),
+    "uwspr_debug_tx_taps": (_ip, _vp2),
+    "uwspr_debug_tx_carrier_counts": (_ip, [_vp]),
+    "uwspr_debug_tx_medium_counts": (_ip, [_vp]),
+    "uwspr_debug_frontend_carrier_counts": (_ip, [_vp]),
+    "uwspr_debug_resample_counts": (_ip, [_vp]),
+    "uwspr_debug_blank_counts": (_ip, [_vp]),
+}
+ABI_SYMBOLS = [k for k in SIGNATURES if not k.startswith("uwspr_debug_")]
 
 _lib = None
 
@@ -328,116 +427,8 @@ def lib():
     except Exception:
         pass
     L = C.CDLL(LIBPATH)
-    vp, ip = C.c_void_p, C.c_int
-    L.uwspr_ctx_create.argtypes = [C.POINTER(Params), ip, C.POINTER(vp)]
-    L.uwspr_ctx_destroy.argtypes = [vp]
-    L.uwspr_ctx_destroy.restype = None
-    L.uwspr_last_error.argtypes = [vp]
-    L.uwspr_last_error.restype = C.c_char_p
-    L.uwspr_status_string.argtypes = [ip]
-    L.uwspr_status_string.restype = C.c_char_p
-    L.uwspr_get_info.argtypes = [vp, C.POINTER(Info)]
-    L.uwspr_set_stream.argtypes = [vp, vp]
-    L.uwspr_synchronize.argtypes = [vp]
-    L.uwspr_frontend_batch.argtypes = [vp, vp, ip, ip, ip, vp]
-    L.uwspr_frontend_design.argtypes = [ip, ip, vp, ip, vp]
-    L.uwspr_frontend_design_at.argtypes = [ip, ip, ip, ip, vp, ip, vp]
-    L.uwspr_frontend_rotator.argtypes = [vp]
-    L.uwspr_resample_design.argtypes = [ip, vp, ip, vp, vp, vp, vp]
-    L.uwspr_resample_batch.argtypes = [vp, vp, C.c_longlong, ip, ip, ip, ip, vp, C.c_longlong]
-    L.uwspr_blank_batch.argtypes = [vp, vp, C.c_longlong, ip, ip, ip, ip, ip, vp, vp, vp]
-    L.uwspr_stream_blank_stats.argtypes = [vp, vp, vp, ip]
-    L.uwspr_pipe_blank_stats.argtypes = [vp, vp, vp, ip]
-    L.uwspr_stream_open.argtypes = [vp, ip, ip]
-    L.uwspr_stream_push.argtypes = [vp, vp, ip, ip, C.POINTER(C.c_int)]
-    L.uwspr_stream_push_audio.argtypes = [vp, vp, ip, ip, ip, C.POINTER(C.c_int)]
-    L.uwspr_stream_take.argtypes = [vp, ip, vp, C.POINTER(vp), C.POINTER(C.c_longlong)]
-    L.uwspr_stream_reset.argtypes = [vp, C.c_longlong]
-    L.uwspr_set_frame_stride.argtypes = [vp, ip]
-    L.uwspr_stream_wait_uploads.argtypes = [vp]
-    L.uwspr_stream_take_view.argtypes = [vp, ip, C.POINTER(vp), C.POINTER(C.c_int), C.POINTER(C.c_longlong)]
-    L.uwspr_device_alloc.argtypes = [C.c_size_t, C.POINTER(vp)]
-    L.uwspr_device_free.argtypes = [vp]
-    L.uwspr_device_free.restype = None
-    L.uwspr_host_alloc.argtypes = [C.c_size_t, C.POINTER(vp)]
-    L.uwspr_host_free.argtypes = [vp]
-    L.uwspr_host_free.restype = None
-    L.uwspr_fdr_batch.argtypes = [vp, vp, ip, ip, vp, vp]
-    L.uwspr_fdr_read_spectrum.argtypes = [vp, ip, vp, vp, vp, vp, vp]
-    L.uwspr_fdr_keep_syncgrid.argtypes = [vp, ip]
-    L.uwspr_fdr_read_syncgrid.argtypes = [vp, ip, vp]
-    L.uwspr_debug_fdr_from_ps.argtypes = [vp, vp, ip, ip, vp, vp]     # diagnostics, outside the ABI header
-    L.uwspr_sync_sweep.argtypes = [vp, vp, ip, vp, ip, ip, vp, vp]
-    L.uwspr_sync_grid.argtypes = [vp, vp, ip, ip, vp, ip, vp, ip, vp, ip, vp, vp, vp]
-    L.uwspr_sync_and_demodulate_batch.argtypes = [vp, vp, ip, ip, vp, ip, vp]
-    L.uwspr_demod_batch.argtypes = [vp, vp, ip, ip, vp, vp, ip, ip, vp]
-    L.uwspr_pipeline_batch.argtypes = [vp, vp, ip, ip, ip, vp, vp, vp]
-    L.uwspr_set_tries.argtypes = [vp, ip]
-    L.uwspr_set_option.argtypes = [vp, C.c_char_p, ip]
-    L.uwspr_get_option.argtypes = [vp, C.c_char_p, vp]
-    L.uwspr_demod_resume.argtypes = [vp, vp, ip, ip, vp, ip, vp]
-    L.uwspr_pack_slabs.argtypes = [vp, ip, ip, vp, ip]
-    L.uwspr_pipeline_slabs.argtypes = [vp, ip, vp]
-    L.uwspr_prof_enable.argtypes = [vp, ip]
-    L.uwspr_prof_read.argtypes = [vp, C.POINTER(Prof)]
-    L.uwspr_prof_intervals.argtypes = [vp, ip, vp, vp, vp, ip, C.POINTER(C.c_int)]
-    L.uwspr_deinterleave.argtypes = [vp]
-    L.uwspr_deinterleave.restype = None
-    L.uwspr_fano_decode.argtypes = [vp, vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
-                                    C.POINTER(C.c_uint32), ip, C.c_uint32]
-    L.uwspr_fano_encode.argtypes = [vp, vp, C.c_uint32]
-    L.uwspr_decode_candidate.argtypes = [vp, vp, C.POINTER(C.c_int32)]
-    L.uwspr_decode_batch.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp]
-    L.uwspr_decode_batch.restype = C.c_int
-    L.uwspr_host_threads.argtypes = []
-    L.uwspr_host_set_ranks.argtypes = [ip]
-    L.uwspr_unpack_message.argtypes = [vp, C.c_char_p, C.c_size_t]
-    L.uwspr_c2_read.argtypes = [C.c_char_p, vp, C.POINTER(C.c_double), C.POINTER(C.c_int32)]
-    L.uwspr_wspr_pack.argtypes = [C.c_char_p, vp]
-    L.uwspr_nhash.argtypes = [C.c_char_p, C.c_size_t, C.c_uint32]
-    L.uwspr_nhash.restype = C.c_uint32
-    L.uwspr_wspr_symbols.argtypes = [vp, vp]
-    L.uwspr_c2_write.argtypes = [C.c_char_p, vp, ip, C.c_double, C.c_int32]
-    L.uwspr_tx_baseband.argtypes = [vp, vp, ip, ip, C.c_longlong, ip, vp, ip]
-    L.uwspr_tx_render.argtypes = [vp, vp, ip, vp, ip, C.c_longlong, C.c_longlong, ip, vp, ip]
-    L.uwspr_tx_baseband_moving.argtypes = [vp, vp, vp, ip, ip, C.c_longlong, ip, vp, ip]
-    L.uwspr_tx_render_moving.argtypes = [vp, vp, vp, ip, vp, ip, C.c_longlong, C.c_longlong, ip, vp, ip]
-    L.uwspr_tx_baseband_at.argtypes = [vp, vp, vp, vp, ip, ip, C.c_longlong, ip, vp, ip]
-    L.uwspr_tx_render_at.argtypes = [vp, vp, vp, vp, ip, vp, ip, C.c_longlong, C.c_longlong, ip, vp, ip]
-    L.uwspr_tx_design_at.argtypes = [ip, ip, vp, vp]
-    L.uwspr_tx_baseband_medium.argtypes = [vp, vp, vp, vp, vp, ip, ip, C.c_longlong, ip, vp, ip]
-    L.uwspr_tx_render_medium.argtypes = [vp, vp, vp, vp, vp, ip, vp, vp, ip, C.c_longlong, C.c_longlong, ip, vp, ip]
-    L.uwspr_tx_fade_design.argtypes = [vp, vp, vp, vp]
-    L.uwspr_subtract_batch.argtypes = [vp, vp, ip, ip, vp, ip, ip, vp, vp]
-    L.uwspr_osd_batch.argtypes = [vp, vp, ip, ip, ip, vp]
-    L.uwspr_blockdemod_batch.argtypes = [vp, vp, ip, ip, vp, ip, vp]
-    L.uwspr_deep_set_list.argtypes = [vp, vp, ip]
-    L.uwspr_deep_batch.argtypes = [vp, vp, ip, ip, vp]
-    L.uwspr_calls_set.argtypes = [vp, vp, ip, vp, C.c_uint32]
-    L.uwspr_calls_batch.argtypes = [vp, vp, ip, ip, vp]
-    L.uwspr_call_message.argtypes = [C.c_char_p, ip, ip, vp]
-    L.uwspr_dist_unique_id.argtypes = [vp]
-    L.uwspr_dist_init.argtypes = [vp, ip, ip, vp]
-    L.uwspr_dist_gather.argtypes = [vp, vp, C.c_size_t, vp, ip, ip]
-    L.uwspr_dist_finalize.argtypes = [vp]
-    L.uwspr_pipe_open.argtypes = [C.POINTER(Params), ip, C.POINTER(PipeOpts), C.POINTER(vp)]
-    L.uwspr_pipe_close.argtypes = [vp]
-    L.uwspr_pipe_close.restype = None
-    L.uwspr_pipe_last_error.argtypes = [vp]
-    L.uwspr_pipe_last_error.restype = C.c_char_p
-    L.uwspr_pipe_acquire.argtypes = [vp, ip, C.POINTER(vp)]
-    L.uwspr_pipe_commit.argtypes = [vp, ip]
-    L.uwspr_pipe_push.argtypes = [vp, vp, ip]
-    L.uwspr_pipe_push_audio.argtypes = [vp, vp, ip, ip]
-    L.uwspr_pipe_push_audio_channels.argtypes = [vp, vp, ip, ip, ip]
-    L.uwspr_pipe_submit_device.argtypes = [vp, vp, ip, ip]
-    L.uwspr_pipe_flush.argtypes = [vp]
-    L.uwspr_pipe_collect.argtypes = [vp, vp, ip, ip]
-    L.uwspr_pipe_get_stats.argtypes = [vp, C.POINTER(PipeStats)]
-    L.uwspr_pipe_inject_failure.argtypes = [vp, C.c_longlong, ip]
-    L.uwspr_pipe_set_option.argtypes = [vp, C.c_char_p, ip]
-    L.uwspr_pipe_set_carriers.argtypes = [vp, vp, ip]
-    L.uwspr_pipe_set_list.argtypes = [vp, vp, ip]
-    L.uwspr_pipe_set_calls.argtypes = [vp, vp, ip, vp, C.c_uint32]
+    for name, (restype, argtypes) in SIGNATURES.items():
+        f = getattr(L, name)
+        f.restype, f.argtypes = restype, argtypes
     _lib = L
     return L

@@ -20,6 +20,72 @@ def test_library_exports_every_declared_symbol(G):
         assert hasattr(L, s), s
 
 
+def _c_class(decl):
+    """the class of one C parameter (or return type) declaration: ptr, str (const char *), i32, i64, size, f64, f32, u32,
+    void"""
+    d = " ".join(decl.replace("UWSPR_API", " ").replace("extern", " ").replace('"C"', " ").split())
+    if "*" in d or "[" in d:
+        return "str" if re.match(r"const char \*", d) else "ptr"
+    for words, cls in (("long long", "i64"), ("int64_t", "i64"), ("uint64_t", "i64"), ("size_t", "size"), ("double", "f64"),
+                       ("float", "f32"), ("uint32_t", "u32"), ("int32_t", "i32"), ("int", "i32"), ("void", "void")):
+        if re.search(r"\b%s\b" % words, d):
+            return cls
+    raise AssertionError("unclassified C declaration %r" % decl)
+
+
+def _py_class(t):
+    """the class of one ctypes type of native.SIGNATURES"""
+    if t is None:
+        return "void"
+    if t is C.c_char_p:
+        return "str"
+    if t is C.c_void_p or hasattr(t, "contents"):         # (POINTER(x) types have .contents)
+        return "ptr"
+    assert C.sizeof(C.c_int) == 4 and C.sizeof(C.c_longlong) == 8
+    return {C.c_int: "i32", C.c_int32: "i32", C.c_longlong: "i64", C.c_int64: "i64", C.c_size_t: "size", C.c_double: "f64",
+            C.c_float: "f32", C.c_uint32: "u32"}[t]
+
+
+def _declared(text, names, body):
+    """{name: (return class, [parameter classes])} of the uwspr_* functions `names` (None: all) declared (body ';') or
+    defined (body '{') in C text"""
+    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
+    text = re.sub(r"//[^\n]*", " ", text)
+    out = {}
+    for m in re.finditer(r"([A-Za-z_][A-Za-z0-9_ \*\"]*?)\b(uwspr_[a-z0-9_]+)\s*\(([^;{}()]*)\)\s*" + re.escape(body), text):
+        ret, name, params = m.group(1), m.group(2), m.group(3).strip()
+        if (names is not None and name not in names) or re.search(r"\b(return|typedef|struct)\b", ret):
+            continue
+        assert name not in out, name
+        out[name] = (_c_class(ret), [] if params in ("", "void") else [_c_class(p) for p in params.split(",")])
+    return out
+
+
+def test_signature_table_matches_the_declarations(G):
+    """native.SIGNATURES against the C text, class by class, in order: every function of the header, and every
+    diagnostics entry against its extern "C" definition under csrc/.  (A wrong class is a silent truncation: a long long
+    passed as a 32-bit int.)  A char * the binding passes as a byte string and a void * are both pointers."""
+    N = G.native
+    table = {k: (_py_class(r), [_py_class(a) for a in args]) for k, (r, args) in N.SIGNATURES.items()}
+    hdr = _declared(open(os.path.join(os.path.dirname(N.CSRC), "..", "include", "uwspr_hip.h")).read(), None, ";")
+    assert set(hdr) == set(N.ABI_SYMBOLS), set(hdr) ^ set(N.ABI_SYMBOLS)
+    debug = {k for k in N.SIGNATURES if k.startswith("uwspr_debug_")}
+    defs = {}
+    for f in sorted(os.listdir(N.CSRC)):
+        if f.endswith((".hip", ".cpp")):
+            for k, v in _declared(open(os.path.join(N.CSRC, f)).read(), debug, "{").items():
+                assert k not in defs, k
+                defs[k] = v
+    assert set(defs) == debug, set(defs) ^ debug
+    same = lambda a, b: a == b or {a, b} == {"str", "ptr"}   # noqa: E731
+    for name, (ret, params) in dict(hdr, **defs).items():
+        pret, pparams = table[name]
+        assert pret == ret, (name, "returns", ret, "bound as", pret)
+        assert len(params) == len(pparams), (name, params, pparams)
+        for k, (c, p) in enumerate(zip(params, pparams)):
+            assert same(c, p), (name, "parameter", k, c, "bound as", p)
+
+
 def test_record_layouts(G):
     N = G.native
     assert N.CAND_DTYPE.itemsize == 48            # candidate_t, lib/candidate_t.h:27-50
