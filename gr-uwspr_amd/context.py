@@ -781,6 +781,40 @@ class Context:
         self._chk(self.L.uwspr_blockdemod_batch(self.h, p, B, N.HOST, ip, len(it), C.c_void_p(out.ctypes.data) if len(it) else None))
         return out
 
+    # -- trajectory fit of a decoded source (K15: uwspr_track_set, uwspr_track_batch) ----
+    def track_set(self, trajs, qf=4, model="delay"):
+        """The trajectory set: (v, d, tc) entries (track_trajs: tuples, dicts, an [n, 3] array or track_grid's result), 1 to
+        native.TRACK_MAX of them; qf: frequency offsets -qf .. qf of 0.0125 Hz around each; model "delay" (Doppler and time
+        compression) or "doppler" (include/uwspr_hip.h states the rules)."""
+        tr = track_trajs(trajs)
+        self._chk(self.L.uwspr_track_set(self.h, C.c_void_p(tr.ctypes.data) if len(tr) else None, len(tr), int(qf), _track_model(model)))
+        self._track = (len(tr), 2 * int(qf) + 1)
+
+    def track(self, frames, items, surface=False):
+        """Fit the set's trajectories to decoded transmissions.  items: Context.subtract's (a SUB_ITEM_DTYPE array, or dicts
+        with "frame", "shift", "f", "drift" and "symbols" / "text" / "message"), sorted by frame; frames: numpy, a torch CUDA
+        tensor or a FrameView.  -> a TRACK_RESULT_DTYPE array (best = trajectory * nf + offset index, t_best, t_ref, f_hz),
+        and with surface=True also T of every hypothesis, numpy [nitems, n, nf] float32."""
+        it = sub_items(items)
+        n, nf = getattr(self, "_track", (0, 1))
+        p, B, where, keep = self._frames(frames)
+        ip = C.c_void_p(it.ctypes.data) if len(it) else None
+        if where == N.DEVICE:   # device frames: the results are written to device memory and copied back
+            import torch
+            dev = frames.device
+            res = torch.zeros(max(len(it), 1) * N.TRACK_RESULT_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+            surf = torch.zeros(max(len(it) * n * nf, 1), dtype=torch.float32, device=dev) if surface else None
+            self._wait_torch(dev, always=True)
+            self._chk(self.L.uwspr_track_batch(self.h, p, B, N.DEVICE_FRAMES, ip, len(it), C.c_void_p(res.data_ptr()),
+                                               C.c_void_p(surf.data_ptr()) if surface else None))
+            out = res.cpu().numpy()[:len(it) * N.TRACK_RESULT_DTYPE.itemsize].view(N.TRACK_RESULT_DTYPE).copy()
+            return (out, surf.cpu().numpy()[:len(it) * n * nf].reshape(len(it), n, nf).copy()) if surface else out
+        out = np.zeros(len(it), N.TRACK_RESULT_DTYPE)
+        surf = np.zeros((len(it), n, nf), np.float32) if surface else None
+        self._chk(self.L.uwspr_track_batch(self.h, p, B, N.HOST, ip, len(it), C.c_void_p(out.ctypes.data) if len(it) else None,
+                                           C.c_void_p(surf.ctypes.data) if surface and surf.size else None))
+        return (out, surf) if surface else out
+
     # -- transmit side (K7: uwspr_tx_*) ------------------------------------
     def tx_baseband(self, signals, n=45000, t0=0, channel=0, out=None):
         """375 S/s baseband samples [t0, t0 + n) of one channel's signals (tx_signals), as c2_read returns a .c2 file:
@@ -1397,6 +1431,94 @@ def slm_drift(traj, t, cf=1500.0):
     return d
 
 
+def _track_model(model):
+    return _TX_MODELS[model] if isinstance(model, str) else int(model)
+
+
+def track_trajs(trajs):
+    """Trajectories (v m/s, d m, tc s) -> a TRACK_TRAJ_DTYPE array: arrays of that dtype pass through; else (v, d, tc)
+    tuples, dicts with those keys, or an [n, 3] array."""
+    if isinstance(trajs, np.ndarray) and trajs.dtype == N.TRACK_TRAJ_DTYPE:
+        return np.ascontiguousarray(trajs).reshape(-1)
+    if isinstance(trajs, dict):
+        trajs = [trajs]
+    rows = [(t["v"], t["d"], t["tc"]) if isinstance(t, dict) else tuple(t) for t in (trajs.tolist() if isinstance(trajs, np.ndarray) else list(trajs))]
+    out = np.zeros(len(rows), N.TRACK_TRAJ_DTYPE)
+    for i, r in enumerate(rows):
+        if len(r) != 3:
+            raise ValueError("trajectory %d: (v, d, tc), not %r" % (i, r))
+        out[i] = tuple(float(x) for x in r)
+    return out
+
+
+def track_grid(v, d, tc):
+    """The product grid of speeds v (m/s), CPA ranges d (m) and CPA times tc (s from the item's first sample) -> a
+    TRACK_TRAJ_DTYPE array, v slowest and tc fastest.  A source at rest has neither a CPA range nor a CPA time that matter:
+    v = 0 gives the single entry (0, d[0], 0)."""
+    v, d, tc = (np.atleast_1d(np.asarray(a, np.float64)) for a in (v, d, tc))
+    if not (v.size and d.size and tc.size):
+        raise ValueError("track_grid: v, d and tc need at least one value each")
+    rows = []
+    for a in v:
+        if a == 0.0:
+            rows.append((0.0, float(d[0]), 0.0))
+        else:
+            rows += [(float(a), float(b), float(c)) for b in d for c in tc]
+    if len(rows) > N.TRACK_MAX:
+        raise ValueError("track_grid: %d trajectories, a set holds at most %d" % (len(rows), N.TRACK_MAX))
+    return track_trajs(rows)
+
+
+def track_from_slm(traj, t_first=0.0):
+    """Straight-line-model parameters (V1, V2, p1, p2), or an [n, 4] array of them (slm_trajectories), with the trajectory
+    time t_first of the item's first sample -> the (v, d, tc) of uwspr_track_from_slm, a TRACK_TRAJ_DTYPE array [n]."""
+    a = np.asarray(traj, np.float64).reshape(-1, 4)
+    out = np.zeros(len(a), N.TRACK_TRAJ_DTYPE)
+    L = N.lib()
+    for i, (v1, v2, p1, p2) in enumerate(a):
+        rc = L.uwspr_track_from_slm(float(v1), float(v2), float(p1), float(p2), float(t_first), C.c_void_p(out[i:i + 1].ctypes.data))
+        if rc != 0:
+            raise N.UwsprError(rc, "track_from_slm: non-finite parameters %r" % ((v1, v2, p1, p2, t_first),))
+    return out
+
+
+def track_doppler(traj, t, cf=1500.0):
+    """The Doppler in Hz of trajectories (track_trajs) at times t (s from the item's first sample), binary64:
+    -(cf / c) Rdot(t) with R(t) = sqrt(d^2 + (v (t - tc))^2), c = 1500 m/s (0 where R = 0) -> [n, len(t)], or [len(t)] for
+    one trajectory given as a tuple or dict."""
+    one = isinstance(traj, (tuple, dict)) or (isinstance(traj, np.ndarray) and traj.dtype == N.TRACK_TRAJ_DTYPE and traj.ndim == 0)
+    tr = track_trajs([traj] if one else traj)
+    t = np.atleast_1d(np.asarray(t, np.float64))
+    a = tr["v"][:, None] * (t[None, :] - tr["tc"][:, None])
+    R = np.sqrt(tr["d"][:, None] * tr["d"][:, None] + a * a)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        out = np.where(R > 0, -(float(cf) / 1500.0) * ((tr["v"][:, None] * a) / np.where(R > 0, R, 1.0)), 0.0)
+    return out[0] if one else out
+
+
+def track_design(trajs, model="delay", cf=1500.0):
+    """uwspr_track_design: the per-symbol tables of trajectories (track_trajs) -> (dfreq [n, 162] float64 Hz relative to
+    mid-transmission, tau [n, 162] int32 samples; all zero for model "doppler")."""
+    tr = track_trajs(trajs)
+    df, ta = np.zeros((len(tr), N.NSYM), np.float64), np.zeros((len(tr), N.NSYM), np.int32)
+    rc = N.lib().uwspr_track_design(C.c_void_p(tr.ctypes.data) if len(tr) else None, len(tr), _track_model(model), float(cf),
+                                    C.c_void_p(df.ctypes.data), C.c_void_p(ta.ctypes.data))
+    if rc != 0:
+        raise N.UwsprError(rc, "track_design: trajectories outside 0 <= v <= 10, 1 <= d <= 1e6, |tc| <= 1e4, an unknown model or a bad cf")
+    return df, ta
+
+
+def track_motion(traj, bearing=0.0, model="delay"):
+    """A (v, d, tc) trajectory as a "motion" dict of tx_signals, so that what Context.track fits can be rendered: the CPA
+    lies at range d in direction `bearing` (rad; the fit cannot see it) and the source passes it at right angles;
+    trajectory time 0 is the transmission's first sample."""
+    tr = track_trajs([traj])[0]
+    v, d, tc = float(tr["v"]), float(tr["d"]), float(tr["tc"])
+    cb, sb = float(np.cos(bearing)), float(np.sin(bearing))
+    V = (-v * sb, v * cb)
+    return {"v": V, "p": (d * cb - V[0] * tc, d * sb - V[1] * tc), "t": 0.0, "model": model}
+
+
 def tx_sigma(snr_db, gain=1.0):
     """AWGN sigma (per 12 kS/s audio sample) that puts a transmission of baseband amplitude `gain` at snr_db in 2500 Hz
     at the transmit chain's output: the chain makes it a real tone of amplitude gain / 32 (the interpolation filter has
@@ -1453,9 +1575,11 @@ class Pipe:
                  threshold=10, device=0, hop=3375, batch_frames=256, max_per_frame=1, lanes=0,
                  host_threads=0, eager=False, sched=None, spare_after_us=0, passes=1, osd=0, osd_gap=None,
                  block=0, audio_rate=None, blank=0, blank_guard=None, carriers=None, frontend_hbw=None, known=None,
-                 deep_min=None, deep_gap=None, calls=None, call_grids=None, call_powers=None, call_min=None, call_gap=None):
+                 deep_min=None, deep_gap=None, calls=None, call_grids=None, call_powers=None, call_min=None, call_gap=None,
+                 tracks=None, track_qf=4, track_model="delay"):
         self.L = N.lib()
         self.carriers = [1500]
+        self.track_trajs, self.track_nf, self.track_qf = None, 1, 0
         self.h = C.c_void_p()
         self.fl = fl
         p = N.Params(fs, fl, spb, maxdrift, maxfreqs, halfbandwidth, cf, threshold)
@@ -1491,6 +1615,8 @@ class Pipe:
             if calls is not None and len(calls):   # the call set: K14 on what Fano timed out on and the list left (records with osd = 3)
                 self.set_calls(calls, call_grids, call_powers)
             options((call_min, "call_min", call_min is not None), (call_gap, "call_gap", call_gap is not None))
+            if tracks is not None and len(tracks):   # the trajectory set: K15 on every decoded record (tracks())
+                self.set_tracks(tracks, track_qf, track_model)
         except N.UwsprError:
             self.close()
             raise
@@ -1577,6 +1703,28 @@ class Pipe:
         arr, A, bm, pm = calls_args(calls, grids, powers)
         self._chk(self.L.uwspr_pipe_set_calls(self.h, arr, A, C.c_void_p(bm.ctypes.data) if bm is not None else None, pm))
 
+    def set_tracks(self, trajs, qf=4, model="delay"):
+        """uwspr_pipe_set_tracks: the trajectory set (as at Context.track_set; empty: the stage is off); only while nothing is
+        in flight"""
+        tr = track_trajs(trajs if trajs is not None else [])
+        self._chk(self.L.uwspr_pipe_set_tracks(self.h, C.c_void_p(tr.ctypes.data) if len(tr) else None, len(tr), int(qf), _track_model(model)))
+        self.track_trajs, self.track_qf, self.track_nf = (tr, int(qf), 2 * int(qf) + 1) if len(tr) else (None, 0, 1)
+
+    def tracks(self, cap=65536):
+        """uwspr_pipe_collect_tracks: the trajectory fits of the decoded records emitted so far (never waits), a
+        TRACK_RECORD_DTYPE array in the order of the decoded records: frame, cand, channel, pass and result (best, t_best,
+        t_ref, f_hz); track_of gives a record's (v, d, tc)."""
+        out = np.zeros(cap, N.TRACK_RECORD_DTYPE)
+        n = self._chk(self.L.uwspr_pipe_collect_tracks(self.h, C.c_void_p(out.ctypes.data), cap))
+        return out[:n].copy()
+
+    def track_of(self, rec):
+        """a track record -> the "track" dict of decode_wav: v, d, tc of the best trajectory, the fitted f, t_best, t_ref"""
+        r = rec["result"]
+        t = self.track_trajs[int(r["best"]) // self.track_nf]
+        return {"v": float(t["v"]), "d": float(t["d"]), "tc": float(t["tc"]), "f": float(r["f_hz"]),
+                "t_best": float(r["t_best"]), "t_ref": float(r["t_ref"])}
+
     def set_carriers(self, hz):
         """uwspr_pipe_set_carriers: K0's centres in Hz (distinct integers, order kept), before the first audio push.  With
         more than one, a record's "channel" field is the plane index: split_plane gives (channel, carrier)."""
@@ -1656,7 +1804,9 @@ def decode_wav(path, channels=None, **pipe_opts):
     the call search gave the message, calls=[callsigns]; else 0).
     channels="all": every channel of the file through one pipe, records in (take, channel, frame) order, each dict with
     its "channel".  carriers=[Hz, ..]: every channel is heard at each of them (Pipe(carriers=..)), records in (take,
-    channel, carrier, frame) order, each dict with its "carrier" in Hz ("channel" stays the audio channel)."""
+    channel, carrier, frame) order, each dict with its "carrier" in Hz ("channel" stays the audio channel).
+    tracks=grid (track_grid; with track_qf, track_model): every decoded dict gets a "track" dict -- v, d, tc of the best
+    straight-line pass, the fitted f, t_best and t_ref (Context.track states them)."""
     x, rate = read_wav(path, channels, any_rate=True)
     carriers = pipe_opts.get("carriers")
     pipe = Pipe(audio_rate=rate, **pipe_opts)
@@ -1666,6 +1816,7 @@ def decode_wav(path, channels=None, **pipe_opts):
             pipe.push_audio(x[k:k + piece])
         pipe.flush()
         recs = pipe.collect(cap=1 << 20)
+        fits = pipe.tracks(cap=1 << 20) if pipe.track_trajs is not None else None
     finally:
         pipe.close()
     out = []
@@ -1673,6 +1824,8 @@ def decode_wav(path, channels=None, **pipe_opts):
         if not r["decoded"]:
             continue
         d = record_dict(r)
+        if fits is not None:   # one per decoded record, in their order
+            d["track"] = pipe.track_of(fits[len(out)])
         ch, car = pipe.split_plane(r["channel"])
         if channels == "all":
             d["channel"] = ch

@@ -79,6 +79,13 @@ struct pipe_lane {
   std::vector<uwspr_block_item> blk_items;
   std::vector<uint8_t> blk_n;                // item -> the block length that decoded (0: none)
   std::vector<int8_t> blk_msg;               // [items][7]
+  // trajectory fit (uwspr_pipe_set_tracks): the decoded records of the running search as K15 items
+  std::vector<uwspr_sub_item> trk_items;
+  std::vector<int> trk_rec;                      // item -> record
+  std::vector<uwspr_track_result> trk_fetch;     // [items] as the kernel wrote them
+  std::vector<uwspr_track_result> trk_by_rec;    // [B*per]: the fit of record i of the running search, where it decoded
+  std::vector<uwspr_track_result> rec_trk;       // beside recs: the fit of each decoded record
+  std::vector<uwspr_track_record> trecs;         // the batch's track records, emitted with recs
 };
 
 // what the host tails of a batch add to the pipe's statistics
@@ -108,6 +115,9 @@ struct uwspr_pipe {
   // device set for all lanes (made and freed by set_calls, read-only in between)
   calls_set *call_set = nullptr;
   int call_min = UWSPR_CALL_MIN_DEFAULT, call_gap = UWSPR_CALL_GAP_DEFAULT;
+  // uwspr_pipe_set_tracks: K15 on every decoded record against the trajectory set; one device set for all lanes (made and
+  // freed by set_tracks, read-only in between)
+  trk_set *track_set = nullptr;
   int block = 0;    // uwspr_pipe_set_option("block"): 2, 3 = K10's soft symbols of block lengths 2 .. block for those records
   int audio_rate = 12000;   // uwspr_pipe_set_option("audio_rate"): the rate of the pushed audio (12000: no resampler, else K11 ahead of K0)
   int blank = 0, blank_guard = 2;   // uwspr_pipe_set_option("blank" / "blank_guard"): K12 ahead of K11 / K0 (blank 0: off)
@@ -136,6 +146,7 @@ struct uwspr_pipe {
   std::mutex m;
   std::condition_variable cv_lane, cv_work, cv_done, cv_turn;
   std::deque<uwspr_decode> done;
+  std::deque<uwspr_track_record> done_trk;   // uwspr_pipe_collect_tracks: pushed with the decode records they belong to
   bool stop = false;
   int64_t next_seq = 0, emit_seq = 0;     // batches launched / emitted (records leave in batch order)
   std::vector<std::thread> coords;         // one coordinator per lane: the host tails of consecutive batches overlap
@@ -367,6 +378,38 @@ static int block_tail(uwspr_pipe *q, pipe_lane &L, const float *frames, int nrec
   return UWSPR_OK;
 }
 
+// uwspr_pipe_set_tracks.  Behind the fallbacks every decoded record of the search -- Fano's, "block"'s, the list's, the call
+// search's and OSD's alike -- becomes one K15 item: the symbols of its message, the jig_shift of the try that decoded and
+// the frequency model the fine search correlated with (rules::fine_model: what the second pass subtracts with), over the
+// frames the search itself read.  The fits go to L.trk_by_rec; no decode record changes.  Its time counts as resume time.
+static int track_tail(uwspr_pipe *q, pipe_lane &L, const float *frames, int nrec, tail_acc &ta) {
+  const int per = q->per;
+  L.trk_items.clear(); L.trk_rec.clear();
+  for (int i = 0; i < nrec; i++) {
+    if (!lane_valid(q, L, i) || !L.dec[i]) continue;
+    const uwspr_demod_out &o = L.h_out[i];
+    uwspr_sub_item it;
+    memset(&it, 0, sizeof(it));
+    it.frame = i / per;
+    it.shift = o.jig_shift[L.idt[i] >= 0 && L.idt[i] < UWSPR_NJIG ? L.idt[i] : 0];
+    rules::fine_model(L.h_cands[i], o, (float)q->p.cf, &it.f_hz, &it.drift_hz);
+    if (uwspr_wspr_symbols(&L.msg[7 * (size_t)i], it.symbols)) return pfail(q, UWSPR_ERR_ARG, "trajectory fit: symbols of a decoded message");
+    L.trk_items.push_back(it); L.trk_rec.push_back(i);
+  }
+  const int n = (int)L.trk_items.size();
+  if (n == 0) return UWSPR_OK;
+  const double t0 = now_s();
+  uwspr_track_result *d_res = nullptr;
+  int rc = subtract_check(L.ctx, L.trk_items.data(), n, (nrec + per - 1) / per);
+  if (!rc) rc = track_run(L.ctx, q->track_set, frames, (size_t)L.ctx->fstride, L.trk_items.data(), n, nullptr, nullptr, &d_res);
+  if (rc) return pfail(q, rc, "trajectory fit: %s", uwspr_last_error(L.ctx));
+  L.trk_fetch.resize((size_t)n);
+  if ((rc = lane_fetch(q, L, L.trk_fetch.data(), d_res, (size_t)n * sizeof(uwspr_track_result)))) return rc;
+  for (int k = 0; k < n; k++) L.trk_by_rec[L.trk_rec[k]] = L.trk_fetch[k];
+  ta.resume_s += now_s() - t0;
+  return UWSPR_OK;
+}
+
 // The host tail of one search of B frames (the batch itself, first = true; or its second pass over the residual frames):
 // waits for the lane's event, runs Fano on what the GPU produced, resumes what try 0 did not decode, then the fallbacks.
 // Leaves L.dec / L.idt / L.msg / L.osdf / L.blkf for the B * per records of L.h_out.
@@ -465,7 +508,9 @@ static int host_tail(uwspr_pipe *q, pipe_lane &L, const float *frames, int B, bo
     if (const int rc = scored_tail(q, L, nrec, kListFallback, ta)) return rc;
   if (q->call_set)
     if (const int rc = scored_tail(q, L, nrec, kCallFallback, ta)) return rc;
-  if (q->osd > 0) return scored_tail(q, L, nrec, kOsdFallback, ta);
+  if (q->osd > 0)
+    if (const int rc = scored_tail(q, L, nrec, kOsdFallback, ta)) return rc;
+  if (q->track_set) return track_tail(q, L, frames, nrec, ta);
   return UWSPR_OK;
 }
 
@@ -493,6 +538,8 @@ static int second_pass(uwspr_pipe *q, pipe_lane &L, tail_acc &ta, int *ncand, in
 static int finish_batch(uwspr_pipe *q, pipe_lane &L) {
   const int per = q->per, B = L.B;
   L.recs.clear();   // (a failure below emits nothing for this batch)
+  L.rec_trk.clear(); L.trecs.clear();
+  const bool tracks = q->track_set != nullptr;
   tail_acc ta;
   if (const int rc = host_tail(q, L, L.frames, B, true, ta)) return rc;
   int ncand = 0, ndec = 0;
@@ -501,12 +548,22 @@ static int finish_batch(uwspr_pipe *q, pipe_lane &L) {
       const int i = b * per + j;
       if (!lane_valid(q, L, i)) continue;
       L.recs.push_back(make_record(L, b, i, j, L.h_npk[b], 0));
+      if (tracks) L.rec_trk.push_back(L.trk_by_rec[i]);
       ncand++; ndec += L.dec[i];
     }
   if (q->passes == 2 && ndec > 0) {
     const int rc = second_pass(q, L, ta, &ncand, &ndec);
-    if (rc) { L.recs.clear(); return rc; }
+    if (rc) { L.recs.clear(); L.rec_trk.clear(); return rc; }
   }
+  if (tracks)   // one track record per decoded record, in their order
+    for (size_t r = 0; r < L.recs.size(); r++) {
+      const uwspr_decode &d = L.recs[r];
+      if (!d.decoded) continue;
+      uwspr_track_record tr;
+      memset(&tr, 0, sizeof(tr));
+      tr.frame = d.frame; tr.cand = d.cand; tr.channel = d.channel; tr.pass = d.pass; tr.result = L.rec_trk[r];
+      L.trecs.push_back(tr);
+    }
   {
     std::lock_guard<std::mutex> lk(q->m);
     q->st.frames += B; q->st.batches += 1; q->st.candidates += ncand; q->st.decoded += ndec;
@@ -564,12 +621,15 @@ static int second_pass(uwspr_pipe *q, pipe_lane &L, tail_acc &ta, int *ncand, in
   // merge: the records of frame b, then what the second pass adds to it
   std::vector<uwspr_decode> merged;
   merged.reserve(L.recs.size() + (size_t)ns * per);
+  const bool tracks = q->track_set != nullptr;   // then L.rec_trk goes through the same merge, beside the records
+  std::vector<uwspr_track_result> mtrk;
+  auto keep = [&](size_t r) { merged.push_back(L.recs[r]); if (tracks) mtrk.push_back(L.rec_trk[r]); };
   size_t r0 = 0;
   for (int s = 0; s < ns; s++) {
     const int64_t fr = L.frame0 + L.slot_frame[s];
-    while (r0 < L.recs.size() && L.recs[r0].frame < fr) merged.push_back(L.recs[r0++]);
+    while (r0 < L.recs.size() && L.recs[r0].frame < fr) keep(r0++);
     const size_t first = r0, mfirst = merged.size();   // the frame's first record in L.recs / in merged
-    while (r0 < L.recs.size() && L.recs[r0].frame == fr) merged.push_back(L.recs[r0++]);
+    while (r0 < L.recs.size() && L.recs[r0].frame == fr) keep(r0++);
     int cand = (int)(r0 - first);
     for (int j = 0; j < per; j++) {
       const int i = s * per + j;
@@ -578,11 +638,13 @@ static int second_pass(uwspr_pipe *q, pipe_lane &L, tail_acc &ta, int *ncand, in
       for (size_t r = mfirst; r < merged.size() && !known; r++) known = merged[r].decoded && !memcmp(merged[r].message, &L.msg[7 * (size_t)i], 7);
       if (known) continue;
       merged.push_back(make_record(L, L.slot_frame[s], i, cand++, npk1[s], 1));
+      if (tracks) mtrk.push_back(L.trk_by_rec[i]);
       (*ncand)++; (*ndec)++;
     }
   }
-  while (r0 < L.recs.size()) merged.push_back(L.recs[r0++]);
+  while (r0 < L.recs.size()) keep(r0++);
   L.recs.swap(merged);
+  if (tracks) L.rec_trk.swap(mtrk);
   return UWSPR_OK;
 }
 
@@ -605,10 +667,11 @@ static void coordinator(uwspr_pipe *q) {
       Lp->claimed = true;
     }
     pipe_lane &L = *Lp;
-    (void)finish_batch(q, L);   // a failure is sticky in q->failed; the lane is released either way
+    if (finish_batch(q, L)) L.trecs.clear();   // a failure is sticky in q->failed; the lane is released either way
     {
       std::unique_lock<std::mutex> lk(q->m);
       q->cv_turn.wait(lk, [&]() { return q->emit_seq == L.seq; });
+      for (const uwspr_track_record &t : L.trecs) q->done_trk.push_back(t);   // (no later than the decode records they belong to)
       for (const uwspr_decode &d : L.recs) q->done.push_back(d);
       q->emit_seq++;
       L.launched = false; L.claimed = false; L.host_since = 0.0;
@@ -732,6 +795,7 @@ extern "C" void uwspr_pipe_close(uwspr_pipe *q) {
   }
   if (q->d_deep_tab) (void)hipFree(q->d_deep_tab);
   calls_free_set(q->call_set);
+  track_free_set(q->track_set);
   q->ring.close();
   for (int k = 0; k < uwspr_pipe::NSTAGE; k++) {
     if (q->h_stage[k]) (void)hipHostFree(q->h_stage[k]);
@@ -793,6 +857,7 @@ extern "C" int uwspr_pipe_open(const uwspr_params *p, int device, const uwspr_pi
     PHIP(q, hipEventCreateWithFlags(&L.ev_done, hipEventDisableTiming | hipEventBlockingSync));
     L.dec.resize((size_t)Bm * per); L.idt.resize((size_t)Bm * per); L.msg.resize((size_t)Bm * per * 7);
     L.osdf.resize((size_t)Bm * per);
+    L.trk_by_rec.resize((size_t)Bm * per);
     L.blkf.resize((size_t)Bm * per);
   }
   // pushed streams: the device ring and the page-locked staging buffers are made by the first acquire (open_ingest):
@@ -1125,6 +1190,40 @@ extern "C" int uwspr_pipe_set_calls(uwspr_pipe *q, const char *const *calls, int
   calls_free_set(q->call_set);   // (nothing in flight: no lane reads it)
   q->call_set = fresh;
   return UWSPR_OK;
+}
+
+// The trajectory set: checked, designed on the host and uploaded before anything of the pipe changes; one set for all lanes
+// (the lanes' contexts live on the pipe's device and only read it).  n = 0 clears it.
+extern "C" int uwspr_pipe_set_tracks(uwspr_pipe *q, const uwspr_track_traj *traj, int n, int qf, int model) {
+  if (!q) return UWSPR_ERR_ARG;
+  char why[256];
+  if (n != 0 && track_check(traj, n, UWSPR_TRACK_MAX, qf, model, why, sizeof(why))) return parg(q, "uwspr_pipe_set_tracks: %s", why);
+  if (const int f = q->failed.load()) return f;
+  trk_set *fresh = nullptr;
+  if (n > 0) {
+    (void)hipSetDevice(q->device);
+    int rc = UWSPR_OK;
+    fresh = track_build(traj, n, qf, model, (double)q->p.cf, &rc, why, sizeof(why));
+    if (!fresh) return rc == UWSPR_ERR_ARG ? parg(q, "uwspr_pipe_set_tracks: %s", why) : pfail(q, rc, "uwspr_pipe_set_tracks: %s", why);
+  }
+  std::lock_guard<std::mutex> lk(q->m);
+  if (!lanes_idle_locked(q, "uwspr_pipe_set_tracks")) {
+    track_free_set(fresh);
+    return UWSPR_ERR_ARG;
+  }
+  track_free_set(q->track_set);   // (nothing in flight: no lane reads it)
+  q->track_set = fresh;
+  return UWSPR_OK;
+}
+
+// the track records emitted so far, at most cap of them; never waits
+extern "C" int uwspr_pipe_collect_tracks(uwspr_pipe *q, uwspr_track_record *out, int cap) {
+  if (!q || (cap > 0 && !out) || cap < 0) return UWSPR_ERR_ARG;
+  std::lock_guard<std::mutex> lk(q->m);
+  if (q->failed.load() && q->done_trk.empty()) return q->failed.load();
+  int n = 0;
+  while (n < cap && !q->done_trk.empty()) { out[n++] = q->done_trk.front(); q->done_trk.pop_front(); }
+  return n;
 }
 
 extern "C" int uwspr_pipe_flush(uwspr_pipe *q) {

@@ -177,6 +177,9 @@ void deep_release(uwspr_ctx *c); // k13_deep.hip: frees what uwspr_deep_set_list
 struct calls_state;
 struct calls_set;
 void calls_release(uwspr_ctx *c); // k14_calls.hip: frees what uwspr_calls_set / uwspr_calls_batch made
+struct trk_state;
+struct trk_set;
+void trk_release(uwspr_ctx *c);  // k15_track.hip: frees what uwspr_track_set / uwspr_track_batch made
 
 }  // namespace uwspr
 
@@ -284,6 +287,8 @@ struct uwspr_ctx {
   uwspr::deep_state *deep;
   // call search (k14_calls.hip): the call set and call scratch, made by uwspr_calls_set / the first use
   uwspr::calls_state *calls;
+  // trajectory fit (k15_track.hip): the set's tables and call scratch, made by uwspr_track_set
+  uwspr::trk_state *trk;
 
   int prof_mask;
   std::vector<uwspr::ev_pair> prof_events;
@@ -338,6 +343,18 @@ long long calls_count(const calls_set *s);
 int blockdemod_check(uwspr_ctx *c, const uwspr_block_item *items, int nitems, int nframes);
 int blockdemod_run(uwspr_ctx *c, const float *src, size_t stride, const uwspr_block_item *items, int nitems, uint8_t *out,
                    uint8_t **out_dev);
+
+// K15 (k15_track.hip): a trajectory set is checked (track_check: null when it keeps the rules at uwspr_track_set, else what
+// is wrong, no device asked) and built into memory of the current device (track_build: null with *status and msg on
+// failure; read-only from then on, freed by track_free_set).  track_run: nitems > 0 items (host records that passed
+// subtract_check) on the context's stream against a set (null = the set of uwspr_track_set); src: device frames, frame b at
+// src + 2 stride b floats; results to res and the surface to surface (device memory), or with either null to a buffer of
+// the context (the results' handed back through *res_out).
+const char *track_check(const uwspr_track_traj *traj, int n, int nmax, int qf, int model, char *msg, size_t cap);
+trk_set *track_build(const uwspr_track_traj *traj, int n, int qf, int model, double cf, int *status, char *msg, size_t cap);
+void track_free_set(trk_set *s);
+int track_run(uwspr_ctx *c, const trk_set *set, const float *src, size_t stride, const uwspr_sub_item *items, int nitems,
+              uwspr_track_result *res, float *surface, uwspr_track_result **res_out);
 
 // ---- launchers (each enqueues on ctx->stream) ------------------------------
 int frontend_design(int mode, int stage, std::vector<double> &out, int *delay);

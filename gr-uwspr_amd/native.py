@@ -26,7 +26,7 @@ LIBPATH = os.path.join(LIBDIR, "libuwspr_hip_exp_%s.so" % _EXTRA_TAG if _EXTRA e
 HOSTLIB = os.path.join(LIBDIR, "libuwspr_blocks.so")
 
 SOURCES = ["uwspr_api.hip", "k0_frontend.hip", "k1_spectrogram.hip", "k2_spectrum.hip", "k3_coarse.hip",
-           "k4_tonecorr.hip", "k4_grid.hip", "k4_pair.hip", "k4_jig.hip", "k5_fold_schedule.hip", "k6_sched.hip", "k7_transmit.hip", "k8_subtract.hip", "k9_osd.hip", "k10_blockdemod.hip", "k11_resample.hip", "k12_blank.hip", "k13_deep.hip", "k14_calls.hip", "pipe.hip", "dist.hip", "host_tail.cpp"]
+           "k4_tonecorr.hip", "k4_grid.hip", "k4_pair.hip", "k4_jig.hip", "k5_fold_schedule.hip", "k6_sched.hip", "k7_transmit.hip", "k8_subtract.hip", "k9_osd.hip", "k10_blockdemod.hip", "k11_resample.hip", "k12_blank.hip", "k13_deep.hip", "k14_calls.hip", "k15_track.hip", "pipe.hip", "dist.hip", "host_tail.cpp"]
 HIPFLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off",
             "-fno-slp-vectorize", "-fhip-fp32-correctly-rounded-divide-sqrt", "-fPIC", "-Wall", "-Wno-unused-function"]
 
@@ -227,6 +227,11 @@ assert CALL_RESULT_DTYPE.itemsize == 32
 CALLS_MAX, CALL_NGRID = 64, 32400   # UWSPR_CALLS_MAX, UWSPR_CALL_NGRID
 P19 = (0, 3, 7, 10, 13, 17, 20, 23, 27, 30, 33, 37, 40, 43, 47, 50, 53, 57, 60)   # the type-1 powers in dBm (UWSPR_CALL_NPOW of them)
 CALL_MIN_DEFAULT, CALL_GAP_DEFAULT = 5370, 725   # UWSPR_CALL_MIN_DEFAULT, UWSPR_CALL_GAP_DEFAULT
+TRACK_TRAJ_DTYPE = np.dtype([("v", "<f8"), ("d", "<f8"), ("tc", "<f8")])
+TRACK_RESULT_DTYPE = np.dtype([("best", "<i4"), ("t_best", "<f4"), ("t_ref", "<f4"), ("f_hz", "<f4")])
+TRACK_RECORD_DTYPE = np.dtype([("frame", "<i8"), ("cand", "<i4"), ("channel", "<i2"), ("pass", "u1"), ("_pad", "u1"), ("result", TRACK_RESULT_DTYPE)])
+assert TRACK_TRAJ_DTYPE.itemsize == 24 and TRACK_RESULT_DTYPE.itemsize == 16 and TRACK_RECORD_DTYPE.itemsize == 32
+TRACK_MAX, TRACK_QF_MAX = 4096, 16
 PIPE_MAX_CHANNELS = 64
 
 
@@ -364,6 +369,10 @@ SIGNATURES = {
     "uwspr_calls_set": (_ip, [_vp, _vp, _ip, _vp, _u32]),
     "uwspr_calls_batch": (_ip, [_vp, _vp, _ip, _ip, _vp]),
     "uwspr_call_message": (_ip, [_str, _ip, _ip, _vp]),
+    "uwspr_track_design": (_ip, [_vp, _ip, _ip, C.c_double, _vp, _vp]),
+    "uwspr_track_from_slm": (_ip, [C.c_double] * 5 + [_vp]),
+    "uwspr_track_set": (_ip, [_vp, _vp, _ip, _ip, _ip]),
+    "uwspr_track_batch": (_ip, [_vp, _vp, _ip, _ip, _vp, _ip, _vp, _vp]),
     "uwspr_dist_unique_id": (_ip, [_vp]),
     "uwspr_dist_init": (_ip, [_vp, _ip, _ip, _vp]),
     "uwspr_dist_gather": (_ip, [_vp, _vp, _sz, _vp, _ip, _ip]),
@@ -385,6 +394,8 @@ SIGNATURES = {
     "uwspr_pipe_set_carriers": (_ip, [_vp, _vp, _ip]),
     "uwspr_pipe_set_list": (_ip, [_vp, _vp, _ip]),
     "uwspr_pipe_set_calls": (_ip, [_vp, _vp, _ip, _vp, _u32]),
+    "uwspr_pipe_set_tracks": (_ip, [_vp, _vp, _ip, _ip, _ip]),
+    "uwspr_pipe_collect_tracks": (_ip, [_vp, _vp, _ip]),
     # diagnostics, outside the ABI header (defined extern "C" under csrc/)
     "uwspr_debug_fdr_from_ps": (_ip, [_vp, _vp, _ip, _ip, _vp, _vp]),
     "uwspr_debug_snr_db": (_ip, _vp3 + [_ll]),
@@ -399,6 +410,7 @@ SIGNATURES = {
     "uwspr_debug_frontend_carrier_counts": (_ip, [_vp]),
     "uwspr_debug_resample_counts": (_ip, [_vp]),
     "uwspr_debug_blank_counts": (_ip, [_vp]),
+    "uwspr_debug_track_time": (_ip, [_vp, _ip, _vp]),
 }
 ABI_SYMBOLS = [k for k in SIGNATURES if not k.startswith("uwspr_debug_")]
 

@@ -58,7 +58,11 @@ extern "C" {
                                     uwspr_pipe_set_calls, the pipe options "call_min" and "call_gap", uwspr_decode.osd = 3;
                                     transmit through a medium (entry points and records only, so the version stays):
                                     uwspr_tx_fade, uwspr_tx_impulse, uwspr_tx_render_medium, uwspr_tx_baseband_medium,
-                                    uwspr_tx_fade_design */
+                                    uwspr_tx_fade_design;
+                                    trajectory fit of a decoded source (entry points and records only, so the version stays):
+                                    uwspr_track_traj, uwspr_track_result, uwspr_track_design, uwspr_track_from_slm,
+                                    uwspr_track_set, uwspr_track_batch, uwspr_track_record, uwspr_pipe_set_tracks,
+                                    uwspr_pipe_collect_tracks */
 
 typedef enum {
   UWSPR_OK = 0,
@@ -1193,6 +1197,86 @@ int uwspr_calls_set(uwspr_ctx *ctx, const char *const *calls, int A, const uint8
                     uint32_t power_mask);
 int uwspr_calls_batch(uwspr_ctx *ctx, const uint8_t *symbols /*[n][162]*/, int n, int where, uwspr_call_result *res);
 int uwspr_call_message(const char *call, int ngrid, int dbm, int8_t *message7);
+
+/* ---- track a decoded source (K15, k15_track.hip) ---------------------------------------------------------------------- */
+/* A decoded transmission is the best probe of the sender's motion there is: all 162 symbols are known, so its Doppler and
+ * its time compression can be fitted over 110 s.  K15 correlates the known symbols over straight-line passes, as K8's
+ * refinement does over lag and frequency.  The reference has no counterpart; the definition is this project's and
+ * tests/track_exact.py restates it in binary64.  Binary32 with fused multiply-adds on the device; everything that decides
+ * an index or a phase is binary64.  df = 375/256, c = 1500 m/s, fc = uwspr_params.cf (the Doppler scale K3 uses).
+ * A trajectory is (v, d, tc): speed in m/s, range at the closest point of approach (CPA) in m, CPA time in s counted from
+ * the item's first sample -- the straight-line model of lib/slm.cc with its redundant degrees of freedom removed (one
+ * hydrophone cannot see bearing).  With t in s from the item's first sample, in binary64 and in this one order,
+ *     a = v (t - tc),   R(t) = sqrt(d d + a a),   Rdot(t) = (v a) / R(t)       (every product and sum rounded on its own)
+ * and symbol i taken at its centre t_i = (256 i + 128) / 375 (the numerator an exact integer).  Per trajectory and symbol
+ *     dfreq[i] = -((fc / c) (Rdot(t_i) - Rdot(t_81)))                     Hz: the Doppler relative to mid-transmission --
+ *                the constant part cannot be told from the sender's oscillator offset and stays in the fitted frequency;
+ *     tau[i]   = rint((375 (R(t_i) - R(t_81))) / c)                       samples, halves to even, with UWSPR_TX_DELAY
+ *                (time compression: a receding source arrives later); 0 with UWSPR_TX_DOPPLER.
+ * A symbol's frequency is constant: the chirp inside a symbol is ignored (at most about 0.1 Hz at v = 2.8 m/s, d = 50 m).
+ * Allowed: 0 <= v <= 10, 1 <= d <= 1e6, |tc| <= 1e4, all finite; then |tau| <= 139.  For SLM parameters (V1, V2, p1, p2)
+ * and the trajectory time t_first of the item's first sample, uwspr_track_from_slm gives v = |V|, d = |V1 p2 - V2 p1| / v,
+ * tc = -(V.p) / v^2 - t_first (v = 0: d = |p|, tc = 0; d is not checked: the receiver's grid holds radial passes, d = 0),
+ * and -(fc / c) Rdot(t) is slmFrequencyDrift.
+ * uwspr_track_design: HOST only, no context: dfreq [n][162] and tau [n][162] of n >= 1 trajectories for model
+ * UWSPR_TX_DOPPLER / UWSPR_TX_DELAY and the Doppler scale cf (Hz, 0 < cf <= 1e6); UWSPR_ERR_ARG for anything else.
+ * The score.  An item is a uwspr_sub_item: frame, shift s, f_hz, drift_hz, symbols.  A hypothesis is
+ * h = j nf + (q + qf): j the trajectory, q = -qf .. qf the frequency offset in K8's step of 0.0125 Hz, nf = 2 qf + 1,
+ * 0 <= qf <= 16:
+ *     f_i(h) = f_hz + 0.0125 q + dfreq[j][i] + (symbols[i] - 1.5) df
+ *     T(h)   = sum_i | sum_{k < 256} x[s + 256 i + tau[j][i] + k] e^{-j 2 pi f_i(h) k / 375} |
+ * Samples outside [0, fl) count as 0 (K8's rule, not the fine search's); the phasor starts at (1, 0) in every symbol; the
+ * hypotheses do NOT use drift_hz (the motion replaces the linear drift).  T_ref is the same sum for the item's own linear
+ * model, f_i = f_hz + (drift_hz / 2)(i - 81) / 81 + (symbols[i] - 1.5) df with tau = 0, through the same code: a v = 0
+ * trajectory at q = 0 of an item with drift_hz = 0 gives the bytes of T_ref.
+ * Result per item: best = the first maximum of T in ascending h (the walk moves on `>` alone: a NaN T is never moved to, a
+ * NaN T(0) is never left -- K8's rule); t_best = T(best); t_ref; f_hz = f_hz + 0.0125 q_best, formed in binary64 and rounded
+ * to binary32.  The trajectory is best / nf.  Every sum has one owner and one order: an item's bytes depend neither on the
+ * rest of the batch nor on where the frames live.
+ * uwspr_track_set: 1 <= n <= 4096 trajectories in HOST memory, qf, model; checked, designed on the host and uploaded before
+ * anything of the context changes (UWSPR_ERR_ARG leaves the set before in place); it replaces the set before.
+ * uwspr_track_batch: frames, items and `where` as for uwspr_blockdemod_batch: items are HOST memory whatever `where` says
+ * and keep the rules of uwspr_subtract_batch; res [nitems] and surface [nitems][n nf] (binary32 T of every hypothesis; NULL:
+ * not written) are host memory with UWSPR_HOST (complete on return), device memory with UWSPR_DEVICE (asynchronous on the
+ * context's stream) and UWSPR_DEVICE_FRAMES (complete on return).  UWSPR_ERR_ARG before any launch, the outputs untouched:
+ * an item that uwspr_subtract_batch would refuse, a call without a set, a device output outside a device allocation of the
+ * context's device.  nitems = 0 is fine.
+ * Not built: the fit is not fed back into the second pass's subtraction or into the fine search; there is no lag search
+ * (a constant shift error costs every hypothesis alike); bearing, which one hydrophone cannot see.
+ * In a pipe.  uwspr_pipe_set_tracks gives a pipe a trajectory set (n = 0 clears it; legal only while no batch is in flight,
+ * as uwspr_pipe_set_list; UWSPR_ERR_ARG otherwise and for a set that breaks the rules, and nothing changes).  With a set,
+ * every DECODED record -- of either pass, and decoded by Fano, "block", "osd", the list or the call search alike -- becomes
+ * one item behind the host tail and the fallbacks: the symbols of the record's message, the jig_shift of the try that decoded,
+ * f1 and drift1 as the second pass forms them (for a NONLINEAR candidate the constant f1 + slmFrequencyDrift(t = 0) the fine
+ * search correlated with, without drift), over the frames that search read (the second pass's records: the residual
+ * frames).  uwspr_decode has no free byte, so the fits leave by a door of their own: uwspr_pipe_collect_tracks never waits
+ * and returns at most cap records {frame, cand, channel, pass, result} in the order of the decoded records; each becomes
+ * available no later than its decode record (both are emitted under one lock, the track records first).  K15's time counts
+ * in resume_s.  Without a set nothing of K15 runs or is allocated, and every record and statistic is what it was. */
+#define UWSPR_TRACK_MAX 4096
+#define UWSPR_TRACK_QF_MAX 16
+typedef struct uwspr_track_traj {
+  double v, d, tc;   /* m/s, m, s */
+} uwspr_track_traj;
+typedef struct uwspr_track_result {
+  int32_t best;      /* h of the first maximum; trajectory best / nf, offset q = best % nf - qf */
+  float t_best, t_ref;
+  float f_hz;        /* f_hz + 0.0125 q */
+} uwspr_track_result;
+int uwspr_track_design(const uwspr_track_traj *traj, int n, int model, double cf, double *dfreq /*[n][162]*/, int32_t *tau /*[n][162]*/);
+int uwspr_track_from_slm(double v1, double v2, double p1, double p2, double t_first, uwspr_track_traj *out);
+int uwspr_track_set(uwspr_ctx *ctx, const uwspr_track_traj *traj, int n, int qf, int model);
+int uwspr_track_batch(uwspr_ctx *ctx, const float *frames, int B, int where, const uwspr_sub_item *items, int nitems,
+                      uwspr_track_result *res, float *surface /*[nitems][n nf] or NULL*/);
+typedef struct uwspr_track_record {
+  int64_t frame;     /* uwspr_decode.frame, .cand, .channel and .pass of the decoded record this fit belongs to */
+  int32_t cand;
+  int16_t channel;
+  uint8_t pass, _pad;
+  uwspr_track_result result;
+} uwspr_track_record;
+int uwspr_pipe_set_tracks(uwspr_pipe *pipe, const uwspr_track_traj *traj, int n, int qf, int model);
+int uwspr_pipe_collect_tracks(uwspr_pipe *pipe, uwspr_track_record *out, int cap);
 
 #ifdef __cplusplus
 }
