@@ -1,7 +1,7 @@
 """gr-uwspr_amd -- MI355X (gfx950) implementation of gr-uwspr's coarse (FDR) and
 fine (sync_and_demodulate) search path behind the C ABI in include/uwspr_hip.h.
 
-    csrc/     hand-written HIP kernels K0..K15 + the C ABI + the host tail
+    csrc/     hand-written HIP kernels K0..K16 + the C ABI + the host tail
     host/     C++ mirror of the gr::uwspr block API on top of the C ABI
     native.py build (hipcc, gfx950) + ctypes binding
     context.py thin Python handle used by tests/ and bench.py

@@ -815,6 +815,45 @@ class Context:
                                            C.c_void_p(surf.ctypes.data) if surface and surf.size else None))
         return (out, surf) if surface else out
 
+    # -- blind demodulation along straight-line passes (K16: uwspr_follow_set, uwspr_follow_batch) ----
+    def follow_set(self, grid, qf=8, lags=1, model="doppler"):
+        """The follow set: (v, d, tc) passes as at track_set; qf: frequency offsets -qf .. qf of 375/2048 Hz (0 .. 16);
+        lags: -lags .. lags steps of 32 samples (0 .. 4); model "doppler" or "delay" (include/uwspr_hip.h states the rules)."""
+        tr = track_trajs(grid)
+        self._chk(self.L.uwspr_follow_set(self.h, C.c_void_p(tr.ctypes.data) if len(tr) else None, len(tr), int(qf), int(lags), _track_model(model)))
+        self._follow = (len(tr), 2 * int(qf) + 1, 2 * int(lags) + 1)
+
+    def follow(self, frames, items, surface=False):
+        """Demodulate records blind along the set's passes.  items: Context.blockdemod's (a BLOCK_ITEM_DTYPE array, or dicts
+        with "frame", "shift", "f", "drift"), sorted by frame; frames: numpy, a torch CUDA tensor or a FrameView.  -> (a
+        FOLLOW_RESULT_DTYPE array (best = (trajectory * nf + offset index) * nlg + lag index, s_best, s_ref, f_hz), the soft
+        symbols of the best hypothesis, numpy [nitems, 162] uint8 as uwspr_demod_out.symbols[idt] holds a vector), and with
+        surface=True also S of every hypothesis, numpy [nitems, n, nf, nlg] float32."""
+        it = block_items(items)
+        n, nf, nlg = getattr(self, "_follow", (0, 1, 1))
+        p, B, where, keep = self._frames(frames)
+        ip = C.c_void_p(it.ctypes.data) if len(it) else None
+        nh = n * nf * nlg
+        if where == N.DEVICE:   # device frames: the results are written to device memory and copied back
+            import torch
+            dev = frames.device
+            res = torch.zeros(max(len(it), 1) * N.FOLLOW_RESULT_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+            sym = torch.zeros(max(len(it), 1) * N.NSYM, dtype=torch.uint8, device=dev)
+            surf = torch.zeros(max(len(it) * nh, 1), dtype=torch.float32, device=dev) if surface else None
+            self._wait_torch(dev, always=True)
+            self._chk(self.L.uwspr_follow_batch(self.h, p, B, N.DEVICE_FRAMES, ip, len(it), C.c_void_p(res.data_ptr()),
+                                                C.c_void_p(sym.data_ptr()), C.c_void_p(surf.data_ptr()) if surface else None))
+            out = res.cpu().numpy()[:len(it) * N.FOLLOW_RESULT_DTYPE.itemsize].view(N.FOLLOW_RESULT_DTYPE).copy()
+            osym = sym.cpu().numpy()[:len(it) * N.NSYM].reshape(len(it), N.NSYM).copy()
+            return (out, osym, surf.cpu().numpy()[:len(it) * nh].reshape(len(it), n, nf, nlg).copy()) if surface else (out, osym)
+        out = np.zeros(len(it), N.FOLLOW_RESULT_DTYPE)
+        osym = np.zeros((len(it), N.NSYM), np.uint8)
+        surf = np.zeros((len(it), n, nf, nlg), np.float32) if surface else None
+        self._chk(self.L.uwspr_follow_batch(self.h, p, B, N.HOST, ip, len(it), C.c_void_p(out.ctypes.data) if len(it) else None,
+                                            C.c_void_p(osym.ctypes.data) if len(it) else None,
+                                            C.c_void_p(surf.ctypes.data) if surface and surf.size else None))
+        return (out, osym, surf) if surface else (out, osym)
+
     # -- transmit side (K7: uwspr_tx_*) ------------------------------------
     def tx_baseband(self, signals, n=45000, t0=0, channel=0, out=None):
         """375 S/s baseband samples [t0, t0 + n) of one channel's signals (tx_signals), as c2_read returns a .c2 file:
@@ -1576,10 +1615,11 @@ class Pipe:
                  host_threads=0, eager=False, sched=None, spare_after_us=0, passes=1, osd=0, osd_gap=None,
                  block=0, audio_rate=None, blank=0, blank_guard=None, carriers=None, frontend_hbw=None, known=None,
                  deep_min=None, deep_gap=None, calls=None, call_grids=None, call_powers=None, call_min=None, call_gap=None,
-                 tracks=None, track_qf=4, track_model="delay"):
+                 tracks=None, track_qf=4, track_model="delay", follow=None, follow_qf=8, follow_lags=1, follow_model="doppler"):
         self.L = N.lib()
         self.carriers = [1500]
         self.track_trajs, self.track_nf, self.track_qf = None, 1, 0
+        self.follow_trajs, self.follow_nf, self.follow_qf, self.follow_nl = None, 1, 0, 0
         self.h = C.c_void_p()
         self.fl = fl
         p = N.Params(fs, fl, spb, maxdrift, maxfreqs, halfbandwidth, cf, threshold)
@@ -1617,6 +1657,8 @@ class Pipe:
             options((call_min, "call_min", call_min is not None), (call_gap, "call_gap", call_gap is not None))
             if tracks is not None and len(tracks):   # the trajectory set: K15 on every decoded record (tracks())
                 self.set_tracks(tracks, track_qf, track_model)
+            if follow is not None and len(follow):   # the follow set: K16 on what Fano timed out on (records with osd = 4, follows())
+                self.set_follow(follow, follow_qf, follow_lags, follow_model)
         except N.UwsprError:
             self.close()
             raise
@@ -1725,6 +1767,31 @@ class Pipe:
         return {"v": float(t["v"]), "d": float(t["d"]), "tc": float(t["tc"]), "f": float(r["f_hz"]),
                 "t_best": float(r["t_best"]), "t_ref": float(r["t_ref"])}
 
+    def set_follow(self, grid, qf=8, lags=1, model="doppler"):
+        """uwspr_pipe_set_follow: the follow set (as at Context.follow_set; empty: the stage is off); only while nothing is in
+        flight"""
+        tr = track_trajs(grid if grid is not None else [])
+        self._chk(self.L.uwspr_pipe_set_follow(self.h, C.c_void_p(tr.ctypes.data) if len(tr) else None, len(tr), int(qf), int(lags),
+                                               _track_model(model)))
+        self.follow_trajs, self.follow_qf, self.follow_nf, self.follow_nl = (tr, int(qf), 2 * int(qf) + 1, int(lags)) if len(tr) else (None, 0, 1, 0)
+
+    def follows(self, cap=65536):
+        """uwspr_pipe_collect_follows: the fits of the records K16 decoded (osd = 4) emitted so far (never waits), a
+        FOLLOW_RECORD_DTYPE array in the order of those records: frame, cand, channel, pass and result (best, s_best, s_ref,
+        f_hz); follow_of gives a record's pass, frequency and lag."""
+        out = np.zeros(cap, N.FOLLOW_RECORD_DTYPE)
+        n = self._chk(self.L.uwspr_pipe_collect_follows(self.h, C.c_void_p(out.ctypes.data), cap))
+        return out[:n].copy()
+
+    def follow_of(self, rec):
+        """a follow record -> the "follow" dict of decode_wav: v, d, tc of the best pass, the fitted f, the lag in samples,
+        s_best, s_ref"""
+        r = rec["result"]
+        nlg = 2 * self.follow_nl + 1
+        t = self.follow_trajs[int(r["best"]) // (self.follow_nf * nlg)]
+        return {"v": float(t["v"]), "d": float(t["d"]), "tc": float(t["tc"]), "f": float(r["f_hz"]),
+                "lag": N.FOLLOW_LSTEP * (int(r["best"]) % nlg - self.follow_nl), "s_best": float(r["s_best"]), "s_ref": float(r["s_ref"])}
+
     def set_carriers(self, hz):
         """uwspr_pipe_set_carriers: K0's centres in Hz (distinct integers, order kept), before the first audio push.  With
         more than one, a record's "channel" field is the plane index: split_plane gives (channel, carrier)."""
@@ -1806,7 +1873,10 @@ def decode_wav(path, channels=None, **pipe_opts):
     its "channel".  carriers=[Hz, ..]: every channel is heard at each of them (Pipe(carriers=..)), records in (take,
     channel, carrier, frame) order, each dict with its "carrier" in Hz ("channel" stays the audio channel).
     tracks=grid (track_grid; with track_qf, track_model): every decoded dict gets a "track" dict -- v, d, tc of the best
-    straight-line pass, the fitted f, t_best and t_ref (Context.track states them)."""
+    straight-line pass, the fitted f, t_best and t_ref (Context.track states them).
+    follow=grid (with follow_qf, follow_lags, follow_model): what Fano times out on is demodulated along the grid's passes
+    (K16), and every decoded dict gets "follow": v, d, tc of the pass, the fitted f, the lag in samples, s_best and s_ref for a
+    record K16 decoded, None for every other."""
     x, rate = read_wav(path, channels, any_rate=True)
     carriers = pipe_opts.get("carriers")
     pipe = Pipe(audio_rate=rate, **pipe_opts)
@@ -1817,6 +1887,8 @@ def decode_wav(path, channels=None, **pipe_opts):
         pipe.flush()
         recs = pipe.collect(cap=1 << 20)
         fits = pipe.tracks(cap=1 << 20) if pipe.track_trajs is not None else None
+        ffits = pipe.follows(cap=1 << 20) if pipe.follow_trajs is not None else None
+        nfol = 0
     finally:
         pipe.close()
     out = []
@@ -1826,6 +1898,9 @@ def decode_wav(path, channels=None, **pipe_opts):
         d = record_dict(r)
         if fits is not None:   # one per decoded record, in their order
             d["track"] = pipe.track_of(fits[len(out)])
+        if ffits is not None:   # one per record K16 decoded, in their order
+            d["follow"] = pipe.follow_of(ffits[nfol]) if r["osd"] == 4 else None
+            nfol += int(r["osd"] == 4)
         ch, car = pipe.split_plane(r["channel"])
         if channels == "all":
             d["channel"] = ch

@@ -155,12 +155,6 @@ __global__ __launch_bounds__(256) void k15_pick(const uwspr_sub_item *__restrict
 
 
 // ---------------------------------------------------------------- host side
-// a trajectory set on the current device: read-only once built (track_build), so one set serves every lane of a pipe
-struct trk_set {
-  int n = 0, qf = 0, model = 0;
-  double *d_dfreq = nullptr; int32_t *d_tau = nullptr;   // [162][n]
-};
-
 struct trk_state {
   trk_set *set = nullptr;   // uwspr_track_set's
   uwspr_sub_item *d_items = nullptr; size_t cap_items = 0;

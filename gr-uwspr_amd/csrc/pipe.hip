@@ -86,6 +86,14 @@ struct pipe_lane {
   std::vector<uwspr_track_result> trk_by_rec;    // [B*per]: the fit of record i of the running search, where it decoded
   std::vector<uwspr_track_result> rec_trk;       // beside recs: the fit of each decoded record
   std::vector<uwspr_track_record> trecs;         // the batch's track records, emitted with recs
+  // blind demodulation along passes (uwspr_pipe_set_follow): what Fano gave up on as K16 items
+  std::vector<uwspr_block_item> fol_items;
+  std::vector<uwspr_follow_result> fol_fetch;    // [items] as the kernel wrote them
+  std::vector<uint8_t> fol_ok;                   // item -> the bytes decoded
+  std::vector<int8_t> fol_msg;                   // [items][7]
+  std::vector<uwspr_follow_result> fol_by_rec;   // [B*per]: the fit of record i of the running search, where K16 decoded it
+  std::vector<uwspr_follow_result> rec_fol;      // beside recs: the fit of each record K16 decoded
+  std::vector<uwspr_follow_record> frecs;        // the batch's follow records, emitted with recs
 };
 
 // what the host tails of a batch add to the pipe's statistics
@@ -118,6 +126,9 @@ struct uwspr_pipe {
   // uwspr_pipe_set_tracks: K15 on every decoded record against the trajectory set; one device set for all lanes (made and
   // freed by set_tracks, read-only in between)
   trk_set *track_set = nullptr;
+  // uwspr_pipe_set_follow: K16 on what Fano gave up on, against the follow set; one device set for all lanes (made and freed
+  // by set_follow, read-only in between)
+  fol_set *follow_set = nullptr;
   int block = 0;    // uwspr_pipe_set_option("block"): 2, 3 = K10's soft symbols of block lengths 2 .. block for those records
   int audio_rate = 12000;   // uwspr_pipe_set_option("audio_rate"): the rate of the pushed audio (12000: no resampler, else K11 ahead of K0)
   int blank = 0, blank_guard = 2;   // uwspr_pipe_set_option("blank" / "blank_guard"): K12 ahead of K11 / K0 (blank 0: off)
@@ -147,6 +158,7 @@ struct uwspr_pipe {
   std::condition_variable cv_lane, cv_work, cv_done, cv_turn;
   std::deque<uwspr_decode> done;
   std::deque<uwspr_track_record> done_trk;   // uwspr_pipe_collect_tracks: pushed with the decode records they belong to
+  std::deque<uwspr_follow_record> done_fol;  // uwspr_pipe_collect_follows: likewise
   bool stop = false;
   int64_t next_seq = 0, emit_seq = 0;     // batches launched / emitted (records leave in batch order)
   std::vector<std::thread> coords;         // one coordinator per lane: the host tails of consecutive batches overlap
@@ -378,6 +390,68 @@ static int block_tail(uwspr_pipe *q, pipe_lane &L, const float *frames, int nrec
   return UWSPR_OK;
 }
 
+// uwspr_pipe_set_follow.  K16 demodulates each item -- the common rule's: collect_items -- along the set's passes from the
+// frames the search itself read, at the try's jig_shift and the frequency model the fine search correlated with
+// (rules::fine_model), as "block" does.  An item whose result and bytes pass rules::follow_gates goes through de-interleave
+// and Fano on the host pool; bytes that unpack make the record a decoded one with osd = 4, and its fit goes to
+// L.fol_by_rec.  Its time counts as resume time, its Fano calls as the batch's.
+static int follow_tail(uwspr_pipe *q, pipe_lane &L, const float *frames, int nrec, tail_acc &ta) {
+  const int per = q->per;
+  const int n = collect_items(q, L, nrec);
+  if (n == 0) return UWSPR_OK;
+  L.fol_items.clear();
+  for (int k = 0; k < n; k++) {
+    const int i = L.fb_rec[k];
+    uwspr_block_item it;
+    it.frame = i / per;
+    it.shift = L.h_out[i].jig_shift[L.fb_idt[k]];
+    rules::fine_model(L.h_cands[i], L.h_out[i], (float)q->p.cf, &it.f_hz, &it.drift_hz);
+    L.fol_items.push_back(it);
+  }
+  const double t0 = now_s();
+  uwspr_follow_result *d_res = nullptr;
+  uint8_t *d_sym = nullptr;
+  int rc = blockdemod_check(L.ctx, L.fol_items.data(), n, (nrec + per - 1) / per);
+  if (!rc) rc = follow_run(L.ctx, q->follow_set, frames, (size_t)L.ctx->fstride, L.fol_items.data(), n, nullptr, nullptr, nullptr, &d_res, &d_sym);
+  if (rc) return pfail(q, rc, "follow: %s", uwspr_last_error(L.ctx));
+  L.fol_fetch.resize((size_t)n);
+  if ((rc = lane_fetch(q, L, L.fol_fetch.data(), d_res, (size_t)n * sizeof(uwspr_follow_result)))) return rc;
+  std::vector<uint8_t> &fol_sym = L.fb_res;   // [items][162]
+  fol_sym.resize((size_t)n * UWSPR_NSYM);
+  if ((rc = lane_fetch(q, L, fol_sym.data(), d_sym, fol_sym.size()))) return rc;
+  L.fol_ok.assign((size_t)n, 0);
+  L.fol_msg.assign((size_t)n * 7, 0);
+  std::atomic<long long> calls(0), fails(0);
+  auto one = [&](int k) {
+    uint8_t sym[UWSPR_NSYM], data[11];
+    memcpy(sym, &fol_sym[(size_t)k * UWSPR_NSYM], UWSPR_NSYM);
+    if (!rules::follow_gates(L.fol_fetch[k], sym)) return;
+    uwspr_deinterleave(sym);
+    memset(data, 0, sizeof(data));
+    uint32_t metric, cycles, maxnp;
+    calls.fetch_add(1, std::memory_order_relaxed);
+    if (uwspr_fano_decode(sym, data, &metric, &cycles, &maxnp, 60, 10000) != 0) { fails.fetch_add(1, std::memory_order_relaxed); return; }
+    int8_t msg[7];
+    char text[32];
+    for (int i = 0; i < 7; i++) msg[i] = (int8_t)data[i];
+    if (uwspr_unpack_message(msg, text, sizeof(text)) != 0) return;
+    L.fol_ok[k] = 1;
+    memcpy(&L.fol_msg[7 * (size_t)k], msg, 7);
+  };
+  if (n <= 2) for (int k = 0; k < n; k++) one(k);
+  else q->pool->run(n, q->o.host_threads, one);
+  for (int k = 0; k < n; k++) {
+    if (!L.fol_ok[k]) continue;
+    const int i = L.fb_rec[k];
+    L.dec[i] = 1; L.idt[i] = L.fb_idt[k]; L.osdf[i] = 4;
+    memcpy(&L.msg[7 * (size_t)i], &L.fol_msg[7 * (size_t)k], 7);
+    L.fol_by_rec[i] = L.fol_fetch[k];
+  }
+  ta.calls += calls.load(); ta.fails += fails.load();
+  ta.resume_s += now_s() - t0;
+  return UWSPR_OK;
+}
+
 // uwspr_pipe_set_tracks.  Behind the fallbacks every decoded record of the search -- Fano's, "block"'s, the list's, the call
 // search's and OSD's alike -- becomes one K15 item: the symbols of its message, the jig_shift of the try that decoded and
 // the frequency model the fine search correlated with (rules::fine_model: what the second pass subtracts with), over the
@@ -393,6 +467,11 @@ static int track_tail(uwspr_pipe *q, pipe_lane &L, const float *frames, int nrec
     it.frame = i / per;
     it.shift = o.jig_shift[L.idt[i] >= 0 && L.idt[i] < UWSPR_NJIG ? L.idt[i] : 0];
     rules::fine_model(L.h_cands[i], o, (float)q->p.cf, &it.f_hz, &it.drift_hz);
+    if (L.osdf[i] == 4) {   // K16 decoded it: at the follower's lag and frequency, without drift
+      const fol_set *fs = q->follow_set;
+      it.shift += 32 * (L.fol_by_rec[i].best % (2 * fs->nl + 1) - fs->nl);
+      it.f_hz = L.fol_by_rec[i].f_hz; it.drift_hz = 0.0f;
+    }
     if (uwspr_wspr_symbols(&L.msg[7 * (size_t)i], it.symbols)) return pfail(q, UWSPR_ERR_ARG, "trajectory fit: symbols of a decoded message");
     L.trk_items.push_back(it); L.trk_rec.push_back(i);
   }
@@ -499,11 +578,13 @@ static int host_tail(uwspr_pipe *q, pipe_lane &L, const float *frames, int B, bo
   ta.gpu_wait_s += (t1 - t0);
   ta.fano_s += (t2 - t1) + (t4 - t3);
   ta.resume_s += (t3 - t2);
-  // block -> list -> calls -> OSD; a record one of them decoded is no item of the next
+  // block -> follow -> list -> calls -> OSD (the blind methods first); a record one of them decoded is no item of the next
   memset(L.osdf.data(), 0, (size_t)nrec);
   memset(L.blkf.data(), 0, (size_t)nrec);
   if (q->block > 0)
     if (const int rc = block_tail(q, L, frames, nrec, ta)) return rc;
+  if (q->follow_set)
+    if (const int rc = follow_tail(q, L, frames, nrec, ta)) return rc;
   if (q->deep_M > 0)
     if (const int rc = scored_tail(q, L, nrec, kListFallback, ta)) return rc;
   if (q->call_set)
@@ -539,7 +620,8 @@ static int finish_batch(uwspr_pipe *q, pipe_lane &L) {
   const int per = q->per, B = L.B;
   L.recs.clear();   // (a failure below emits nothing for this batch)
   L.rec_trk.clear(); L.trecs.clear();
-  const bool tracks = q->track_set != nullptr;
+  L.rec_fol.clear(); L.frecs.clear();
+  const bool tracks = q->track_set != nullptr, follows = q->follow_set != nullptr;
   tail_acc ta;
   if (const int rc = host_tail(q, L, L.frames, B, true, ta)) return rc;
   int ncand = 0, ndec = 0;
@@ -549,12 +631,22 @@ static int finish_batch(uwspr_pipe *q, pipe_lane &L) {
       if (!lane_valid(q, L, i)) continue;
       L.recs.push_back(make_record(L, b, i, j, L.h_npk[b], 0));
       if (tracks) L.rec_trk.push_back(L.trk_by_rec[i]);
+      if (follows) L.rec_fol.push_back(L.fol_by_rec[i]);
       ncand++; ndec += L.dec[i];
     }
   if (q->passes == 2 && ndec > 0) {
     const int rc = second_pass(q, L, ta, &ncand, &ndec);
-    if (rc) { L.recs.clear(); L.rec_trk.clear(); return rc; }
+    if (rc) { L.recs.clear(); L.rec_trk.clear(); L.rec_fol.clear(); return rc; }
   }
+  if (follows)   // one follow record per record K16 decoded, in their order
+    for (size_t r = 0; r < L.recs.size(); r++) {
+      const uwspr_decode &d = L.recs[r];
+      if (!d.decoded || d.osd != 4) continue;
+      uwspr_follow_record fr;
+      memset(&fr, 0, sizeof(fr));
+      fr.frame = d.frame; fr.cand = d.cand; fr.channel = d.channel; fr.pass = d.pass; fr.result = L.rec_fol[r];
+      L.frecs.push_back(fr);
+    }
   if (tracks)   // one track record per decoded record, in their order
     for (size_t r = 0; r < L.recs.size(); r++) {
       const uwspr_decode &d = L.recs[r];
@@ -622,8 +714,14 @@ static int second_pass(uwspr_pipe *q, pipe_lane &L, tail_acc &ta, int *ncand, in
   std::vector<uwspr_decode> merged;
   merged.reserve(L.recs.size() + (size_t)ns * per);
   const bool tracks = q->track_set != nullptr;   // then L.rec_trk goes through the same merge, beside the records
+  const bool follows = q->follow_set != nullptr;   // and L.rec_fol likewise
   std::vector<uwspr_track_result> mtrk;
-  auto keep = [&](size_t r) { merged.push_back(L.recs[r]); if (tracks) mtrk.push_back(L.rec_trk[r]); };
+  std::vector<uwspr_follow_result> mfol;
+  auto keep = [&](size_t r) {
+    merged.push_back(L.recs[r]);
+    if (tracks) mtrk.push_back(L.rec_trk[r]);
+    if (follows) mfol.push_back(L.rec_fol[r]);
+  };
   size_t r0 = 0;
   for (int s = 0; s < ns; s++) {
     const int64_t fr = L.frame0 + L.slot_frame[s];
@@ -639,12 +737,14 @@ static int second_pass(uwspr_pipe *q, pipe_lane &L, tail_acc &ta, int *ncand, in
       if (known) continue;
       merged.push_back(make_record(L, L.slot_frame[s], i, cand++, npk1[s], 1));
       if (tracks) mtrk.push_back(L.trk_by_rec[i]);
+      if (follows) mfol.push_back(L.fol_by_rec[i]);
       (*ncand)++; (*ndec)++;
     }
   }
   while (r0 < L.recs.size()) keep(r0++);
   L.recs.swap(merged);
   if (tracks) L.rec_trk.swap(mtrk);
+  if (follows) L.rec_fol.swap(mfol);
   return UWSPR_OK;
 }
 
@@ -667,11 +767,12 @@ static void coordinator(uwspr_pipe *q) {
       Lp->claimed = true;
     }
     pipe_lane &L = *Lp;
-    if (finish_batch(q, L)) L.trecs.clear();   // a failure is sticky in q->failed; the lane is released either way
+    if (finish_batch(q, L)) { L.trecs.clear(); L.frecs.clear(); }   // a failure is sticky in q->failed; the lane is released either way
     {
       std::unique_lock<std::mutex> lk(q->m);
       q->cv_turn.wait(lk, [&]() { return q->emit_seq == L.seq; });
       for (const uwspr_track_record &t : L.trecs) q->done_trk.push_back(t);   // (no later than the decode records they belong to)
+      for (const uwspr_follow_record &t : L.frecs) q->done_fol.push_back(t);
       for (const uwspr_decode &d : L.recs) q->done.push_back(d);
       q->emit_seq++;
       L.launched = false; L.claimed = false; L.host_since = 0.0;
@@ -796,6 +897,7 @@ extern "C" void uwspr_pipe_close(uwspr_pipe *q) {
   if (q->d_deep_tab) (void)hipFree(q->d_deep_tab);
   calls_free_set(q->call_set);
   track_free_set(q->track_set);
+  follow_free_set(q->follow_set);
   q->ring.close();
   for (int k = 0; k < uwspr_pipe::NSTAGE; k++) {
     if (q->h_stage[k]) (void)hipHostFree(q->h_stage[k]);
@@ -1214,6 +1316,45 @@ extern "C" int uwspr_pipe_set_tracks(uwspr_pipe *q, const uwspr_track_traj *traj
   track_free_set(q->track_set);   // (nothing in flight: no lane reads it)
   q->track_set = fresh;
   return UWSPR_OK;
+}
+
+// The follow set: K15's rules (checked, designed on the host and uploaded before anything of the pipe changes; one set for
+// all lanes).  n = 0 clears it.
+extern "C" int uwspr_pipe_set_follow(uwspr_pipe *q, const uwspr_track_traj *traj, int n, int qf, int nl, int model) {
+  if (!q) return UWSPR_ERR_ARG;
+  char why[256];
+  if (n != 0 && follow_check(traj, n, qf, nl, model, why, sizeof(why))) return parg(q, "uwspr_pipe_set_follow: %s", why);
+  if (n == 0 && (qf < 0 || qf > UWSPR_FOLLOW_QF_MAX || nl < 0 || nl > UWSPR_FOLLOW_NL_MAX || (model != UWSPR_TX_DOPPLER && model != UWSPR_TX_DELAY)))
+    return parg(q, "uwspr_pipe_set_follow: n 0 clears the set, but qf %d (0..%d), nl %d (0..%d), model %d are no set's", qf, UWSPR_FOLLOW_QF_MAX, nl,
+                UWSPR_FOLLOW_NL_MAX, model);
+  if (const int f = q->failed.load()) return f;
+  fol_set *fresh = nullptr;
+  if (n > 0) {
+    (void)hipSetDevice(q->device);
+    int rc = UWSPR_OK;
+    fresh = follow_build(traj, n, qf, nl, model, (double)q->p.cf, &rc, why, sizeof(why));
+    if (!fresh) return rc == UWSPR_ERR_ARG ? parg(q, "uwspr_pipe_set_follow: %s", why) : pfail(q, rc, "uwspr_pipe_set_follow: %s", why);
+  }
+  std::lock_guard<std::mutex> lk(q->m);
+  if (!lanes_idle_locked(q, "uwspr_pipe_set_follow")) {
+    follow_free_set(fresh);
+    return UWSPR_ERR_ARG;
+  }
+  if (fresh)   // (the per-record fits exist only in a pipe that follows)
+    for (pipe_lane &L : q->lanes) L.fol_by_rec.resize(L.dec.size());
+  follow_free_set(q->follow_set);   // (nothing in flight: no lane reads it)
+  q->follow_set = fresh;
+  return UWSPR_OK;
+}
+
+// the follow records emitted so far, at most cap of them; never waits
+extern "C" int uwspr_pipe_collect_follows(uwspr_pipe *q, uwspr_follow_record *out, int cap) {
+  if (!q || (cap > 0 && !out) || cap < 0) return UWSPR_ERR_ARG;
+  std::lock_guard<std::mutex> lk(q->m);
+  if (q->failed.load() && q->done_fol.empty()) return q->failed.load();
+  int n = 0;
+  while (n < cap && !q->done_fol.empty()) { out[n++] = q->done_fol.front(); q->done_fol.pop_front(); }
+  return n;
 }
 
 // the track records emitted so far, at most cap of them; never waits

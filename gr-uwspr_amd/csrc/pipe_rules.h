@@ -40,6 +40,20 @@ static inline bool calls_accepts(const uwspr_call_result &r, long long nhyp, int
          (nhyp <= 1 || gap_holds(r.sbest, r.snext, gap));
 }
 
+// The rms of 162 soft-symbol bytes about 128 as the fine search forms it before its gate (cc:469-474): binary32 sum of
+// squares in ascending order, the root in binary64, rounded to binary32.
+static inline float bytes_rms(const uint8_t *sym) {
+  float sq = 0.0f;
+  for (int i = 0; i < UWSPR_NSYM; i++) { const float y = (float)((double)(float)sym[i] - 128.0); sq += y * y; }
+  return (float)sqrt((double)sq / 162.0);
+}
+
+// K16: the picked hypothesis' sync metric above the fine search's gate and the bytes' rms above its rms gate, both strict (a
+// NaN s_best passes neither); the caller then asks that the bytes go through de-interleave, Fano and uwspr_unpack_message
+static inline bool follow_gates(const uwspr_follow_result &r, const uint8_t *sym) {
+  return r.s_best > kMinSync2 && bytes_rms(sym) > kMinRms;
+}
+
 // slmFrequencyDrift (lib/slm.cc:36-73) at t = 0: the constant the fine search adds to a nonlinear candidate's f0
 static inline float slm_at_zero(const uwspr_candidate &c, float cf) {
   const double V1 = c.m_nonlinear.V1, V2 = c.m_nonlinear.V2, q1 = (double)c.m_nonlinear.p1, q2 = (double)c.m_nonlinear.p2;

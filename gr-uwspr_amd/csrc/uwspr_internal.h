@@ -180,6 +180,9 @@ void calls_release(uwspr_ctx *c); // k14_calls.hip: frees what uwspr_calls_set /
 struct trk_state;
 struct trk_set;
 void trk_release(uwspr_ctx *c);  // k15_track.hip: frees what uwspr_track_set / uwspr_track_batch made
+struct fol_state;
+struct fol_set;
+void fol_release(uwspr_ctx *c);  // k16_follow.hip: frees what uwspr_follow_set / uwspr_follow_batch made
 
 }  // namespace uwspr
 
@@ -289,6 +292,8 @@ struct uwspr_ctx {
   uwspr::calls_state *calls;
   // trajectory fit (k15_track.hip): the set's tables and call scratch, made by uwspr_track_set
   uwspr::trk_state *trk;
+  // blind demodulation along passes (k16_follow.hip): the set and call scratch, made by uwspr_follow_set
+  uwspr::fol_state *fol;
 
   int prof_mask;
   std::vector<uwspr::ev_pair> prof_events;
@@ -350,11 +355,33 @@ int blockdemod_run(uwspr_ctx *c, const float *src, size_t stride, const uwspr_bl
 // subtract_check) on the context's stream against a set (null = the set of uwspr_track_set); src: device frames, frame b at
 // src + 2 stride b floats; results to res and the surface to surface (device memory), or with either null to a buffer of
 // the context (the results' handed back through *res_out).
+// A trajectory set on the current device: read-only once built (track_build), so one set serves every lane of a pipe.
+// K16's sets are the same object (the tables are exactly uwspr_track_design's).
+struct trk_set {
+  int n = 0, qf = 0, model = 0;
+  double *d_dfreq = nullptr; int32_t *d_tau = nullptr;   // [162][n]
+};
 const char *track_check(const uwspr_track_traj *traj, int n, int nmax, int qf, int model, char *msg, size_t cap);
 trk_set *track_build(const uwspr_track_traj *traj, int n, int qf, int model, double cf, int *status, char *msg, size_t cap);
 void track_free_set(trk_set *s);
 int track_run(uwspr_ctx *c, const trk_set *set, const float *src, size_t stride, const uwspr_sub_item *items, int nitems,
               uwspr_track_result *res, float *surface, uwspr_track_result **res_out);
+
+// K16 (k16_follow.hip): a follow set is a trajectory set (track_check / track_build, qf the reach in steps of df / 8) and a
+// lag reach nl (follow_check: null, or what is wrong).  follow_run: nitems > 0 items (host records that passed
+// blockdemod_check) on the context's stream against a set (null = the set of uwspr_follow_set); results, the [nitems][162]
+// bytes and the surface go to res / symbols / surface (device memory), or with any of them null to buffers of the context
+// (results and bytes handed back through *res_out / *sym_out).
+struct fol_set {
+  trk_set *t = nullptr;
+  int nl = 0;
+  float2 *d_W = nullptr;   // the 2048 roots of unity e^{-j 2 pi m / 2048}, made on the device by k16_roots
+};
+const char *follow_check(const uwspr_track_traj *traj, int n, int qf, int nl, int model, char *msg, size_t cap);
+fol_set *follow_build(const uwspr_track_traj *traj, int n, int qf, int nl, int model, double cf, int *status, char *msg, size_t cap);
+void follow_free_set(fol_set *s);
+int follow_run(uwspr_ctx *c, const fol_set *set, const float *src, size_t stride, const uwspr_block_item *items, int nitems,
+               uwspr_follow_result *res, uint8_t *symbols, float *surface, uwspr_follow_result **res_out, uint8_t **sym_out);
 
 // ---- launchers (each enqueues on ctx->stream) ------------------------------
 int frontend_design(int mode, int stage, std::vector<double> &out, int *delay);

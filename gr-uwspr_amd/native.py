@@ -26,7 +26,7 @@ LIBPATH = os.path.join(LIBDIR, "libuwspr_hip_exp_%s.so" % _EXTRA_TAG if _EXTRA e
 HOSTLIB = os.path.join(LIBDIR, "libuwspr_blocks.so")
 
 SOURCES = ["uwspr_api.hip", "k0_frontend.hip", "k1_spectrogram.hip", "k2_spectrum.hip", "k3_coarse.hip",
-           "k4_tonecorr.hip", "k4_grid.hip", "k4_pair.hip", "k4_jig.hip", "k5_fold_schedule.hip", "k6_sched.hip", "k7_transmit.hip", "k8_subtract.hip", "k9_osd.hip", "k10_blockdemod.hip", "k11_resample.hip", "k12_blank.hip", "k13_deep.hip", "k14_calls.hip", "k15_track.hip", "pipe.hip", "dist.hip", "host_tail.cpp"]
+           "k4_tonecorr.hip", "k4_grid.hip", "k4_pair.hip", "k4_jig.hip", "k5_fold_schedule.hip", "k6_sched.hip", "k7_transmit.hip", "k8_subtract.hip", "k9_osd.hip", "k10_blockdemod.hip", "k11_resample.hip", "k12_blank.hip", "k13_deep.hip", "k14_calls.hip", "k15_track.hip", "k16_follow.hip", "pipe.hip", "dist.hip", "host_tail.cpp"]
 HIPFLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off",
             "-fno-slp-vectorize", "-fhip-fp32-correctly-rounded-divide-sqrt", "-fPIC", "-Wall", "-Wno-unused-function"]
 
@@ -232,6 +232,11 @@ TRACK_RESULT_DTYPE = np.dtype([("best", "<i4"), ("t_best", "<f4"), ("t_ref", "<f
 TRACK_RECORD_DTYPE = np.dtype([("frame", "<i8"), ("cand", "<i4"), ("channel", "<i2"), ("pass", "u1"), ("_pad", "u1"), ("result", TRACK_RESULT_DTYPE)])
 assert TRACK_TRAJ_DTYPE.itemsize == 24 and TRACK_RESULT_DTYPE.itemsize == 16 and TRACK_RECORD_DTYPE.itemsize == 32
 TRACK_MAX, TRACK_QF_MAX = 4096, 16
+FOLLOW_RESULT_DTYPE = np.dtype([("best", "<i4"), ("s_best", "<f4"), ("s_ref", "<f4"), ("f_hz", "<f4")])
+FOLLOW_RECORD_DTYPE = np.dtype([("frame", "<i8"), ("cand", "<i4"), ("channel", "<i2"), ("pass", "u1"), ("_pad", "u1"), ("result", FOLLOW_RESULT_DTYPE)])
+assert FOLLOW_RESULT_DTYPE.itemsize == 16 and FOLLOW_RECORD_DTYPE.itemsize == 32
+FOLLOW_QF_MAX, FOLLOW_NL_MAX = 16, 4   # UWSPR_FOLLOW_QF_MAX, UWSPR_FOLLOW_NL_MAX
+FOLLOW_Q, FOLLOW_LSTEP = 375.0 / 2048.0, 32   # K16's frequency step in Hz and lag step in samples
 PIPE_MAX_CHANNELS = 64
 
 
@@ -373,6 +378,8 @@ SIGNATURES = {
     "uwspr_track_from_slm": (_ip, [C.c_double] * 5 + [_vp]),
     "uwspr_track_set": (_ip, [_vp, _vp, _ip, _ip, _ip]),
     "uwspr_track_batch": (_ip, [_vp, _vp, _ip, _ip, _vp, _ip, _vp, _vp]),
+    "uwspr_follow_set": (_ip, [_vp, _vp, _ip, _ip, _ip, _ip]),
+    "uwspr_follow_batch": (_ip, [_vp, _vp, _ip, _ip, _vp, _ip, _vp, _vp, _vp]),
     "uwspr_dist_unique_id": (_ip, [_vp]),
     "uwspr_dist_init": (_ip, [_vp, _ip, _ip, _vp]),
     "uwspr_dist_gather": (_ip, [_vp, _vp, _sz, _vp, _ip, _ip]),
@@ -396,6 +403,8 @@ SIGNATURES = {
     "uwspr_pipe_set_calls": (_ip, [_vp, _vp, _ip, _vp, _u32]),
     "uwspr_pipe_set_tracks": (_ip, [_vp, _vp, _ip, _ip, _ip]),
     "uwspr_pipe_collect_tracks": (_ip, [_vp, _vp, _ip]),
+    "uwspr_pipe_set_follow": (_ip, [_vp, _vp, _ip, _ip, _ip, _ip]),
+    "uwspr_pipe_collect_follows": (_ip, [_vp, _vp, _ip]),
     # diagnostics, outside the ABI header (defined extern "C" under csrc/)
     "uwspr_debug_fdr_from_ps": (_ip, [_vp, _vp, _ip, _ip, _vp, _vp]),
     "uwspr_debug_snr_db": (_ip, _vp3 + [_ll]),
@@ -411,6 +420,7 @@ SIGNATURES = {
     "uwspr_debug_resample_counts": (_ip, [_vp]),
     "uwspr_debug_blank_counts": (_ip, [_vp]),
     "uwspr_debug_track_time": (_ip, [_vp, _ip, _vp]),
+    "uwspr_debug_follow_time": (_ip, [_vp, _ip, _vp]),
 }
 ABI_SYMBOLS = [k for k in SIGNATURES if not k.startswith("uwspr_debug_")]
 

@@ -62,7 +62,11 @@ extern "C" {
                                     trajectory fit of a decoded source (entry points and records only, so the version stays):
                                     uwspr_track_traj, uwspr_track_result, uwspr_track_design, uwspr_track_from_slm,
                                     uwspr_track_set, uwspr_track_batch, uwspr_track_record, uwspr_pipe_set_tracks,
-                                    uwspr_pipe_collect_tracks */
+                                    uwspr_pipe_collect_tracks;
+                                    blind demodulation along straight-line passes (entry points and records only, so the
+                                    version stays): uwspr_follow_result, uwspr_follow_set, uwspr_follow_batch,
+                                    uwspr_follow_record, uwspr_pipe_set_follow, uwspr_pipe_collect_follows,
+                                    uwspr_decode.osd = 4 */
 
 typedef enum {
   UWSPR_OK = 0,
@@ -582,7 +586,9 @@ typedef struct uwspr_decode {
                              carriers (uwspr_pipe_set_carriers): the plane index channel * n + carrier index */
   uint8_t pass;           /* 1: found by the second pass (option "passes" = 2), in the frame with its decoded signals taken out; 0 otherwise */
   uint8_t osd;            /* 1: ordered-statistics decoding, 2: list search, 3: call search -- Fano timed out on every gated try and K9
-                             (option "osd"), K13 (uwspr_pipe_set_list) or K14 (uwspr_pipe_set_calls) gave the message; 0 otherwise */
+                             (option "osd"), K13 (uwspr_pipe_set_list) or K14 (uwspr_pipe_set_calls) gave the message; 4: Fano timed
+                             out on every gated try and decoded K16's soft symbols along a straight-line pass
+                             (uwspr_pipe_set_follow); 0 otherwise */
 } uwspr_decode;
 typedef struct uwspr_pipe_stats {
   int64_t frames, batches, candidates, decoded, resumed;   /* resumed: records whose other tries were produced */
@@ -1277,6 +1283,79 @@ typedef struct uwspr_track_record {
 } uwspr_track_record;
 int uwspr_pipe_set_tracks(uwspr_pipe *pipe, const uwspr_track_traj *traj, int n, int qf, int model);
 int uwspr_pipe_collect_tracks(uwspr_pipe *pipe, uwspr_track_record *out, int cap);
+
+/* ---- decode a moving source: soft symbols along straight-line passes (K16, k16_follow.hip) ----------------------------- */
+/* The fine search holds a candidate at one frequency plus a linear drift.  A source whose closest point of approach falls
+ * in mid-transmission sweeps an S-curve of more than a tone spacing, and no (f, drift) pair follows it: Fano times out on
+ * every try.  K16 demodulates such a record BLIND -- no symbol is known -- along the passes of a trajectory set, K15's
+ * tables (uwspr_track_design: dfreq, tau) removing the motion, over a grid of frequency offsets and lags, scores every
+ * hypothesis with the fine search's own sync metric and hands out the soft symbols of the best one.  The reference has no
+ * counterpart; tests/follow_exact.py restates this text in binary64.  Binary32 with fused multiply-adds on the device;
+ * every phase and index in binary64 or integers.
+ * Constants: df = 375/256; Q = df / 8 = 375/2048 Hz, the frequency step; LSTEP = 32 samples, the lag step; pr3[i] = the
+ * sync bit of symbol i (the LSB of any uwspr_wspr_symbols).
+ * The set (uwspr_follow_set): 1 <= n <= 4096 trajectories (uwspr_track_traj, K15's rules), 0 <= qf <= 16 (nf = 2 qf + 1
+ * offsets q = -qf .. qf), 0 <= nl <= 4 (nlg = 2 nl + 1 lags l = -nl .. nl), model UWSPR_TX_DOPPLER or UWSPR_TX_DELAY; its
+ * tables are exactly uwspr_track_design's with cf = uwspr_params.cf.  K15's rules: checked and designed on the host before
+ * anything of the context changes, UWSPR_ERR_ARG leaves the set before in place, read-only once built.
+ * An item is a uwspr_block_item under uwspr_blockdemod_batch's rules: frame, shift s, f_hz; drift_hz is used by s_ref alone.
+ * Grid powers, for trajectory j, lag l, symbol i and grid index g = -(qf + 12) .. qf + 12:
+ *     f = (f_hz + dfreq[j][i]) + g Q                                                              (binary64, this order)
+ *     P_i(j, l)[g] = | sum_{k < 256} x[s + 32 l + 256 i + tau[j][i] + k] e^{-j 2 pi f k / 375} |
+ * Samples outside [0, fl) count as 0 (K15's rule); the phasor starts at (1, 0) in every symbol.
+ * A hypothesis is h = (j nf + (q + qf)) nlg + (l + nl).  Tone t = 0..3 of symbol i is p_i[t] = P_i(j, l)[q + 8 t - 12]: the
+ * tone offsets (t - 1.5) df lie on the grid.  The score is the fine search's sync metric,
+ *     S(h) = sum_i (2 pr3[i] - 1) ((p_i[1] + p_i[3]) - (p_i[0] + p_i[2])) / sum_i (((p_i[0] + p_i[1]) + p_i[2]) + p_i[3]),
+ * both sums in ascending i with one owner each; 0 when the denominator is 0.
+ * best = the first maximum of S in ascending h (K8's rule: the walk moves on `>` alone, a NaN is never moved to and a NaN
+ * S(0) is never left).  s_ref is the same S for the item's own linear model through the same code: f_i = f_hz +
+ * (drift_hz / 2)(i - 81) / 81, tau = 0, l = 0, q = 0; a v = 0 trajectory at q = 0, l = 0 of an item with drift 0 gives the
+ * bytes of s_ref.
+ * Soft symbols at best: soft[i] = p_i[pr3[i] + 2] - p_i[pr3[i]], normalised and written as K10's text says (fsum, f2sum,
+ * fac = sqrt(f2sum - fsum^2), v = 50 soft / fac clipped to [-128, 127], byte = (uint8)(v + 128); a fac that is no positive
+ * finite number gives 128 in every byte), interleaved as uwspr_demod_out.symbols[idt] holds a vector.
+ * Result per item: best; s_best = S(best); s_ref; f_hz = f_hz + Q q_best, formed in binary64 and rounded to binary32.  The
+ * trajectory is best / (nf nlg), q = (best / nlg) % nf - qf, l = best % nlg - nl.
+ * uwspr_follow_batch: frames, items and `where` as for uwspr_track_batch (items in HOST memory whatever `where` says); res
+ * [nitems], symbols [nitems][162] and surface [nitems][n nf nlg] (binary32 S of every hypothesis; NULL: not written) are
+ * host memory with UWSPR_HOST (complete on return), device memory with UWSPR_DEVICE (asynchronous on the context's stream)
+ * and UWSPR_DEVICE_FRAMES (complete on return).  UWSPR_ERR_ARG before any launch, the outputs untouched: an item that
+ * uwspr_blockdemod_batch would refuse, a call without a set, a device output outside a device allocation of the context's
+ * device.  nitems = 0 is fine.  Every sum has one owner and one order: an item's bytes depend neither on the rest of the
+ * batch nor on where the frames live.
+ * In a pipe.  uwspr_pipe_set_follow gives a pipe a follow set (n = 0 clears it; legal only while no batch is in flight, as
+ * uwspr_pipe_set_tracks; UWSPR_ERR_ARG otherwise and for a set that breaks the rules -- qf, nl and model are checked with
+ * n = 0 as well --, and nothing changes).  With a set, behind "block" and before the list search -- the blind methods first -- every record that Fano gave up on becomes an item
+ * by the fallbacks' common rule (the gated try with the largest jig_sync): that try's jig_shift, f and drift as for "block".
+ * The record becomes a decoded one when s_best > 0.12 (strict: a NaN fails), the rms of the bytes about 128 is above the
+ * fine search's gate (cc:470), and the bytes go through de-interleave, Fano (60, 10000) and uwspr_unpack_message; then
+ * decoded = 1, idt = the picked try and osd = 4.  The Fano call counts in the statistics, the time in resume_s.  The fit
+ * leaves by uwspr_pipe_collect_follows -- K15's door, copied: records {frame, cand, channel, pass, result} in the order of
+ * the records that K16 decoded, each available no later than its decode record.  When the pipe also has a trajectory set
+ * (uwspr_pipe_set_tracks), K15's item of a record that K16 decoded is taken at shift s + 32 l_best and f = result.f_hz with
+ * drift 0; no other record's item changes.  Without a follow set nothing of K16 runs or is allocated, and every record,
+ * statistic and byte is what it was.
+ * Not built: the second pass ("passes" = 2) subtracts a record that K16 decoded with the linear model, as it does any
+ * decoded record; the chirp inside a symbol; bearing. */
+#define UWSPR_FOLLOW_QF_MAX 16
+#define UWSPR_FOLLOW_NL_MAX 4
+typedef struct uwspr_follow_result {
+  int32_t best;      /* h of the first maximum */
+  float s_best, s_ref;
+  float f_hz;        /* f_hz + (375/2048) q */
+} uwspr_follow_result;
+int uwspr_follow_set(uwspr_ctx *ctx, const uwspr_track_traj *traj, int n, int qf, int nl, int model);
+int uwspr_follow_batch(uwspr_ctx *ctx, const float *frames, int B, int where, const uwspr_block_item *items, int nitems,
+                       uwspr_follow_result *res, uint8_t *symbols /*[nitems][162]*/, float *surface /*[nitems][n nf nlg] or NULL*/);
+typedef struct uwspr_follow_record {
+  int64_t frame;     /* uwspr_decode.frame, .cand, .channel and .pass of the record K16 decoded */
+  int32_t cand;
+  int16_t channel;
+  uint8_t pass, _pad;
+  uwspr_follow_result result;
+} uwspr_follow_record;
+int uwspr_pipe_set_follow(uwspr_pipe *pipe, const uwspr_track_traj *traj, int n, int qf, int nl, int model);
+int uwspr_pipe_collect_follows(uwspr_pipe *pipe, uwspr_follow_record *out, int cap);
 
 #ifdef __cplusplus
 }
